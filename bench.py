@@ -6,7 +6,9 @@ re-associate (transform + exact 5-NN + plane fit + gates) -> linearise (residual
 corrector + Gram reduction) -> [all-reduce of counts and Gram when --gpus > 1] -> Gauss-Newton update
 of the pose, all on the device, inputs resident in HBM before the timed region starts.
 
-    python bench.py                      # 1 GPU, defaults finish within minutes
+    python bench.py                      # 1 GPU: set-up, warm-up, the timed steps, the result line
+    python bench.py --full               # + roofline, CPU baseline and pose parity, extras (other configs, stages, regions)
+    python bench.py --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -67,6 +69,21 @@ def single_socket_cpus():
         return cpus or None
     except Exception:   # noqa: BLE001
         return None
+
+
+def dump_outputs(out_dir, m, n_q):
+    """What the last timed step handed back through slot 0, one float32 / float64 .npy per array (about 9 MB at 200 k queries): the pose
+    after its Gauss-Newton update, that step (dt, rotation vector) and its status, and the surf correspondences of its association in
+    query order (the library copies them out ordered, so equal inputs give equal files)."""
+    os.makedirs(out_dir, exist_ok=True)
+    t, q, st = m.pose_get(0)
+    delta, _, _ = m.last_step(0)
+    rec = m.surf_records(0, n_q)
+    arrays = {"pose_t": t, "pose_q": q, "gn_status": np.array([st], np.float64), "last_step_delta": delta,
+              "surf_query_index": rec["query_index"].astype(np.float64), "surf_cur_pt": rec["cp"], "surf_normal": rec["n"],
+              "surf_neg_oa_dot_norm": rec["d"], "surf_score": rec["score"]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(w, queries, t0, q0):
@@ -351,7 +368,7 @@ def main():
                     help="untimed device pre-heat before the W warm-up steps: registrations of the same loop until this many milliseconds have passed, so that the K timed "
                          "steps do not start on a GPU that idled at low clocks while the host generated the workload (0 = none; reported in config.device_preheat_ms)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (window of 3 slots, ROT extractor)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (window of 3 slots, ROT extractor)")
     ap.add_argument("--collective", choices=["auto", "p2p", "rccl", "torch"], default="auto",
                     help="N > 1: who does the two tiny all-reduces per iteration — auto = lili_p2p, else RCCL from C, else torch.distributed")
     ap.add_argument("--no-native-rccl", action="store_true", help="same as --collective torch (A/B: the two all-reduces stay in the Python loop)")
@@ -360,7 +377,18 @@ def main():
     ap.add_argument("--no-focus", action="store_true", help="A/B: build the super-row copy for the whole map instead of the sensor's surroundings (lili_map_focus)")
     ap.add_argument("--reach", type=int, default=0, help="map grid reach (1 = cells of the gate radius, 2 = half-size cells); 0 = library default")
     ap.add_argument("--cell-pct", type=int, default=0, help="reach-2 cell edge in %% of the gate radius (50..100); 0 = library default")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: roofline replay, CPU baseline and pose parity, headline regions, inner "
+                         "iteration, extras (other configs, stages, window modes), multi-GPU self-checks.  Without it a run only sets up, warms up, "
+                         "times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (pose, last GN step, the surf correspondences of its "
+                         "association) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.config != 2 or args.window or args.assoc_only or os.environ.get("LILI_PHASES")):
+        ap.error("--dump-outputs covers the headline workload only (--config 2, no --window / --assoc-only / LILI_PHASES)")
     if args.no_native_rccl:
         args.collective = "torch"
 
@@ -664,11 +692,13 @@ def main():
     if rank == 0:
         log(f"[bench] host enqueue {t_enqueue / args.steps * 1e6:.1f} us/step, wall {elapsed / args.steps * 1e6:.1f} us/step")
     t_fin, q_fin, gn_status = m.pose_get(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m, queries.shape[0])
     # Pose-parity registration: ONE registration of `ips` outer iterations from the EXPLICIT start pose (t0, q0) — written
     # into slot 0 here, never read from a slot a later helper could have touched — taken right after the timed region, before any secondary
     # measurement runs.  Compared with the oracle's registration from the same start once cpu_baseline() has produced it.
     reg_pose = None
-    if world == 1 and dist is None:
+    if world == 1 and dist is None and args.full:
         m.pose_set(0, t0, q0)
         m.iterate(0, ips, L.MASK_SURF)
         t_reg, q_reg, st_reg = m.pose_get(0)
@@ -677,7 +707,7 @@ def main():
     # Run-to-run spread of the headline (a 20-step region is two registrations): five more regions of >= 200 steps each, same
     # schedule; `value` stays the K-step region the contract asks for, the regions go to extras.headline_regions.
     regions = None
-    if world == 1 and dist is None and not args.no_extras:
+    if args.full and world == 1 and dist is None and not args.no_extras:
         n_reg = max(200, args.steps)
         regs = sorted(n_reg / timed(0, n_reg)[0] for _ in range(5))
         regions = {"steps_per_region": n_reg, "iterations_per_s": [round(r, 1) for r in regs], "median": round(regs[2], 1),
@@ -689,7 +719,7 @@ def main():
 
     # ---------------- roofline of the dominant kernel (k_associate_surf), HIP events on its stream ----------------
     roofline = None
-    if rank == 0:
+    if args.full and rank == 0:
         # The poses the association kernel sees over the timed schedule (restart every `ips` steps) are logged first;
         # then exactly those launches are replayed back to back on the context's stream between ONE pair of HIP events,
         # so the per-launch figure carries no inter-kernel event overhead and is comparable with rocprofv3's average.
@@ -730,7 +760,7 @@ def main():
 
     # ---------------- secondary timed figures that need every rank (collective paths) ----------------
     weak_extra = None
-    if world > 1 and args.scaling == "strong":
+    if args.full and world > 1 and args.scaling == "strong":
         # the flattering variant, kept out of `value`: every rank matches its OWN 200k-point shard of an (N x 200k)-point scan
         qw = queries_for("weak")
         m.set_queries(0, L.KIND_SURF, qw)
@@ -744,7 +774,7 @@ def main():
     # Self-check: the ranks run the same deterministic code on the same data, so their final poses must be identical bit for bit (and equal to
     # the N = 1 run's final_pose for the same --steps / --warmup).
     replica_extra, replica_pose = None, None
-    if world > 1:
+    if args.full and world > 1:
         m.set_queries(0, L.KIND_SURF, scan)
         m.pose_set(1, t0, q0)
 
@@ -776,7 +806,7 @@ def main():
     # rank i, every iteration ONE exchange of the N x 72 doubles (an all-gather carried by the rank-order sum) and the Gauss-Newton update of every slot on every rank.
     # value = N slot-iterations per window iteration / max-over-ranks time.  Self-check: all ranks hold bit-identical poses for all slots.
     gather_extra = None
-    if world > 1 and world <= 8 and native is not None:
+    if args.full and world > 1 and world <= 8 and native is not None:
         try:
             from lili_om_amd import sharding
             owner = sharding.window_owners(world, world)
@@ -818,7 +848,7 @@ def main():
     # Multi-GPU self-check: every rank must hold the SAME final pose, bit for bit (strong split: one scan, all ranks apply the same
     # update to the same reduced record).  all-reduce MIN and MAX of the pose bit patterns: equal <=> identical on every rank.
     multi = None
-    if dist is not None and args.scaling == "strong":
+    if args.full and dist is not None and args.scaling == "strong":
         bits = torch.from_numpy(np.concatenate([np.asarray(t_fin, np.float64), np.asarray(q_fin, np.float64)]).view(np.int64).copy()).to(dev)
         lo, hi = bits.clone(), bits.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
@@ -865,7 +895,7 @@ def main():
         extras = dict(weak_extra or {})
         extras.update(replica_extra or {})
         extras.update(gather_extra or {})
-        if world > 1:      # which mode a SCALE record's `value` has to be read against
+        if args.full and world > 1:      # which mode a SCALE record's `value` has to be read against
             extras["scaling_modes_note"] = ("`value` is the " + ("STRONG split of ONE 200k-pt scan over the ranks (configs[3]): per-rank work shrinks with N while three dependent "
                                             "kernel chains per iteration do not, so ~1.1-1.2x at 8 GPUs is the expected ceiling (DESIGN §5)" if args.scaling == "strong" else
                                             "weak split (one 200k-pt shard per rank)") + "; the modes that scale by construction are printed beside it: replicas_iterations_per_s "
@@ -875,7 +905,7 @@ def main():
             failures.append(f"window_gather {gather_extra}")
         if regions:
             extras["headline_regions"] = regions
-        if world == 1 and dist is None:
+        if args.full and world == 1 and dist is None:
             # ---- the reference back-end's INNER iteration ("report it separately, never mix the two"): fixed correspondences,
             # linearise (residual + Jacobian + Cauchy corrector + cost) + reduce + 6x6 solve + pose update = ONE launch each
             try:
@@ -902,7 +932,7 @@ def main():
                                           "hbm_frac": round(41 * queries.shape[0] / (us_in * 1e-6) / 1e9 / HBM_PEAK_GBS, 5)}
             except Exception as e:      # noqa: BLE001
                 out["inner_iteration"] = {"error": repr(e)}
-        if world == 1 and dist is None and not args.no_extras:
+        if args.full and world == 1 and dist is None and not args.no_extras:
             # Secondary measurements (NOT the headline).  Every block runs in ITS OWN lili context (pose slots, options, map focus and map
             # indices are per context): nothing here can touch the headline context `ctx` / matcher `m` (VERDICT r3 #1 — the shared
             # context let three helpers overwrite pose slot 1, which the parity check then started from).
@@ -1048,7 +1078,7 @@ def main():
             extras["configs"] = cfgs
         if extras:
             out["extras"] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, t_cpu, q_cpu = cpu_baseline(w, queries, t0, q0)
             out["cpu_baseline"] = cb
             out["gpu_over_cpu"] = round(value / cb["value"], 1)

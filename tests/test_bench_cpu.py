@@ -29,3 +29,14 @@ def test_secondary_measurements_never_get_the_headline_context():
     assert extras.count("cx = own_ctx()") >= 6 and extras.count("cx.close()") >= 6
     # the parity registration starts from the explicit pose, right after the timed region, and a failure is fatal
     assert "m.pose_set(0, t0, q0)\n        m.iterate(0, ips, L.MASK_SURF)" in src and "sys.exit(exit_code)" in src and "exit_code = 3 if failures else 0" in src
+
+
+def test_bench_options_parse_without_a_gpu():
+    """--full and --dump-outputs exist; --steps below 1 and a dump outside the headline workload are refused before any device work."""
+    import subprocess
+    bench = os.path.join(ROOT, "bench.py")
+    h = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True, timeout=120)
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs" in h.stdout
+    for bad in (["--steps", "0"], ["--config", "1", "--dump-outputs", "unused"]):
+        r = subprocess.run([sys.executable, bench] + bad, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "error" in r.stderr, (bad, r.stderr)

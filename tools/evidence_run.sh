@@ -10,8 +10,8 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT tools/_probe
 grep -E "passed|failed" $OUT/pytest_all.log | tail -2
 bash tools/make_profiles.sh $TAG > $OUT/profile_summary.txt 2>&1
 tail -24 $OUT/profile_summary.txt
-( time timeout 900 python bench.py ) > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"
-( time timeout 600 python bench.py --steps 20 --warmup 5 ) > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err; echo "bench (driver command) rc $?"
+( time timeout 900 python bench.py --full ) > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"
+( time timeout 600 python bench.py --steps 20 --warmup 5 --full ) > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err; echo "bench (driver command) rc $?"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o frame -- python bench.py --config 1 --no-cpu-baseline > $OUT/frame_bench.json 2> $OUT/frame.err
 echo "== front-end frame pipeline (configs[1])"; python tools/kstats.py $OUT/frame_kernel_stats.csv | head -16
 for cfg in "2000 0" "25000 0"; do
