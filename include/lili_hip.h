@@ -258,8 +258,17 @@ int lili_voxel_filter(lili_ctx* ctx, const lili_cloud* cloud, float leaf, lili_f
 int lili_localmap_reset(lili_ctx* ctx, int kind);
 int lili_localmap_push(lili_ctx* ctx, int kind, const lili_cloud* features, const double t[3], const double q[4], int width);
 int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radius, int64_t* n_raw, int64_t* n_map);
+/* The ring's keyframes (oldest first, n = ring size of every kind in kind_mask) take new map-frame poses (t: 3n, q: 4n, wxyz) —
+ * buildLocalMapWithLandMark's warm-up branch (L/src/BackendFusion.cpp:1407-1443): transformCloud is re-run from the LiDAR-frame points the
+ * ring keeps.  Asynchronous; the next lili_localmap_commit / lili_backend_keyframe_prepare builds the map from the new poses.  Only keyframes
+ * whose pose is not bit-equal to the stored one (or was read on the device: lili_frontend_frame) are re-transformed; a repose that changes
+ * nothing enqueues nothing.  After a change confined to the newest keyframes (at most 8 from the oldest changed one to the end, pending pushes
+ * included) the next commit is one merge step on the sorted ring (counted as incremental); otherwise it rebuilds.  The map is the same bit for
+ * bit as after lili_localmap_reset and pushes at the new poses.  LILI_E_ARG (ring untouched): empty or unknown mask, null pointer, n differing
+ * from the size of a ring in the mask. */
+int lili_localmap_repose(lili_ctx* ctx, int kind_mask, int n, const double* t, const double* q);
 /* How the commits of this context were served: steps on the ring kept sorted by voxel (one keyframe popped / pushed since the last commit, the
- * reference's steady state, L/src/BackendFusion.cpp:1407-1477) against full rebuilds (first commit, several keyframes pending, another leaf).
+ * reference's steady state, L/src/BackendFusion.cpp:1407-1477, or a re-posed suffix merged back, lili_localmap_repose) against full rebuilds (first commit, several keyframes pending, another leaf).
  * The map is the same bit for bit either way (option "localmap_incremental" = 0 forces rebuilds). */
 int lili_localmap_stats(lili_ctx* ctx, int32_t* incremental_commits, int32_t* full_commits);
 /* How the VoxelGrid filters of more than 8192 points (lili_voxel_filter, lili_localmap_commit's rebuild, lili_frontend_frame's query filter) were served: a filter
@@ -334,7 +343,7 @@ int lili_frontend_flush(lili_ctx* ctx, const lili_s2m_params* match, const lili_
 /* Replaces, for one keyframe of the reference's back end (L/src/BackendFusion.cpp:830-980):
  *   buildLocalMapWithLandMark (L:1387-1484, steady state :1444-1476) — the keyframe whose pose the previous solve fixed (`join_*`, its LiDAR pose in the map frame
  *       t_join / q_join = q_po * q_bl, q_po * t_bl + t_po; NULL: nothing joins, e.g. the first call) is transformed and appended to both rings, the oldest leaves
- *       beyond opt->width;
+ *       beyond opt->width (warm-up, the rings shorter than opt->width, L:1407-1443: lili_localmap_repose of both rings at the solve's poses comes first);
  *   downSampleCloud (L:1486-1519) — both rings -> VoxelGrid(leaf_*_map) -> kd_tree_*_local_map->setInputCloud (L:839-840); the NEW keyframe's features
  *       (`new_surf`, `new_edge`, LiDAR frame) -> VoxelGrid(leaf_surf / leaf_edge) = surf_lasts_ds / edge_lasts_ds -> the queries of slots[n_slots - 1];
  *   findCorrespondingCornerFeatures / findCorrespondingSurfFeatures (L:919-936) — every keyframe of the window (slots[i], oldest first; the older slots keep the

@@ -161,6 +161,7 @@ _SIGS = {
     "lili_localmap_commit": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "lili_localmap_get": (C.c_int, [C.c_void_p, C.POINTER(FeatureOut)]),
     "lili_localmap_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "lili_localmap_repose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "lili_voxel_filter_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lili_map_set": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Cloud), C.c_double]),
     "lili_map_density": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -692,6 +693,19 @@ class LocalMap:
         self.ctx._chk(self.ctx.lib.lili_localmap_commit(self.ctx.h, self.kind, self.leaf, self.max_sq_radius, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def repose(self, ts, qs):
+        """The ring's keyframes (oldest first) take new map-frame poses (buildLocalMapWithLandMark's warm-up branch, L/src/BackendFusion.cpp:1407-1443);
+        ts: (n, 3), qs: (n, 4) wxyz, n = ring size (keyframe_map_poses turns body poses into these).  Asynchronous; the next commit uses them."""
+        _repose(self.ctx, 1 << self.kind, ts, qs)
+
+
+def _repose(ctx, kind_mask, ts, qs):
+    t = np.ascontiguousarray(np.asarray(ts, np.float64).reshape(-1, 3))
+    q = np.ascontiguousarray(np.asarray(qs, np.float64).reshape(-1, 4))
+    if t.shape[0] != q.shape[0]:
+        raise ValueError("repose: as many translations as rotations")
+    ctx._chk(ctx.lib.lili_localmap_repose(ctx.h, int(kind_mask), t.shape[0], _ptr(t), _ptr(q)))
+
 
 class RotExtractor:
     """Host-side mirror of LiLi-OM-ROT's Preprocessing::cloudHandler (R/src/Preprocessing.cpp:248-535)."""
@@ -935,6 +949,11 @@ class BackendKeyframes:
             info["stage_us"] = [r.stage_us[j] for j in range(3)]
         return [(int(counts[k, 0]), int(counts[k, 1])) for k in range(n)], info
 
+    def repose(self, ts, qs):
+        """Warm-up of the local map (while the reference's recent_surf_keyframes.size() < local_map_width, L/src/BackendFusion.cpp:1407-1443): the keyframes of both
+        rings, oldest first, take the map-frame poses (keyframe_map_poses) the last solve gave them — before the next prepare, which pushes the joining keyframe at its own."""
+        _repose(self.ctx, MASK_SURF | MASK_EDGE, ts, qs)
+
 
 def gn_step_host(gram, t, q):
     lib = load_library()
@@ -988,6 +1007,13 @@ def keyframe_map_pose(t_po, q_po, t_bl, q_bl):
     uv = np.cross(u, v)
     uv = uv + uv
     return (v + uv * a[0]) + np.cross(u, uv) + np.asarray(t_po, np.float64), q
+
+
+def keyframe_map_poses(ts_po, qs_po, t_bl, q_bl):
+    """keyframe_map_pose of every keyframe of a ring (body poses (n, 3) / (n, 4) wxyz, oldest first): the (n, 3), (n, 4) arrays LocalMap.repose and
+    BackendKeyframes.repose take — Ttmp of the warm-up branch, L/src/BackendFusion.cpp:1413-1436."""
+    out = [keyframe_map_pose(t, q, t_bl, q_bl) for t, q in zip(np.asarray(ts_po, np.float64).reshape(-1, 3), np.asarray(qs_po, np.float64).reshape(-1, 4))]
+    return np.array([o[0] for o in out]).reshape(-1, 3), np.array([o[1] for o in out]).reshape(-1, 4)
 
 
 def body_pose_from_lidar(t_lidar, q_lidar, params):

@@ -630,6 +630,38 @@ __global__ void k_merge(const unsigned long long* __restrict__ key, const float4
         merge_old_item(key, pt, seq, keep, rank, i, nkey, n_new, okey, opt, oseq);
     } else if (i < n + n_new) merge_new_item(nkey, npt, (int)(i - n), nseq, key, rank, n, okey, opt, oseq);
 }
+
+// ---- the commit after lili_localmap_repose: the re-posed suffix of the ring and the pending pushes are merged in as ONE list (several keyframes, a sequence number
+// per entry).  The ring's sequence numbers rise in ring order, so the entries that stay are exactly those of ONE range [keep_lo, keep_hi] of sequence numbers: the
+// popped keyframes lie below it, the re-posed ones (renumbered) above — no limit on the number of keyframes dropped.
+__global__ void k_keep_range_flags(const unsigned* __restrict__ seq, long long n, unsigned keep_lo, unsigned keep_hi, int* __restrict__ flags) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned q = seq[i];
+    flags[i] = (q >= keep_lo && q <= keep_hi) ? 1 : 0;
+}
+// k_rank_scatter for the concatenation of several keyframes: the sequence number of an entry is its keyframe's, found by bisection over the segments (k_sorted_gather)
+__global__ void k_rank_scatter_segs(const float4* __restrict__ pts, int n, float inv_leaf, const lili_detail::ConcatSeg* __restrict__ segs, const unsigned* __restrict__ seg_seq, int n_seg,
+                                    const int* __restrict__ rank, float4* __restrict__ out_pt, unsigned long long* __restrict__ out_key, unsigned* __restrict__ out_seq) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first <= (long long)e) lo = mid; else hi = mid - 1; }
+    const float4 p = pts[e];
+    const int r = rank[e];
+    out_pt[r] = p; out_key[r] = abs_voxel_key(p, inv_leaf); out_seq[r] = seg_seq[lo];
+}
+// k_merge with the keep rule of the range and a sequence number per new entry (all of them newer than every kept entry: new after old inside a voxel stays the rule)
+__global__ void k_merge_seqs(const unsigned long long* __restrict__ key, const float4* __restrict__ pt, const unsigned* __restrict__ seq, const int* __restrict__ flags, unsigned keep_lo,
+                             unsigned keep_hi, const int* __restrict__ rank, long long n, const unsigned long long* __restrict__ nkey, const float4* __restrict__ npt,
+                             const unsigned* __restrict__ nseq, int n_new, unsigned long long* __restrict__ okey, float4* __restrict__ opt, unsigned* __restrict__ oseq) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const unsigned q = seq[i];
+        const bool keep = flags ? flags[i] != 0 : (q >= keep_lo && q <= keep_hi);
+        merge_old_item(key, pt, seq, keep, rank, i, nkey, n_new, okey, opt, oseq);
+    } else if (i < n + n_new) { const int j = (int)(i - n); merge_new_item(nkey, npt, j, nseq[j], key, rank, n, okey, opt, oseq); }
+}
 __global__ void k_vox_heads64(const unsigned long long* __restrict__ keys, long long n, int* __restrict__ flags) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) flags[i] = (keys[i] < ~0ull - 1ull && (i == 0 || keys[i] != keys[i - 1])) ? 1 : 0;
@@ -693,31 +725,53 @@ __global__ void k_vox_centroid64(const unsigned long long* __restrict__ keys, co
     }
 }
 
-// transformCloud — L/src/BackendFusion.cpp:713-790: p' = q * p + t in f64, stored f32; aux carried along
-__global__ void k_transform_cloud(const float4* __restrict__ in, int n, dq q, d3 t, float4* __restrict__ out) {
+// transformCloud — L/src/BackendFusion.cpp:713-790: p' = q * p + t in f64, stored f32; aux carried along.  The ONE expression of every kernel that places a keyframe
+// in the map frame (push, push at a device pose, repose): a re-posed keyframe is bit-identical to one pushed at that pose.
+__device__ __forceinline__ float4 transform_point(float4 p, dq q, d3 t) {
+    const d3 r = qrot(q, d3{(double)p.x, (double)p.y, (double)p.z}) + t;
+    return make_float4((float)r.x, (float)r.y, (float)r.z, p.w);
+}
+// `src`: the rows as pushed (LiDAR frame), kept by the ring for lili_localmap_repose
+__global__ void k_transform_cloud(const float4* __restrict__ in, int n, dq q, d3 t, float4* __restrict__ out, float4* __restrict__ src) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float4 p = in[i];
-    d3 r = qrot(q, d3{(double)p.x, (double)p.y, (double)p.z}) + t;
-    out[i] = make_float4((float)r.x, (float)r.y, (float)r.z, p.w);
+    out[i] = transform_point(p, q, t);
+    src[i] = p;
 }
 
 // the same with the pose read from a slot's device state (lili_frontend_frame: the keyframe is pushed at the pose the matcher has just reached, before the
 // host has seen it) — same expression, same operands
-__global__ void k_transform_cloud_state(const float4* __restrict__ in, int n, const SlotState* __restrict__ st, float4* __restrict__ out) {
+__global__ void k_transform_cloud_state(const float4* __restrict__ in, int n, const SlotState* __restrict__ st, float4* __restrict__ out, float4* __restrict__ src) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const dq q{st->pose[3], st->pose[4], st->pose[5], st->pose[6]};
     const d3 t{st->pose[0], st->pose[1], st->pose[2]};
     float4 p = in[i];
-    d3 r = qrot(q, d3{(double)p.x, (double)p.y, (double)p.z}) + t;
-    out[i] = make_float4((float)r.x, (float)r.y, (float)r.z, p.w);
+    out[i] = transform_point(p, q, t);
+    src[i] = p;
+}
+
+// lili_localmap_repose: the changed keyframes of both rings re-transformed from their LiDAR-frame rows in ONE launch; thread i finds its keyframe by bisection over the
+// (ascending) first positions of the segment table, as k_concat does
+struct ReposeSeg { const float4* src; float4* dst; long long first; double t[3], q[4]; };
+__global__ void k_ring_repose(const ReposeSeg* __restrict__ segs, int n_seg, long long total) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first <= i) lo = mid; else hi = mid - 1; }
+    const ReposeSeg& s = segs[lo];
+    const long long j = i - s.first;
+    s.dst[j] = transform_point(s.src[j], dq{s.q[0], s.q[1], s.q[2], s.q[3]}, d3{s.t[0], s.t[1], s.t[2]});
 }
 
 }  // namespace lili
 
 namespace lili_detail {
-struct Keyframe { DevBuf pts; int n = 0; unsigned seq = 0; };
+// `src`: the rows as pushed (LiDAR frame) — lili_localmap_repose re-runs transformCloud from them —, in the same allocation as the map-frame rows, behind them (one
+// allocation per keyframe, as before it kept them: a hipMalloc / hipFree is a device-wide synchronisation); `t` / `q`: the pose `pts` was placed at, unknown
+// (pose_known false) for a push at a pose read on the device (lili_localmap_push_dev)
+struct Keyframe { DevBuf pts; float4* src = nullptr; int n = 0; unsigned seq = 0; double t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0}; bool pose_known = false; void release() { pts.release(); src = nullptr; } };
 // the ring of one kind, sorted by absolute voxel key (older keyframes first inside a voxel): see k_merge_old / k_merge_new
 struct SortedRing {
     DevBuf key[2], pt[2], seq[2];
@@ -736,6 +790,11 @@ struct VoxelBuffers {
     unsigned next_seq = 1;
     DevBuf head_pos;
     DevBuf kf_key, kf_pt, seg_seq;     // the new keyframe sorted by key; sequence numbers of the concatenation's segments
+    DevBuf kf_seq;                     // the commit after a repose: the sequence number of every new entry (several keyframes merged in at once)
+    // lili_localmap_repose's segment table: page-locked staging owned by the context (never an async copy from a host vector that goes out of scope), reused
+    // once the copy recorded by `repose_ev` has run; the device copy in repose_tab
+    void* repose_pin = nullptr; size_t repose_pin_cap = 0; hipEvent_t repose_ev = nullptr; bool repose_ev_armed = false;
+    DevBuf repose_tab;
     std::vector<unsigned> seg_seq_host;
     int incremental_commits = 0, full_commits = 0;
     std::vector<ConcatSeg> seg_host;   // the table k_concat reads, kept alive until the upload has certainly happened (an async copy from a local vector)
@@ -752,11 +811,13 @@ struct VoxelBuffers {
     unsigned out_box[6] = {0, 0, 0, 0, 0, 0};   // bounding box of `out` (ordered-uint words, k_bbox_dev) after an incremental commit
     void release() {
         for (DevBuf* b : {&keys_a, &keys_b, &vals_a, &vals_b, &hist, &hist_scan, &sums, &flags, &slots, &out, &out_cnt, &in, &concat, &concat_tab}) b->release();
-        for (auto& r : ring) { for (auto* k : r) { k->pts.release(); delete k; } r.clear(); }
-        for (auto* k : pool) { k->pts.release(); delete k; }
+        for (auto& r : ring) { for (auto* k : r) { k->release(); delete k; } r.clear(); }
+        for (auto* k : pool) { k->release(); delete k; }
         pool.clear();
         for (auto& sr : sorted) sr.release();
-        kf_key.release(); kf_pt.release(); seg_seq.release(); head_pos.release(); spts.release(); qout.release(); qout_cnt.release();
+        kf_key.release(); kf_pt.release(); seg_seq.release(); kf_seq.release(); head_pos.release(); spts.release(); qout.release(); qout_cnt.release(); repose_tab.release();
+        if (repose_ev) { (void)hipEventSynchronize(repose_ev); (void)hipEventDestroy(repose_ev); repose_ev = nullptr; }
+        if (repose_pin) { (void)hipHostFree(repose_pin); repose_pin = nullptr; repose_pin_cap = 0; }
     }
 };
 }  // namespace lili_detail
@@ -833,14 +894,16 @@ __global__ __launch_bounds__(256) void k_scan_tiles(const int* __restrict__ in, 
 //   kScanHead64 : item i starts a voxel of the sorted ring (64-bit absolute keys); head_pos[its slot] = i on the way      — was k_vox_heads64 + scan + k_vox_head_pos
 //   kScanHead32 : item i starts a voxel of a sorted cloud (32-bit keys, `sentinel` = no voxel); spts[i] = pts[vals[i]]     — was k_vox_heads + scan
 // Same tiles, same sums; the items in front of a tile are re-derived from the keys (the same bytes the flags would have been, twice for 64-bit keys).
-enum { kScanKeep = 1, kScanHead64 = 2, kScanHead32 = 3 };
-struct ScanFlagArgs { const void* a; DropSeqs drop; unsigned sentinel; const int* vals; const float4* pts; float4* spts; int* head_pos; };
+//   kScanKeepRange : item i of the sorted ring survives the merge after a repose (its sequence number lies in [keep_lo, keep_hi]) — was k_keep_range_flags + scan
+enum { kScanKeep = 1, kScanHead64 = 2, kScanHead32 = 3, kScanKeepRange = 4 };
+constexpr bool scan_keep_mode(int m) { return m == kScanKeep || m == kScanKeepRange; }
+struct ScanFlagArgs { const void* a; DropSeqs drop; unsigned sentinel; const int* vals; const float4* pts; float4* spts; int* head_pos; unsigned keep_lo, keep_hi; };
 // the raw words behind four consecutive flags (two steps, so that a caller can request several groups before it looks at any: a load behind a branch, or mixed with
 // the arithmetic of the previous group, waits for its own round trip)
 struct ScanRaw { uint4 a, b; unsigned long long prev; };
 template <int MODE> __device__ __forceinline__ ScanRaw scan_flags_load(const ScanFlagArgs& A, int i /*multiple of 4*/) {
     ScanRaw r{};
-    if (MODE == kScanKeep) r.a = *reinterpret_cast<const uint4*>(static_cast<const unsigned*>(A.a) + i);
+    if (scan_keep_mode(MODE)) r.a = *reinterpret_cast<const uint4*>(static_cast<const unsigned*>(A.a) + i);
     else if (MODE == kScanHead64) {
         const unsigned long long* key = static_cast<const unsigned long long*>(A.a);
         r.a = *reinterpret_cast<const uint4*>(key + i); r.b = *reinterpret_cast<const uint4*>(key + i + 2); r.prev = key[max(i - 1, 0)];
@@ -861,6 +924,10 @@ template <int MODE> __device__ __forceinline__ void scan_flags_eval(const ScanFl
             for (int d = 0; d < 4; d++) drop = drop || (d < A.drop.n && s[k] == A.drop.s[d]);
             v[k] = (i + k < n && !drop) ? 1 : 0;
         }
+    } else if (MODE == kScanKeepRange) {
+        const unsigned s[4] = {r.a.x, r.a.y, r.a.z, r.a.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = (i + k < n && s[k] >= A.keep_lo && s[k] <= A.keep_hi) ? 1 : 0;
     } else if (MODE == kScanHead64) {
         const unsigned long long kk[5] = {r.prev, ((unsigned long long)r.a.y << 32) | r.a.x, ((unsigned long long)r.a.w << 32) | r.a.z, ((unsigned long long)r.b.y << 32) | r.b.x,
                                           ((unsigned long long)r.b.w << 32) | r.b.z};
@@ -915,8 +982,8 @@ template <int MODE> __global__ __launch_bounds__(kScanFlagThreads) void k_scan_f
     int s8 = 0, inc = 0;
     if (wave < 4) {
         unsigned e0m = 0, e1m = 0;
-        scan_flags_eval<MODE>(A, r0, i0, n, v, MODE == kScanKeep ? nullptr : &e0m);
-        scan_flags_eval<MODE>(A, r1, i0 + 4, n, v + 4, MODE == kScanKeep ? nullptr : &e1m);
+        scan_flags_eval<MODE>(A, r0, i0, n, v, scan_keep_mode(MODE) ? nullptr : &e0m);
+        scan_flags_eval<MODE>(A, r1, i0 + 4, n, v + 4, scan_keep_mode(MODE) ? nullptr : &e1m);
         endm = e0m | (e1m << 4);
         if (MODE == kScanHead32) {
             const float4* __restrict__ gp = A.pts;
@@ -950,7 +1017,7 @@ template <int MODE> __global__ __launch_bounds__(kScanFlagThreads) void k_scan_f
 #pragma unroll
         for (int k = 0; k < 8; k++) if (i0 + k < n) out[i0 + k] = e0 + v[k];
     }
-    if (MODE != kScanKeep && A.head_pos) {      // (wave-uniform) compacted head positions, closed by the position where the voxels end: head_pos[number of voxels]
+    if (!scan_keep_mode(MODE) && A.head_pos) {      // (wave-uniform) compacted head positions, closed by the position where the voxels end: head_pos[number of voxels]
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             if (flag[k]) A.head_pos[e0 + v[k]] = i0 + k;
@@ -959,7 +1026,7 @@ template <int MODE> __global__ __launch_bounds__(kScanFlagThreads) void k_scan_f
     }
     if (blockIdx.x == gridDim.x - 1 && tid == 0) {
         out[n] = front_total + tile_total;
-        if (MODE != kScanKeep && A.head_pos) {      // no item that is no voxel: the voxels end at n
+        if (!scan_keep_mode(MODE) && A.head_pos) {      // no item that is no voxel: the voxels end at n
             bool none;
             if (MODE == kScanHead64) none = static_cast<const unsigned long long*>(A.a)[n - 1] < ~0ull - 1ull;
             else none = static_cast<const unsigned*>(A.a)[n - 1] != A.sentinel;
@@ -1209,7 +1276,7 @@ int lili_localmap_reset(lili_ctx* ctx, int kind) {
     ARGCHK(kind == 0 || kind == 1, "localmap_reset: bad kind");
     auto* V = vox_of(ctx);
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (auto* k : V->ring[kind]) { k->pts.release(); delete k; }
+    for (auto* k : V->ring[kind]) { k->release(); delete k; }
     V->ring[kind].clear();
     V->sorted[kind].valid = false; V->sorted[kind].n = 0; V->sorted[kind].members.clear();
     return LILI_OK;
@@ -1220,16 +1287,19 @@ static int localmap_push_f4(lili_ctx* ctx, int kind, const float4* d_in, int n, 
     auto* V = vox_of(ctx);
     // a buffer from the pool of popped keyframes if one is large enough (the steady state: keyframes of similar size), else a new one
     lili_detail::Keyframe* kf = nullptr;
-    for (size_t i = 0; i < V->pool.size(); i++) if (V->pool[i]->pts.cap >= (size_t)n * 16) { kf = V->pool[i]; V->pool.erase(V->pool.begin() + (long)i); break; }
+    for (size_t i = 0; i < V->pool.size(); i++) if (V->pool[i]->pts.cap >= (size_t)n * 32) { kf = V->pool[i]; V->pool.erase(V->pool.begin() + (long)i); break; }
     if (!kf) kf = new lili_detail::Keyframe();
     kf->n = n;
     kf->seq = V->next_seq++;
+    kf->pose_known = !d_state;
+    if (!d_state) { std::memcpy(kf->t, t, sizeof(kf->t)); std::memcpy(kf->q, q, sizeof(kf->q)); }
     if (kf->n > 0) {
-        hipError_t e = kf->pts.ensure((size_t)kf->n * 16);
+        hipError_t e = kf->pts.ensure((size_t)kf->n * 32);      // map-frame rows, then the rows as pushed
         if (e != hipSuccess) { delete kf; return ctx->fail(LILI_E_HIP, "localmap_push: allocation failed"); }
-        if (d_state) hipLaunchKernelGGL(k_transform_cloud_state, dim3(nblocks(kf->n, 256)), dim3(256), 0, ctx->stream, d_in, kf->n, d_state, kf->pts.as<float4>());
+        kf->src = kf->pts.as<float4>() + kf->n;
+        if (d_state) hipLaunchKernelGGL(k_transform_cloud_state, dim3(nblocks(kf->n, 256)), dim3(256), 0, ctx->stream, d_in, kf->n, d_state, kf->pts.as<float4>(), kf->src);
         else hipLaunchKernelGGL(k_transform_cloud, dim3(nblocks(kf->n, 256)), dim3(256), 0, ctx->stream, d_in, kf->n,
-                                dq{q[0], q[1], q[2], q[3]}, d3{t[0], t[1], t[2]}, kf->pts.as<float4>());
+                                dq{q[0], q[1], q[2], q[3]}, d3{t[0], t[1], t[2]}, kf->pts.as<float4>(), kf->src);
         hipError_t le = hipGetLastError();
         if (le != hipSuccess) { delete kf; return ctx->fail(LILI_E_HIP, std::string("localmap_push: ") + hipGetErrorString(le)); }
     }
@@ -1239,7 +1309,7 @@ static int localmap_push_f4(lili_ctx* ctx, int kind, const float4* d_in, int n, 
         auto* old = V->ring[kind].front();
         V->ring[kind].erase(V->ring[kind].begin());
         if (V->pool.size() < 4) V->pool.push_back(old);
-        else { HIPCHK(hipStreamSynchronize(ctx->stream)); old->pts.release(); delete old; }
+        else { HIPCHK(hipStreamSynchronize(ctx->stream)); old->release(); delete old; }
     }
     return LILI_OK;
 }
@@ -1252,6 +1322,66 @@ int lili_localmap_push(lili_ctx* ctx, int kind, const lili_cloud* features, cons
     int rc = lili_ingest_cloud(ctx, features, V->in);
     if (rc != LILI_OK) return rc;
     return localmap_push_f4(ctx, kind, V->in.as<float4>(), (int)features->n, t, q, nullptr, width);
+}
+
+// buildLocalMapWithLandMark's warm-up branch (L/src/BackendFusion.cpp:1407-1443): the ring's keyframes take the poses the sliding-window solve has just rewritten.
+// A keyframe whose pose is bit-equal to the stored one (and known) keeps its points; the others are re-transformed from their LiDAR-frame rows, both kinds in ONE
+// launch.  The suffix of the ring from the oldest changed keyframe on is renumbered in ring order, so that the next commit merges it back in one step.
+int lili_localmap_repose(lili_ctx* ctx, int kind_mask, int n, const double* t, const double* q) {
+    if (!ctx) return LILI_E_ARG;
+    const int all = LILI_MASK_SURF | LILI_MASK_EDGE;
+    ARGCHK((kind_mask & all) != 0 && (kind_mask & ~all) == 0 && t && q && n >= 0, "localmap_repose: bad argument");
+    auto* V = vox_of(ctx);
+    for (int kind = 0; kind < 2; kind++) ARGCHK(!(kind_mask & (1 << kind)) || (int)V->ring[kind].size() == n, "localmap_repose: n differs from the ring size");
+    HIPCHK(hipSetDevice(ctx->device));
+    // the plan: per kind, the first changed keyframe and the segments to re-transform (nothing changes on the host before the launch is enqueued)
+    std::vector<ReposeSeg> segs;
+    size_t first[2] = {(size_t)n, (size_t)n};
+    std::vector<char> changed[2];
+    long long total = 0;
+    for (int kind = 0; kind < 2; kind++) {
+        if (!(kind_mask & (1 << kind))) continue;
+        const auto& ring = V->ring[kind];
+        changed[kind].assign((size_t)n, 0);
+        for (int j = 0; j < n; j++) {
+            const lili_detail::Keyframe* k = ring[(size_t)j];
+            const bool c = !k->pose_known || std::memcmp(k->t, t + 3 * j, sizeof(k->t)) != 0 || std::memcmp(k->q, q + 4 * j, sizeof(k->q)) != 0;
+            changed[kind][(size_t)j] = c;
+            if (c && first[kind] == (size_t)n) first[kind] = (size_t)j;
+            if (c && k->n > 0) {
+                ReposeSeg s{k->src, k->pts.as<float4>(), total, {t[3 * j], t[3 * j + 1], t[3 * j + 2]}, {q[4 * j], q[4 * j + 1], q[4 * j + 2], q[4 * j + 3]}};
+                segs.push_back(s);
+                total += k->n;
+            }
+        }
+    }
+    if (total > 0) {
+        const size_t bytes = segs.size() * sizeof(ReposeSeg);
+        if (V->repose_ev_armed) { HIPCHK(hipEventSynchronize(V->repose_ev)); V->repose_ev_armed = false; }      // (the previous table's copy has run long ago: no wait in practice)
+        if (!V->repose_ev) HIPCHK(hipEventCreateWithFlags(&V->repose_ev, hipEventDisableTiming));
+        if (V->repose_pin_cap < bytes) {
+            if (V->repose_pin) { HIPCHK(hipHostFree(V->repose_pin)); V->repose_pin = nullptr; V->repose_pin_cap = 0; }
+            HIPCHK(hipHostMalloc(&V->repose_pin, bytes * 2));
+            V->repose_pin_cap = bytes * 2;
+        }
+        std::memcpy(V->repose_pin, segs.data(), bytes);
+        HIPCHK(V->repose_tab.ensure(bytes));
+        HIPCHK(hipMemcpyAsync(V->repose_tab.p, V->repose_pin, bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipEventRecord(V->repose_ev, ctx->stream));
+        V->repose_ev_armed = true;
+        hipLaunchKernelGGL(k_ring_repose, dim3(nblocks(total, 256)), dim3(256), 0, ctx->stream, V->repose_tab.as<ReposeSeg>(), (int)segs.size(), total);
+        HIPCHK(hipGetLastError());
+    }
+    for (int kind = 0; kind < 2; kind++) {
+        if (!(kind_mask & (1 << kind))) continue;
+        auto& ring = V->ring[kind];
+        for (size_t j = first[kind]; j < (size_t)n; j++) {
+            lili_detail::Keyframe* k = ring[j];
+            k->seq = V->next_seq++;      // fresh numbers in ring order: above every entry the sorted ring keeps
+            if (changed[kind][j]) { std::memcpy(k->t, t + 3 * j, sizeof(k->t)); std::memcpy(k->q, q + 4 * j, sizeof(k->q)); k->pose_known = true; }
+        }
+    }
+    return LILI_OK;
 }
 
 // One keyframe step on the sorted ring: drop the entries of the keyframes in `drop`, merge the keyframe `add` (may be null) in.
@@ -1305,6 +1435,67 @@ static int sorted_ring_step(lili_ctx* ctx, lili_detail::VoxelBuffers* V, lili_de
     return LILI_OK;
 }
 
+// The commit after lili_localmap_repose as ONE merge step: the entries outside the sequence range [keep_lo, keep_hi] go (popped keyframes, the re-posed suffix under its
+// old numbers), the keyframes `add` (the re-posed suffix under fresh numbers, then the pending pushes: ring order) come in, concatenated and stably sorted by key as one
+// list — (key, ring position, point order), the order a full rebuild gives them — and merged behind the kept entries of their voxel.
+constexpr size_t kResuffixMaxAdd = 8;      // keyframes merged in at once; more (a long re-posed suffix, a loop closure) take the full rebuild
+static int sorted_ring_resuffix(lili_ctx* ctx, lili_detail::VoxelBuffers* V, lili_detail::SortedRing& S, unsigned keep_lo, unsigned keep_hi, long long n_drop,
+                                const std::vector<lili_detail::Keyframe*>& add, float leaf, unsigned* d_bad) {
+    std::vector<lili_detail::ConcatSeg>& segs = V->seg_host;      // members, not locals: hipMemcpyAsync may read them after this call
+    std::vector<unsigned>& sseq = V->seg_seq_host;
+    segs.clear(); sseq.clear();
+    long long n_new = 0;
+    for (auto* k : add) { if (k->n) { segs.push_back({k->pts.as<float4>(), n_new}); sseq.push_back(k->seq); } n_new += k->n; }
+    const float inv_leaf = 1.0f / leaf;
+    if (n_new > 0) {
+        HIPCHK(V->concat.ensure((size_t)n_new * 16)); HIPCHK(V->concat_tab.ensure(segs.size() * sizeof(lili_detail::ConcatSeg))); HIPCHK(V->seg_seq.ensure(sseq.size() * 4));
+        HIPCHK(V->kf_key.ensure((size_t)n_new * 8)); HIPCHK(V->kf_pt.ensure((size_t)n_new * 16)); HIPCHK(V->kf_seq.ensure((size_t)n_new * 4));
+        HIPCHK(hipMemcpyAsync(V->concat_tab.p, segs.data(), segs.size() * sizeof(lili_detail::ConcatSeg), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(V->seg_seq.p, sseq.data(), sseq.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        const auto* d_segs = V->concat_tab.as<lili_detail::ConcatSeg>();
+        hipLaunchKernelGGL(k_concat, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, d_segs, (int)segs.size(), n_new, V->concat.as<float4>());
+        const float4* cat = V->concat.as<float4>();
+        if (n_new <= kVoxSmallMax && ctx->voxel_small) {      // counting sort of the whole list (k_rank_count; the rank words were zeroed by the commit)
+            int* d_rank = reinterpret_cast<int*>(ctx->misc.as<char>() + kRankOff);
+            const int slices = nblocks(n_new, 64);
+            hipLaunchKernelGGL(k_rank_count, dim3(slices, nblocks(slices, kRankWaves)), dim3(64 * kRankWaves), 0, ctx->stream, cat, (int)n_new, inv_leaf, d_rank, d_bad);
+            hipLaunchKernelGGL(k_rank_scatter_segs, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, cat, (int)n_new, inv_leaf, d_segs, V->seg_seq.as<unsigned>(), (int)segs.size(),
+                               (const int*)d_rank, V->kf_pt.as<float4>(), V->kf_key.as<unsigned long long>(), V->kf_seq.as<unsigned>());
+        } else {      // the radix path of sorted_ring_step on the concatenation; the gather finds every entry's keyframe in the segment table
+            unsigned* d_mm = ctx->misc.as<unsigned>();
+            hipLaunchKernelGGL(k_box_init, dim3(1), dim3(64), 0, ctx->stream, d_mm);
+            hipLaunchKernelGGL(k_bbox, dim3(std::min(nblocks(n_new, kBlock), 512)), dim3(kBlock), 0, ctx->stream, cat, (int)n_new, d_mm);
+            HIPCHK(V->keys_a.ensure((size_t)n_new * 4)); HIPCHK(V->vals_a.ensure((size_t)n_new * 4));
+            hipLaunchKernelGGL(k_vox_key_packed, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, cat, (int)n_new, inv_leaf, (const unsigned*)d_mm, V->keys_a.as<unsigned>(),
+                               V->vals_a.as<int>(), d_bad);
+            const int rc = radix_sort(ctx, V, (int)n_new, 32);
+            if (rc != LILI_OK) return rc;
+            hipLaunchKernelGGL(k_sorted_gather, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, cat, V->vals_a.as<int>(), (int)n_new, inv_leaf, 0u, d_segs,
+                               V->seg_seq.as<unsigned>(), (int)segs.size(), V->kf_pt.as<float4>(), V->kf_key.as<unsigned long long>(), V->kf_seq.as<unsigned>(), d_bad);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    const long long n_old = S.n, n_out = n_old - n_drop + n_new;
+    const int dst = 1 - S.cur;
+    HIPCHK(S.key[dst].ensure((size_t)std::max<long long>(n_out, 1) * 8)); HIPCHK(S.pt[dst].ensure((size_t)std::max<long long>(n_out, 1) * 16)); HIPCHK(S.seq[dst].ensure((size_t)std::max<long long>(n_out, 1) * 4));
+    HIPCHK(V->flags.ensure((size_t)std::max<long long>(n_old, 1) * 4)); HIPCHK(V->slots.ensure(((size_t)n_old + 1) * 4));
+    const bool fused_flags = n_old <= kScanFlagsMax;
+    if (fused_flags) {
+        ScanFlagArgs A{}; A.a = S.seq[S.cur].p; A.keep_lo = keep_lo; A.keep_hi = keep_hi;
+        hipLaunchKernelGGL(k_scan_flags<kScanKeepRange>, dim3(nblocks(n_old, kScanTile)), dim3(kScanFlagThreads), 0, ctx->stream, A, (int)n_old, V->slots.as<int>());
+    } else {
+        hipLaunchKernelGGL(k_keep_range_flags, dim3(nblocks(n_old, 256)), dim3(256), 0, ctx->stream, S.seq[S.cur].as<unsigned>(), n_old, keep_lo, keep_hi, V->flags.as<int>());
+        const int rc = exclusive_scan(ctx, V, V->flags.as<int>(), n_old, V->slots.as<int>());
+        if (rc != LILI_OK) return rc;
+    }
+    hipLaunchKernelGGL(k_merge_seqs, dim3(nblocks(n_old + n_new, 256)), dim3(256), 0, ctx->stream, S.key[S.cur].as<unsigned long long>(), S.pt[S.cur].as<float4>(), S.seq[S.cur].as<unsigned>(),
+                       fused_flags ? (const int*)nullptr : (const int*)V->flags.as<int>(), keep_lo, keep_hi, (const int*)V->slots.as<int>(), n_old, V->kf_key.as<unsigned long long>(),
+                       V->kf_pt.as<float4>(), V->kf_seq.as<unsigned>(), (int)n_new, S.key[dst].as<unsigned long long>(), S.pt[dst].as<float4>(), S.seq[dst].as<unsigned>());
+    HIPCHK(hipGetLastError());
+    S.cur = dst; S.n = n_out;
+    return LILI_OK;
+}
+
 int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radius, int64_t* n_raw, int64_t* n_map) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK((kind == 0 || kind == 1) && leaf > 0, "localmap_commit: bad argument");
@@ -1320,9 +1511,24 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
     bool inc = ctx->localmap_incremental && S.valid && S.leaf == leaf && S.n > 0 && !ring.empty() && total < (1ull << 31);
     DropSeqs drop{}; long long n_drop = 0;
     std::vector<lili_detail::Keyframe*> add;
+    bool resuffix = false;      // lili_localmap_repose renumbered a suffix of the ring: one merge step of several keyframes (sorted_ring_resuffix)
+    unsigned keep_lo = 0, keep_hi = 0;
     if (inc) {
-        size_t f = 0;
+        size_t f = 0, m = 0;
         while (f < S.members.size() && S.members[f].first != ring.front()->seq) f++;
+        if (f < S.members.size()) while (f + m < S.members.size() && m < ring.size() && S.members[f + m].first == ring[m]->seq) m++;
+        if (f < S.members.size() && f + m < S.members.size()) {
+            // members behind the kept ones that the ring no longer holds under their numbers: a re-posed suffix (its fresh numbers are above every member's)
+            if (m < ring.size() && ring[m]->seq > S.members.back().first && ring.size() - m <= kResuffixMaxAdd) {
+                resuffix = true;
+                keep_lo = S.members[f].first; keep_hi = S.members[f + m - 1].first;
+                for (size_t i = 0; i < S.members.size(); i++) if (i < f || i >= f + m) n_drop += S.members[i].second;
+                for (size_t i = m; i < ring.size(); i++) add.push_back(ring[i]);
+                long long n_add = 0;
+                for (auto* k : add) n_add += k->n;
+                if (S.n - n_drop + n_add != (long long)total) inc = false;      // (the merge writes exactly the ring's points; anything else is not this case)
+            } else inc = false;
+        } else
         if (f == S.members.size() || f > 4) inc = false;
         else {
             for (size_t i = 0; i < f; i++) { drop.s[i] = S.members[i].first; n_drop += S.members[i].second; }
@@ -1340,8 +1546,9 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
         { const int rl = lili_lazy_sources_clear_of(ctx, d_bad, kRankOff - 256 + (size_t)kVoxSmallMax * 4); if (rl != LILI_OK) return rl; }
         HIPCHK(hipMemsetAsync(d_bad, 0, kRankOff - 256 + (size_t)kVoxSmallMax * 4, ctx->stream));      // *bad ... the rank words of k_rank_count: one fill
         int rc = LILI_OK;
-        if (add.empty()) rc = sorted_ring_step(ctx, V, S, drop, n_drop, nullptr, leaf, d_bad);
-        for (size_t i = 0; i < add.size() && rc == LILI_OK; i++) {
+        if (resuffix) rc = sorted_ring_resuffix(ctx, V, S, keep_lo, keep_hi, n_drop, add, leaf, d_bad);
+        else if (add.empty()) rc = sorted_ring_step(ctx, V, S, drop, n_drop, nullptr, leaf, d_bad);
+        for (size_t i = 0; i < add.size() && rc == LILI_OK && !resuffix; i++) {
             if (i > 0) HIPCHK(hipMemsetAsync(ctx->misc.as<char>() + kRankOff, 0, (size_t)kVoxSmallMax * 4, ctx->stream));      // (a second pending keyframe counts from zero again)
             rc = sorted_ring_step(ctx, V, S, i == 0 ? drop : DropSeqs{}, i == 0 ? n_drop : 0, add[i], leaf, d_bad);
         }
