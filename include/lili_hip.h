@@ -634,6 +634,54 @@ int lili_imu_integrate(lili_imu_state* st, const double* stamps, const double* g
  * parameter_block_idx of the keyframe's translation / rotation block.  Host function. */
 int lili_marg_add_lidar(const double gram[64], double* A, size_t ld, double* b, size_t pos, size_t idx_t, size_t idx_q);
 
+/* ---- loop-closure registration (performLoopClosure, L/src/BackendFusion.cpp:2552-2642) ---------------
+ * The submaps of detectLoopClosure (L:2423-2550) are assembled on the device and registered by the restatement of
+ * pcl::IterativeClosestPoint's default pipeline (no rejectors, TransformationEstimationSVD, DefaultConvergenceCriteria) in
+ * f64.  The pose-graph update (iSAM2) stays with the caller.  A context holds one source and one target cloud of its own:
+ * nothing here touches the matcher's maps and slots, the local map or the voxel filter's state. */
+enum { LILI_LOOP_SOURCE = 0, LILI_LOOP_TARGET = 1 };
+/* pcl::registration::DefaultConvergenceCriteria::ConvergenceState, same order */
+enum { LILI_ICP_NOT_CONVERGED = 0, LILI_ICP_ITERATIONS = 1, LILI_ICP_TRANSFORM = 2, LILI_ICP_ABS_MSE = 3,
+       LILI_ICP_REL_MSE = 4, LILI_ICP_NO_CORRESPONDENCES = 5 };
+typedef struct lili_icp_params {
+    double max_corr_dist;              /* 30 (setMaxCorrespondenceDistance): a correspondence is rejected when d2 > max_corr_dist^2 */
+    int32_t max_iterations;            /* 100 (>= 1) */
+    int32_t reserved_;
+    double transformation_epsilon;     /* 1e-6: |t_inc|^2 <= eps and cos(angle of R_inc) >= 1 - eps */
+    double euclidean_fitness_epsilon;  /* 1e-6: |mse - prev| / prev */
+} lili_icp_params;
+#define LILI_ICP_MAX_LOG 128
+typedef struct lili_icp_iteration {
+    double mse;                        /* mean d2 of the iteration's correspondences (before its update) */
+    double cos_angle, translation_sqr; /* of the iteration's increment */
+    int32_t n_corr, state;             /* correspondences; LILI_ICP_* after the convergence check */
+} lili_icp_iteration;
+typedef struct lili_icp_result {
+    double transform[16];              /* final_transformation_, row-major, f64 */
+    int32_t converged, state, iterations, n_logged;
+    double fitness;                    /* getFitnessScore() (max_range = DBL_MAX); DBL_MAX if no source point has a finite distance */
+    double stage_us[4];                /* [0] wall time of the call (us), [1] host synchronisations, [2] iterations enqueued (a batch may run past the end), [3] spare */
+    lili_icp_iteration it[LILI_ICP_MAX_LOG];
+} lili_icp_result;
+void lili_icp_default_params(lili_icp_params* p);
+/* transformCloud of cloud i by (t + 3i, q + 4i) (the LiDAR pose q_po*q_bl, q_po*t_bl + t_po), concatenated in the given order
+ * (per keyframe edge then surf, keyframes ascending: L:2476-2493, 2502-2521), then VoxelGrid(leaf) (leaf <= 0: none) -> the
+ * context's source or target (`which`).  The clouds may be host, page-locked host or device memory.  The target is indexed
+ * for the search.  n_raw / n_ds (optional): points before / after the filter.  Blocking. */
+int lili_loop_cloud(lili_ctx* ctx, int which, const lili_cloud* clouds, int n_clouds, const double* t, const double* q, float leaf, int64_t* n_raw, int64_t* n_ds);
+/* an already assembled cloud as the source / target (copied; the target is indexed).  Blocking. */
+int lili_icp_set_cloud(lili_ctx* ctx, int which, const lili_cloud* cloud);
+/* the context's source / target as float4 rows (x, y, z, aux) */
+int lili_icp_get_cloud(lili_ctx* ctx, int which, lili_feature_out* out);
+/* align(source -> target) from `guess` (row-major 4x4, NULL = identity).  LILI_E_STATE if a cloud is missing.  Blocking. */
+int lili_icp_align(lili_ctx* ctx, const lili_icp_params* p, const double guess[16], lili_icp_result* res);
+/* mean exact 1-NN d2 of the source under T over the points with d2 <= max_range (getFitnessScore(max_range)); DBL_MAX and
+ * n_used = 0 if there is none.  Blocking. */
+int lili_icp_fitness(lili_ctx* ctx, const double T[16], double max_range, double* fitness, int64_t* n_used);
+/* the correspondences of the last iteration of the last align, per source point: target index (-1: rejected or none) and d2
+ * (+inf where rejected).  capacity = entries the arrays hold (either may be NULL).  Blocking. */
+int lili_icp_get_correspondences(lili_ctx* ctx, size_t capacity, int32_t* target_idx, float* d2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,23 @@ class S2MParams(C.Structure):
                 ("scale_edge_num", C.c_double)]
 
 
+class IcpParams(C.Structure):
+    _fields_ = [("max_corr_dist", C.c_double), ("max_iterations", C.c_int32), ("reserved_", C.c_int32), ("transformation_epsilon", C.c_double),
+                ("euclidean_fitness_epsilon", C.c_double)]
+
+
+ICP_MAX_LOG = 128
+
+
+class IcpIteration(C.Structure):
+    _fields_ = [("mse", C.c_double), ("cos_angle", C.c_double), ("translation_sqr", C.c_double), ("n_corr", C.c_int32), ("state", C.c_int32)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("transform", C.c_double * 16), ("converged", C.c_int32), ("state", C.c_int32), ("iterations", C.c_int32), ("n_logged", C.c_int32),
+                ("fitness", C.c_double), ("stage_us", C.c_double * 4), ("it", IcpIteration * ICP_MAX_LOG)]
+
+
 def make_params(variant="rot", **kw):
     """Matcher parameters of the reference configs:
     L/config/config_fr_iosb.yaml ('livox'), R/config/config_fr_iosb.yaml ('rot'),
@@ -221,6 +238,13 @@ _SIGS = {
     "lili_marg_add_lidar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
     "lili_gn_step_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_gram_to_factor": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "lili_icp_default_params": (None, [C.POINTER(IcpParams)]),
+    "lili_loop_cloud": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Cloud), C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lili_icp_set_cloud": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Cloud)]),
+    "lili_icp_get_cloud": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FeatureOut)]),
+    "lili_icp_align": (C.c_int, [C.c_void_p, C.POINTER(IcpParams), C.c_void_p, C.POINTER(IcpResult)]),
+    "lili_icp_fitness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "lili_icp_get_correspondences": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 
 

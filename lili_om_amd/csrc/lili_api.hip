@@ -185,6 +185,7 @@ void lili_ctx_destroy(lili_ctx* ctx) {
     if (ctx->ext_rot && ctx->ext_rot_free) ctx->ext_rot_free(ctx->ext_rot);
     if (ctx->ext_livox && ctx->ext_livox_free) ctx->ext_livox_free(ctx->ext_livox);
     if (ctx->ext_voxel && ctx->ext_voxel_free) ctx->ext_voxel_free(ctx->ext_voxel);
+    if (ctx->ext_loop && ctx->ext_loop_free) ctx->ext_loop_free(ctx->ext_loop);
     for (auto& st : ctx->side) if (st) (void)hipStreamDestroy(st);
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
     if (ctx->extract_fork_ev) (void)hipEventDestroy(ctx->extract_fork_ev);

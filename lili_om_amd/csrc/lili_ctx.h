@@ -203,6 +203,8 @@ struct lili_ctx {
     void (*ext_livox_free)(void*) = nullptr;
     void* ext_voxel = nullptr;               // voxel filter / local-map ring buffer (lili_voxel.hip)
     void (*ext_voxel_free)(void*) = nullptr;
+    void* ext_loop = nullptr;                // loop-closure registration: its source, target, index and work buffers (lili_loop.hip)
+    void (*ext_loop_free)(void*) = nullptr;
 
     int fail(int code, const std::string& m) { err = m; return code; }
     SlotState* state(int slot) { return states.as<SlotState>() + slot; }

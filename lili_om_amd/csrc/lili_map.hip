@@ -125,6 +125,22 @@ int lili_map_set(lili_ctx* ctx, int kind, const lili_cloud* cloud, double max_sq
 
 }  // extern "C"
 
+// lili_loop.hip: the index of a loop-closure target — the same count / scan / scatter into an index the caller owns, with none of a map build's extras: no box guess,
+// 32-bit counts, the three-kernel scan (no status or error words in ctx->misc), no super-rows, no density measurement.  Asynchronous.
+int lili_grid_build_plain(lili_ctx* ctx, MapIndex& m, const float4* d_pts, int n, const double mn[3], const double mx[3], double cell, GridView& out) {
+    m.n = n; m.has_aux = false; m.has_fine = false;
+    SrcCloud src{};
+    src.p = reinterpret_cast<const unsigned char*>(d_pts); src.stride = (int)sizeof(float4); src.aux_off = -1; src.f4 = 1;
+    int64_t n_cells = 0;
+    double cell_used = 0;
+    const bool lookback = ctx->scan_lookback;
+    ctx->scan_lookback = false;
+    const int rc = build_grid(ctx, m, src, mn, mx, cell, 1, m.sorted, m.aux_sorted, m.cell_start, m.cell_start9, out, n_cells, cell_used, nullptr, false, 0.f, false, false, false);
+    ctx->scan_lookback = lookback;
+    m.n_cells = n_cells; m.cell = cell_used; m.view = out; m.valid = rc == LILI_OK;
+    return rc;
+}
+
 // where the box of a build comes from
 enum BoxSource { kBoxMeasure = 0,   // a bounding-box pass over the cloud and a read-back before the grid exists
                  kBoxGiven,         // the caller's (lili_localmap_commit: the centroids' box travels with their count), or the true box of a build whose guess failed

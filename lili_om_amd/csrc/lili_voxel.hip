@@ -765,6 +765,21 @@ __global__ void k_ring_repose(const ReposeSeg* __restrict__ segs, int n_seg, lon
     s.dst[j] = transform_point(s.src[j], dq{s.q[0], s.q[1], s.q[2], s.q[3]}, d3{s.t[0], s.t[1], s.t[2]});
 }
 
+// lili_loop_cloud: detectLoopClosure's transformCloud + concatenation (L/src/BackendFusion.cpp:2476-2493, 2502-2521) of a caller's keyframe clouds in ONE launch —
+// the rows read where they lie as k_cloud_to_f4 reads them, placed by the same expression as the ring's keyframes; thread i finds its cloud by bisection
+struct LoopSeg { const unsigned char* src; long long first; int stride, aux_off; double t[3], q[4]; };
+__global__ void k_loop_gather(const LoopSeg* __restrict__ segs, int n_seg, long long total, float4* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first <= i) lo = mid; else hi = mid - 1; }
+    const LoopSeg& s = segs[lo];
+    const unsigned char* row = s.src + (size_t)(i - s.first) * s.stride;
+    const float* p = reinterpret_cast<const float*>(row);
+    const float4 v = make_float4(p[0], p[1], p[2], s.aux_off >= 0 ? *reinterpret_cast<const float*>(row + s.aux_off) : 0.f);
+    out[i] = transform_point(v, dq{s.q[0], s.q[1], s.q[2], s.q[3]}, d3{s.t[0], s.t[1], s.t[2]});
+}
+
 }  // namespace lili
 
 namespace lili_detail {
@@ -1730,3 +1745,67 @@ int lili_localmap_push_dev(lili_ctx* ctx, int kind, const float4* d_pts, int n, 
 }
 int lili_localmap_ring_size(lili_ctx* ctx, int kind) { return (int)vox_of(ctx)->ring[kind].size(); }
 
+
+// lili_loop.hip: detectLoopClosure's submap — transformCloud of every cloud, concatenated, then VoxelGrid(leaf) (leaf <= 0: none) — into `out` (float4 rows).  The filter
+// runs on a VoxelBuffers of the loop's own (`*priv`, created here, freed by lili_loop_vox_free) and always the measured way: the local map's buffers, its ring and the key-bit
+// guesses of lili_voxel_filter_stats stay as they are.  Blocking.
+struct LoopVox { lili_detail::VoxelBuffers V; DevBuf segs, staging, raw; std::vector<LoopSeg> seg_host; };
+void lili_loop_vox_free(void* p) { if (p) { auto* L = static_cast<LoopVox*>(p); L->V.release(); delete L; } }
+int lili_loop_assemble(lili_ctx* ctx, void** priv, const lili_cloud* clouds, int n_clouds, const double* t, const double* q, float leaf, DevBuf& out, int64_t* n_raw, int64_t* n_ds) {
+    if (!*priv) *priv = new LoopVox();
+    auto* L = static_cast<LoopVox*>(*priv);
+    L->seg_host.assign(n_clouds, LoopSeg{});
+    long long total = 0, host_bytes = 0;
+    for (int k = 0; k < n_clouds; k++) {
+        const lili_cloud& c = clouds[k];
+        ARGCHK(c.n == 0 || c.data, "loop_cloud: null data");
+        ARGCHK(c.stride >= 12 && c.stride % 4 == 0, "loop_cloud: stride must be a multiple of 4 and >= 12");
+        ARGCHK(c.aux_offset < 0 || (size_t)c.aux_offset + 4 <= c.stride, "loop_cloud: aux_offset outside the point");
+        ARGCHK(c.mem == LILI_MEM_HOST || c.mem == LILI_MEM_DEVICE, "loop_cloud: bad mem");
+        if (c.mem == LILI_MEM_HOST && c.n && !lili_pinned_dev_ptr(c.data, 4)) host_bytes += (long long)((c.n * c.stride + 255) / 256 * 256);
+        total += (long long)c.n;
+    }
+    ARGCHK(total < (1ll << 31), "loop_cloud: too many points");
+    if (host_bytes) HIPCHK(L->staging.ensure((size_t)host_bytes));
+    long long off = 0;
+    for (int k = 0; k < n_clouds; k++) {      // pageable rows go through one staging buffer as they are; page-locked and device rows are read where they lie
+        const lili_cloud& c = clouds[k];
+        LoopSeg& s = L->seg_host[k];
+        s.stride = (int)c.stride; s.aux_off = c.aux_offset;
+        for (int j = 0; j < 3; j++) s.t[j] = t[3 * k + j];
+        for (int j = 0; j < 4; j++) s.q[j] = q[4 * k + j];
+        s.src = static_cast<const unsigned char*>(c.data);
+        if (c.mem == LILI_MEM_HOST && c.n) {
+            if (void* d = lili_pinned_dev_ptr(c.data, 4)) s.src = static_cast<const unsigned char*>(d);
+            else {
+                HIPCHK(hipMemcpyAsync(L->staging.as<unsigned char>() + off, c.data, c.n * c.stride, hipMemcpyHostToDevice, ctx->stream));
+                s.src = L->staging.as<unsigned char>() + off;
+                off += (long long)((c.n * c.stride + 255) / 256 * 256);
+            }
+        }
+    }
+    // first positions (empty clouds keep the position of the next one: the bisection never lands on them)
+    { long long first = 0; for (int k = 0; k < n_clouds; k++) { L->seg_host[k].first = first; first += (long long)clouds[k].n; } }
+    if (n_raw) *n_raw = total;
+    if (n_ds) *n_ds = 0;
+    if (total == 0) { HIPCHK(hipStreamSynchronize(ctx->stream)); return LILI_OK; }
+    HIPCHK(L->segs.ensure((size_t)n_clouds * sizeof(LoopSeg)));
+    HIPCHK(hipMemcpyAsync(L->segs.p, L->seg_host.data(), (size_t)n_clouds * sizeof(LoopSeg), hipMemcpyHostToDevice, ctx->stream));
+    const bool filter = leaf > 0.f;
+    DevBuf& dst = filter ? L->raw : out;
+    HIPCHK(dst.ensure((size_t)total * sizeof(float4)));
+    hipLaunchKernelGGL(k_loop_gather, dim3(nblocks(total, 256)), dim3(256), 0, ctx->stream, L->segs.as<LoopSeg>(), n_clouds, total, dst.as<float4>());
+    HIPCHK(hipGetLastError());
+    int n_out = (int)total;
+    if (filter) {
+        { const int rl = lili_lazy_sources_clear_of(ctx, ctx->misc.p, 64); if (rl != LILI_OK) return rl; }      // the filter's box words (ctx->misc)
+        int rc = voxel_filter_measured(ctx, &L->V, L->raw.as<float4>(), (int)total, leaf, false);
+        if (rc != LILI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        n_out = L->V.n_out;
+        HIPCHK(out.ensure((size_t)std::max(n_out, 1) * sizeof(float4)));
+        if (n_out) HIPCHK(hipMemcpyAsync(out.p, L->V.out.p, (size_t)n_out * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // (the segment table and the staging rows are read by then)
+    if (n_ds) *n_ds = n_out;
+    return LILI_OK;
+}
