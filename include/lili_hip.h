@@ -111,12 +111,13 @@ int lili_set_debug(lili_ctx* ctx, int keep_neighbors);
  *   local map     "localmap_incremental" (default 1, see lili_localmap_commit), "localmap_super_rows" (1 = ring maps below 400 k points get the
  *                 super-row copy too; default 0), "sort_digit_bits" (8, or 4 = the round-2 radix passes), "sort_fused_scan" (1 = radix passes of at most
  *                 "sort_fused_max_tiles" (256) tiles derive their offsets inside the scatter kernel; default 1), "sort_ride_hist" (1 = in the frame pipeline's query filter the
- *                 digit histograms ride on the key kernel and the scatter passes, one launch per pass; default 1), "voxel_small" (1 = clouds of <= 8192
+ *                 digit histograms ride on the key kernel and the scatter passes, one launch per pass, for sorts of at most 256 tiles whatever sort_fused_max_tiles says;
+ *                 default 1), "voxel_small" (1 = clouds of <= 8192
  *                 points are voxel-filtered / keyframe-sorted by ONE workgroup in LDS; default 1), "voxel_guess_bits" (see lili_voxel_filter_stats; default 1);
  *   host          "readback_gather" (1 = the small reads of a synchronisation are gathered by one kernel writing into page-locked memory instead of
  *                 one copy launch each; default 1), "frame_guess_counts" (1 = lili_frontend_frame_rot with LILI_FRAME_EXTERNAL_MAP and leaf_query 0 enqueues the
  *                 matcher behind the extractor for GUESSED feature counts — the previous scan's plus a margin, padding rows select nothing — and synchronises once;
- *                 a scan with more features than guessed is matched again the plain way; results identical either way; default 1), "frame_extract_stream" (1 = a frame whose
+ *                 a scan with more features than guessed is matched again the plain way; results identical either way; not taken with persistent_iterate; default 1), "frame_extract_stream" (1 = a frame whose
  *                 local map is still to be built runs its extraction on a stream of its own, next to the ring merge instead of in front of it: 15-30 us per frame faster in a
  *                 process with one context, ~100 us SLOWER in a process that holds many streams (they share the runtime's few hardware queues); default 0).
  *   extraction    "rot_fold" (1 = the ring stage of lili_extract_rot writes the scan's feature lists itself, four launches; 0 = per-ring lists and a concatenation

@@ -75,7 +75,9 @@ int lili_s2m_set_queries(lili_ctx* ctx, int slot, int kind, const lili_cloud* cl
 // `n_guess` queries; the producer (k_rot_ring through a lili_query_sink) writes the first min(count, n_guess) rows and fills the rest with NaN rows — a non-finite query
 // selects nothing (cell_of, the key selector), leaves no record and no count, so every sum of the iteration is the sum over the real queries in the order a slot of exactly
 // `count` queries would take it (the partition of the queries into association / linearisation workgroups depends on the query's index alone; the padding workgroups add
-// +0.0).  lili_s2m_trim_queries afterwards, once the count is known (count <= n_guess, else the caller sets the queries again).
+// +0.0).  lili_s2m_trim_queries afterwards, once the count is known (count <= n_guess, else the caller sets the queries again); it keeps the last association's
+// n_assoc_blocks: that launch wrote one count per block of ITS partition (64 queries; 16 for the dense association; 256 / L for the cooperative ones and k_iterate_coop), the blocks
+// of padding rows hold 0, and a later linearize / solve_lm on the slot must sum them all.
 int lili_s2m_set_queries_counted(lili_ctx* ctx, int slot, int kind, int n_guess) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS && (kind == 0 || kind == 1) && n_guess > 0, "set_queries_counted: bad argument");
@@ -102,7 +104,6 @@ int lili_s2m_trim_queries(lili_ctx* ctx, int slot, int kind, int n) {
     ARGCHK(ks.has_queries && n >= 0 && n <= ks.n_q, "trim_queries: bad argument");
     ks.n_q = n;
     ks.n_blocks = nblocks(ks.n_q, kAssocBlock);
-    ks.n_assoc_blocks = std::min(ks.n_assoc_blocks, ks.n_blocks);
     ks.n_lin_blocks = std::min(nblocks(ks.n_q, kLinBlock), kMaxLinBlocks);
     return LILI_OK;
 }

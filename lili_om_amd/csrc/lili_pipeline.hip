@@ -129,9 +129,10 @@ static int frame_impl(lili_ctx* ctx, const FrameExtractor& ex, const lili_s2m_pa
     //      kernel writes its lists into the slot's query arrays as well, fills the rows behind them with NaN (such a row selects nothing, so every sum is the one an exactly
     //      sized slot takes: lili_s2m_set_queries_counted) and sets the slot's pose; the matcher is enqueued right behind it and the call synchronises ONCE — the pose comes
     //      back with the counts.  A scan with more features than guessed, or one whose lists a second pass of the extractor rewrote, is matched again below the plain way.
+    //      Not with persistent_iterate: k_iterate_coop picks its lanes per query and block layout from the slot sizes, so padded slots would partition its sums differently.
     bool guessed = false;
     int ge = 0, gs = 0;
-    if (ctx->frame_guess_counts && ctx->rot_fold && ext_map && !(opt->leaf_query > 0) && ex.prev && ex.enqueue_sink && opt->n_iters > 0 && ctx->map[LILI_KIND_SURF].valid &&
+    if (ctx->frame_guess_counts && !ctx->persistent_iterate && ctx->rot_fold && ext_map && !(opt->leaf_query > 0) && ex.prev && ex.enqueue_sink && opt->n_iters > 0 && ctx->map[LILI_KIND_SURF].valid &&
         ctx->map[LILI_KIND_SURF].n >= 10 && (!edges || ctx->map[LILI_KIND_EDGE].valid)) {
         int pe = 0, ps = 0;
         ex.prev(&pe, &ps);

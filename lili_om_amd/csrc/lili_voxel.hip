@@ -1070,10 +1070,13 @@ static int exclusive_scan(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const int
 // round-2 passes, for A/B)
 // `ride`: the digit counts of pass 0 are already in table 0 of V->hist (k_vox_key_dev counted them) and tables 1 .. are zero: every scatter pass counts the next pass's
 // digits as it places its keys — a pass is ONE launch (round 6; the caller has sized and cleared V->hist through radix_ride_tables).
+// At most 256 tiles, whatever sort_fused_max_tiles says: the riding histograms count through wave_hist_add, whose ballots match 16 bits of digit * nb + tile —
+// distinct table entries of one wave stay apart only while nb <= 256 (the fused-scan passes without the ride read the whole table and take any nb).
 static bool radix_can_ride(const lili_ctx* ctx, int n) {
     if (ctx->sort_digit_bits == 4 || !ctx->sort_fused_scan || !ctx->sort_ride_hist) return false;
     const int items8 = n <= 262144 ? 4 : 16;
-    return (n + 256 * items8 - 1) / (256 * items8) <= ctx->sort_fused_max_tiles;
+    const int nb = (n + 256 * items8 - 1) / (256 * items8);
+    return nb <= 256 && nb <= ctx->sort_fused_max_tiles;
 }
 static void radix_geometry(int n, int& items8, int& nb) { items8 = n <= 262144 ? 4 : 16; nb = (n + 256 * items8 - 1) / (256 * items8); }
 static int radix_sort(lili_ctx* ctx, lili_detail::VoxelBuffers* V, int n, int bits, bool ride = false) {

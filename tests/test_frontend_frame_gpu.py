@@ -199,6 +199,57 @@ def test_frontend_frame_rot_guessed_feature_counts_change_nothing():
         assert np.array_equal(g[0], want[0]) and np.array_equal(g[1], want[1])
 
 
+@pytest.mark.parametrize("persistent", [0, 1])
+def test_frontend_frame_rot_guessed_feature_counts_leave_the_slot_as_an_exact_one(persistent):
+    """The slot a guessed-count frame leaves behind must be the one an exactly sized frame leaves: a later linearize / solve_lm on it reads every block count the
+    association wrote (the trim to the real count keeps the association's block partition — a cooperative association writes one count per 256 / L queries, the
+    dense one one per 16 — so the ROT scaling by the correspondence count and the Gram are those of all the records).  Full scan, the same again (hit), then the thin
+    scan (hit with fewer features than guessed); the counts linearize sums must equal the records' valid flags."""
+    import torch
+    w = synth.make_workload(n_map=200_000, n_az=400, half_extent=(150.0, 150.0), verbose=False)
+    raw = np.concatenate([w["scan_xyz"], np.full((w["scan_xyz"].shape[0], 1), 50.0, np.float32)], 1)
+    n_az = raw.shape[0] // 64
+    thin = np.ascontiguousarray(raw.reshape(n_az, 64, 4)[:, ::4].reshape(-1, 4))
+    P = L.make_params("rot")
+    q_lb = np.array(list(P.q_lb))
+    tb, qb = L.api.body_pose_from_lidar(w["lidar_t"], w["lidar_q"], P)
+    t0, q0 = synth.perturbed_pose(tb, qb, np.random.default_rng(synth.SEED_POSE), 0.2, 1.0)
+    d_raw, d_thin = torch.from_numpy(raw).cuda(), torch.from_numpy(thin).cuda()
+    cloud = L.api.cloud_from_device(d_raw.data_ptr(), raw.shape[0], 16, 12)
+    cloud_thin = L.api.cloud_from_device(d_thin.data_ptr(), thin.shape[0], 16, 12)
+
+    def run(guess):
+        ctx = L.Context(0)
+        try:
+            ctx.set_option("frame_guess_counts", guess)
+            ctx.set_option("persistent_iterate", persistent)
+            m = L.ScanToMapMatcher(ctx, P)
+            m.set_input_cloud(L.KIND_SURF, w["map_xyz"]); m.set_input_cloud(L.KIND_EDGE, w["edge_map_xyz"])
+            odo = L.RotFrontendOdometry(ctx, params=P, n_scans=64, ds_rate=1, q_lb=q_lb, leaf_query=0.0, scan_match_cnt=2, external_map=True, edges=True, slot=1)
+            out = []
+            for c in (cloud, cloud, cloud_thin):
+                t, q, info = odo.frame(c, t0, q0)
+                assert info["matched"] and info["gn_status"] == 0
+                G, cost, counts = m.linearize(1, t, q)
+                n_surf, n_edge = m.surf_records(1, 1)["count"], m.edge_records(1, 1)["count"]
+                assert (int(counts[0]), int(counts[1])) == (n_surf, n_edge), (guess, counts, n_surf, n_edge)
+                summ = m.solve_lm(1)
+                t_lm, q_lm, st = m.pose_get(1)
+                out.append((t.copy(), q.copy(), G, cost, counts.copy(), summ, t_lm, q_lm, st))
+            return out
+        finally:
+            ctx.close()
+
+    plain, got = run(0), run(1)
+    assert plain[2][4][0] < 0.6 * plain[0][4][0] and plain[0][4][0] > 1000          # the thin scan has far fewer correspondences than the full one
+    for g, want in zip(got, plain):
+        assert np.array_equal(g[0], want[0]) and np.array_equal(g[1], want[1])
+        assert np.array_equal(g[4], want[4]), (g[4], want[4])
+        assert np.array_equal(g[2], want[2]) and g[3] == want[3]
+        assert g[5] == want[5]
+        assert np.array_equal(g[6], want[6]) and np.array_equal(g[7], want[7]) and g[8] == want[8]
+
+
 @pytest.mark.parametrize("edges", [False, True])
 def test_frontend_frame_rot_guess_behind_a_second_pass_of_the_extractor(edges):
     """The guessed-count frame when the extractor REWRITES its lists after the matcher has been enqueued: with a 5 cm VoxelGrid leaf the voxel keys of a 150 m scene leave
