@@ -210,3 +210,85 @@ def test_dense_map_livox_flavour_reads_reflectivity_through_the_fine_index(gpu_c
         assert np.array_equal(res[1][1][k], res[0][1][k]), k
     o = oracle.associate_surf(oracle.KdTree(mp), refl, q_local, q_refl, q_true, t_true, PO)
     assert res[1][0] == o["count"] and np.array_equal(res[1][1]["query_index"], np.nonzero(o["valid"])[0])
+
+
+def _lattice_room(h=0.0625, half=(2.0, 1.5), height=2.5):
+    """the six faces of a room sampled on an exact lattice of spacing h (a power of two): distances between lattice points and the queries below tie
+    exactly, and the edges of the room hold each point twice (two faces), so equal distances at equal positions are common."""
+    sx, sy = half
+    xs, ys, zs = np.arange(-sx, sx + h / 2, h), np.arange(-sy, sy + h / 2, h), np.arange(0.0, height + h / 2, h)
+    faces = []
+    for z in (0.0, height):
+        X, Y = np.meshgrid(xs, ys, indexing="ij"); faces.append(np.stack([X.ravel(), Y.ravel(), np.full(X.size, z)], 1))
+    for x in (-sx, sx):
+        Y, Z = np.meshgrid(ys, zs, indexing="ij"); faces.append(np.stack([np.full(Y.size, x), Y.ravel(), Z.ravel()], 1))
+    for y in (-sy, sy):
+        X, Z = np.meshgrid(xs, zs, indexing="ij"); faces.append(np.stack([X.ravel(), np.full(X.size, y), Z.ravel()], 1))
+    return np.concatenate(faces)
+
+
+def _lattice_queries(mp_f64, fg, h, rng):
+    """lattice points, midpoints and cell centres (on and a few lattice steps off the surfaces), and the f32 nearest to faces, edges and corners of
+    the model's fine cells, each also +-1 ulp."""
+    n = mp_f64.shape[0]
+    qs = [mp_f64[rng.choice(n, 300)]]
+    base = mp_f64[rng.choice(n, 600)]
+    steps = np.array([[h / 2, 0, 0], [0, h / 2, 0], [0, 0, h / 2], [h / 2, h / 2, 0], [h / 2, 0, h / 2], [0, h / 2, h / 2], [h / 2, h / 2, h / 2]])
+    qs.append(base + steps[rng.integers(0, len(steps), base.shape[0])] * rng.choice([-1, 1], (base.shape[0], 1)))
+    qs.append(base[:200] + rng.integers(-6, 7, (200, 3)) * h)                                 # up to 6 lattice steps off: ring levels, still exact
+    o, cell = np.array([fg.ox, fg.oy, fg.oz]), fg.cell
+    for n_axes in (1, 2, 3):                                                                    # faces, edges, corners of the fine cells
+        p = mp_f64[rng.choice(n, 240)] + rng.uniform(-0.5, 0.5, (240, 3)) * h
+        for r in range(p.shape[0]):
+            for k in rng.choice(3, n_axes, replace=False):
+                i = np.floor((p[r, k] - o[k]) / cell + 0.5)
+                p[r, k] = float(np.float32(o[k] + i * cell))
+        f = p.astype(np.float32)
+        qs += [f, np.nextafter(f, np.float32(np.inf)), np.nextafter(f, np.float32(-np.inf))]
+    return np.concatenate([np.asarray(q, np.float32) for q in qs])
+
+
+@pytest.mark.parametrize("offset", [(0.0, 0.0, 0.0), (4096.0, -3000.0, 50.0)], ids=["origin", "far"])
+def test_dense_map_lattice_ties_and_fine_cell_faces(oracle, offset):
+    """A room on an exact 1/16 m lattice, dense enough for the fine index, near the origin and at (4096, -3000, 50) m where f32 distances tie
+    massively.  Queries on lattice points, at midpoints and cell centres, and at the f32 nearest to faces, edges and corners of the fine cells (placed
+    with tests/dense_grid_model.py, which lili_map_density must equal bit for bit), each also +-1 ulp.  Both kinds, the bucket-key selector and the
+    exact selector (LILI_DEBUG bit 32768): neighbours and f32 distances equal the (d2, index)-ordered brute force bit for bit."""
+    import os
+    from tests import dense_grid_model as DM
+    from tests.knn_brute import BruteKnn5
+    h = 0.0625
+    mp = (_lattice_room(h) + np.array(offset)).astype(np.float32)
+    assert np.array_equal(mp.astype(np.float64), _lattice_room(h) + np.array(offset))         # the lattice is exact in f32 there too
+    P = L.make_params("rot")
+    ctx = L.Context(0)
+    results = {}
+    try:
+        ctx.set_option("map_guess_box", 0)
+        ctx.set_debug(True)
+        m = L.ScanToMapMatcher(ctx, P)
+        m.set_input_cloud(L.KIND_SURF, mp)
+        m.set_input_cloud(L.KIND_EDGE, mp, max_sq_radius=P.edge_gate)
+        mn, mx = DM.box_of(mp)
+        for kind, r2 in ((L.KIND_SURF, P.kd_max_radius), (L.KIND_EDGE, P.edge_gate)):
+            occ, fcell, fr2 = m.map_density(kind)
+            fg, fc, fb = DM.fine_index(mn, mx, r2, occ)
+            assert fg is not None and (fcell, fr2) == (fc, fb), (kind, occ, fcell, fc, fr2, fb)
+        q = _lattice_queries(mp.astype(np.float64), fg, h, np.random.default_rng(17))
+        for dbg in ("0", "32768"):
+            os.environ["LILI_DEBUG"] = dbg
+            for kind, find in ((L.KIND_SURF, m.find_corresponding_surf_features), (L.KIND_EDGE, m.find_corresponding_corner_features)):
+                m.set_queries(0, kind, q)
+                find(0, [1.0, 0, 0, 0], [0.0, 0, 0])                                       # identity: the device sees q exactly
+                results[(dbg, kind)] = m.neighbors(0, kind, q.shape[0])
+    finally:
+        os.environ.pop("LILI_DEBUG", None)
+        ctx.close()
+    want_i, want_d = BruteKnn5(mp).query(q)
+    inside = want_d[:, 4] < 1.0
+    assert inside.sum() > 0.9 * q.shape[0]
+    d = want_d[inside]
+    assert (d[:, 3] == d[:, 4]).mean() > 0.15                                                 # ties at the fifth place are the rule here
+    for key, (idx, d2) in results.items():
+        bad = np.nonzero(((idx != want_i) | (d2.view(np.uint32) != want_d.view(np.uint32))).any(1) & inside)[0]
+        assert bad.size == 0, (key, bad[:5], q[bad[:2]], idx[bad[:2]], want_i[bad[:2]], d2[bad[:2]], want_d[bad[:2]])

@@ -723,3 +723,46 @@ def test_native_rccl_communicator_single_rank(gpu_ctx, oracle, launch_by_launch)
         comm.close()
 
 
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+def test_iterate_restart_equals_pose_copy_and_iterate(gpu_ctx, oracle, launch_by_launch, variant):
+    """lili_s2m_iterate_restart — the loop the headline and configs[2] variant B time — with n_iters not a multiple of restart_every: the pose of
+    pose_copy + iterate per registration bit for bit, on the three-launch path (rot) and the fused one (livox, frontend); with time_association
+    (events around the association launches, the three-launch path for every flavour) a positive time and the pose of fuse_lin = 0; bad restart
+    arguments raise."""
+    room = synth.make_room(seed=16, n_query=5000, n_edge_query=300)
+    P, PO, m = _setup(gpu_ctx, oracle, variant, room, with_refl=(variant == "livox"))
+    t, q, _, _ = _pose(room, P, variant, np.random.default_rng(12), 0.08, 0.8)
+    mask = L.MASK_SURF | L.MASK_EDGE
+    n_iters, every = 7, 3                                      # registrations of 3, 3 and 1 iterations
+    m.pose_set(1, t, q)
+    m.pose_set(0, *synth.perturbed_pose(t, q, np.random.default_rng(13), 0.2, 1.0))     # replaced by the first restart
+    m.iterate_restart(0, n_iters, every, 1, mask)
+    t_r, q_r, st_r = m.pose_get(0)
+    ends = []
+    for k in range(0, n_iters, every):
+        m.pose_copy(0, 1)
+        m.iterate(0, min(every, n_iters - k), mask)
+        ends.append(m.pose_get(0))
+    t_m, q_m, st_m = ends[-1]
+    assert st_r == st_m == 0
+    assert np.array_equal(t_r, t_m) and np.array_equal(q_r, q_m)
+    assert not np.array_equal(ends[0][0], t_m)                 # the last registration is one iteration long: it ends elsewhere than a full one
+    try:
+        gpu_ctx.set_option("fuse_lin", 0)
+        m.iterate_restart(0, n_iters, every, 1, mask)
+        t_u, q_u, _ = m.pose_get(0)
+        gpu_ctx.set_option("fuse_lin", 1)
+        ms = m.iterate_restart(0, n_iters, every, 1, mask, time_association=True)
+        t_e, q_e, st_e = m.pose_get(0)
+    finally:
+        gpu_ctx.set_option("fuse_lin", 1)
+    assert ms > 0 and st_e == 0
+    assert np.array_equal(t_e, t_u) and np.array_equal(q_e, q_u)
+    if variant == "rot":                                       # no fused path for count-scaled flavours: all four runs are one computation
+        assert np.array_equal(t_e, t_r) and np.array_equal(q_e, q_r)
+    with pytest.raises(L.LiliError):
+        m.iterate_restart(0, n_iters, every, 0, mask)          # restart_slot == slot
+    with pytest.raises(L.LiliError):
+        m.iterate_restart(0, n_iters, -1, 1, mask)
