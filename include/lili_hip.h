@@ -123,6 +123,9 @@ int lili_set_debug(lili_ctx* ctx, int keep_neighbors);
  *   extraction    "rot_fold" (1 = the ring stage of lili_extract_rot writes the scan's feature lists itself, four launches; 0 = per-ring lists and a concatenation
  *                 launch, also the fallback of a look-back that gave up; default 1), "rot_segment_wait" (1 = a segment whose pick may lie under marks of the
  *                 segment before it waits for them inside the segment stage; 0 = the ring stage repeats such a segment; default 1).
+ *   archive / map "archive_max_mb" (bound on the keyframe archive's slab pool in MiB; 0 = unlimited, the default; a push beyond it fails), "archive_slab_mb" (size of
+ *                 one slab in MiB, default 64; a keyframe larger than a slab gets a slab of its own), "global_map_batch_points" (points lili_global_map places,
+ *                 sorts and folds at a time, 1024 .. 2^27, default 2^21: about 100 bytes of work buffers per point next to the table).
  * One knob that DOES choose between two definitions of a result: "rot_atan" — lili_extract_rot's atan / atan2 on float arguments
  * (R/src/Preprocessing.cpp:285-288,315,349): 2 (default) = glibc's float routines statement for statement (atanf / atan2f of
  * every glibc up to 2.40 — the bits a build of the reference produces), 1 = the f64 functions rounded to f32 (libm-independent). */
@@ -682,6 +685,64 @@ int lili_icp_fitness(lili_ctx* ctx, const double T[16], double max_range, double
 /* the correspondences of the last iteration of the last align, per source point: target index (-1: rejected or none) and d2
  * (+inf where rejected).  capacity = entries the arrays hold (either may be NULL).  Blocking. */
 int lili_icp_get_correspondences(lili_ctx* ctx, size_t capacity, int32_t* target_idx, float* d2);
+
+/* ---- keyframe archive and global map (saveKeyFramesAndFactors L/src/BackendFusion.cpp:1494-1514, correctPoses L:2177-2311,
+ * publishCompleteMap L:2644-2685 and the PCD save L:2697-2723) -------------------------------------------
+ * Every keyframe's clouds stay in device memory as float4 rows (x, y, z, aux) in the LiDAR frame, as pushed, with the
+ * keyframe's body pose and time on the host; a pose change moves no point.  Storage is a pool of large slabs ("archive_slab_mb")
+ * that never move: a view stays valid until lili_archive_reset / lili_ctx_destroy.  Nothing is ever evicted.  The archive and
+ * the global map have buffers of their own: the matcher, the local map, the voxel filter's state and the loop-closure clouds
+ * (other than through lili_loop_cloud_archive) are untouched.  Argument errors return LILI_E_ARG with the archive as it was. */
+enum { LILI_ARCHIVE_EDGE = 0, LILI_ARCHIVE_SURF = 1, LILI_ARCHIVE_FULL = 2 };
+int lili_archive_reset(lili_ctx* ctx);
+/* body -> LiDAR extrinsic (default identity): a keyframe's map pose is (q_po * q_bl, q_po * t_bl + t_po), f64 on the host */
+int lili_archive_set_extrinsic(lili_ctx* ctx, const double t_bl[3], const double q_bl[4]);
+/* Appends a keyframe; *id (optional) = number of keyframes before the call.  Any cloud may be NULL (kind absent) and may lie in
+ * host, page-locked host or device memory with any stride / aux offset (aux absent: 0).  Fails with LILI_E_NOMEM, archive
+ * untouched, if the pool would exceed "archive_max_mb".  Blocking. */
+int lili_archive_push(lili_ctx* ctx, const lili_cloud* edge, const lili_cloud* surf, const lili_cloud* full, double time,
+                      const double t_po[3], const double q_po[4], int* id);
+/* the same with edge / surf = the QUERIES of matcher slot `slot` (what lili_s2m_set_queries or lili_backend_keyframe_prepare
+ * left there), copied device to device on the context's stream; a kind without queries is absent */
+int lili_archive_push_slot(lili_ctx* ctx, int slot, const lili_cloud* full, double time, const double t_po[3], const double q_po[4], int* id);
+/* keyframes first .. first + n - 1 take new body poses (t_po: 3 n doubles, q_po: 4 n doubles w x y z) */
+int lili_archive_set_poses(lili_ctx* ctx, int first, int n, const double* t_po, const double* q_po);
+/* n_points: edge, surf, full; bytes_used: device memory of the slab pool (all pointers optional) */
+int lili_archive_info(lili_ctx* ctx, int* n_keyframes, int64_t n_points[3], int64_t* bytes_used);
+/* body pose and time of keyframe id (any pointer may be NULL) */
+int lili_archive_pose(lili_ctx* ctx, int id, double t_po[3], double q_po[4], double* time);
+/* the rows of keyframe id / kind; out->count = the cloud's size (0: absent or empty).  Blocking. */
+int lili_archive_get(lili_ctx* ctx, int id, int kind, lili_feature_out* out);
+/* LILI_MEM_DEVICE view (stride 16, aux offset 12) of the rows, complete when the call returns */
+int lili_archive_view(lili_ctx* ctx, int id, int kind, lili_cloud* view);
+/* lili_loop_cloud with clouds and poses from the archive: per id, in the order given, edge then surf, at the keyframe's map pose.
+ * Same gather, filter and buffers: bit for bit the submap lili_loop_cloud makes of the same clouds and poses. */
+int lili_loop_cloud_archive(lili_ctx* ctx, int which, const int* ids, int n_ids, float leaf, int64_t* n_raw, int64_t* n_ds);
+/* detectLoopClosure's candidate selection (L:2431-2473, R:2240-2263), host code without a context: the keyframes with f32
+ * d2 = (dx dx + dy dy) + dz dz < (float)(radius radius) of select_pose in ascending d2 (ties: smaller index); his = the first whose
+ * |time - t_now| exceeds global_thres; variant 0 (Livox): failing that the one with the largest |time - t_now| inside
+ * (local_thres, global_thres); variant 1 (ROT): none, and none either within 0.2 s of time_last_loop.  Returns 1 and fills
+ * latest = n - slide_window_width and his, 0 if there is no candidate, LILI_E_ARG on a bad argument. */
+int lili_loop_detect(const float* positions, const double* times, int n, const float select_pose[3], double t_now, int variant, double radius,
+                     double local_thres, double global_thres, double time_last_loop, int slide_window_width, int* latest, int* his);
+/* publishCompleteMap: keyframes 0, interval, 2 interval, ... of `kind` at their current map poses -> VoxelGrid(leaf), on the
+ * device.  The result equals lili_voxel_filter(leaf) of the concatenation, in keyframe order, of the selected clouds placed
+ * as lili_loop_cloud places them (centroids, counts and order, bit for bit), but is kept as an accumulating table
+ * (voxel key, running f32 sum, count): a call folds only the keyframes the table does not hold yet (`incremental`) when the
+ * table was built with the same kind, interval, leaf and extrinsic and every keyframe it holds still has the map pose, bit
+ * for bit, it was folded at; otherwise it starts from an empty table (`rebuild`).  Points are folded in batches of
+ * "global_map_batch_points".  PCL's int32 voxel-index guard applies to everything folded: beyond it the call fails with
+ * lili_voxel_filter's error and the next call rebuilds; so does a point farther than 2^20 voxels from the origin.
+ * n_raw = points folded in all (non-finite ones included, which the filter drops), n_map = voxels.  An empty selection
+ * gives an empty map.  Blocking. */
+int lili_global_map(lili_ctx* ctx, int kind, int interval, float leaf, int64_t* n_raw, int64_t* n_map);
+/* the map of the last successful lili_global_map: rows (x, y, z, aux) in voxel-index order; `out` may be device memory;
+ * counts (optional, host or device, out->capacity entries): members per voxel.  Blocking. */
+int lili_global_map_get(lili_ctx* ctx, lili_feature_out* out, int32_t* counts);
+/* calls served incrementally / from an empty table so far, and the points the last call folded */
+int lili_global_map_stats(lili_ctx* ctx, int32_t* incremental, int32_t* rebuilds, int64_t* points_folded_last);
+/* device memory of the global map: the table and the work buffers of a batch (bytes) */
+int lili_global_map_info(lili_ctx* ctx, int64_t* table_bytes, int64_t* work_bytes);
 
 #ifdef __cplusplus
 }

@@ -245,6 +245,22 @@ _SIGS = {
     "lili_icp_align": (C.c_int, [C.c_void_p, C.POINTER(IcpParams), C.c_void_p, C.POINTER(IcpResult)]),
     "lili_icp_fitness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "lili_icp_get_correspondences": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lili_archive_reset": (C.c_int, [C.c_void_p]),
+    "lili_archive_set_extrinsic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lili_archive_push": (C.c_int, [C.c_void_p, C.POINTER(Cloud), C.POINTER(Cloud), C.POINTER(Cloud), C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "lili_archive_push_slot": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Cloud), C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "lili_archive_set_poses": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "lili_archive_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lili_archive_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "lili_archive_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(FeatureOut)]),
+    "lili_archive_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Cloud)]),
+    "lili_loop_cloud_archive": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lili_loop_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lili_global_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lili_global_map_get": (C.c_int, [C.c_void_p, C.POINTER(FeatureOut), C.c_void_p]),
+    "lili_global_map_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "lili_global_map_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 

@@ -1,0 +1,712 @@
+// Keyframe archive and global map on gfx950:
+//   saveKeyFramesAndFactors — L/src/BackendFusion.cpp:1494-1514 (the clouds of every keyframe are kept), correctPoses — L:2177-2311 (they take new poses),
+//   detectLoopClosure — L:2423-2550 (submaps of archived keyframes), publishCompleteMap — L:2644-2685 / the PCD save L:2697-2723 (every interval-th keyframe's cloud at
+//   its current pose, VoxelGrid over all of them).
+// Pieces:
+//   * the archive: float4 rows (x, y, z, aux) in the LiDAR frame, as pushed, in a pool of large slabs that never move (a hipMalloc / hipFree is a device-wide
+//     synchronisation: none per keyframe); body pose and time on the host, the map pose (q_po q_bl, q_po t_bl + t_po) in f64 in Eigen's operation order;
+//   * loop-closure submaps from the archive: device views handed to lili_loop_cloud — the same gather, the same filter, the same buffers;
+//   * the global map as an ACCUMULATING voxel table: per occupied voxel the absolute 64-bit key (k, j, i) = floor(p * inverse_leaf) packed lexicographically — the
+//     order pcl::VoxelGrid's box-relative index induces whatever the box is —, the running f32 sum and the count, sorted by key.  A batch of placed points is sorted
+//     stably by its own box-relative voxel index (lili_voxel.hip's radix sort: the same order, 32-bit keys), and every voxel of the batch CONTINUES the left fold
+//     from the table's sum (or from 0.0f): a voxel's members of a later batch all come after those of the earlier ones in concatenation order, so the sequence of f32
+//     additions per voxel is the one-shot filter's for any split into batches.  New keys are merged in by prefix sum and binary search (as k_merge does for the ring).
+// No floating-point atomics anywhere: the order of the additions is the contract.
+#include "lili_ctx.h"
+#include "lili_device_math.h"
+
+#include <climits>
+#include <memory>
+
+namespace lili {
+
+__global__ void k_scan_block_sums(const int*, int64_t, int*);
+__global__ void k_scan_sums(int*, int);
+__global__ void k_scan_apply(const int*, int64_t, const int*, int*);
+
+// a pushed cloud's rows -> float4 (x, y, z, aux; aux absent: 0), read where they lie as k_loop_gather reads them
+__global__ void k_arc_rows(const unsigned char* __restrict__ src, int n, int stride, int aux_off, float4* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned char* row = src + (size_t)i * stride;
+    const float* p = reinterpret_cast<const float*>(row);
+    out[i] = make_float4(p[0], p[1], p[2], aux_off >= 0 ? *reinterpret_cast<const float*>(row + aux_off) : 0.f);
+}
+
+// one batch of the global map: runs of archived rows placed at their keyframes' map poses, concatenated (thread i finds its run by bisection, as k_loop_gather)
+struct GmSeg { const float4* src; long long first; double t[3], q[4]; };
+__global__ void k_gm_gather(const GmSeg* __restrict__ segs, int n_seg, int total, float4* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first <= (long long)i) lo = mid; else hi = mid - 1; }
+    const GmSeg& s = segs[lo];
+    out[i] = transform_point(s.src[(long long)i - s.first], dq{s.q[0], s.q[1], s.q[2], s.q[3]}, d3{s.t[0], s.t[1], s.t[2]});
+}
+
+// absolute voxel key of a FINITE point (the sorted ring's, lili_voxel.hip): ~0 beyond +-2^20 voxels
+__device__ __forceinline__ unsigned long long gm_key(float4 p, float inv_leaf) {
+    const long long i = (long long)floorf(p.x * inv_leaf) + (1ll << 20), j = (long long)floorf(p.y * inv_leaf) + (1ll << 20), k = (long long)floorf(p.z * inv_leaf) + (1ll << 20);
+    if ((i | j | k) < 0 || i >= (1ll << 21) || j >= (1ll << 21) || k >= (1ll << 21)) return ~0ull;
+    return ((unsigned long long)k << 42) | ((unsigned long long)j << 21) | (unsigned long long)i;
+}
+
+// head flags of the batch's sorted keys; the points are copied into sorted order on the way (a voxel's members become one contiguous run)
+__global__ void k_gm_heads(const unsigned* __restrict__ keys, const int* __restrict__ order, const float4* __restrict__ raw, int n, unsigned sentinel, int* __restrict__ flags,
+                           float4* __restrict__ spts) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    spts[r] = raw[order[r]];
+    flags[r] = (keys[r] != sentinel && (r == 0 || keys[r] != keys[r - 1])) ? 1 : 0;
+}
+
+// per voxel of the batch (its head's thread): where its members start, its absolute key and its place in the table — pos = lower_bound(table keys, key), is_new = the
+// table does not hold the key.  head_pos[number of voxels] = where the voxels end (the non-finite rows sort behind them).  res[0] is raised by a key out of range.
+__global__ void k_gm_voxels(const unsigned* __restrict__ keys, const int* __restrict__ flags, const int* __restrict__ slot /*[n+1]*/, const float4* __restrict__ spts, int n,
+                            unsigned sentinel, float inv_leaf, const unsigned long long* __restrict__ tkey, int n_tab, int* __restrict__ head_pos,
+                            unsigned long long* __restrict__ bkey, int* __restrict__ pos, int* __restrict__ is_new, int* __restrict__ res) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const bool live = keys[r] != sentinel;
+    if (live && (r == n - 1 || keys[r + 1] == sentinel)) head_pos[slot[n]] = r + 1;
+    if (!flags[r]) return;
+    const int v = slot[r];
+    const unsigned long long key = gm_key(spts[r], inv_leaf);
+    if (key == ~0ull) res[0] = 1;
+    int lo = 0, hi = n_tab;
+    while (lo < hi) { const int mid = (int)(((long long)lo + hi) >> 1); if (tkey[mid] < key) lo = mid + 1; else hi = mid; }
+    head_pos[v] = r; bkey[v] = key; pos[v] = lo;
+    is_new[v] = (lo < n_tab && tkey[lo] == key) ? 0 : 1;
+}
+
+__device__ __forceinline__ void gm_wave_lds_order() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
+
+// The fold, ONE THREAD PER VOXEL of the batch: the running sum starts at the table's (a voxel the table holds) or at 0.0f and takes the batch's members in order — the
+// member count is known from the head positions before the first load, so the loads of a trip of eight leave together and only the additions are serial.  A voxel of
+// more than kGmShort members in this batch (next to a stationary sensor: thousands) is left to k_gm_fold_long through `long_list` (its order does not matter: every
+// entry is a voxel of its own).  bcnt = the voxel's count after the fold.
+constexpr int kGmShort = 48;
+__global__ void k_gm_fold(int n_vox, const int* __restrict__ head_pos, const float4* __restrict__ spts, const int* __restrict__ pos, const int* __restrict__ is_new,
+                          const float4* __restrict__ tsum, const int* __restrict__ tcnt, float4* __restrict__ bsum, int* __restrict__ bcnt, int* __restrict__ long_list,
+                          int* __restrict__ res) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vox) return;
+    const int i = head_pos[v], end = head_pos[v + 1];
+    float sx = 0.f, sy = 0.f, sz = 0.f, sa = 0.f;
+    int c0 = 0;
+    if (!is_new[v]) { const float4 s = tsum[pos[v]]; sx = s.x; sy = s.y; sz = s.z; sa = s.w; c0 = tcnt[pos[v]]; }
+    bcnt[v] = c0 + (end - i);
+    if (end - i > kGmShort) {
+        long_list[atomicAdd(&res[1], 1)] = v;
+        bsum[v] = make_float4(sx, sy, sz, sa);
+        return;
+    }
+    for (int m = i; m < end; m += 8) {
+        float4 pp[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) pp[u] = spts[m + u < end ? m + u : end - 1];
+#pragma unroll
+        for (int u = 0; u < 8; u++) if (m + u < end) { sx += pp[u].x; sy += pp[u].y; sz += pp[u].z; sa += pp[u].w; }
+    }
+    bsum[v] = make_float4(sx, sy, sz, sa);
+}
+// the crowded voxels, one WAVE each (as k_vox_centroid treats them): the wave requests kGmStage members at once, parks them in LDS, and lane c of every four carries
+// component c of the sum — one dependent addition per member, the operands read from a wave-uniform LDS address sixteen ahead of the additions
+constexpr int kGmStage = 512;
+__global__ __launch_bounds__(256) void k_gm_fold_long(const int* __restrict__ long_list, const int* __restrict__ res, const int* __restrict__ head_pos,
+                                                      const float4* __restrict__ spts, float4* __restrict__ bsum) {
+    __shared__ float4 stage[4][kGmStage];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n_long = res[1];
+    for (int j = blockIdx.x * 4 + wave; j < n_long; j += gridDim.x * 4) {      // (wave-uniform)
+        const int v = long_list[j];
+        int m = head_pos[v];
+        const int end = head_pos[v + 1];
+        const int comp = lane & 3;
+        const float4 s0 = bsum[v];
+        float acc = comp == 0 ? s0.x : comp == 1 ? s0.y : comp == 2 ? s0.z : s0.w;
+        const float* st = reinterpret_cast<const float*>(stage[wave]) + comp;
+        while (m < end) {
+            const int cnt = min(end - m, kGmStage);
+            float4 reg[kGmStage / 64];
+#pragma unroll
+            for (int r = 0; r < kGmStage / 64; r++) reg[r] = spts[min(m + 64 * r + lane, end - 1)];      // (every request leaves before the first answer is awaited)
+#pragma unroll
+            for (int r = 0; r < kGmStage / 64; r++) stage[wave][64 * r + lane] = reg[r];
+            gm_wave_lds_order();
+            float p[16];
+#pragma unroll
+            for (int t = 0; t < 16; t++) p[t] = st[4 * t];
+            for (int u = 0; u < cnt; u += 16) {
+                float nx[16];
+#pragma unroll
+                for (int t = 0; t < 16; t++) nx[t] = st[4 * min(u + 16 + t, kGmStage - 1)];
+#pragma unroll
+                for (int t = 0; t < 16; t++) if (u + t < cnt) acc += p[t];
+#pragma unroll
+                for (int t = 0; t < 16; t++) p[t] = nx[t];
+            }
+            m += cnt;
+            gm_wave_lds_order();      // the next members overwrite the stage
+        }
+        const float ax = __shfl(acc, 0), ay = __shfl(acc, 1), az = __shfl(acc, 2), aw = __shfl(acc, 3);
+        if (lane == 0) bsum[v] = make_float4(ax, ay, az, aw);
+    }
+}
+
+// The merge, one streaming pass: threads [0, n_tab) move the table's entries — entry i goes to i + (new voxels of the batch with a smaller key), and takes the batch's sum
+// and count if the batch holds its key —, threads [n_tab, n_tab + n_vox) place the batch's NEW voxels at (table keys below theirs) + (new voxels before them).
+__global__ void k_gm_merge(const unsigned long long* __restrict__ tkey, const float4* __restrict__ tsum, const int* __restrict__ tcnt, long long n_tab,
+                           const unsigned long long* __restrict__ bkey, const float4* __restrict__ bsum, const int* __restrict__ bcnt, const int* __restrict__ pos,
+                           const int* __restrict__ is_new, const int* __restrict__ new_rank /*exclusive scan of is_new, [n_vox+1]*/, int n_vox,
+                           unsigned long long* __restrict__ okey, float4* __restrict__ osum, int* __restrict__ ocnt) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_tab) {
+        const unsigned long long k = tkey[i];
+        int lo = 0, hi = n_vox;                       // lower_bound(bkey, k)
+        while (lo < hi) { const int mid = (int)(((long long)lo + hi) >> 1); if (bkey[mid] < k) lo = mid + 1; else hi = mid; }
+        const long long dst = i + new_rank[lo];
+        const bool hit = lo < n_vox && bkey[lo] == k;
+        okey[dst] = k; osum[dst] = hit ? bsum[lo] : tsum[i]; ocnt[dst] = hit ? bcnt[lo] : tcnt[i];
+    } else if (i < n_tab + n_vox) {
+        const int v = (int)(i - n_tab);
+        if (!is_new[v]) return;
+        const long long dst = (long long)pos[v] + new_rank[v];
+        okey[dst] = bkey[v]; osum[dst] = bsum[v]; ocnt[dst] = bcnt[v];
+    }
+}
+
+// CentroidPoint::get: sum / (float)count
+__global__ void k_gm_centroid(const float4* __restrict__ tsum, const int* __restrict__ tcnt, long long n, float4* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 s = tsum[i];
+    const float fn = (float)tcnt[i];
+    out[i] = make_float4(s.x / fn, s.y / fn, s.z / fn, s.w / fn);
+}
+
+}  // namespace lili
+
+namespace {
+
+constexpr int kKinds = 3;
+
+struct Slab { void* p = nullptr; size_t cap = 0, used = 0; };
+struct ArcCloud { float4* p = nullptr; int n = 0; bool present = false; };
+struct ArcKeyframe { ArcCloud c[kKinds]; double time = 0, t_po[3] = {0, 0, 0}, q_po[4] = {1, 0, 0, 0}, t_map[3] = {0, 0, 0}, q_map[4] = {1, 0, 0, 0}; };
+
+struct Folded { int id; double t[3], q[4]; };      // a keyframe the table holds and the map pose it was folded at
+struct GlobalMap {
+    void* sort = nullptr;                            // the batch sort's own buffers (lili_voxel.hip)
+    DevBuf key[2], sum[2], cnt[2];
+    int cur = 0;
+    long long n_tab = 0;
+    bool valid = false;                              // the table is the fold of `folded`
+    int kind = -1, interval = 0;
+    float leaf = 0.f;
+    double t_bl[3] = {0, 0, 0}, q_bl[4] = {1, 0, 0, 0};
+    std::vector<Folded> folded;
+    bool box_any = false;
+    float box[6] = {0, 0, 0, 0, 0, 0};               // of every finite point folded
+    int64_t n_raw = 0, folded_last = 0;
+    int incremental = 0, rebuilds = 0;
+    DevBuf raw, spts, flags, slot, head_pos, bkey, pos, is_new, new_rank, bsum, bcnt, long_list, sums, segs, res, out;
+    std::vector<lili::GmSeg> seg_host;
+    bool has_map = false;                            // `out` holds the centroids of a successful build
+    void clear_table() { n_tab = 0; folded.clear(); box_any = false; n_raw = 0; valid = false; has_map = false; }
+    void release() {
+        lili_vox_sort_free(sort); sort = nullptr;
+        for (DevBuf* b : {&key[0], &key[1], &sum[0], &sum[1], &cnt[0], &cnt[1], &raw, &spts, &flags, &slot, &head_pos, &bkey, &pos, &is_new, &new_rank, &bsum, &bcnt, &long_list, &sums,
+                          &segs, &res, &out}) b->release();
+        clear_table();
+    }
+    size_t table_bytes() const { size_t b = out.cap; for (int k = 0; k < 2; k++) b += key[k].cap + sum[k].cap + cnt[k].cap; return b; }
+    size_t work_bytes() const {
+        size_t b = lili_vox_sort_bytes(sort);
+        for (const DevBuf* d : {&raw, &spts, &flags, &slot, &head_pos, &bkey, &pos, &is_new, &new_rank, &bsum, &bcnt, &long_list, &sums, &segs, &res}) b += d->cap;
+        return b;
+    }
+};
+
+struct ArchiveState {
+    std::vector<Slab> slabs;
+    std::vector<ArcKeyframe> kf;
+    double t_bl[3] = {0, 0, 0}, q_bl[4] = {1, 0, 0, 0};
+    int64_t n_points[kKinds] = {0, 0, 0};
+    size_t bytes = 0;
+    std::vector<lili_cloud> view_tmp;
+    std::vector<double> pose_tmp;
+    GlobalMap gm;
+    void free_slabs() { for (auto& s : slabs) if (s.p) (void)hipFree(s.p); slabs.clear(); bytes = 0; }
+    void release() { free_slabs(); kf.clear(); gm.release(); }
+};
+
+ArchiveState* archive_of(lili_ctx* ctx) {
+    if (!ctx->ext_archive) { ctx->ext_archive = new ArchiveState(); ctx->ext_archive_free = [](void* p) { auto* s = static_cast<ArchiveState*>(p); s->release(); delete s; }; }
+    return static_cast<ArchiveState*>(ctx->ext_archive);
+}
+
+// keyframe_map_pose: (q_po * q_bl, q_po * t_bl + t_po) in f64, Eigen's operation order (L:2659-2660, 2489-2490; lili_om_amd/api.py keyframe_map_pose)
+void map_pose(const double t_po[3], const double a[4], const double t_bl[3], const double b[4], double t[3], double q[4]) {
+    q[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
+    q[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
+    q[2] = a[0] * b[2] + a[2] * b[0] + a[3] * b[1] - a[1] * b[3];
+    q[3] = a[0] * b[3] + a[3] * b[0] + a[1] * b[2] - a[2] * b[1];
+    const double u[3] = {a[1], a[2], a[3]};
+    double uv[3] = {u[1] * t_bl[2] - u[2] * t_bl[1], u[2] * t_bl[0] - u[0] * t_bl[2], u[0] * t_bl[1] - u[1] * t_bl[0]};
+    for (int k = 0; k < 3; k++) uv[k] = uv[k] + uv[k];
+    const double c[3] = {u[1] * uv[2] - u[2] * uv[1], u[2] * uv[0] - u[0] * uv[2], u[0] * uv[1] - u[1] * uv[0]};
+    for (int k = 0; k < 3; k++) t[k] = ((t_bl[k] + uv[k] * a[0]) + c[k]) + t_po[k];
+}
+
+size_t round256(size_t b) { return (b + 255) / 256 * 256; }
+
+int check_cloud(lili_ctx* ctx, const lili_cloud* c) {
+    if (!c) return LILI_OK;
+    ARGCHK(c->n == 0 || c->data, "archive_push: null data");
+    ARGCHK(c->stride >= 12 && c->stride % 4 == 0, "archive_push: stride must be a multiple of 4 and >= 12");
+    ARGCHK(c->aux_offset < 0 || (size_t)c->aux_offset + 4 <= c->stride, "archive_push: aux_offset outside the point");
+    ARGCHK(c->mem == LILI_MEM_HOST || c->mem == LILI_MEM_DEVICE, "archive_push: bad mem");
+    ARGCHK(c->n < (size_t)1 << 31, "archive_push: too many points");
+    return LILI_OK;
+}
+
+// room for `need` bytes in one piece: the last slab, or a new one (the keyframe's three clouds share one piece, so a push opens at most one slab).  The archive is
+// changed only by commit_room, once nothing of the push can fail any more.
+struct Room { int slab = -1; size_t off = 0; void* fresh = nullptr; size_t fresh_cap = 0; };
+int find_room(lili_ctx* ctx, ArchiveState* A, size_t need, Room& r) {
+    r = Room{};
+    if (need == 0) return LILI_OK;
+    if (!A->slabs.empty() && A->slabs.back().used + need <= A->slabs.back().cap) { r.slab = (int)A->slabs.size() - 1; r.off = A->slabs.back().used; return LILI_OK; }
+    const size_t cap = std::max(need, (size_t)ctx->archive_slab_mb << 20);
+    if (ctx->archive_max_mb > 0 && A->bytes + cap > ((size_t)ctx->archive_max_mb << 20))
+        return ctx->fail(LILI_E_NOMEM, "archive_push: the slab pool would exceed archive_max_mb (nothing is evicted; the archive is unchanged)");
+    if (hipMalloc(&r.fresh, cap + 256) != hipSuccess) { (void)hipGetLastError(); r.fresh = nullptr; return ctx->fail(LILI_E_NOMEM, "archive_push: out of device memory (the archive is unchanged)"); }
+    r.fresh_cap = cap;
+    return LILI_OK;
+}
+unsigned char* room_ptr(ArchiveState* A, const Room& r) { return r.fresh ? static_cast<unsigned char*>(r.fresh) : static_cast<unsigned char*>(A->slabs[r.slab].p) + r.off; }
+void commit_room(ArchiveState* A, const Room& r, size_t need) {
+    if (need == 0) return;
+    if (r.fresh) { Slab s; s.p = r.fresh; s.cap = r.fresh_cap; s.used = need; A->slabs.push_back(s); A->bytes += r.fresh_cap; }
+    else A->slabs[r.slab].used += need;
+}
+
+// the rows of a described cloud into `dst` (float4 rows), enqueued on the context's stream
+int ingest_rows(lili_ctx* ctx, const lili_cloud* c, float4* dst) {
+    if (c->n == 0) return LILI_OK;
+    const unsigned char* src = static_cast<const unsigned char*>(c->data);
+    if (c->mem == LILI_MEM_HOST) {
+        if (void* d = lili_pinned_dev_ptr(c->data, 4)) src = static_cast<const unsigned char*>(d);
+        else {
+            HIPCHK(ctx->staging.ensure(c->n * c->stride));
+            HIPCHK(hipMemcpyAsync(ctx->staging.p, c->data, c->n * c->stride, hipMemcpyHostToDevice, ctx->stream));
+            src = ctx->staging.as<unsigned char>();
+        }
+    }
+    hipLaunchKernelGGL(lili::k_arc_rows, dim3(nblocks((int64_t)c->n, 256)), dim3(256), 0, ctx->stream, src, (int)c->n, (int)c->stride, c->aux_offset, dst);
+    HIPCHK(hipGetLastError());
+    return LILI_OK;
+}
+
+// `dev[k]` (push_slot): float4 rows already on the device instead of a described cloud
+int push_keyframe(lili_ctx* ctx, const lili_cloud* const clouds[kKinds], const float4* const dev[kKinds], const int dev_n[kKinds], double time, const double t_po[3],
+                  const double q_po[4], int* id) {
+    ARGCHK(t_po && q_po, "archive_push: null pose");
+    for (int k = 0; k < kKinds; k++) { const int rc = check_cloud(ctx, clouds[k]); if (rc != LILI_OK) return rc; }
+    HIPCHK(hipSetDevice(ctx->device));
+    ArchiveState* A = archive_of(ctx);
+    ARGCHK(A->kf.size() < (size_t)INT_MAX, "archive_push: too many keyframes");
+    size_t need = 0, off[kKinds] = {0, 0, 0};
+    int n[kKinds] = {0, 0, 0};
+    bool present[kKinds] = {false, false, false};
+    for (int k = 0; k < kKinds; k++) {
+        present[k] = clouds[k] || dev[k];
+        n[k] = clouds[k] ? (int)clouds[k]->n : dev[k] ? dev_n[k] : 0;
+        off[k] = need;
+        need += round256((size_t)n[k] * sizeof(float4));
+    }
+    Room room;
+    int rc = find_room(ctx, A, need, room);
+    if (rc != LILI_OK) return rc;
+    unsigned char* base = need ? room_ptr(A, room) : nullptr;
+    bool sync = false;
+    for (int k = 0; k < kKinds && rc == LILI_OK; k++) {
+        if (!n[k]) continue;
+        float4* dst = reinterpret_cast<float4*>(base + off[k]);
+        if (clouds[k]) { rc = ingest_rows(ctx, clouds[k], dst); sync = true; }      // (a page-locked cloud is read across PCIe by the kernel: the call returns when it has been)
+        else if (hipMemcpyAsync(dst, dev[k], (size_t)n[k] * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) rc = ctx->fail(LILI_E_HIP, "archive_push: device copy failed");
+    }
+    if (rc == LILI_OK && sync && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ctx->fail(LILI_E_HIP, "archive_push: synchronisation failed");
+    if (rc != LILI_OK) { (void)hipStreamSynchronize(ctx->stream); if (room.fresh) (void)hipFree(room.fresh); return rc; }
+    commit_room(A, room, need);
+    ArcKeyframe kf;
+    for (int k = 0; k < kKinds; k++) {
+        kf.c[k].present = present[k]; kf.c[k].n = n[k]; kf.c[k].p = n[k] ? reinterpret_cast<float4*>(base + off[k]) : nullptr;
+        A->n_points[k] += n[k];
+    }
+    kf.time = time;
+    for (int k = 0; k < 3; k++) kf.t_po[k] = t_po[k];
+    for (int k = 0; k < 4; k++) kf.q_po[k] = q_po[k];
+    map_pose(kf.t_po, kf.q_po, A->t_bl, A->q_bl, kf.t_map, kf.q_map);
+    if (id) *id = (int)A->kf.size();
+    A->kf.push_back(kf);
+    return LILI_OK;
+}
+
+int copy_rows_out(lili_ctx* ctx, const void* d_rows, size_t count, lili_feature_out* out, const char* what) {
+    out->count = count;
+    const size_t k = std::min(out->count, out->capacity);
+    if (out->data && k) {
+        const size_t stride = out->stride ? out->stride : 16;
+        if (stride < 16) return ctx->fail(LILI_E_ARG, std::string(what) + ": stride must be >= 16");
+        const hipMemcpyKind kind = out->mem == LILI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (stride == 16) HIPCHK(hipMemcpyAsync(out->data, d_rows, k * 16, kind, ctx->stream));
+        else HIPCHK(hipMemcpy2DAsync(out->data, stride, d_rows, 16, 16, k, kind, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return LILI_OK;
+}
+
+int gm_scan(lili_ctx* ctx, GlobalMap& G, const int* in, int64_t n, int* out /*[n+1]*/) {
+    const int nb = nblocks(n, 2048);
+    HIPCHK(G.sums.ensure((size_t)nb * sizeof(int)));
+    hipLaunchKernelGGL(lili::k_scan_block_sums, dim3(nb), dim3(256), 0, ctx->stream, in, n, G.sums.as<int>());
+    hipLaunchKernelGGL(lili::k_scan_sums, dim3(1), dim3(256), 0, ctx->stream, G.sums.as<int>(), nb);
+    hipLaunchKernelGGL(lili::k_scan_apply, dim3(nb), dim3(256), 0, ctx->stream, in, n, G.sums.as<int>(), out);
+    HIPCHK(hipGetLastError());
+    return LILI_OK;
+}
+
+// a buffer of the table that is about to be WRITTEN from scratch grows by half at least (its old content is not needed: the merge fills it)
+hipError_t grow(DevBuf& b, size_t bytes) { return bytes + 256 <= b.cap ? hipSuccess : b.ensure(std::max(bytes, b.cap + b.cap / 2)); }
+
+// folds the batch described by G.seg_host (`total` >= 1 points) into the table.  Blocking.
+int fold_batch(lili_ctx* ctx, GlobalMap& G, int total) {
+    const int n = total, n_seg = (int)G.seg_host.size();
+    HIPCHK(G.segs.ensure((size_t)n_seg * sizeof(lili::GmSeg)));
+    HIPCHK(hipMemcpyAsync(G.segs.p, G.seg_host.data(), (size_t)n_seg * sizeof(lili::GmSeg), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(G.raw.ensure((size_t)n * 16));
+    hipLaunchKernelGGL(lili::k_gm_gather, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, G.segs.as<lili::GmSeg>(), n_seg, n, G.raw.as<float4>());
+    HIPCHK(hipGetLastError());
+    int status = 0;
+    float box[6];
+    unsigned sentinel = 0;
+    const unsigned* d_keys = nullptr;
+    const int* d_order = nullptr;
+    int rc = lili_voxel_sort_dev(ctx, &G.sort, G.raw.as<float4>(), n, G.leaf, &status, box, &sentinel, &d_keys, &d_order);
+    if (rc != LILI_OK) return rc;
+    if (status == 2) return LILI_OK;      // no finite point: nothing to fold
+    if (status == 3) return ctx->fail(LILI_E_ARG, kVoxelOverflowMsg);
+    // PCL's guard over EVERYTHING folded so far plus this batch: the box a one-shot filter of the concatenation would find
+    float nb6[6];
+    for (int k = 0; k < 3; k++) { nb6[k] = G.box_any ? std::min(G.box[k], box[k]) : box[k]; nb6[3 + k] = G.box_any ? std::max(G.box[3 + k], box[3 + k]) : box[3 + k]; }
+    {
+        const float inv_leaf = 1.0f / G.leaf;
+        double tot = 1.0;
+        for (int k = 0; k < 3; k++) { const int mn = (int)std::floor(nb6[k] * inv_leaf); tot *= (double)((int)std::floor(nb6[3 + k] * inv_leaf) - mn + 1); }
+        if (tot > 2147483647.0) return ctx->fail(LILI_E_ARG, kVoxelOverflowMsg);
+    }
+    const size_t w = (size_t)n + 1;
+    HIPCHK(G.spts.ensure((size_t)n * 16)); HIPCHK(G.flags.ensure(w * 4)); HIPCHK(G.slot.ensure(w * 4)); HIPCHK(G.head_pos.ensure(w * 4)); HIPCHK(G.bkey.ensure(w * 8));
+    HIPCHK(G.pos.ensure(w * 4)); HIPCHK(G.is_new.ensure(w * 4)); HIPCHK(G.new_rank.ensure(w * 4)); HIPCHK(G.bsum.ensure(w * 16)); HIPCHK(G.bcnt.ensure(w * 4));
+    HIPCHK(G.long_list.ensure(((size_t)n / lili::kGmShort + 1) * 4)); HIPCHK(G.res.ensure(16));
+    HIPCHK(hipMemsetAsync(G.res.p, 0, 16, ctx->stream));
+    hipLaunchKernelGGL(lili::k_gm_heads, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, d_keys, d_order, (const float4*)G.raw.as<float4>(), n, sentinel, G.flags.as<int>(), G.spts.as<float4>());
+    rc = gm_scan(ctx, G, G.flags.as<int>(), n, G.slot.as<int>());
+    if (rc != LILI_OK) return rc;
+    const int n_tab = (int)G.n_tab;
+    hipLaunchKernelGGL(lili::k_gm_voxels, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, d_keys, (const int*)G.flags.as<int>(), (const int*)G.slot.as<int>(), (const float4*)G.spts.as<float4>(), n,
+                       sentinel, 1.0f / G.leaf, (const unsigned long long*)G.key[G.cur].as<unsigned long long>(), n_tab, G.head_pos.as<int>(), G.bkey.as<unsigned long long>(), G.pos.as<int>(),
+                       G.is_new.as<int>(), G.res.as<int>());
+    HIPCHK(hipGetLastError());
+    int n_vox = 0, bad = 0;
+    rc = lili_readback_add(ctx, &n_vox, G.slot.as<int>() + n, sizeof(int));
+    if (rc == LILI_OK) rc = lili_readback_add(ctx, &bad, G.res.p, sizeof(int));
+    if (rc == LILI_OK) rc = lili_readback_finish(ctx);
+    if (rc != LILI_OK) return rc;
+    if (bad) return ctx->fail(LILI_E_ARG, "global_map: a point lies farther than 2^20 voxels from the origin");
+    if (n_vox <= 0 || n_vox > n) return ctx->fail(LILI_E_STATE, "global_map: internal: voxel count of a batch out of range");
+    if ((long long)n_tab + n_vox > 2147483647ll) return ctx->fail(LILI_E_ARG, kVoxelOverflowMsg);
+    rc = gm_scan(ctx, G, G.is_new.as<int>(), n_vox, G.new_rank.as<int>());
+    if (rc != LILI_OK) return rc;
+    hipLaunchKernelGGL(lili::k_gm_fold, dim3(nblocks(n_vox, 256)), dim3(256), 0, ctx->stream, n_vox, (const int*)G.head_pos.as<int>(), (const float4*)G.spts.as<float4>(), (const int*)G.pos.as<int>(),
+                       (const int*)G.is_new.as<int>(), (const float4*)G.sum[G.cur].as<float4>(), (const int*)G.cnt[G.cur].as<int>(), G.bsum.as<float4>(), G.bcnt.as<int>(), G.long_list.as<int>(),
+                       G.res.as<int>());
+    hipLaunchKernelGGL(lili::k_gm_fold_long, dim3(std::min(nblocks(n / lili::kGmShort + 1, 4), 2048)), dim3(256), 0, ctx->stream, (const int*)G.long_list.as<int>(), (const int*)G.res.as<int>(),
+                       (const int*)G.head_pos.as<int>(), (const float4*)G.spts.as<float4>(), G.bsum.as<float4>());
+    HIPCHK(hipGetLastError());
+    const int nxt = G.cur ^ 1;
+    const size_t cap = (size_t)n_tab + (size_t)n_vox;      // (upper bound: the number of new voxels comes back with the merge)
+    HIPCHK(grow(G.key[nxt], cap * 8)); HIPCHK(grow(G.sum[nxt], cap * 16)); HIPCHK(grow(G.cnt[nxt], cap * 4));
+    hipLaunchKernelGGL(lili::k_gm_merge, dim3(nblocks((int64_t)cap, 256)), dim3(256), 0, ctx->stream, (const unsigned long long*)G.key[G.cur].as<unsigned long long>(),
+                       (const float4*)G.sum[G.cur].as<float4>(), (const int*)G.cnt[G.cur].as<int>(), (long long)n_tab, (const unsigned long long*)G.bkey.as<unsigned long long>(),
+                       (const float4*)G.bsum.as<float4>(), (const int*)G.bcnt.as<int>(), (const int*)G.pos.as<int>(), (const int*)G.is_new.as<int>(), (const int*)G.new_rank.as<int>(), n_vox,
+                       G.key[nxt].as<unsigned long long>(), G.sum[nxt].as<float4>(), G.cnt[nxt].as<int>());
+    HIPCHK(hipGetLastError());
+    int n_new = 0;
+    rc = lili_readback_add(ctx, &n_new, G.new_rank.as<int>() + n_vox, sizeof(int));
+    if (rc == LILI_OK) rc = lili_readback_finish(ctx);
+    if (rc != LILI_OK) return rc;
+    if (n_new < 0 || n_new > n_vox) return ctx->fail(LILI_E_STATE, "global_map: internal: new-voxel count of a batch out of range");
+    G.cur = nxt;
+    G.n_tab = (long long)n_tab + n_new;
+    for (int k = 0; k < 6; k++) G.box[k] = nb6[k];
+    G.box_any = true;
+    return LILI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lili_archive_reset(lili_ctx* ctx) {
+    if (!ctx) return LILI_E_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ArchiveState* A = archive_of(ctx);
+    A->free_slabs();
+    A->kf.clear();
+    for (auto& n : A->n_points) n = 0;
+    A->gm.clear_table();      // (the extrinsic, the options and the statistics stay)
+    return LILI_OK;
+}
+
+int lili_archive_set_extrinsic(lili_ctx* ctx, const double t_bl[3], const double q_bl[4]) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(t_bl && q_bl, "archive_set_extrinsic: null argument");
+    ArchiveState* A = archive_of(ctx);
+    for (int k = 0; k < 3; k++) A->t_bl[k] = t_bl[k];
+    for (int k = 0; k < 4; k++) A->q_bl[k] = q_bl[k];
+    for (auto& kf : A->kf) map_pose(kf.t_po, kf.q_po, A->t_bl, A->q_bl, kf.t_map, kf.q_map);
+    return LILI_OK;
+}
+
+int lili_archive_push(lili_ctx* ctx, const lili_cloud* edge, const lili_cloud* surf, const lili_cloud* full, double time, const double t_po[3], const double q_po[4], int* id) {
+    if (!ctx) return LILI_E_ARG;
+    const lili_cloud* clouds[kKinds] = {edge, surf, full};
+    const float4* dev[kKinds] = {nullptr, nullptr, nullptr};
+    const int dev_n[kKinds] = {0, 0, 0};
+    return push_keyframe(ctx, clouds, dev, dev_n, time, t_po, q_po, id);
+}
+
+int lili_archive_push_slot(lili_ctx* ctx, int slot, const lili_cloud* full, double time, const double t_po[3], const double q_po[4], int* id) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "archive_push_slot: bad slot");
+    const KindSlot& e = ctx->slots[slot].k[LILI_KIND_EDGE];
+    const KindSlot& s = ctx->slots[slot].k[LILI_KIND_SURF];
+    static const float4 kNone{};      // a kind with queries but none of them: present, empty
+    const lili_cloud* clouds[kKinds] = {nullptr, nullptr, full};
+    const float4* dev[kKinds] = {e.has_queries ? (e.n_q ? e.q.as<float4>() : &kNone) : nullptr, s.has_queries ? (s.n_q ? s.q.as<float4>() : &kNone) : nullptr, nullptr};
+    const int dev_n[kKinds] = {e.has_queries ? (int)e.n_q : 0, s.has_queries ? (int)s.n_q : 0, 0};
+    return push_keyframe(ctx, clouds, dev, dev_n, time, t_po, q_po, id);
+}
+
+int lili_archive_set_poses(lili_ctx* ctx, int first, int n, const double* t_po, const double* q_po) {
+    if (!ctx) return LILI_E_ARG;
+    ArchiveState* A = archive_of(ctx);
+    ARGCHK(t_po && q_po, "archive_set_poses: null pose");
+    ARGCHK(first >= 0 && n >= 0 && (long long)first + n <= (long long)A->kf.size(), "archive_set_poses: first + n beyond the archive");
+    for (int i = 0; i < n; i++) {
+        ArcKeyframe& kf = A->kf[(size_t)first + i];
+        for (int k = 0; k < 3; k++) kf.t_po[k] = t_po[3 * i + k];
+        for (int k = 0; k < 4; k++) kf.q_po[k] = q_po[4 * i + k];
+        map_pose(kf.t_po, kf.q_po, A->t_bl, A->q_bl, kf.t_map, kf.q_map);
+    }
+    return LILI_OK;
+}
+
+int lili_archive_info(lili_ctx* ctx, int* n_keyframes, int64_t n_points[3], int64_t* bytes_used) {
+    if (!ctx) return LILI_E_ARG;
+    ArchiveState* A = archive_of(ctx);
+    if (n_keyframes) *n_keyframes = (int)A->kf.size();
+    if (n_points) for (int k = 0; k < kKinds; k++) n_points[k] = A->n_points[k];
+    if (bytes_used) *bytes_used = (int64_t)A->bytes;
+    return LILI_OK;
+}
+
+int lili_archive_pose(lili_ctx* ctx, int id, double t_po[3], double q_po[4], double* time) {
+    if (!ctx) return LILI_E_ARG;
+    ArchiveState* A = archive_of(ctx);
+    ARGCHK(id >= 0 && (size_t)id < A->kf.size(), "archive_pose: id out of range");
+    const ArcKeyframe& kf = A->kf[id];
+    if (t_po) for (int k = 0; k < 3; k++) t_po[k] = kf.t_po[k];
+    if (q_po) for (int k = 0; k < 4; k++) q_po[k] = kf.q_po[k];
+    if (time) *time = kf.time;
+    return LILI_OK;
+}
+
+int lili_archive_get(lili_ctx* ctx, int id, int kind, lili_feature_out* out) {
+    if (!ctx) return LILI_E_ARG;
+    ArchiveState* A = archive_of(ctx);
+    ARGCHK(out, "archive_get: null out");
+    ARGCHK(id >= 0 && (size_t)id < A->kf.size(), "archive_get: id out of range");
+    ARGCHK(kind >= 0 && kind < kKinds, "archive_get: unknown kind");
+    HIPCHK(hipSetDevice(ctx->device));
+    const ArcCloud& c = A->kf[id].c[kind];
+    return copy_rows_out(ctx, c.p, (size_t)c.n, out, "archive_get");
+}
+
+int lili_archive_view(lili_ctx* ctx, int id, int kind, lili_cloud* view) {
+    if (!ctx) return LILI_E_ARG;
+    ArchiveState* A = archive_of(ctx);
+    ARGCHK(view, "archive_view: null view");
+    ARGCHK(id >= 0 && (size_t)id < A->kf.size(), "archive_view: id out of range");
+    ARGCHK(kind >= 0 && kind < kKinds, "archive_view: unknown kind");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // (a push_slot copy may still be on the stream)
+    const ArcCloud& c = A->kf[id].c[kind];
+    view->data = c.p; view->n = (size_t)c.n; view->stride = 16; view->aux_offset = 12; view->mem = LILI_MEM_DEVICE;
+    return LILI_OK;
+}
+
+int lili_loop_cloud_archive(lili_ctx* ctx, int which, const int* ids, int n_ids, float leaf, int64_t* n_raw, int64_t* n_ds) {
+    if (!ctx) return LILI_E_ARG;
+    ArchiveState* A = archive_of(ctx);
+    ARGCHK(ids && n_ids >= 1, "loop_cloud_archive: bad argument");
+    for (int i = 0; i < n_ids; i++) ARGCHK(ids[i] >= 0 && (size_t)ids[i] < A->kf.size(), "loop_cloud_archive: id out of range");
+    A->view_tmp.clear(); A->pose_tmp.clear();
+    std::vector<double> q;
+    for (int i = 0; i < n_ids; i++) {
+        const ArcKeyframe& kf = A->kf[ids[i]];
+        for (int kind : {LILI_ARCHIVE_EDGE, LILI_ARCHIVE_SURF}) {
+            lili_cloud c{};
+            c.data = kf.c[kind].p; c.n = (size_t)kf.c[kind].n; c.stride = 16; c.aux_offset = 12; c.mem = LILI_MEM_DEVICE;
+            A->view_tmp.push_back(c);
+            for (int k = 0; k < 3; k++) A->pose_tmp.push_back(kf.t_map[k]);
+            for (int k = 0; k < 4; k++) q.push_back(kf.q_map[k]);
+        }
+    }
+    return lili_loop_cloud(ctx, which, A->view_tmp.data(), (int)A->view_tmp.size(), A->pose_tmp.data(), q.data(), leaf, n_raw, n_ds);
+}
+
+int lili_loop_detect(const float* positions, const double* times, int n, const float select_pose[3], double t_now, int variant, double radius, double local_thres,
+                     double global_thres, double time_last_loop, int slide_window_width, int* latest, int* his) {
+    if (n < 0 || (n > 0 && (!positions || !times)) || !select_pose || !latest || !his || (variant != 0 && variant != 1)) return LILI_E_ARG;
+    if (n == 0) return 0;
+    const float r2 = (float)(radius * radius);
+    std::vector<std::pair<float, int>> in;      // kd_tree_his_key_poses->radiusSearch in f32: d2 < radius^2, ascending d2 (ties: smaller index)
+    for (int i = 0; i < n; i++) {
+        const float dx = positions[3 * i] - select_pose[0], dy = positions[3 * i + 1] - select_pose[1], dz = positions[3 * i + 2] - select_pose[2];
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (d2 < r2) in.emplace_back(d2, i);
+    }
+    std::stable_sort(in.begin(), in.end(), [](const std::pair<float, int>& a, const std::pair<float, int>& b) { return a.first < b.first; });
+    int h = -1;
+    for (const auto& c : in)
+        if (std::fabs(times[c.second] - t_now) > global_thres) { h = c.second; break; }
+    if (variant == 0) {
+        if (h == -1) {
+            double max_time = 0.0;
+            int max_id = -1;
+            for (const auto& c : in) {
+                const double dt = std::fabs(times[c.second] - t_now);
+                if (local_thres < dt && dt < global_thres && dt > max_time) { max_time = dt; max_id = c.second; }
+            }
+            if (max_id == -1) return 0;
+            h = max_id;
+        }
+    } else if (h == -1 || std::fabs(time_last_loop - t_now) < 0.2) return 0;
+    *latest = n - slide_window_width;
+    *his = h;
+    return 1;
+}
+
+int lili_global_map(lili_ctx* ctx, int kind, int interval, float leaf, int64_t* n_raw, int64_t* n_map) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(kind >= 0 && kind < kKinds, "global_map: unknown kind");
+    ARGCHK(interval >= 1, "global_map: interval must be >= 1");
+    ARGCHK(leaf > 0 && std::isfinite(leaf), "global_map: leaf must be positive");
+    HIPCHK(hipSetDevice(ctx->device));
+    ArchiveState* A = archive_of(ctx);
+    GlobalMap& G = A->gm;
+    std::vector<int> sel;
+    for (size_t i = 0; i < A->kf.size(); i += (size_t)interval) sel.push_back((int)i);
+    // incremental: the table rests on the same settings, holds a prefix of the selection, and every keyframe it holds still has the map pose it was folded at, bit for bit
+    bool inc = G.valid && G.kind == kind && G.interval == interval && std::memcmp(&G.leaf, &leaf, sizeof(float)) == 0 && std::memcmp(G.t_bl, A->t_bl, sizeof(G.t_bl)) == 0 &&
+               std::memcmp(G.q_bl, A->q_bl, sizeof(G.q_bl)) == 0 && G.folded.size() <= sel.size();
+    for (size_t i = 0; inc && i < G.folded.size(); i++) {
+        const ArcKeyframe& kf = A->kf[sel[i]];
+        inc = G.folded[i].id == sel[i] && std::memcmp(G.folded[i].t, kf.t_map, sizeof(kf.t_map)) == 0 && std::memcmp(G.folded[i].q, kf.q_map, sizeof(kf.q_map)) == 0;
+    }
+    if (inc) G.incremental++;
+    else {
+        G.clear_table(); G.rebuilds++;
+        G.kind = kind; G.interval = interval; G.leaf = leaf;
+        std::memcpy(G.t_bl, A->t_bl, sizeof(G.t_bl)); std::memcpy(G.q_bl, A->q_bl, sizeof(G.q_bl));
+    }
+    G.valid = false; G.has_map = false;      // until the call is through: a failure leaves no half-built table behind
+    G.folded_last = 0;
+    const long long batch = ctx->global_map_batch_points;
+    const size_t first_new = G.folded.size();
+    // batches: runs of rows in keyframe order, cut wherever `batch` points are full (a keyframe may straddle batches: its rows stay in point order)
+    long long in_batch = 0;
+    G.seg_host.clear();
+    int rc = LILI_OK;
+    for (size_t s = first_new; s < sel.size() && rc == LILI_OK; s++) {
+        const ArcKeyframe& kf = A->kf[sel[s]];
+        long long done = 0;
+        const long long n = kf.c[kind].n;
+        while (done < n && rc == LILI_OK) {
+            const long long take = std::min(n - done, batch - in_batch);
+            lili::GmSeg g{};
+            g.src = kf.c[kind].p + done; g.first = in_batch;
+            for (int k = 0; k < 3; k++) g.t[k] = kf.t_map[k];
+            for (int k = 0; k < 4; k++) g.q[k] = kf.q_map[k];
+            G.seg_host.push_back(g);
+            in_batch += take; done += take;
+            if (in_batch == batch) { rc = fold_batch(ctx, G, (int)in_batch); G.folded_last += in_batch; in_batch = 0; G.seg_host.clear(); }
+        }
+    }
+    if (rc == LILI_OK && in_batch > 0) { rc = fold_batch(ctx, G, (int)in_batch); G.folded_last += in_batch; G.seg_host.clear(); }
+    if (rc != LILI_OK) { (void)hipStreamSynchronize(ctx->stream); G.clear_table(); return rc; }
+    for (size_t s = first_new; s < sel.size(); s++) {
+        const ArcKeyframe& kf = A->kf[sel[s]];
+        Folded f{};
+        f.id = sel[s];
+        std::memcpy(f.t, kf.t_map, sizeof(f.t)); std::memcpy(f.q, kf.q_map, sizeof(f.q));
+        G.folded.push_back(f);
+    }
+    G.n_raw += G.folded_last;
+    if (G.n_tab) {
+        HIPCHK(grow(G.out, (size_t)G.n_tab * 16));
+        hipLaunchKernelGGL(lili::k_gm_centroid, dim3(nblocks(G.n_tab, 256)), dim3(256), 0, ctx->stream, (const float4*)G.sum[G.cur].as<float4>(), (const int*)G.cnt[G.cur].as<int>(), G.n_tab,
+                           G.out.as<float4>());
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    G.valid = true; G.has_map = true;
+    if (n_raw) *n_raw = G.n_raw;
+    if (n_map) *n_map = G.n_tab;
+    return LILI_OK;
+}
+
+int lili_global_map_get(lili_ctx* ctx, lili_feature_out* out, int32_t* counts) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(out, "global_map_get: null out");
+    GlobalMap& G = archive_of(ctx)->gm;
+    if (!G.has_map) return ctx->fail(LILI_E_STATE, "global_map_get: no map yet (lili_global_map first)");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t k = std::min((size_t)G.n_tab, out->capacity);
+    if (counts && k) HIPCHK(hipMemcpyAsync(counts, G.cnt[G.cur].p, k * 4, hipMemcpyDefault, ctx->stream));
+    return copy_rows_out(ctx, G.out.p, (size_t)G.n_tab, out, "global_map_get");
+}
+
+int lili_global_map_stats(lili_ctx* ctx, int32_t* incremental, int32_t* rebuilds, int64_t* points_folded_last) {
+    if (!ctx) return LILI_E_ARG;
+    const GlobalMap& G = archive_of(ctx)->gm;
+    if (incremental) *incremental = G.incremental;
+    if (rebuilds) *rebuilds = G.rebuilds;
+    if (points_folded_last) *points_folded_last = G.folded_last;
+    return LILI_OK;
+}
+
+int lili_global_map_info(lili_ctx* ctx, int64_t* table_bytes, int64_t* work_bytes) {
+    if (!ctx) return LILI_E_ARG;
+    const GlobalMap& G = archive_of(ctx)->gm;
+    if (table_bytes) *table_bytes = (int64_t)G.table_bytes();
+    if (work_bytes) *work_bytes = (int64_t)G.work_bytes();
+    return LILI_OK;
+}
+
+}  // extern "C"

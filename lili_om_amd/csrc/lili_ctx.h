@@ -205,6 +205,11 @@ struct lili_ctx {
     void (*ext_voxel_free)(void*) = nullptr;
     void* ext_loop = nullptr;                // loop-closure registration: its source, target, index and work buffers (lili_loop.hip)
     void (*ext_loop_free)(void*) = nullptr;
+    void* ext_archive = nullptr;             // keyframe archive and global map (lili_archive.hip)
+    void (*ext_archive_free)(void*) = nullptr;
+    int archive_max_mb = 0;                  // bound on the archive's slab pool (0: none)
+    int archive_slab_mb = 64;
+    int global_map_batch_points = 1 << 21;   // points lili_global_map places, sorts and folds at a time
 
     int fail(int code, const std::string& m) { err = m; return code; }
     SlotState* state(int slot) { return states.as<SlotState>() + slot; }
@@ -223,6 +228,9 @@ struct lili_ctx {
         if (_e != hipSuccess) return ctx->fail(LILI_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 #define ARGCHK(cond, msg) do { if (!(cond)) return ctx->fail(LILI_E_ARG, msg); } while (0)
+
+// PCL's "leaf size is too small for the input dataset": the refusal of lili_voxel_filter, and of lili_global_map for everything it has folded
+constexpr const char* kVoxelOverflowMsg = "voxel_filter: leaf size too small for the cloud extent (voxel index would overflow int32, as in PCL)";
 
 static inline int nblocks(int64_t n, int per) { return (int)((n + per - 1) / per); }
 
@@ -249,6 +257,13 @@ int lili_voxel_filter_dev_enqueue(lili_ctx* ctx, const float4* d_pts, int n, flo
 int lili_voxel_filter_dev_complete(lili_ctx* ctx, const float4** d_out, int* n_out);
 int lili_localmap_push_dev(lili_ctx* ctx, int kind, const float4* d_pts, int n, const lili::SlotState* d_state, int width);
 int lili_localmap_ring_size(lili_ctx* ctx, int kind);
+// lili_voxel.hip -> lili_archive.hip: the stable order of a device cloud by pcl::VoxelGrid's box-relative voxel index, on sort buffers of the caller's own (`*priv`, created
+// here, freed by lili_vox_sort_free): the filter's state, its ring and its key-bit guesses stay as they are.  *status: 0 = sorted (keys / order valid until the next sort
+// on `*priv`; keys equal to `*sentinel` are the non-finite rows, last), 2 = no finite point, 3 = PCL's int32 voxel-index overflow; box = min xyz, max xyz of the finite
+// rows.  Blocking (the box is read back).
+int lili_voxel_sort_dev(lili_ctx* ctx, void** priv, const float4* d_pts, int n, float leaf, int* status, float box[6], unsigned* sentinel, const unsigned** d_keys, const int** d_order);
+void lili_vox_sort_free(void* priv);
+size_t lili_vox_sort_bytes(const void* priv);
 // lili_extract_livox.hip -> lili_pipeline.hip: the extraction enqueued without its synchronisation, and the counts taken afterwards
 int lili_extract_livox_enqueue(lili_ctx* ctx, const lili_cloud* scan, int curvature_offset, const double q_imu[4], const lili_livox_params* params);
 int lili_extract_livox_complete(lili_ctx* ctx);

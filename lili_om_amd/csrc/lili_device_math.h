@@ -24,6 +24,12 @@ __device__ __forceinline__ d3 qrot(dq q, d3 v) {
     uv = uv + uv;
     return (v + q.w * uv) + cross3(u, uv);
 }
+// transformCloud — L/src/BackendFusion.cpp:713-790: p' = q * p + t in f64, stored f32; aux carried along.  The ONE expression of every kernel that places a keyframe
+// in the map frame (push, push at a device pose, repose, loop submaps, global map): a re-posed keyframe is bit-identical to one pushed at that pose.
+__device__ __forceinline__ float4 transform_point(float4 p, dq q, d3 t) {
+    const d3 r = qrot(q, d3{(double)p.x, (double)p.y, (double)p.z}) + t;
+    return make_float4((float)r.x, (float)r.y, (float)r.z, p.w);
+}
 __device__ __forceinline__ dq qmul(dq a, dq b) {
     return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z,
             a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,

@@ -725,12 +725,7 @@ __global__ void k_vox_centroid64(const unsigned long long* __restrict__ keys, co
     }
 }
 
-// transformCloud — L/src/BackendFusion.cpp:713-790: p' = q * p + t in f64, stored f32; aux carried along.  The ONE expression of every kernel that places a keyframe
-// in the map frame (push, push at a device pose, repose): a re-posed keyframe is bit-identical to one pushed at that pose.
-__device__ __forceinline__ float4 transform_point(float4 p, dq q, d3 t) {
-    const d3 r = qrot(q, d3{(double)p.x, (double)p.y, (double)p.z}) + t;
-    return make_float4((float)r.x, (float)r.y, (float)r.z, p.w);
-}
+// (transform_point, the one expression that places a keyframe in the map frame, lives in lili_device_math.h: lili_archive.hip places keyframes with it too)
 // `src`: the rows as pushed (LiDAR frame), kept by the ring for lili_localmap_repose
 __global__ void k_transform_cloud(const float4* __restrict__ in, int n, dq q, d3 t, float4* __restrict__ out, float4* __restrict__ src) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1118,7 +1113,8 @@ static int radix_sort(lili_ctx* ctx, lili_detail::VoxelBuffers* V, int n, int bi
 
 // Stable order of a device cloud by pcl::VoxelGrid's voxel index (box-relative, App. B2): keys in V->keys_a, the order (source indices) in
 // V->vals_a.  Blocking: the bounding box is read back.
-static int voxel_sort(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const float4* d_pts, int n, float leaf, VoxDev& P, bool alt = false) {
+// `status` / `box` (lili_voxel_sort_dev): the two refusals come back as *status = 2 / 3 with LILI_OK instead of an error, and the finite rows' box as floats
+static int voxel_sort(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const float4* d_pts, int n, float leaf, VoxDev& P, bool alt = false, int* status = nullptr, float* box = nullptr) {
     unsigned* d_mm = ctx->misc.as<unsigned>();
     hipLaunchKernelGGL(k_box_init, dim3(1), dim3(64), 0, ctx->stream, d_mm);
     hipLaunchKernelGGL(k_bbox, dim3(std::min(nblocks(n, kBlock), 512)), dim3(kBlock), 0, ctx->stream, d_pts, n, d_mm);
@@ -1130,12 +1126,14 @@ static int voxel_sort(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const float4*
     int div_b[3];
     for (int k = 0; k < 3; k++) {
         float mn = dec(mm[k]), mx = dec(mm[3 + k]);
-        if (!(mn <= mx)) return ctx->fail(LILI_E_ARG, "voxel_filter: cloud holds no finite point");
+        if (!(mn <= mx)) { if (status) { *status = 2; return LILI_OK; } return ctx->fail(LILI_E_ARG, "voxel_filter: cloud holds no finite point"); }
+        if (box) { box[k] = mn; box[3 + k] = mx; }
         P.min_b[k] = (int)std::floor(mn * P.inv_leaf);
         div_b[k] = (int)std::floor(mx * P.inv_leaf) - P.min_b[k] + 1;
     }
     const double total = (double)div_b[0] * (double)div_b[1] * (double)div_b[2];
-    if (total > 2147483647.0) return ctx->fail(LILI_E_ARG, "voxel_filter: leaf size too small for the cloud extent (voxel index would overflow int32, as in PCL)");
+    if (total > 2147483647.0) { if (status) { *status = 3; return LILI_OK; } return ctx->fail(LILI_E_ARG, kVoxelOverflowMsg); }
+    if (status) *status = 0;
     P.mul[0] = 1; P.mul[1] = div_b[0]; P.mul[2] = div_b[0] * div_b[1];
     P.sentinel = (unsigned)total;                 // <= 2^31 - 1
     int bits = 1; while (bits < 32 && (1ull << bits) < (unsigned long long)total + 1ull) bits++;   // keys 0 .. total (sentinel included)
@@ -1810,5 +1808,24 @@ int lili_loop_assemble(lili_ctx* ctx, void** priv, const lili_cloud* clouds, int
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));      // (the segment table and the staging rows are read by then)
     if (n_ds) *n_ds = n_out;
+    return LILI_OK;
+}
+
+// lili_archive.hip: the sort of one batch of the global map (declared in lili_ctx.h), the measured way on buffers of its own
+struct SortVox { lili_detail::VoxelBuffers V; };
+void lili_vox_sort_free(void* p) { if (p) { auto* S = static_cast<SortVox*>(p); S->V.release(); delete S; } }
+size_t lili_vox_sort_bytes(const void* p) {
+    if (!p) return 0;
+    const auto& V = static_cast<const SortVox*>(p)->V;
+    return V.keys_a.cap + V.keys_b.cap + V.vals_a.cap + V.vals_b.cap + V.hist.cap + V.hist_scan.cap + V.sums.cap;
+}
+int lili_voxel_sort_dev(lili_ctx* ctx, void** priv, const float4* d_pts, int n, float leaf, int* status, float box[6], unsigned* sentinel, const unsigned** d_keys, const int** d_order) {
+    if (!*priv) *priv = new SortVox();
+    auto* S = static_cast<SortVox*>(*priv);
+    { const int rl = lili_lazy_sources_clear_of(ctx, ctx->misc.p, 64); if (rl != LILI_OK) return rl; }      // the box words (ctx->misc)
+    VoxDev P;
+    const int rc = voxel_sort(ctx, &S->V, d_pts, n, leaf, P, false, status, box);
+    if (rc != LILI_OK || *status != 0) return rc;
+    *sentinel = P.sentinel; *d_keys = S->V.keys_a.as<unsigned>(); *d_order = S->V.vals_a.as<int>();
     return LILI_OK;
 }

@@ -83,10 +83,11 @@ def _as_cloud(a):
 class LoopClosure:
     """The reference's loop-closure thread minus iSAM2.  variant "livox" (LiLi-OM: one source keyframe, two time thresholds) or "rot" (LiLi-OM-ROT: six source
     keyframes, one threshold, no second attempt within 0.2 s of the last loop).  Keyframe clouds (edge_frames[i], surf_frames[i]) are numpy rows (x, y, z[, aux])
-    or api.Cloud descriptions of host, page-locked or device memory: the caller keeps the keyframe archive."""
+    or api.Cloud descriptions of host, page-locked or device memory kept by the caller — or, with `archive` (a KeyframeArchive), the keyframes the archive holds on the
+    device: assemble and perform then take keyframe ids only, and detect / perform may read positions (the body translations) and times from the archive."""
 
     def __init__(self, ctx, variant="livox", lc_search_radius=10.0, lc_map_width=20, lc_icp_thres=0.2, local_lc_time_thres=25.0, global_lc_time_thres=25.0,
-                 lc_time_thres=120.0, q_bl=(1.0, 0.0, 0.0, 0.0), t_bl=(0.0, 0.0, 0.0), leaf=0.4, slide_window_width=3):
+                 lc_time_thres=120.0, q_bl=(1.0, 0.0, 0.0, 0.0), t_bl=(0.0, 0.0, 0.0), leaf=0.4, slide_window_width=3, archive=None):
         if variant not in ("livox", "rot"):
             raise ValueError("variant must be 'livox' or 'rot'")
         self.ctx, self.lib, self.variant = ctx, ctx.lib, variant
@@ -97,11 +98,17 @@ class LoopClosure:
         self.time_last_loop = 0.0
         self.params = default_icp_params()
         self.last = None
+        self.archive = archive      # (its extrinsic is the archive's own: KeyframeArchive(ctx, q_bl, t_bl))
 
     # ---- detectLoopClosure: candidate selection (L:2431-2473, R:2240-2263) ----
     def detect(self, positions, times, select_pose, t_now):
         """(latest_idx, his_idx) or None.  positions (n, 3) keyframe positions (pose_cloud_frame), times (n,), select_pose the query position, t_now time_new_odom.
-        The radius search is kd_tree_his_key_poses->radiusSearch in f32: d2 < radius^2, ascending d2 (ties: smaller index)."""
+        The radius search is kd_tree_his_key_poses->radiusSearch in f32: d2 < radius^2, ascending d2 (ties: smaller index).  With an archive, positions / times
+        may be None: the archive's body translations and times."""
+        if self.archive is not None and (positions is None or times is None):
+            ts, _, tm = self.archive.poses()
+            positions = ts if positions is None else positions
+            times = tm if times is None else times
         pos = np.asarray(positions, np.float32).reshape(-1, 3)
         times = np.asarray(times, np.float64).reshape(-1)
         if pos.shape[0] == 0:
@@ -154,9 +161,17 @@ class LoopClosure:
         self.ctx._chk(self.lib.lili_loop_cloud(self.ctx.h, which, arr, len(clouds), _ptr(t), _ptr(q), float(self.leaf), C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def assemble(self, latest_idx, his_idx, ts_po, qs_po, edge_frames, surf_frames):
+    def _cloud_archive(self, which, keyframes):
+        ids = (C.c_int * len(keyframes))(*[int(k) for k in keyframes])
+        a, b = C.c_int64(0), C.c_int64(0)
+        self.ctx._chk(self.lib.lili_loop_cloud_archive(self.ctx.h, which, ids, len(keyframes), float(self.leaf), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def assemble(self, latest_idx, his_idx, ts_po=None, qs_po=None, edge_frames=None, surf_frames=None):
         """Both submaps of detectLoopClosure on the device (L:2475-2548): per keyframe edge then surf, transformCloud at (q_po q_bl, q_po t_bl + t_po),
-        VoxelGrid(leaf).  Returns ((n_raw, n_ds) of the source, (n_raw, n_ds) of the target)."""
+        VoxelGrid(leaf).  Returns ((n_raw, n_ds) of the source, (n_raw, n_ds) of the target).  With an archive: clouds and poses are the archive's."""
+        if self.archive is not None and edge_frames is None:
+            return (self._cloud_archive(LOOP_SOURCE, self.source_keyframes(latest_idx)), self._cloud_archive(LOOP_TARGET, self.target_keyframes(latest_idx, his_idx)))
         ts_po = np.asarray(ts_po, np.float64).reshape(-1, 3)
         qs_po = np.asarray(qs_po, np.float64).reshape(-1, 4)
         s = self._cloud(LOOP_SOURCE, self.source_keyframes(latest_idx), ts_po, qs_po, edge_frames, surf_frames)
@@ -171,10 +186,15 @@ class LoopClosure:
         self.last = _result_dict(r)
         return self.last
 
-    def perform(self, positions, times, select_pose, t_now, ts_po, qs_po, edge_frames, surf_frames):
+    def perform(self, positions, times, select_pose, t_now, ts_po=None, qs_po=None, edge_frames=None, surf_frames=None):
         """performLoopClosure up to the BetweenFactor: None, or (latest_idx, his_idx, pose_from, pose_to, between, noise_score) with poses as (t (3,), q (4,) wxyz):
         pose_from = the latest keyframe's pose corrected by the ICP transform, pose_to = the candidate's, between = pose_from^-1 pose_to; noise_score = the
-        fitness (the variances of the reference's Diagonal noise model).  The caller adds BetweenFactor(latest, his, between, noise) and updates iSAM2."""
+        fitness (the variances of the reference's Diagonal noise model).  The caller adds BetweenFactor(latest, his, between, noise) and updates iSAM2.
+        With an archive: the keyframes' clouds, poses and (where None) positions and times are the archive's."""
+        if self.archive is not None and edge_frames is None:
+            ts_po, qs_po, a_tm = self.archive.poses()
+            positions = ts_po if positions is None else positions
+            times = a_tm if times is None else times
         det = self.detect(positions, times, select_pose, t_now)
         if det is None:
             return None
