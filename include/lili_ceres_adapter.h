@@ -14,6 +14,12 @@
 // by ONE cost function per keyframe:
 //   problem.AddResidualBlock(new lili::LidarBatchFactor(ctx, slot, mask, params), nullptr, t_ptr, q_ptr);
 //
+// Without Ceres at all: lili_window_solve (lili_hip.h) takes the place of ceres::Solve in optimizeSlidingWindowWithLandMark —
+//   lili_window_problem pr = {n_kf, mask, slots, imu /* n_kf - 1 lili_window_imu from the pre-integrations */, prior_or_null, sb_prior_or_null, {0}, {0}};
+//   lili_window_solve(ctx, &pr, &params, nullptr, state /* n_kf x (t3, q4, speed-bias9) */, &summary);
+// the pre-integration, the construction of the marginalisation prior, the write-back gates and the quaternion sign unification stay the caller's
+// (INTEGRATION.md §1).  The classes below are for callers that keep ceres::Solve.
+//
 // Contract mirrored from ceres::CostFunction: Evaluate(parameters, residuals, jacobians) with
 // parameters[0] = t[3], parameters[1] = q[4] (w,x,y,z); jacobians / jacobians[i] may be NULL; row-major
 // num_residuals x block_size; returning false makes Ceres reject the step.  The block has 9 residuals:

@@ -467,8 +467,9 @@ void lili_lm_default_options(lili_lm_options* opt);
 int lili_s2m_solve_lm(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, const lili_lm_options* options,
                       lili_lm_summary* summary);
 /* The same for several slots (the keyframes of the sliding window) concurrently, one launch per slot on forked streams; summaries:
- * n_slots entries (optional).  The joint window of the reference couples the keyframes through the IMU factors, which stay with the
- * caller's solver (include/lili_ceres_adapter.h); this call is for per-keyframe refinements and for the front-end. */
+ * n_slots entries (optional).  The joint window of the reference couples the keyframes through the IMU factors: that problem is
+ * lili_window_solve below (or the caller's solver around include/lili_ceres_adapter.h); this call is for per-keyframe refinements and
+ * for the front-end. */
 int lili_s2m_solve_lm_window(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params,
                              const lili_lm_options* options, lili_lm_summary* summaries);
 
@@ -601,6 +602,58 @@ int lili_gn_step_host(const double gram[64], double t[3], double q[4], double de
 /* Square-root form of a Gram record for ceres (see include/lili_ceres_adapter.h): a 9-residual block whose
  * J^T J, J^T r and cost equal those of the N robustified lidar residuals the Gram was reduced from. */
 int lili_gram_to_factor(const double gram[64], double cost, double residuals[9], double jacobian[63]);
+
+/* ---- the joint keyframe window on the device: lidar + IMU factors + priors (lili_window.hip) -----------------
+ * The problem ceres::Solve gets in optimizeSlidingWindowWithLandMark (L/src/BackendFusion.cpp:843-1007): n_kf keyframes x (t[3], q[4] w x y z
+ * with QuaternionParameterization, speed-bias[9] = v, ba, bg), the lidar blocks of every keyframe (the records of the slots' last association,
+ * robustified by params->loss; correspondences stay fixed), one IMU factor between consecutive keyframes (ImuFactor.h:18-144), and either the
+ * marginalisation prior (MarginalizationFactor::Evaluate) or the speed-bias priors (PriorFactor.h:13-23); the last three enter without a loss.
+ * What stays with the caller: the IMU pre-integration, building the marginalisation prior (Schur complement, eigen-decomposition), the
+ * write-back gates and the quaternion sign unification — their RESULTS are handed in as the plain arrays below (host memory, copied once per
+ * call).  A state is n_kf x 16 doubles: t[3], q[4], speed-bias[9] per keyframe; "local" means 15 per keyframe: t, the 3 quaternion-plus
+ * coordinates, speed-bias. */
+#define LILI_WINDOW_MAX_KF 4          /* 15 * n_kf <= 60 local dimensions: every matrix of the solve stays in LDS */
+#define LILI_WINDOW_STATE_DOUBLES 16
+typedef struct lili_window_imu {      /* what Preintegration holds when the solve starts */
+    double sum_dt, g[3];
+    double delta_p[3], delta_q[4] /* w x y z */, delta_v[3];
+    double lin_ba[3], lin_bg[3];      /* the biases the pre-integration was linearised at */
+    double jacobian[225], covariance[225];   /* 15 x 15 row-major, order O_P O_R O_V O_BA O_BG */
+} lili_window_imu;
+typedef struct lili_window_prior {    /* r = r0 + J0 * dx(x, x0) over the kept blocks */
+    int32_t n_rows, n_cols;           /* J0 is n_rows x n_cols row-major, both <= 60; n_cols = sum of the blocks' local sizes (3, 3, 9) */
+    int32_t n_blocks, reserved_;
+    const int32_t* block_kind;        /* per kept block: 0 = t, 1 = q (dx = +-2 vec(normalized(q0^-1 q)), sign of its w), 2 = speed-bias */
+    const int32_t* block_keyframe;    /* keyframe of the window the block belongs to; a (keyframe, kind) pair at most once */
+    const double* x0;                 /* the blocks' linearisation points, global sizes (3, 4, 9), concatenated */
+    const double* J0;
+    const double* r0;
+} lili_window_prior;
+typedef struct lili_window_problem {
+    int32_t n_kf;                     /* 2 .. LILI_WINDOW_MAX_KF */
+    int32_t kind_mask;                /* lidar kinds; 0 = no lidar blocks (lili_window_evaluate only) */
+    const int32_t* slots;             /* matcher slot of every keyframe */
+    const lili_window_imu* imu;       /* n_kf - 1 factors, or NULL */
+    const lili_window_prior* prior;   /* or NULL */
+    const double* sb_prior;           /* n_kf x 9 speed-bias prior means, a row starting with NaN = none on that keyframe; or NULL.  r = 15 (sb - mean) */
+    double q_lb[4], t_lb[3];          /* extrinsic of the lidar blocks; q_lb all zero = the one in params */
+} lili_window_problem;
+/* sqrt_info = LLT(covariance^-1).matrixL()^T of an IMU factor, as the calls below compute it once per solve on the host (15 x 15 row-major).
+ * LILI_E_ARG if the covariance is not positive definite.  Needs no context and no GPU. */
+int lili_window_sqrt_info(const double covariance[225], double sqrt_info[225]);
+/* What Ceres' evaluator hands its minimiser at `state`: cost = sum 1/2 rho(r^2) of the lidar records + 1/2 |r|^2 of every other block, gradient
+ * (15 n_kf) and J^T J ((15 n_kf)^2 row-major, optional) in local coordinates.  The slots' poses are not touched.  Blocking. */
+int lili_window_evaluate(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const double* state,
+                         double* cost, double* gradient, double* JtJ);
+/* ceres::Solve on that problem as ONE persistent launch (the loop of lili_s2m_solve_lm on 15 n_kf dimensions, the accept / reject decision
+ * taken on the whole window).  state: in = initial, out = final (written when summary != NULL; with summary == NULL the call is asynchronous
+ * and lili_window_state_get fetches it later).  The slots' device poses end at the final (t, q) of their keyframes.  Refusals (bad n_kf,
+ * a slot without records, a covariance that is not positive definite, a prior whose n_cols does not match its blocks) leave them untouched.
+ * summary->n_surf / n_edge: the first keyframe's. */
+int lili_window_solve(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const lili_lm_options* options,
+                      double* state, lili_lm_summary* summary);
+/* the final state of the last lili_window_solve of this context (n_kf x 16 doubles).  Blocking. */
+int lili_window_state_get(lili_ctx* ctx, int n_kf, double* state);
 
 /* ---- callers / data formats either side of the path ------------------------- */
 

@@ -87,6 +87,21 @@ class LmSummary(C.Structure):
                          for e in self.it[:self.n_logged]])
 
 
+class WindowImu(C.Structure):
+    _fields_ = [("sum_dt", C.c_double), ("g", C.c_double * 3), ("delta_p", C.c_double * 3), ("delta_q", C.c_double * 4), ("delta_v", C.c_double * 3),
+                ("lin_ba", C.c_double * 3), ("lin_bg", C.c_double * 3), ("jacobian", C.c_double * 225), ("covariance", C.c_double * 225)]
+
+
+class WindowPrior(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("n_cols", C.c_int32), ("n_blocks", C.c_int32), ("reserved_", C.c_int32), ("block_kind", C.POINTER(C.c_int32)),
+                ("block_keyframe", C.POINTER(C.c_int32)), ("x0", C.POINTER(C.c_double)), ("J0", C.POINTER(C.c_double)), ("r0", C.POINTER(C.c_double))]
+
+
+class WindowProblem(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("kind_mask", C.c_int32), ("slots", C.POINTER(C.c_int32)), ("imu", C.POINTER(WindowImu)), ("prior", C.POINTER(WindowPrior)),
+                ("sb_prior", C.POINTER(C.c_double)), ("q_lb", C.c_double * 4), ("t_lb", C.c_double * 3)]
+
+
 class S2MParams(C.Structure):
     _fields_ = [("variant", C.c_int), ("loss", C.c_int), ("loss_a", C.c_double), ("lidar_const", C.c_double),
                 ("kd_max_radius", C.c_double), ("edge_gate", C.c_double), ("surf_dist_thres", C.c_double),
@@ -261,6 +276,10 @@ _SIGS = {
     "lili_global_map_get": (C.c_int, [C.c_void_p, C.POINTER(FeatureOut), C.c_void_p]),
     "lili_global_map_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "lili_global_map_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lili_window_sqrt_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lili_window_evaluate": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lili_window_solve": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.POINTER(LmOptions), C.c_void_p, C.POINTER(LmSummary)]),
+    "lili_window_state_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 
@@ -993,6 +1012,108 @@ class BackendKeyframes:
         """Warm-up of the local map (while the reference's recent_surf_keyframes.size() < local_map_width, L/src/BackendFusion.cpp:1407-1443): the keyframes of both
         rings, oldest first, take the map-frame poses (keyframe_map_poses) the last solve gave them — before the next prepare, which pushes the joining keyframe at its own."""
         _repose(self.ctx, MASK_SURF | MASK_EDGE, ts, qs)
+
+
+def window_sqrt_info(covariance):
+    """sqrt_info = LLT(covariance^-1).matrixL()^T of an IMU factor as lili_window_evaluate / lili_window_solve compute it (host code, no GPU)."""
+    cov = np.ascontiguousarray(np.asarray(covariance, np.float64).reshape(15, 15))
+    out = np.zeros((15, 15))
+    if load_library().lili_window_sqrt_info(_ptr(cov), _ptr(out)) != 0:
+        raise LiliError("window_sqrt_info: the covariance is not positive definite")
+    return out
+
+
+def pack_preintegration(pre, g=None):
+    """lili_window_imu from an object with a pre-integration's attributes: delta_p, delta_q (w x y z), delta_v, jacobian, covariance (15 x 15),
+    linearized_ba, linearized_bg (or ba, bg), sum_dt; g: the gravity vector of the factor (default: pre.g_vec, else (0, 0, -9.805))."""
+    w = WindowImu()
+    w.sum_dt = float(pre.sum_dt)
+    if g is None:
+        g = getattr(pre, "g_vec", (0.0, 0.0, -9.805))
+    ba = pre.linearized_ba if hasattr(pre, "linearized_ba") else pre.ba
+    bg = pre.linearized_bg if hasattr(pre, "linearized_bg") else pre.bg
+    for name, val, n in (("g", g, 3), ("delta_p", pre.delta_p, 3), ("delta_q", pre.delta_q, 4), ("delta_v", pre.delta_v, 3), ("lin_ba", ba, 3), ("lin_bg", bg, 3),
+                         ("jacobian", pre.jacobian, 225), ("covariance", pre.covariance, 225)):
+        a = np.asarray(val, np.float64).reshape(-1)
+        if a.size != n:
+            raise LiliError(f"pack_preintegration: {name} has {a.size} values, expected {n}")
+        getattr(w, name)[:] = a.tolist()
+    return w
+
+
+class WindowSolver:
+    """The joint keyframe window on the device (lili_window_evaluate / lili_window_solve): lidar blocks of the matcher's slots + IMU factors + the
+    marginalisation prior or the speed-bias priors.  A state is (n_kf, 16): t[3], q[4] (w x y z), speed-bias[9] per keyframe."""
+
+    def __init__(self, ctx, matcher):
+        self.ctx, self.lib, self.matcher = ctx, ctx.lib, matcher
+        self._keep = []
+        self.problem = None
+
+    def set_problem(self, slots, kind_mask=MASK_SURF | MASK_EDGE, imu=None, prior=None, sb_prior=None, n_kf=None):
+        """slots: matcher slot per keyframe (None with kind_mask 0); imu: n_kf - 1 WindowImu or pre-integration objects; prior: dict(block_kind,
+        block_keyframe, x0, J0 (rows x cols), r0[, n_cols]); sb_prior: (n_kf, 9) means, a NaN row = no prior on that keyframe."""
+        n_kf = int(n_kf if n_kf is not None else len(slots))
+        pr = WindowProblem()
+        keep = []
+        pr.n_kf, pr.kind_mask = n_kf, int(kind_mask)
+        if slots is not None:
+            arr = (C.c_int32 * len(slots))(*[int(s) for s in slots])
+            keep.append(arr)
+            pr.slots = arr
+        if imu is not None:
+            arr = (WindowImu * len(imu))(*[f if isinstance(f, WindowImu) else pack_preintegration(f) for f in imu])
+            if len(imu) != n_kf - 1:
+                raise LiliError("WindowSolver: n_kf - 1 IMU factors expected")
+            keep.append(arr)
+            pr.imu = arr
+        if prior is not None:
+            wp = WindowPrior()
+            kind = np.ascontiguousarray(prior["block_kind"], np.int32)
+            kf = np.ascontiguousarray(prior["block_keyframe"], np.int32)
+            x0 = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float64).reshape(-1) for v in prior["x0"]]) if isinstance(prior["x0"], (list, tuple)) else prior["x0"], np.float64)
+            J0 = np.ascontiguousarray(prior["J0"], np.float64)
+            r0 = np.ascontiguousarray(prior["r0"], np.float64)
+            wp.n_rows, wp.n_cols, wp.n_blocks = J0.shape[0], int(prior.get("n_cols", J0.shape[1])), len(kind)
+            wp.block_kind = kind.ctypes.data_as(C.POINTER(C.c_int32)); wp.block_keyframe = kf.ctypes.data_as(C.POINTER(C.c_int32))
+            wp.x0 = x0.ctypes.data_as(C.POINTER(C.c_double)); wp.J0 = J0.ctypes.data_as(C.POINTER(C.c_double)); wp.r0 = r0.ctypes.data_as(C.POINTER(C.c_double))
+            keep += [wp, kind, kf, x0, J0, r0]
+            pr.prior = C.pointer(wp)
+        if sb_prior is not None:
+            sb = np.ascontiguousarray(np.asarray(sb_prior, np.float64).reshape(n_kf, 9))
+            keep.append(sb)
+            pr.sb_prior = sb.ctypes.data_as(C.POINTER(C.c_double))
+        self._keep, self.problem = keep, pr
+        return self
+
+    def _state(self, state):
+        s = np.ascontiguousarray(np.asarray(state, np.float64).reshape(-1, 16)).copy()
+        if self.problem is None or s.shape[0] != self.problem.n_kf:
+            raise LiliError("WindowSolver: set_problem first, state must be (n_kf, 16)")
+        return s
+
+    def evaluate(self, state, want_jtj=True):
+        """(cost, gradient[15 n_kf], JtJ[15 n_kf, 15 n_kf] or None) in local coordinates at `state`."""
+        s = self._state(state)
+        n = 15 * s.shape[0]
+        cost, g = np.zeros(1), np.zeros(n)
+        H = np.zeros((n, n)) if want_jtj else None
+        self.ctx._chk(self.lib.lili_window_evaluate(self.ctx.h, C.byref(self.problem), C.byref(self.matcher.params), _ptr(s), _ptr(cost), _ptr(g), _ptr(H)))
+        return float(cost[0]), g, H
+
+    def solve(self, state, options=None, want_summary=True):
+        """ceres::Solve on the window, one persistent launch: (final state (n_kf, 16), summary dict) — or (None, None) asynchronously
+        (want_summary=False; last_state() fetches the state later)."""
+        s = self._state(state)
+        sm = LmSummary() if want_summary else None
+        self.ctx._chk(self.lib.lili_window_solve(self.ctx.h, C.byref(self.problem), C.byref(self.matcher.params), C.byref(options) if options is not None else None,
+                                                 _ptr(s), C.byref(sm) if sm is not None else None))
+        return (s, sm.as_dict()) if sm is not None else (None, None)
+
+    def last_state(self):
+        s = np.zeros((self.problem.n_kf, 16))
+        self.ctx._chk(self.lib.lili_window_state_get(self.ctx.h, self.problem.n_kf, _ptr(s)))
+        return s
 
 
 def gn_step_host(gram, t, q):

@@ -64,6 +64,11 @@ struct IterArgs {      // must match lili_s2m_coop.hip
 template <int L> __global__ void k_iterate_coop(AssocArgs, AssocArgs, MatchParams, IterArgs);
 }  // namespace lili
 
+// lili_match.hip -> lili_window.hip (the lidar blocks of the joint window)
+int lili_match_window_records(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const double* t, const double* q, double* d_gram);
+int lili_match_lm_args(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, const lili_lm_options* options, int max_blocks, lili::LmArgs* out);
+lili::MatchParams lili_match_device_params(const lili_s2m_params* params);
+
 // A kernel launch that may drop the barrier against the kernels enqueued before it on the stream (`any_order`: hipExtAnyOrderLaunch — the AQL packet goes without the
 // barrier bit, so it is dispatched as soon as the packets in front of it have been DISPATCHED, not completed).  Only the association that follows a reduction + GN
 // kernel uses it (option "overlap_gn"): its waves poll for the pose that kernel publishes.  Where the runtime ignores the flag the launch is an ordinary one.

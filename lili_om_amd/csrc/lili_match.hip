@@ -1612,3 +1612,13 @@ int lili_gram_to_factor(const double gram[64], double cost, double residuals[9],
 }
 
 }  // extern "C"
+
+// lili_window.hip builds the joint window on what this file already does for the lidar blocks: the slots' Gram records at host poses
+// (lili_s2m_linearize_window's launches, records left in d_gram), the arguments of a slot's share of a persistent LM launch, the device parameters.
+int lili_match_window_records(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const double* t, const double* q, double* d_gram) {
+    return linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, nullptr, nullptr, d_gram, 0);
+}
+int lili_match_lm_args(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, const lili_lm_options* options, int max_blocks, lili::LmArgs* out) {
+    return launch_solve_lm(ctx, slot, kind_mask, params, options, max_blocks, out);
+}
+lili::MatchParams lili_match_device_params(const lili_s2m_params* params) { return to_device_params(params); }

@@ -1,0 +1,807 @@
+// The joint keyframe window on the device (include/lili_hip.h: lili_window_*): what ceres::Solve gets in optimizeSlidingWindowWithLandMark
+// (L/src/BackendFusion.cpp:843-1007) — n_kf keyframes x (t, q, speed-bias), the lidar blocks of every keyframe, the IMU factors between consecutive
+// keyframes (ImuFactor.h:18-144), the marginalisation prior (MarginalizationFactor.cpp:233-286) or the speed-bias priors (PriorFactor.h:13-23).
+//
+//   lili_window_evaluate   cost, gradient and J^T J in local coordinates at one state: the lidar part is the per-slot Gram of lili_s2m_linearize_window
+//                          (same launches, same fixed-order reduction), k_window_evaluate (ONE wave) projects it to local coordinates and adds the
+//                          O(1) factors in f64 (win_build).
+//   lili_window_solve      Ceres' trust-region loop as lili_s2m_lm.hip restates it, on 15 n_kf local dimensions, ONE persistent launch: the workgroups
+//                          of slot k evaluate that keyframe's records at the candidate (lin_surf_body / lin_edge_body, partials published as keyed
+//                          granules), wave 0 of EVERY workgroup gathers the partials of ALL slots in index order (<= kWinGroup workgroups per slot: one
+//                          hop), runs win_build, takes the accept / reject decision and proposes the next candidate from a Cholesky factorisation of
+//                          the Jacobi-scaled J^T J + D^2 / radius in LDS — the same instructions on the same bits in every workgroup, so no decision
+//                          is broadcast.  Partial buffers are double-buffered by the evaluation's parity as in k_solve_lm; every wait is bounded
+//                          (xchg_gather) and ends the launch with LILI_LM_STALLED.
+//
+// The factors are restated from the semantics SURVEY records; the checker's restatement (tests/test_window_solve_gpu.py) is the referee.
+#include "lili_s2m_dev.h"
+#include "lili_launch.h"
+
+#include <cmath>
+#include <cstring>
+
+namespace lili {
+
+constexpr int kWinMaxKf = LILI_WINDOW_MAX_KF, kWinMaxN = 15 * kWinMaxKf, kWinMaxBlocks = 3 * kWinMaxKf;
+constexpr int kWinThreads = 512;      // as k_solve_lm: 8 waves, the launch may use 256 VGPRs per lane
+constexpr int kWinGroup = 16;         // workgroups per slot at most: every slot's partials are gathered in ONE hop
+
+struct WinImuDev {
+    double sum_dt, g[3], dp[3], dq[4], dv[3], ba[3], bg[3];
+    double dp_dba[9], dp_dbg[9], dq_dbg[9], dv_dba[9], dv_dbg[9];      // blocks of the pre-integration's Jacobian
+    double sqrt_info[225];
+};
+struct WinDev {      // the problem as the kernels read it (one upload per call)
+    int n_kf, n_imu, has_prior, n_rows, n_cols, n_blocks, pad0_, pad1_;
+    int blk_kind[kWinMaxBlocks], blk_kf[kWinMaxBlocks], blk_col[kWinMaxBlocks] /* first column in J0 */, blk_x0[kWinMaxBlocks] /* offset in x0 */;
+    int col_blk[kWinMaxN];      // block of every column of J0
+    int sb_has[kWinMaxKf];
+    double sb_mean[9 * kWinMaxKf];
+    double state[16 * kWinMaxKf];
+    double x0[16 * kWinMaxKf];
+    double r0[kWinMaxN];
+    double J0[kWinMaxN * kWinMaxN];      // n_rows x n_cols, tight
+    double A0[kWinMaxN * kWinMaxN];      // J0^T J0, n_cols x n_cols (host, once per call)
+    WinImuDev imu[kWinMaxKf - 1];
+};
+
+// one evaluation of the window in LDS: inputs x and lid, outputs H, g, cost; the rest is scratch of win_build
+struct WinSys {
+    double H[kWinMaxN * kWinMaxN];      // N x N, N = 15 n_kf
+    double g[kWinMaxN];
+    double cost;
+    double x[kWinMaxKf][16];            // t, q, speed-bias per keyframe
+    double lid[kWinMaxKf][72];          // per keyframe: the 8x8 lidar Gram (rows J0..J6, r), [64] = its robust cost
+    double Jraw[kWinMaxKf - 1][15][31]; // IMU factors: un-whitened local Jacobian (30 columns: keyframe i, keyframe j) and residual (column 30)
+    double Jw[15][31];                  // one factor, whitened
+    double pr[kWinMaxN], dx[kWinMaxN], pv[kWinMaxN];
+    double T[kWinMaxBlocks][9];         // prior, quaternion blocks: d dx / d local (3x3)
+};
+
+__device__ __forceinline__ dq qnormalized(dq q) {
+    const double n = sqrt(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+    return {q.w / n, q.x / n, q.y / n, q.z / n};
+}
+// rows 1..3 of Qleft(q) (math_tools.h): [v | w I + [v]x]
+__device__ __forceinline__ void qleft_rows(dq q, double m[3][4]) {
+    m[0][0] = q.x; m[0][1] = q.w; m[0][2] = -q.z; m[0][3] = q.y;
+    m[1][0] = q.y; m[1][1] = q.z; m[1][2] = q.w; m[1][3] = -q.x;
+    m[2][0] = q.z; m[2][1] = -q.y; m[2][2] = q.x; m[2][3] = q.w;
+}
+// ceres::QuaternionParameterization::ComputeJacobian (4x3)
+__device__ __forceinline__ void plus_jac(const double* q, double m[4][3]) {
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    m[0][0] = -x; m[0][1] = -y; m[0][2] = -z;
+    m[1][0] = w; m[1][1] = z; m[1][2] = -y;
+    m[2][0] = -z; m[2][1] = w; m[2][2] = x;
+    m[3][0] = y; m[3][1] = -x; m[3][2] = w;
+}
+__device__ __forceinline__ void qmat3(dq q, double R[3][3]) {      // Eigen toRotationMatrix
+    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
+    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w, txx = tx * q.x, txy = ty * q.x, txz = tz * q.x, tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
+    R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
+    R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
+    R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
+}
+__device__ __forceinline__ d3 m3v(const double* m, d3 v) {
+    return {m[0] * v.x + m[1] * v.y + m[2] * v.z, m[3] * v.x + m[4] * v.y + m[5] * v.z, m[6] * v.x + m[7] * v.y + m[8] * v.z};
+}
+__device__ __forceinline__ double d3c(d3 v, int i) { return i == 0 ? v.x : i == 1 ? v.y : v.z; }
+
+// ImuFactor::Evaluate of ONE factor by ONE lane, un-whitened, Jacobians in local coordinates: J[15][31] (zeroed by the caller), column 30 = residual
+__device__ __noinline__ void win_imu_raw(const WinImuDev& f, const double* xi, const double* xj, double (*J)[31]) {
+    const d3 Pi{xi[0], xi[1], xi[2]}, Pj{xj[0], xj[1], xj[2]};
+    const dq Qi = qnormalized(dq{xi[3], xi[4], xi[5], xi[6]}), Qj = qnormalized(dq{xj[3], xj[4], xj[5], xj[6]});
+    const d3 Vi{xi[7], xi[8], xi[9]}, Bai{xi[10], xi[11], xi[12]}, Bgi{xi[13], xi[14], xi[15]};
+    const d3 Vj{xj[7], xj[8], xj[9]}, Baj{xj[10], xj[11], xj[12]}, Bgj{xj[13], xj[14], xj[15]};
+    const d3 g{f.g[0], f.g[1], f.g[2]};
+    const double s = f.sum_dt;
+    const d3 dba = Bai - d3{f.ba[0], f.ba[1], f.ba[2]}, dbg = Bgi - d3{f.bg[0], f.bg[1], f.bg[2]};
+    const d3 th = m3v(f.dq_dbg, dbg);
+    const dq cq = qmul(dq{f.dq[0], f.dq[1], f.dq[2], f.dq[3]}, dq{1.0, 0.5 * th.x, 0.5 * th.y, 0.5 * th.z});
+    const d3 cv = (d3{f.dv[0], f.dv[1], f.dv[2]} + m3v(f.dv_dba, dba)) + m3v(f.dv_dbg, dbg);
+    const d3 cp = (d3{f.dp[0], f.dp[1], f.dp[2]} + m3v(f.dp_dba, dba)) + m3v(f.dp_dbg, dbg);
+    const dq Qi_inv = qinv(Qi);
+    const d3 tmp = (((-0.5 * s * s) * g + Pj) - Pi) - s * Vi;
+    const d3 tmp1 = ((-s) * g + Vj) - Vi;
+    const d3 rp = qrot(Qi_inv, tmp) - cp;
+    const dq rq = qnormalized(qmul(qinv(cq), qmul(Qi_inv, Qj)));
+    const d3 rv = qrot(Qi_inv, tmp1) - cv;
+    const d3 rba = Baj - Bai, rbg = Bgj - Bgi;
+    for (int i = 0; i < 3; i++) {
+        J[i][30] = d3c(rp, i); J[3 + i][30] = 2.0 * (i == 0 ? rq.x : i == 1 ? rq.y : rq.z); J[6 + i][30] = d3c(rv, i);
+        J[9 + i][30] = d3c(rba, i); J[12 + i][30] = d3c(rbg, i);
+    }
+    double Ri[3][3];
+    qmat3(Qi_inv, Ri);
+    double Pq_i[4][3], Pq_j[4][3];
+    plus_jac(xi + 3, Pq_i);
+    plus_jac(xj + 3, Pq_j);
+    const d3 u{Qi.x, Qi.y, Qi.z};
+    // d(Qi^-1 v) / d(w | x y z) as the reference writes it (ImuFactor.h:63-64, 71-72), times the plus-Jacobian of Qi: rows r0.., local columns 3..5
+    auto dq_block = [&](d3 v, int r0) {
+        const d3 uxv = cross3(u, v);
+        const double uv = dot3(u, v);
+        double m[3][4];
+        for (int i = 0; i < 3; i++) {
+            m[i][0] = 2.0 * (Qi.w * d3c(v, i) + d3c(uxv, i));
+            for (int c = 0; c < 3; c++) {
+                // u.v I + u v^T - v u^T - w [v]x
+                const double sk = (i == c) ? 0.0 : ((c == (i + 1) % 3) ? -d3c(v, 3 - i - c) : d3c(v, 3 - i - c));
+                m[i][1 + c] = 2.0 * ((((i == c ? uv : 0.0) + d3c(u, i) * d3c(v, c)) - d3c(v, i) * d3c(u, c)) - Qi.w * sk);
+            }
+        }
+        for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++)
+            J[r0 + i][3 + c] = ((m[i][0] * Pq_i[0][c] + m[i][1] * Pq_i[1][c]) + m[i][2] * Pq_i[2][c]) + m[i][3] * Pq_i[3][c];
+    };
+    dq_block(tmp, 0);
+    dq_block(tmp1, 6);
+    for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++) {
+        J[i][c] = -Ri[i][c];                    // d r_p / d Pi
+        J[i][6 + c] = -Ri[i][c] * s;            // d r_p / d Vi
+        J[i][9 + c] = -f.dp_dba[3 * i + c];
+        J[i][12 + c] = -f.dp_dbg[3 * i + c];
+        J[6 + i][6 + c] = -Ri[i][c];            // d r_v / d Vi
+        J[6 + i][9 + c] = -f.dv_dba[3 * i + c];
+        J[6 + i][12 + c] = -f.dv_dbg[3 * i + c];
+        J[9 + i][9 + c] = i == c ? -1.0 : 0.0;
+        J[12 + i][12 + c] = i == c ? -1.0 : 0.0;
+        J[i][15 + c] = Ri[i][c];                // d r_p / d Pj
+        J[6 + i][21 + c] = Ri[i][c];            // d r_v / d Vj
+        J[9 + i][24 + c] = i == c ? 1.0 : 0.0;
+        J[12 + i][27 + c] = i == c ? 1.0 : 0.0;
+    }
+    {   // d r_q / d Qi = -2 (Qleft(Qj^-1) Qright(cq)) rows 1..3, times the plus-Jacobian of Qi
+        double L[3][4];
+        qleft_rows(qinv(Qj), L);
+        // Qright(p): [p0, -pv^T; pv, p0 I - [pv]x]
+        const double R[4][4] = {{cq.w, -cq.x, -cq.y, -cq.z}, {cq.x, cq.w, cq.z, -cq.y}, {cq.y, -cq.z, cq.w, cq.x}, {cq.z, cq.y, -cq.x, cq.w}};
+        for (int i = 0; i < 3; i++) {
+            double m[4];
+            for (int c = 0; c < 4; c++) m[c] = -2.0 * (((L[i][0] * R[0][c] + L[i][1] * R[1][c]) + L[i][2] * R[2][c]) + L[i][3] * R[3][c]);
+            for (int c = 0; c < 3; c++) J[3 + i][3 + c] = ((m[0] * Pq_i[0][c] + m[1] * Pq_i[1][c]) + m[2] * Pq_i[2][c]) + m[3] * Pq_i[3][c];
+        }
+    }
+    {   // d r_q / d Bgi = -LeftQuatMatrix(Qj^-1 Qi cq)[0:3, 0:3] dq_dbg,  [0:3, 0:3] = w I + [v]x
+        const dq a = qmul(qmul(qinv(Qj), Qi), cq);
+        const double M[3][3] = {{a.w, -a.z, a.y}, {a.z, a.w, -a.x}, {-a.y, a.x, a.w}};
+        for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++)
+            J[3 + i][12 + c] = -((M[i][0] * f.dq_dbg[c] + M[i][1] * f.dq_dbg[3 + c]) + M[i][2] * f.dq_dbg[6 + c]);
+    }
+    {   // d r_q / d Qj = 2 Qleft(cq^-1 Qi^-1) rows 1..3, times the plus-Jacobian of Qj
+        double L[3][4];
+        qleft_rows(qmul(qinv(cq), Qi_inv), L);
+        for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++)
+            J[3 + i][18 + c] = 2.0 * (((L[i][0] * Pq_j[0][c] + L[i][1] * Pq_j[1][c]) + L[i][2] * Pq_j[2][c]) + L[i][3] * Pq_j[3][c]);
+    }
+}
+
+// MarginalizationFactor::Evaluate, block b by ONE lane: dx of the block, and for a quaternion block T = +-2 Qleft(q0^-1)[1:4, :] * plus(q) — the reference's own
+// Jacobian of dx in global columns times Ceres' plus-Jacobian, not the derivative of the normalised expression
+__device__ __noinline__ void win_prior_block(const WinDev* pb, WinSys& s, int b) {
+    const int kind = pb->blk_kind[b], kf = pb->blk_kf[b], col = pb->blk_col[b];
+    const double* x0 = pb->x0 + pb->blk_x0[b];
+    if (kind == 0) { for (int i = 0; i < 3; i++) s.dx[col + i] = s.x[kf][i] - x0[i]; }
+    else if (kind == 2) { for (int i = 0; i < 9; i++) s.dx[col + i] = s.x[kf][7 + i] - x0[i]; }
+    else {
+        const dq q0i = qinv(dq{x0[0], x0[1], x0[2], x0[3]});
+        const dq d = qmul(q0i, dq{s.x[kf][3], s.x[kf][4], s.x[kf][5], s.x[kf][6]});
+        const double sg = d.w >= 0.0 ? 2.0 : -2.0;
+        const dq n = qnormalized(d);
+        s.dx[col] = sg * n.x; s.dx[col + 1] = sg * n.y; s.dx[col + 2] = sg * n.z;
+        double L[3][4], Pq[4][3];
+        qleft_rows(q0i, L);
+        plus_jac(&s.x[kf][3], Pq);
+        for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++)
+            s.T[b][3 * i + c] = sg * (((L[i][0] * Pq[0][c] + L[i][1] * Pq[1][c]) + L[i][2] * Pq[2][c]) + L[i][3] * Pq[3][c]);
+    }
+}
+__device__ __forceinline__ int win_blk_local(const WinDev* pb, int b) { return 15 * pb->blk_kf[b] + (pb->blk_kind[b] == 0 ? 0 : pb->blk_kind[b] == 1 ? 3 : 6); }
+
+// The local system of the window at s.x by ONE wave (all 64 lanes call it, control flow uniform): s.H = J^T J, s.g = J^T r, s.cost.  Every sum runs in a
+// fixed order, so every workgroup of the solve holds the same bits.
+__device__ __noinline__ void win_build(const WinDev* __restrict__ pb, WinSys& s) {
+    const int lane = threadIdx.x & 63;
+    const int n_kf = pb->n_kf, N = 15 * n_kf, n_imu = pb->n_imu;
+    for (int e = lane; e < N * N; e += 64) s.H[e] = 0.0;
+    if (lane < N) s.g[lane] = 0.0;
+    for (int e = lane; e < n_imu * 15 * 31; e += 64) (&s.Jraw[0][0][0])[e] = 0.0;
+    LILI_WAVE_SYNC();
+    double cost = 0.0;      // lane 0's is the one that counts
+    // ---- lidar: H_kk = P^T G77 P, g_k = P^T G7r with P = diag(I3, plus-Jacobian(q_k)) (lm_local_system of lili_s2m_lm.hip)
+    for (int k = 0; k < n_kf; k++) {
+        const double* gram = s.lid[k];
+        const double x0 = s.x[k][3], x1 = s.x[k][4], x2 = s.x[k][5], x3 = s.x[k][6];
+        auto jcol = [&](int c, double o[4]) {
+            o[0] = c == 0 ? -x1 : c == 1 ? -x2 : -x3;
+            o[1] = c == 0 ? x0 : c == 1 ? x3 : -x2;
+            o[2] = c == 0 ? -x3 : c == 1 ? x0 : x1;
+            o[3] = c == 0 ? x2 : c == 1 ? -x1 : x0;
+        };
+        if (lane < 42) {
+            const int a = lane < 36 ? lane / 6 : lane - 36, b = lane < 36 ? lane % 6 : 7;
+            double jb[4] = {0, 0, 0, 0}, ja[4] = {0, 0, 0, 0};
+            if (b >= 3 && b < 6) jcol(b - 3, jb);
+            if (a >= 3) jcol(a - 3, ja);
+            auto Mrow = [&](int i) -> double {
+                if (b < 3 || b == 7) return gram[i * 8 + b];
+                return ((gram[i * 8 + 3] * jb[0] + gram[i * 8 + 4] * jb[1]) + gram[i * 8 + 5] * jb[2]) + gram[i * 8 + 6] * jb[3];
+            };
+            double v;
+            if (a < 3) v = Mrow(a);
+            else v = ((ja[0] * Mrow(3) + ja[1] * Mrow(4)) + ja[2] * Mrow(5)) + ja[3] * Mrow(6);
+            if (lane < 36) s.H[(15 * k + a) * N + 15 * k + b] = v; else s.g[15 * k + a] = v;
+        }
+        cost += gram[64];
+    }
+    // ---- speed-bias priors: r = 15 (sb - mean), J = 15 I
+    if (lane < 9 * n_kf) {
+        const int k = lane / 9, i = lane - 9 * k;
+        double r = 0.0;
+        if (pb->sb_has[k]) {
+            r = 15.0 * (s.x[k][7 + i] - pb->sb_mean[9 * k + i]);
+            const int c = 15 * k + 6 + i;
+            s.H[c * N + c] = 225.0;
+            s.g[c] = 15.0 * r;
+        }
+        s.pr[lane] = r;
+    }
+    // ---- IMU factors, raw: one lane per factor
+    if (lane < n_imu) win_imu_raw(pb->imu[lane], s.x[lane], s.x[lane + 1], s.Jraw[lane]);
+    LILI_WAVE_SYNC();
+    {
+        double c = 0.0;
+        for (int i = 0; i < 9 * n_kf; i++) c += s.pr[i] * s.pr[i];
+        cost += 0.5 * c;
+    }
+    for (int f = 0; f < n_imu; f++) {
+        const double* S = pb->imu[f].sqrt_info;
+        LILI_WAVE_SYNC();
+        for (int e = lane; e < 15 * 31; e += 64) {
+            const int i = e / 31, c = e - 31 * i;
+            double v = 0.0;
+            for (int j = 0; j < 15; j++) v += S[15 * i + j] * s.Jraw[f][j][c];
+            s.Jw[i][c] = v;
+        }
+        LILI_WAVE_SYNC();
+        for (int e = lane; e < 900; e += 64) {
+            const int a = e / 30, b = e - 30 * a;
+            double v = 0.0;
+            for (int i = 0; i < 15; i++) v += s.Jw[i][a] * s.Jw[i][b];
+            s.H[(15 * f + a) * N + 15 * f + b] += v;
+        }
+        if (lane < 30) {
+            double v = 0.0;
+            for (int i = 0; i < 15; i++) v += s.Jw[i][lane] * s.Jw[i][30];
+            s.g[15 * f + lane] += v;
+        }
+        double c = 0.0;
+        for (int i = 0; i < 15; i++) c += s.Jw[i][30] * s.Jw[i][30];
+        cost += 0.5 * c;
+    }
+    // ---- marginalisation prior: r = r0 + J0 dx; H += T^T (J0^T J0) T, g += T^T J0^T r
+    if (pb->has_prior) {
+        const int n_rows = pb->n_rows, n_cols = pb->n_cols, n_blocks = pb->n_blocks;
+        LILI_WAVE_SYNC();
+        if (lane < n_blocks) win_prior_block(pb, s, lane);
+        LILI_WAVE_SYNC();
+        if (lane < n_rows) {
+            double r = pb->r0[lane];
+            for (int c = 0; c < n_cols; c++) r += pb->J0[lane * n_cols + c] * s.dx[c];
+            s.pr[lane] = r;
+        }
+        LILI_WAVE_SYNC();
+        if (lane < n_cols) {
+            double v = 0.0;
+            for (int r = 0; r < n_rows; r++) v += pb->J0[r * n_cols + lane] * s.pr[r];
+            s.pv[lane] = v;
+        }
+        LILI_WAVE_SYNC();
+        if (lane < n_cols) {
+            const int b = pb->col_blk[lane], a = lane - pb->blk_col[b];
+            double v = s.pv[lane];
+            if (pb->blk_kind[b] == 1) { const int c0 = pb->blk_col[b]; v = (s.T[b][a] * s.pv[c0] + s.T[b][3 + a] * s.pv[c0 + 1]) + s.T[b][6 + a] * s.pv[c0 + 2]; }
+            s.g[win_blk_local(pb, b) + a] += v;
+        }
+        for (int e = lane; e < n_cols * n_cols; e += 64) {
+            const int ca = e / n_cols, cb = e - n_cols * ca;
+            const int ba = pb->col_blk[ca], bb = pb->col_blk[cb];
+            const int ia = ca - pb->blk_col[ba], ib = cb - pb->blk_col[bb];
+            const bool qa = pb->blk_kind[ba] == 1, qb = pb->blk_kind[bb] == 1;
+            double v = 0.0;
+            for (int i = 0; i < (qa ? 3 : 1); i++) {
+                const int ra = qa ? pb->blk_col[ba] + i : ca;
+                const double wa = qa ? s.T[ba][3 * i + ia] : 1.0;
+                double row = 0.0;
+                for (int j = 0; j < (qb ? 3 : 1); j++) {
+                    const int rb = qb ? pb->blk_col[bb] + j : cb;
+                    row += pb->A0[ra * n_cols + rb] * (qb ? s.T[bb][3 * j + ib] : 1.0);
+                }
+                v += wa * row;
+            }
+            s.H[(win_blk_local(pb, ba) + ia) * N + win_blk_local(pb, bb) + ib] += v;
+        }
+        double c = 0.0;
+        for (int r = 0; r < n_rows; r++) c += s.pr[r] * s.pr[r];
+        cost += 0.5 * c;
+    }
+    if (lane == 0) s.cost = cost;
+    LILI_WAVE_SYNC();
+}
+
+// lili_window_evaluate: one workgroup of one wave.  rec: n_kf lidar records of k_window_reduce (64 Gram + cost + counts) or nullptr; out: cost, g[N], H[N * N]
+__global__ __launch_bounds__(64) void k_window_evaluate(const WinDev* __restrict__ pb, const double* __restrict__ rec, double* __restrict__ out, int want_h) {
+    __shared__ WinSys s;
+    const int lane = threadIdx.x;
+    const int n_kf = pb->n_kf, N = 15 * n_kf;
+    for (int e = lane; e < 16 * n_kf; e += 64) s.x[e / 16][e % 16] = pb->state[e];
+    for (int e = lane; e < 72 * n_kf; e += 64) s.lid[e / 72][e % 72] = rec ? rec[e] : 0.0;
+    LILI_WAVE_SYNC();
+    win_build(pb, s);
+    if (lane == 0) out[0] = s.cost;
+    if (lane < N) out[1 + lane] = s.g[lane];
+    if (want_h) for (int e = lane; e < N * N; e += 64) out[1 + N + e] = s.H[e];
+}
+
+struct WinSolveArgs {
+    LmArgs a[kWinMaxKf];
+    int first_block[kWinMaxKf];
+    int n;
+    const WinDev* prob;
+    double* state_out;             // n x 16 doubles
+    lili_lm_summary* summary;
+};
+struct WinShared {
+    WinSys sys;                    // the candidate: sys.x is what the workgroups evaluate next; sys.H doubles as the work matrix of the Cholesky factorisation
+    double H[kWinMaxN * kWinMaxN], g[kWinMaxN];      // the system at the accepted point
+    double scale[kWinMaxN], d[kWinMaxN], tr[kWinMaxN];
+    double x[kWinMaxKf][16];       // accepted point
+    double vals[kWinGroup][40];
+    double tot[kWinMaxKf][40];
+    double cost, radius, decrease, model_change, step_norm;
+    int it, n_ok, term, go, n_invalid, stalled, take, max_iter;
+    int counts[2];
+    double function_tolerance, gradient_tolerance, parameter_tolerance;
+    double max_radius, min_radius, min_relative_decrease, min_lm_diagonal, max_lm_diagonal;
+};
+
+// The trust-region step from the accepted point by ONE wave (lm_propose of lili_s2m_lm.hip on N dimensions): returns with sh.go = 1 and sh.sys.x = candidate,
+// or sh.go = 0.  (H_s + D^2) d = -g_s by a left-looking Cholesky factorisation, lane = row; a non-positive pivot is an INVALID step like a model that does
+// not descend (radius halved, five in a row end the solve with LILI_LM_NUMERICAL_FAILURE).
+__device__ __noinline__ void win_propose(WinShared& sh, const int n_kf) {
+    const int lane = threadIdx.x & 63;
+    const int N = 15 * n_kf;
+    const bool in = lane < N;
+    double* A = sh.sys.H;
+    for (;;) {
+        const int it = sh.it;
+        if (it >= sh.max_iter) { if (lane == 0) { sh.term = LILI_LM_MAX_ITERATIONS; sh.go = 0; } return; }
+        double gmax = 0.0;
+        for (int i = 0; i < N; i++) gmax = fmax(gmax, fabs(sh.g[i]));
+        if (gmax <= sh.gradient_tolerance) { if (lane == 0) { sh.term = LILI_LM_GRADIENT_TOLERANCE; sh.it = it + 1; sh.go = 0; } return; }
+        const double radius = sh.radius;
+        if (!(radius > sh.min_radius)) { if (lane == 0) { sh.term = LILI_LM_MIN_RADIUS; sh.go = 0; } return; }
+        for (int e = lane; e < N * N; e += 64) {
+            const int i = e / N, j = e - N * i;
+            double v = sh.H[e] * sh.scale[i] * sh.scale[j];
+            if (i == j) v += fmin(fmax(v, sh.min_lm_diagonal), sh.max_lm_diagonal) / radius;      // D^2 = clamp(diag H_s) / radius
+            A[e] = v;
+        }
+        LILI_WAVE_SYNC();
+        bool okc = true;
+        for (int j = 0; j < N; j++) {
+            double acc = 0.0;
+            if (in && lane >= j) {
+                acc = A[lane * N + j];
+                for (int k = 0; k < j; k++) acc -= A[lane * N + k] * A[j * N + k];
+            }
+            const double piv = __shfl(acc, j);
+            okc = okc && (piv > 0.0);
+            const double l = sqrt(piv);
+            if (in && lane >= j) A[lane * N + j] = lane == j ? l : acc / l;
+            LILI_WAVE_SYNC();
+        }
+        double bv = in ? -(sh.g[lane] * sh.scale[lane]) : 0.0;
+        for (int j = 0; j < N; j++) {                // L y = -g_s
+            const double yj = __shfl(bv, j) / A[j * N + j];
+            if (lane == j) bv = yj; else if (in && lane > j) bv -= A[lane * N + j] * yj;
+        }
+        for (int j = N - 1; j >= 0; j--) {           // L^T d = y
+            const double dj = __shfl(bv, j) / A[j * N + j];
+            if (lane == j) bv = dj; else if (lane < j) bv -= A[j * N + lane] * dj;
+        }
+        okc = okc && __all(bv == bv);
+        if (in) sh.d[lane] = bv;
+        LILI_WAVE_SYNC();
+        // model_cost_change = -d^T (g_s + H_s d / 2)
+        if (in) {
+            double hd = 0.0;
+            for (int j = 0; j < N; j++) hd += (sh.H[lane * N + j] * sh.scale[lane] * sh.scale[j]) * sh.d[j];
+            sh.tr[lane] = bv * (sh.g[lane] * sh.scale[lane] + 0.5 * hd);
+        }
+        LILI_WAVE_SYNC();
+        double mc = 0.0;
+        for (int i = 0; i < N; i++) mc += sh.tr[i];
+        mc = -mc;
+        if (!okc || !(mc > 0.0)) {
+            // Ceres' INVALID step (TrustRegionMinimizer::HandleInvalidStep): the iteration counts, nothing is evaluated, the radius is halved
+            const int n_inv = sh.n_invalid + 1;
+            LILI_WAVE_SYNC();
+            if (lane == 0) { sh.n_invalid = n_inv; sh.radius = radius * 0.5; sh.it = it + 1; }
+            if (n_inv >= 5) { if (lane == 0) { sh.term = LILI_LM_NUMERICAL_FAILURE; sh.go = 0; } return; }
+            LILI_WAVE_SYNC();
+            continue;
+        }
+        if (in) sh.d[lane] = bv * sh.scale[lane];          // delta in the unscaled local coordinates
+        LILI_WAVE_SYNC();
+        if (lane < n_kf) {                                  // x (+) delta of keyframe `lane`
+            const double* d = sh.d + 15 * lane;
+            const double* x = sh.x[lane];
+            double* xn = sh.sys.x[lane];
+            for (int i = 0; i < 3; i++) xn[i] = x[i] + d[i];
+            for (int i = 0; i < 9; i++) xn[7 + i] = x[7 + i] + d[6 + i];
+            const double nd2 = d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
+            if (nd2 > 0.0) {      // ceres::QuaternionParameterization::Plus; sin / cos as lm_propose takes them
+                double sbd, cw;
+                if (nd2 < 0.25) sinc_cos_small(nd2, sbd, cw);
+                else {
+                    double h2 = nd2; int k = 0;
+                    while (h2 >= 0.25 && k < 60) { h2 *= 0.25; k++; }
+                    double sc, c;
+                    sinc_cos_small(h2, sc, c);
+                    double sn = sc * sqrt(h2);
+                    for (int i = 0; i < k; i++) { const double s2 = 2.0 * sn * c, c2 = c * c - sn * sn; sn = s2; c = c2; }
+                    sbd = sn / sqrt(nd2); cw = c;
+                }
+                const dq r = qmul(dq{cw, sbd * d[3], sbd * d[4], sbd * d[5]}, dq{x[3], x[4], x[5], x[6]});
+                xn[3] = r.w; xn[4] = r.x; xn[5] = r.y; xn[6] = r.z;
+            } else { xn[3] = x[3]; xn[4] = x[4]; xn[5] = x[5]; xn[6] = x[6]; }
+        }
+        if (lane == 0) {
+            double n2 = 0.0;
+            for (int i = 0; i < N; i++) n2 += sh.d[i] * sh.d[i];
+            sh.model_change = mc; sh.n_invalid = 0; sh.step_norm = sqrt(n2);
+            sh.go = 1;
+        }
+        return;
+    }
+}
+
+// persistent launch: workgroup bid belongs to the last slot whose first_block <= bid; dynamic LDS = kWinThreads * kRow doubles (Gram staging rows)
+__global__ __launch_bounds__(kWinThreads) void k_window_solve(WinSolveArgs W, MatchParams P) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ WinShared sh;
+    const int bid = (int)blockIdx.x;
+    int slot = 0;
+#pragma unroll
+    for (int k = 1; k < kWinMaxKf; k++) if (k < W.n && bid >= W.first_block[k]) slot = k;
+    const LmArgs& a = W.a[slot];
+    const int b = bid - W.first_block[slot];
+    const WinDev* pb = W.prob;
+    const int n_kf = W.n, N = 15 * n_kf;
+    const bool surf = b < a.S.nb;
+    const bool wave0 = threadIdx.x < 64;
+    const bool boss = bid == 0 && threadIdx.x == 0;
+    {
+        const int n_s = (a.S.n_q > 0 && a.S.block_counts) ? sum_block_counts(a.S.block_counts, a.S.n_bc) : 0;
+        __syncthreads();
+        const int n_e = (a.E.n_q > 0 && a.E.block_counts) ? sum_block_counts(a.E.block_counts, a.E.n_bc) : 0;
+        for (int e = threadIdx.x; e < 16 * n_kf; e += blockDim.x) { sh.x[e / 16][e % 16] = pb->state[e]; sh.sys.x[e / 16][e % 16] = pb->state[e]; }
+        if (threadIdx.x == 0) {
+            const LmArgs& o = W.a[0];
+            sh.counts[0] = n_s; sh.counts[1] = n_e;
+            sh.max_iter = o.max_iter;
+            sh.function_tolerance = o.function_tolerance; sh.gradient_tolerance = o.gradient_tolerance; sh.parameter_tolerance = o.parameter_tolerance;
+            sh.max_radius = o.max_radius; sh.min_radius = o.min_radius; sh.min_relative_decrease = o.min_relative_decrease;
+            sh.min_lm_diagonal = o.min_lm_diagonal; sh.max_lm_diagonal = o.max_lm_diagonal;
+            sh.radius = o.initial_radius; sh.decrease = 2.0; sh.it = 0; sh.n_ok = 0; sh.term = LILI_LM_MAX_ITERATIONS; sh.go = 1; sh.stalled = 0; sh.take = 0; sh.n_invalid = 0;
+            sh.cost = 0.0; sh.model_change = 0.0; sh.step_norm = 0.0;
+        }
+        __syncthreads();
+    }
+    LinArgs S = a.S, E = a.E;
+    S.block_counts = nullptr; E.block_counts = nullptr;         // the bodies then take N from n_global (= sh.counts)
+    int n_log = 0;
+    double cost0 = 0.0;
+    for (int eval = 0;; eval++) {
+        const int par = eval & 1;
+        const unsigned long long key = xchg_key(W.a[0].launch, eval);
+        double* part = a.part + (size_t)par * a.nb * kPartialStride;
+        PoseArg pa{};
+        for (int i = 0; i < 3; i++) pa.t[i] = sh.sys.x[slot][i];
+        for (int i = 0; i < 4; i++) pa.q[i] = sh.sys.x[slot][3 + i];
+        pa.state = nullptr; pa.derive_assoc = 0;
+        // ---- this workgroup's share of its keyframe's records at the candidate, published as granules
+        S.partials = part; E.partials = part + (size_t)a.S.nb * kPartialStride;
+        if (surf) lin_surf_body(S, b, pa, P, a.state, sh.counts, lds, key);
+        else lin_edge_body(E, b - a.S.nb, pa, P, a.state, sh.counts, lds, key);
+        if (wave0) {
+            // ---- exchange: the partials of EVERY slot, slot by slot, each in index order
+            bool ok = true;
+            for (int k = 0; k < n_kf; k++)
+                ok = xchg_gather<40>(W.a[k].part + (size_t)par * W.a[k].nb * kPartialStride, W.a[k].nb, key, sh.vals, sh.tot[k]) && ok;
+            if (!ok && threadIdx.x == 0) sh.stalled = 1;
+            for (int k = 0; k < n_kf; k++) {
+                const int lane = threadIdx.x, r = lane >> 3, c = lane & 7;
+                const int lo = r < c ? r : c, hi = r < c ? c : r;
+                sh.sys.lid[k][lane] = sh.tot[k][lo * 8 - lo * (lo - 1) / 2 + (hi - lo)];
+                if (lane == 0) sh.sys.lid[k][64] = sh.tot[k][36];
+            }
+            LILI_WAVE_SYNC();
+            win_build(pb, sh.sys);
+            // ---- step logic, identical in every workgroup
+            if (eval == 0) {
+                for (int e = threadIdx.x; e < N * N; e += 64) sh.H[e] = sh.sys.H[e];
+                if (threadIdx.x < N) { sh.g[threadIdx.x] = sh.sys.g[threadIdx.x]; sh.scale[threadIdx.x] = 1.0 / (1.0 + sqrt(sh.sys.H[threadIdx.x * N + threadIdx.x])); }      // Jacobi scaling, kept for the whole solve
+                if (threadIdx.x == 0) { sh.cost = sh.sys.cost; cost0 = sh.cost; if (sh.stalled) { sh.term = LILI_LM_STALLED; sh.go = 0; } }
+            } else {
+                if (threadIdx.x == 0) {
+                    int accepted = 0, stop = 0;
+                    const double new_cost = sh.sys.cost;
+                    const double rho = (sh.cost - new_cost) / sh.model_change;
+                    if (boss && W.summary && n_log < LILI_LM_MAX_LOG) {
+                        lili_lm_iteration& L = W.summary->it[n_log];
+                        L.cost = sh.cost; L.new_cost = new_cost; L.rho = rho; L.radius = sh.radius; L.step_norm = sh.step_norm; L.accepted = 0; L.iteration = sh.it;
+                    }
+                    double xn2 = 0.0;
+                    for (int k = 0; k < n_kf; k++) for (int i = 0; i < 16; i++) xn2 += sh.x[k][i] * sh.x[k][i];
+                    const double xnorm = sqrt(xn2);
+                    if (sh.stalled) { sh.term = LILI_LM_STALLED; stop = 1; }
+                    // Ceres returns from ParameterToleranceReached / FunctionToleranceReached BEFORE HandleSuccessfulStep: that candidate is never taken
+                    else if (sh.step_norm <= sh.parameter_tolerance * (xnorm + sh.parameter_tolerance)) { sh.term = LILI_LM_PARAMETER_TOLERANCE; stop = 1; }
+                    else if (fabs(sh.cost - new_cost) <= sh.function_tolerance * sh.cost) { sh.term = LILI_LM_FUNCTION_TOLERANCE; stop = 1; }
+                    else if (rho > sh.min_relative_decrease) {
+                        accepted = 1;
+                        const double f = 2.0 * rho - 1.0;
+                        sh.radius = fmin(sh.max_radius, sh.radius / fmax(1.0 / 3.0, 1.0 - f * f * f));
+                        sh.decrease = 2.0;
+                    } else {
+                        sh.radius = sh.radius / sh.decrease; sh.decrease *= 2.0;      // LevenbergMarquardtStrategy::StepRejected
+                        if (!(sh.radius > sh.min_radius)) { sh.term = sh.it + 1 >= sh.max_iter ? LILI_LM_MAX_ITERATIONS : LILI_LM_MIN_RADIUS; stop = 1; }
+                    }
+                    if (accepted) { sh.cost = new_cost; sh.n_ok++; }
+                    if (boss && W.summary && n_log < LILI_LM_MAX_LOG) W.summary->it[n_log].accepted = accepted;
+                    n_log++;
+                    sh.it++;
+                    sh.go = stop ? 0 : 1;
+                    sh.take = accepted;
+                }
+                LILI_WAVE_SYNC();
+                if (sh.take) {
+                    for (int e = threadIdx.x; e < N * N; e += 64) sh.H[e] = sh.sys.H[e];
+                    if (threadIdx.x < N) sh.g[threadIdx.x] = sh.sys.g[threadIdx.x];
+                    for (int e = threadIdx.x; e < 16 * n_kf; e += 64) sh.x[e / 16][e % 16] = sh.sys.x[e / 16][e % 16];
+                }
+            }
+            LILI_WAVE_SYNC();
+            if (sh.go) win_propose(sh, n_kf);      // the next candidate (or the end), from the accepted point
+            LILI_WAVE_SYNC();
+        }
+        __syncthreads();
+        if (!sh.go) break;
+    }
+    if (bid == 0 && threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        for (int e = lane; e < 16 * n_kf; e += 64) W.state_out[e] = sh.x[e / 16][e % 16];
+        if (lane < n_kf) {
+            SlotState* st = W.a[lane].state;
+            for (int i = 0; i < 7; i++) st->pose[i] = sh.x[lane][i];
+            st->gn_status = (sh.term == LILI_LM_STALLED || sh.term == LILI_LM_NUMERICAL_FAILURE) ? 1 : 0;
+            st->iters += sh.n_ok;
+        }
+        if (lane == 0 && W.summary) {
+            W.summary->iterations = sh.it; W.summary->successful_steps = sh.n_ok; W.summary->termination = sh.term;
+            W.summary->initial_cost = cost0; W.summary->final_cost = sh.cost; W.summary->final_radius = sh.radius;
+            W.summary->n_logged = n_log < LILI_LM_MAX_LOG ? n_log : LILI_LM_MAX_LOG;
+            W.summary->n_surf = sh.counts[0]; W.summary->n_edge = sh.counts[1];
+        }
+    }
+}
+
+}  // namespace lili
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------------------------------------------------------------------
+// sqrt_info = LLT(cov^-1).matrixL()^T in plain C++ (long double accumulation): cov = C C^T, cov^-1 = C^-T C^-1, Cholesky of that.  false: not positive definite
+static bool window_sqrt_info(const double* cov, double* out) {
+    constexpr int n = 15;
+    long double C[n][n] = {}, Ci[n][n] = {}, A[n][n] = {}, L[n][n] = {};
+    auto chol = [&](long double (*M)[n], long double (*R)[n]) {
+        for (int j = 0; j < n; j++) {
+            long double d = M[j][j];
+            for (int k = 0; k < j; k++) d -= R[j][k] * R[j][k];
+            if (!(d > 0.0L) || !std::isfinite((double)d)) return false;
+            R[j][j] = sqrtl(d);
+            for (int i = j + 1; i < n; i++) {
+                long double v = M[i][j];
+                for (int k = 0; k < j; k++) v -= R[i][k] * R[j][k];
+                R[i][j] = v / R[j][j];
+            }
+        }
+        return true;
+    };
+    long double M[n][n];
+    for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) {
+        if (!std::isfinite(cov[n * i + j])) return false;
+        M[i][j] = 0.5L * ((long double)cov[n * i + j] + (long double)cov[n * j + i]);
+    }
+    if (!chol(M, C)) return false;
+    for (int j = 0; j < n; j++) {          // C^-1, lower triangular
+        Ci[j][j] = 1.0L / C[j][j];
+        for (int i = j + 1; i < n; i++) {
+            long double v = 0.0L;
+            for (int k = j; k < i; k++) v -= C[i][k] * Ci[k][j];
+            Ci[i][j] = v / C[i][i];
+        }
+    }
+    for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) {
+        long double v = 0.0L;
+        for (int k = std::max(i, j); k < n; k++) v += Ci[k][i] * Ci[k][j];
+        A[i][j] = v;
+    }
+    if (!chol(A, L)) return false;
+    for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) out[n * i + j] = (double)L[j][i];
+    return true;
+}
+
+// validates the problem and packs it (with `state`) into ctx->win_host; nothing is enqueued
+static int window_pack(lili_ctx* ctx, const lili_window_problem* pr, const double* state, bool solve, const char* who) {
+    const std::string w(who);
+    ARGCHK(pr && state, w + ": null argument");
+    ARGCHK(pr->n_kf >= 2 && pr->n_kf <= LILI_WINDOW_MAX_KF, w + ": n_kf must be in 2..LILI_WINDOW_MAX_KF");
+    ARGCHK((pr->kind_mask & ~3) == 0 && (pr->kind_mask != 0 || !solve), w + ": bad kind mask");
+    const int n_kf = pr->n_kf;
+    if (pr->kind_mask) {
+        ARGCHK(pr->slots, w + ": null slots");
+        for (int i = 0; i < n_kf; i++) {
+            ARGCHK(pr->slots[i] >= 0 && pr->slots[i] < LILI_MAX_SLOTS, w + ": bad slot");
+            for (int k = 0; k < i; k++) ARGCHK(pr->slots[k] != pr->slots[i], w + ": duplicate slot");
+            for (int kind = 0; kind < 2; kind++) if (pr->kind_mask & (1 << kind))
+                if (!ctx->slots[pr->slots[i]].k[kind].has_records) return ctx->fail(LILI_E_STATE, w + ": a slot has no records (associate first)");
+        }
+    }
+    for (int i = 0; i < 16 * n_kf; i++) ARGCHK(std::isfinite(state[i]), w + ": state is not finite");
+    ctx->win_host.assign(sizeof(WinDev), 0);
+    WinDev& D = *reinterpret_cast<WinDev*>(ctx->win_host.data());
+    D.n_kf = n_kf;
+    std::memcpy(D.state, state, sizeof(double) * 16 * n_kf);
+    if (pr->imu) {
+        D.n_imu = n_kf - 1;
+        for (int f = 0; f < D.n_imu; f++) {
+            const lili_window_imu& s = pr->imu[f];
+            WinImuDev& d = D.imu[f];
+            d.sum_dt = s.sum_dt;
+            std::memcpy(d.g, s.g, sizeof d.g); std::memcpy(d.dp, s.delta_p, sizeof d.dp); std::memcpy(d.dq, s.delta_q, sizeof d.dq); std::memcpy(d.dv, s.delta_v, sizeof d.dv);
+            std::memcpy(d.ba, s.lin_ba, sizeof d.ba); std::memcpy(d.bg, s.lin_bg, sizeof d.bg);
+            auto blk = [&](double* o, int r0, int c0) { for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++) o[3 * i + c] = s.jacobian[15 * (r0 + i) + c0 + c]; };
+            blk(d.dp_dba, 0, 9); blk(d.dp_dbg, 0, 12); blk(d.dq_dbg, 3, 12); blk(d.dv_dba, 6, 9); blk(d.dv_dbg, 6, 12);
+            if (!window_sqrt_info(s.covariance, d.sqrt_info)) return ctx->fail(LILI_E_ARG, w + ": an IMU covariance is not positive definite");
+        }
+    }
+    if (pr->sb_prior) for (int k = 0; k < n_kf; k++) {
+        D.sb_has[k] = std::isnan(pr->sb_prior[9 * k]) ? 0 : 1;
+        if (D.sb_has[k]) for (int i = 0; i < 9; i++) { ARGCHK(std::isfinite(pr->sb_prior[9 * k + i]), w + ": speed-bias prior is not finite"); D.sb_mean[9 * k + i] = pr->sb_prior[9 * k + i]; }
+    }
+    if (pr->prior) {
+        const lili_window_prior& p = *pr->prior;
+        ARGCHK(p.n_blocks >= 1 && p.n_blocks <= kWinMaxBlocks && p.block_kind && p.block_keyframe && p.x0 && p.J0 && p.r0, w + ": bad prior");
+        ARGCHK(p.n_rows >= 1 && p.n_rows <= kWinMaxN && p.n_cols >= 1 && p.n_cols <= kWinMaxN, w + ": prior size out of range");
+        int col = 0, off = 0;
+        for (int b = 0; b < p.n_blocks; b++) {
+            const int kind = p.block_kind[b], kf = p.block_keyframe[b];
+            ARGCHK(kind >= 0 && kind <= 2 && kf >= 0 && kf < n_kf, w + ": bad prior block");
+            for (int k = 0; k < b; k++) ARGCHK(!(p.block_kind[k] == kind && p.block_keyframe[k] == kf), w + ": duplicate prior block");
+            D.blk_kind[b] = kind; D.blk_kf[b] = kf; D.blk_col[b] = col; D.blk_x0[b] = off;
+            const int ls = kind == 2 ? 9 : 3, gs = kind == 0 ? 3 : kind == 1 ? 4 : 9;
+            for (int i = 0; i < ls && col + i < kWinMaxN; i++) D.col_blk[col + i] = b;
+            col += ls; off += gs;
+        }
+        ARGCHK(col == p.n_cols, w + ": n_cols of the prior does not match its blocks");
+        D.has_prior = 1; D.n_rows = p.n_rows; D.n_cols = p.n_cols; D.n_blocks = p.n_blocks;
+        std::memcpy(D.x0, p.x0, sizeof(double) * off);
+        std::memcpy(D.r0, p.r0, sizeof(double) * p.n_rows);
+        std::memcpy(D.J0, p.J0, sizeof(double) * p.n_rows * p.n_cols);
+        for (int a = 0; a < p.n_cols; a++) for (int b = 0; b < p.n_cols; b++) {
+            double v = 0.0;
+            for (int r = 0; r < p.n_rows; r++) v += p.J0[r * p.n_cols + a] * p.J0[r * p.n_cols + b];
+            D.A0[a * p.n_cols + b] = v;
+        }
+    }
+    return LILI_OK;
+}
+static lili_s2m_params window_params(const lili_window_problem* pr, const lili_s2m_params* params) {
+    lili_s2m_params p = *params;
+    if (pr->q_lb[0] != 0 || pr->q_lb[1] != 0 || pr->q_lb[2] != 0 || pr->q_lb[3] != 0) { std::memcpy(p.q_lb, pr->q_lb, sizeof p.q_lb); std::memcpy(p.t_lb, pr->t_lb, sizeof p.t_lb); }
+    return p;
+}
+
+extern "C" {
+
+int lili_window_sqrt_info(const double covariance[225], double sqrt_info[225]) {
+    if (!covariance || !sqrt_info) return LILI_E_ARG;
+    return window_sqrt_info(covariance, sqrt_info) ? LILI_OK : LILI_E_ARG;
+}
+
+int lili_window_evaluate(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const double* state,
+                         double* cost, double* gradient, double* JtJ) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(params && cost && gradient, "window_evaluate: null argument");
+    int rc = window_pack(ctx, problem, state, false, "window_evaluate");
+    if (rc != LILI_OK) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int n_kf = problem->n_kf, N = 15 * n_kf;
+    const size_t n_out = (size_t)1 + N + (size_t)N * N;
+    HIPCHK(ctx->win_prob.ensure(sizeof(WinDev)));
+    HIPCHK(ctx->win_out.ensure(sizeof(double) * (1 + kWinMaxN + kWinMaxN * kWinMaxN) + sizeof(lili_lm_summary)));
+    const double* rec = nullptr;
+    if (problem->kind_mask) {
+        double t[3 * kWinMaxKf], q[4 * kWinMaxKf];
+        for (int k = 0; k < n_kf; k++) { std::memcpy(t + 3 * k, state + 16 * k, 3 * sizeof(double)); std::memcpy(q + 4 * k, state + 16 * k + 3, 4 * sizeof(double)); }
+        const lili_s2m_params p = window_params(problem, params);
+        HIPCHK(ctx->win_rec.ensure(sizeof(double) * LILI_GRAM_DOUBLES * LILI_MAX_SLOTS));
+        if ((rc = lili_match_window_records(ctx, problem->slots, n_kf, problem->kind_mask, &p, t, q, ctx->win_rec.as<double>())) != LILI_OK) return rc;
+        rec = ctx->win_rec.as<double>();
+    }
+    HIPCHK(hipMemcpyAsync(ctx->win_prob.p, ctx->win_host.data(), sizeof(WinDev), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_window_evaluate, dim3(1), dim3(64), 0, ctx->stream, ctx->win_prob.as<WinDev>(), rec, ctx->win_out.as<double>(), JtJ ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    const double* d = ctx->win_out.as<double>();
+    rc = lili_readback_add(ctx, cost, d, sizeof(double));
+    if (rc == LILI_OK) rc = lili_readback_add(ctx, gradient, d + 1, sizeof(double) * N);
+    if (rc == LILI_OK && JtJ) rc = lili_readback_add(ctx, JtJ, d + 1 + N, sizeof(double) * N * N);
+    (void)n_out;
+    if (rc != LILI_OK) { (void)lili_readback_finish(ctx); return rc; }
+    return lili_readback_finish(ctx);
+}
+
+int lili_window_solve(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const lili_lm_options* options,
+                      double* state, lili_lm_summary* summary) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(params, "window_solve: null params");
+    int rc = window_pack(ctx, problem, state, true, "window_solve");
+    if (rc != LILI_OK) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int n_kf = problem->n_kf;
+    const lili_s2m_params p = window_params(problem, params);
+    // every workgroup has to be resident: the share of the CUs lili_s2m_solve_lm_window gives a slot, and at most kWinGroup per slot (one exchange hop)
+    const int max_blocks = std::max(1, std::min(std::min(ctx->n_simd / 4 - 16, 240) / n_kf, kWinGroup));
+    HIPCHK(ctx->win_prob.ensure(sizeof(WinDev)));
+    HIPCHK(ctx->win_out.ensure(sizeof(double) * (1 + kWinMaxN + kWinMaxN * kWinMaxN) + sizeof(lili_lm_summary)));
+    WinSolveArgs W{};
+    W.n = n_kf;
+    int nb = 0;
+    for (int i = 0; i < n_kf; i++) {
+        if ((rc = lili_match_lm_args(ctx, problem->slots[i], problem->kind_mask, &p, options, max_blocks, &W.a[i])) != LILI_OK) return rc;
+        if (W.a[i].nb > kWinGroup) return ctx->fail(LILI_E_STATE, "window_solve: internal: too many workgroups for one exchange hop");
+        W.first_block[i] = nb;
+        nb += W.a[i].nb;
+    }
+    W.prob = ctx->win_prob.as<WinDev>();
+    W.state_out = ctx->win_out.as<double>();
+    W.summary = reinterpret_cast<lili_lm_summary*>(ctx->win_out.as<double>() + 1 + kWinMaxN + kWinMaxN * kWinMaxN);
+    MatchParams P = lili_match_device_params(&p);
+    P.no_cost = 0;                              // the robust cost drives the accept / reject decisions
+    HIPCHK(hipMemcpyAsync(ctx->win_prob.p, ctx->win_host.data(), sizeof(WinDev), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_window_solve, dim3(nb), dim3(kWinThreads), lds_linearize(kWinThreads), ctx->stream, W, P);
+    HIPCHK(hipGetLastError());
+    if (summary) {
+        rc = lili_readback_add(ctx, summary, W.summary, sizeof(lili_lm_summary));
+        if (rc == LILI_OK) rc = lili_readback_add(ctx, state, W.state_out, sizeof(double) * 16 * n_kf);
+        if (rc != LILI_OK) { (void)lili_readback_finish(ctx); return rc; }
+        return lili_readback_finish(ctx);
+    }
+    return LILI_OK;
+}
+
+int lili_window_state_get(lili_ctx* ctx, int n_kf, double* state) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(state && n_kf >= 2 && n_kf <= LILI_WINDOW_MAX_KF, "window_state_get: bad argument");
+    if (!ctx->win_out.p) return ctx->fail(LILI_E_STATE, "window_state_get: no lili_window_solve yet");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int rc = lili_readback_add(ctx, state, ctx->win_out.p, sizeof(double) * 16 * n_kf);
+    if (rc != LILI_OK) { (void)lili_readback_finish(ctx); return rc; }
+    return lili_readback_finish(ctx);
+}
+
+}  // extern "C"
