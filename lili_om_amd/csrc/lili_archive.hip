@@ -12,43 +12,29 @@
 //     from the table's sum (or from 0.0f): a voxel's members of a later batch all come after those of the earlier ones in concatenation order, so the sequence of f32
 //     additions per voxel is the one-shot filter's for any split into batches.  New keys are merged in by prefix sum and binary search (as k_merge does for the ring).
 // No floating-point atomics anywhere: the order of the additions is the contract.
-#include "lili_ctx.h"
+#include "lili_launch.h"
 #include "lili_device_math.h"
+#include "lili_device_cloud.h"
 
 #include <climits>
 #include <memory>
 
 namespace lili {
 
-__global__ void k_scan_block_sums(const int*, int64_t, int*);
-__global__ void k_scan_sums(int*, int);
-__global__ void k_scan_apply(const int*, int64_t, const int*, int*);
-
-// a pushed cloud's rows -> float4 (x, y, z, aux; aux absent: 0), read where they lie as k_loop_gather reads them
+// a pushed cloud's rows -> float4 (x, y, z, aux; aux absent: 0), read where they lie
 __global__ void k_arc_rows(const unsigned char* __restrict__ src, int n, int stride, int aux_off, float4* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const unsigned char* row = src + (size_t)i * stride;
-    const float* p = reinterpret_cast<const float*>(row);
-    out[i] = make_float4(p[0], p[1], p[2], aux_off >= 0 ? *reinterpret_cast<const float*>(row + aux_off) : 0.f);
+    out[i] = load_row_f4(src + (size_t)i * stride, aux_off);
 }
 
-// one batch of the global map: runs of archived rows placed at their keyframes' map poses, concatenated (thread i finds its run by bisection, as k_loop_gather)
+// one batch of the global map: runs of archived rows placed at their keyframes' map poses, concatenated (thread i finds its run by bisection)
 struct GmSeg { const float4* src; long long first; double t[3], q[4]; };
 __global__ void k_gm_gather(const GmSeg* __restrict__ segs, int n_seg, int total, float4* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first <= (long long)i) lo = mid; else hi = mid - 1; }
-    const GmSeg& s = segs[lo];
+    const GmSeg& s = segs[seg_of(segs, n_seg, i)];
     out[i] = transform_point(s.src[(long long)i - s.first], dq{s.q[0], s.q[1], s.q[2], s.q[3]}, d3{s.t[0], s.t[1], s.t[2]});
-}
-
-// absolute voxel key of a FINITE point (the sorted ring's, lili_voxel.hip): ~0 beyond +-2^20 voxels
-__device__ __forceinline__ unsigned long long gm_key(float4 p, float inv_leaf) {
-    const long long i = (long long)floorf(p.x * inv_leaf) + (1ll << 20), j = (long long)floorf(p.y * inv_leaf) + (1ll << 20), k = (long long)floorf(p.z * inv_leaf) + (1ll << 20);
-    if ((i | j | k) < 0 || i >= (1ll << 21) || j >= (1ll << 21) || k >= (1ll << 21)) return ~0ull;
-    return ((unsigned long long)k << 42) | ((unsigned long long)j << 21) | (unsigned long long)i;
 }
 
 // head flags of the batch's sorted keys; the points are copied into sorted order on the way (a voxel's members become one contiguous run)
@@ -61,7 +47,8 @@ __global__ void k_gm_heads(const unsigned* __restrict__ keys, const int* __restr
 }
 
 // per voxel of the batch (its head's thread): where its members start, its absolute key and its place in the table — pos = lower_bound(table keys, key), is_new = the
-// table does not hold the key.  head_pos[number of voxels] = where the voxels end (the non-finite rows sort behind them).  res[0] is raised by a key out of range.
+// table does not hold the key.  head_pos[number of voxels] = where the voxels end (the non-finite rows sort behind them).  res[0] is raised by either sentinel of
+// abs_voxel_key (a head is a finite point, so only "beyond +-2^20 voxels" can occur).
 __global__ void k_gm_voxels(const unsigned* __restrict__ keys, const int* __restrict__ flags, const int* __restrict__ slot /*[n+1]*/, const float4* __restrict__ spts, int n,
                             unsigned sentinel, float inv_leaf, const unsigned long long* __restrict__ tkey, int n_tab, int* __restrict__ head_pos,
                             unsigned long long* __restrict__ bkey, int* __restrict__ pos, int* __restrict__ is_new, int* __restrict__ res) {
@@ -71,15 +58,13 @@ __global__ void k_gm_voxels(const unsigned* __restrict__ keys, const int* __rest
     if (live && (r == n - 1 || keys[r + 1] == sentinel)) head_pos[slot[n]] = r + 1;
     if (!flags[r]) return;
     const int v = slot[r];
-    const unsigned long long key = gm_key(spts[r], inv_leaf);
-    if (key == ~0ull) res[0] = 1;
+    const unsigned long long key = abs_voxel_key(spts[r], inv_leaf);
+    if (key >= ~0ull - 1ull) res[0] = 1;
     int lo = 0, hi = n_tab;
     while (lo < hi) { const int mid = (int)(((long long)lo + hi) >> 1); if (tkey[mid] < key) lo = mid + 1; else hi = mid; }
     head_pos[v] = r; bkey[v] = key; pos[v] = lo;
     is_new[v] = (lo < n_tab && tkey[lo] == key) ? 0 : 1;
 }
-
-__device__ __forceinline__ void gm_wave_lds_order() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
 
 // The fold, ONE THREAD PER VOXEL of the batch: the running sum starts at the table's (a voxel the table holds) or at 0.0f and takes the batch's members in order — the
 // member count is known from the head positions before the first load, so the loads of a trip of eight leave together and only the additions are serial.  A voxel of
@@ -110,8 +95,7 @@ __global__ void k_gm_fold(int n_vox, const int* __restrict__ head_pos, const flo
     }
     bsum[v] = make_float4(sx, sy, sz, sa);
 }
-// the crowded voxels, one WAVE each (as k_vox_centroid treats them): the wave requests kGmStage members at once, parks them in LDS, and lane c of every four carries
-// component c of the sum — one dependent addition per member, the operands read from a wave-uniform LDS address sixteen ahead of the additions
+// the crowded voxels, one WAVE each (fold_staged, kGmStage members at a time), continued from what k_gm_fold left in bsum
 constexpr int kGmStage = 512;
 __global__ __launch_bounds__(256) void k_gm_fold_long(const int* __restrict__ long_list, const int* __restrict__ res, const int* __restrict__ head_pos,
                                                       const float4* __restrict__ spts, float4* __restrict__ bsum) {
@@ -120,35 +104,11 @@ __global__ __launch_bounds__(256) void k_gm_fold_long(const int* __restrict__ lo
     const int n_long = res[1];
     for (int j = blockIdx.x * 4 + wave; j < n_long; j += gridDim.x * 4) {      // (wave-uniform)
         const int v = long_list[j];
-        int m = head_pos[v];
-        const int end = head_pos[v + 1];
+        const int m = head_pos[v], end = head_pos[v + 1];
         const int comp = lane & 3;
         const float4 s0 = bsum[v];
         float acc = comp == 0 ? s0.x : comp == 1 ? s0.y : comp == 2 ? s0.z : s0.w;
-        const float* st = reinterpret_cast<const float*>(stage[wave]) + comp;
-        while (m < end) {
-            const int cnt = min(end - m, kGmStage);
-            float4 reg[kGmStage / 64];
-#pragma unroll
-            for (int r = 0; r < kGmStage / 64; r++) reg[r] = spts[min(m + 64 * r + lane, end - 1)];      // (every request leaves before the first answer is awaited)
-#pragma unroll
-            for (int r = 0; r < kGmStage / 64; r++) stage[wave][64 * r + lane] = reg[r];
-            gm_wave_lds_order();
-            float p[16];
-#pragma unroll
-            for (int t = 0; t < 16; t++) p[t] = st[4 * t];
-            for (int u = 0; u < cnt; u += 16) {
-                float nx[16];
-#pragma unroll
-                for (int t = 0; t < 16; t++) nx[t] = st[4 * min(u + 16 + t, kGmStage - 1)];
-#pragma unroll
-                for (int t = 0; t < 16; t++) if (u + t < cnt) acc += p[t];
-#pragma unroll
-                for (int t = 0; t < 16; t++) p[t] = nx[t];
-            }
-            m += cnt;
-            gm_wave_lds_order();      // the next members overwrite the stage
-        }
+        acc = fold_staged<kGmStage>(spts, m, end, stage[wave], lane, acc);
         const float ax = __shfl(acc, 0), ay = __shfl(acc, 1), az = __shfl(acc, 2), aw = __shfl(acc, 3);
         if (lane == 0) bsum[v] = make_float4(ax, ay, az, aw);
     }
@@ -368,16 +328,6 @@ int copy_rows_out(lili_ctx* ctx, const void* d_rows, size_t count, lili_feature_
     return LILI_OK;
 }
 
-int gm_scan(lili_ctx* ctx, GlobalMap& G, const int* in, int64_t n, int* out /*[n+1]*/) {
-    const int nb = nblocks(n, 2048);
-    HIPCHK(G.sums.ensure((size_t)nb * sizeof(int)));
-    hipLaunchKernelGGL(lili::k_scan_block_sums, dim3(nb), dim3(256), 0, ctx->stream, in, n, G.sums.as<int>());
-    hipLaunchKernelGGL(lili::k_scan_sums, dim3(1), dim3(256), 0, ctx->stream, G.sums.as<int>(), nb);
-    hipLaunchKernelGGL(lili::k_scan_apply, dim3(nb), dim3(256), 0, ctx->stream, in, n, G.sums.as<int>(), out);
-    HIPCHK(hipGetLastError());
-    return LILI_OK;
-}
-
 // a buffer of the table that is about to be WRITTEN from scratch grows by half at least (its old content is not needed: the merge fills it)
 hipError_t grow(DevBuf& b, size_t bytes) { return bytes + 256 <= b.cap ? hipSuccess : b.ensure(std::max(bytes, b.cap + b.cap / 2)); }
 
@@ -413,7 +363,7 @@ int fold_batch(lili_ctx* ctx, GlobalMap& G, int total) {
     HIPCHK(G.long_list.ensure(((size_t)n / lili::kGmShort + 1) * 4)); HIPCHK(G.res.ensure(16));
     HIPCHK(hipMemsetAsync(G.res.p, 0, 16, ctx->stream));
     hipLaunchKernelGGL(lili::k_gm_heads, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, d_keys, d_order, (const float4*)G.raw.as<float4>(), n, sentinel, G.flags.as<int>(), G.spts.as<float4>());
-    rc = gm_scan(ctx, G, G.flags.as<int>(), n, G.slot.as<int>());
+    rc = lili_scan_exclusive3(ctx, G.flags.as<int>(), n, G.sums, G.slot.as<int>());
     if (rc != LILI_OK) return rc;
     const int n_tab = (int)G.n_tab;
     hipLaunchKernelGGL(lili::k_gm_voxels, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, d_keys, (const int*)G.flags.as<int>(), (const int*)G.slot.as<int>(), (const float4*)G.spts.as<float4>(), n,
@@ -428,7 +378,7 @@ int fold_batch(lili_ctx* ctx, GlobalMap& G, int total) {
     if (bad) return ctx->fail(LILI_E_ARG, "global_map: a point lies farther than 2^20 voxels from the origin");
     if (n_vox <= 0 || n_vox > n) return ctx->fail(LILI_E_STATE, "global_map: internal: voxel count of a batch out of range");
     if ((long long)n_tab + n_vox > 2147483647ll) return ctx->fail(LILI_E_ARG, kVoxelOverflowMsg);
-    rc = gm_scan(ctx, G, G.is_new.as<int>(), n_vox, G.new_rank.as<int>());
+    rc = lili_scan_exclusive3(ctx, G.is_new.as<int>(), n_vox, G.sums, G.new_rank.as<int>());
     if (rc != LILI_OK) return rc;
     hipLaunchKernelGGL(lili::k_gm_fold, dim3(nblocks(n_vox, 256)), dim3(256), 0, ctx->stream, n_vox, (const int*)G.head_pos.as<int>(), (const float4*)G.spts.as<float4>(), (const int*)G.pos.as<int>(),
                        (const int*)G.is_new.as<int>(), (const float4*)G.sum[G.cur].as<float4>(), (const int*)G.cnt[G.cur].as<int>(), G.bsum.as<float4>(), G.bcnt.as<int>(), G.long_list.as<int>(),

@@ -94,15 +94,20 @@ struct Slot {
     int assoc_since_pose = 0;         // association launches since the slot's pose was (re)set: the first one is the far-from-converged launch (coop_lanes)
 };
 
-constexpr int kLinBlock = 1024;      // must match lili_s2m.hip
-
 constexpr int kMaxLinBlocks = 256;
 inline size_t lds_linearize(int threads) { return (size_t)threads * 12 * sizeof(double); }   // rows [J r | 1 cost 0 0]; reused for the per-wave result blocks
 
 }  // namespace lili_detail
 using namespace lili_detail;
 
-constexpr size_t kMiscAlloc = 2 * 64 * 128 + 256 + 2 * ((8192 + 2) * 8 + 112);      // ctx->misc: scratch words of a map build, laid out in lili_map.hip
+// ctx->misc, the scratch words of a map build (lili_map.hip; ONE memset arms all of it — round 4: five small fills and a host-to-device copy per build were ~25 us
+// of serialised launches): 64 banks of 128 bytes for the bounding box, 64 for the density and the check
+// of a guessed box, the sticky error word of the look-back scans in 256 bytes of its own, then the status words of the build's two single-pass scans (cell table,
+// super-rows; <= kScanStatusTiles tiles each).  Between builds the voxel filter and the ring commit use the same words (lili_voxel.hip): their box and flag words lie
+// in the box banks, the rank words of k_rank_count where the scans' status words are.
+constexpr size_t kMiscBoxOff = 0, kMiscDensityOff = 64 * 128, kMiscErrOff = 2 * 64 * 128, kMiscStatusOff = kMiscErrOff + 256, kMiscRankOff = kMiscStatusOff;
+constexpr size_t kScanStatusTiles = 8192, kScanStatusBytes = (kScanStatusTiles + 2) * sizeof(unsigned long long) + 112 /* -> a multiple of 128 */;
+constexpr size_t kMiscAlloc = kMiscStatusOff + 2 * kScanStatusBytes;
 struct lili_ctx {
     int device = 0;
     hipStream_t stream = nullptr;

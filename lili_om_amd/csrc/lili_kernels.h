@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/lili_hip.h"
 #include "lili_p2p_dev.h"
 
 namespace lili {
@@ -108,7 +109,8 @@ struct AssocArgs {
 };
 
 // The slots of a sliding window handed to ONE reduction / count launch (k_window_reduce, k_window_counts in lili_s2m.hip)
-constexpr int kWindowMaxSlots = 8;       // = LILI_MAX_SLOTS
+constexpr int kWindowMaxSlots = 8;
+static_assert(kWindowMaxSlots == LILI_MAX_SLOTS, "a window launch carries every slot of a context");
 struct WindowSlot {
     const double* part_surf; int nb_surf;      // block partials of the slot's last linearisation (k_linearize)
     const double* part_edge; int nb_edge;
@@ -143,5 +145,32 @@ constexpr int kPartialDoubles = 40;  // per-block partial: 36 upper-triangle Gra
 constexpr int kPartialStride = 80;   // doubles per block slot of the partial buffers: 40 plain doubles, or 40 16-byte granules {value, value ^ key}
 constexpr int kBlock = 256;
 constexpr int kAssocBlock = 64;   // association (one query per thread): one wave per workgroup, so the dispatcher balances SIMDs wave by wave
+constexpr int kLinBlock = 1024;   // linearisation block (16 waves; the launch covers the queries with <= 256 blocks)
+constexpr int kLmThreads = 512;   // k_solve_lm*: 8 waves: the launch may use 256 VGPRs per lane (1024-thread workgroups cap it at 128 and the loop spilled ~150 words)
+constexpr int kLmGroup = 16;      // k_solve_lm*: workgroups per group sum; up to this many workgroups exchange in ONE hop (32: measured slower, one wave polls 1280 granules)
+
+// Arguments of the Levenberg-Marquardt loop on fixed correspondences, one persistent launch (k_solve_lm, k_solve_lm_window in lili_s2m_lm.hip)
+struct LmArgs {
+    LinArgs S, E;                 // records of the two kinds; S.nb / E.nb = workgroups of each kind (either may be 0)
+    SlotState* state;
+    double* part;                 // [2 parities][nb][kPartialStride]   block partials as granules
+    double* gsum;                 // [2 parities][ng][kPartialStride]   group sums as granules
+    int nb, ng;
+    int max_iter;
+    unsigned long long launch;    // host counter: makes the granule keys of this launch unique
+    lili_lm_summary* summary;     // device copy, written by workgroup 0
+    double function_tolerance, gradient_tolerance, parameter_tolerance;
+    double initial_radius, max_radius, min_radius, min_relative_decrease, min_lm_diagonal, max_lm_diagonal;
+};
+struct WinLmArgs { LmArgs a[kWindowMaxSlots]; int first_block[kWindowMaxSlots]; int n; };
+// Arguments of the persistent outer iteration of small scans (k_iterate_coop in lili_s2m_coop.hip)
+struct IterArgs {
+    SlotState* state;
+    double* part;                 // [2 parities][nb][kPartialStride]
+    double* gsum;                 // [2 parities][ng][kPartialStride]
+    double* cpart;                // [2 parities][nb + ng][4]            correspondence counts (surf, edge) as granules
+    int nb, ng, n_iters, derive_assoc;
+    unsigned long long launch;
+};
 
 }  // namespace lili

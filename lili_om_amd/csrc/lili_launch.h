@@ -1,4 +1,5 @@
-// Internal: forward declarations of every kernel the host files launch (definitions: lili_s2m.hip, lili_s2m_coop.hip, lili_s2m_lm.hip) and the launch helper.
+// Internal: forward declarations of every kernel that a file other than its own launches (definitions: lili_s2m.hip, lili_s2m_coop.hip, lili_s2m_dense.hip,
+// lili_s2m_lm.hip) — the only place a kernel is declared for another file — and the launch helper.
 #pragma once
 #include "lili_ctx.h"
 
@@ -8,6 +9,7 @@ namespace lili {
 // kernels (lili_s2m.hip)
 __global__ void k_cloud_to_f4(const unsigned char*, int, int, int, float4*, unsigned*);
 __global__ void k_bbox(const float4*, int, unsigned*);
+__global__ void k_bbox_dev(const float4*, const int*, int, unsigned*);
 __global__ void k_bbox_src(SrcCloud, int, unsigned*);
 __global__ void k_cell_count(SrcCloud, int, GridView, int*, int*, unsigned long long*, int, float);
 __global__ void k_scan_block_sums(const int*, int64_t, int*);
@@ -35,35 +37,16 @@ __global__ void k_window_counts(WindowArgs, int*, P2PView);
 // lili_s2m_dense.hip: the association on a dense map (fine index)
 __global__ void k_associate_fine(AssocArgs, int, int, int, PoseArg, MatchParams);
 // lili_s2m_lm.hip: the Levenberg-Marquardt loop on fixed correspondences, one persistent launch
-struct LmArgs {      // must match lili_s2m_lm.hip
-    LinArgs S, E;
-    SlotState* state;
-    double* part;
-    double* gsum;
-    int nb, ng;
-    int max_iter;
-    unsigned long long launch;
-    lili_lm_summary* summary;
-    double function_tolerance, gradient_tolerance, parameter_tolerance;
-    double initial_radius, max_radius, min_radius, min_relative_decrease, min_lm_diagonal, max_lm_diagonal;
-};
-struct WinLmArgs { LmArgs a[kWindowMaxSlots]; int first_block[kWindowMaxSlots]; int n; };      // must match lili_s2m_lm.hip
 __global__ void k_solve_lm(LmArgs, MatchParams);
 __global__ void k_solve_lm_window(WinLmArgs, MatchParams);
 // lili_s2m_coop.hip: L lanes per query (small launches)
 template <int L, bool LIN> __global__ void k_associate_coop(AssocArgs, AssocArgs, PoseArg, MatchParams, double*, double*, SlotState*, int);
 template <int L> __global__ void k_associate_coop_window(WinAssocArgs, MatchParams);
-struct IterArgs {      // must match lili_s2m_coop.hip
-    SlotState* state;
-    double* part;
-    double* gsum;
-    double* cpart;
-    int nb, ng, n_iters, derive_assoc;
-    unsigned long long launch;
-};
 template <int L> __global__ void k_iterate_coop(AssocArgs, AssocArgs, MatchParams, IterArgs);
 }  // namespace lili
 
+// lili_map.hip: the three-kernel exclusive scan (k_scan_block_sums, k_scan_sums, k_scan_apply) of n words into out[0 .. n]; in == out is allowed
+int lili_scan_exclusive3(lili_ctx* ctx, const int* in, int64_t n, lili_detail::DevBuf& sums, int* out);
 // lili_match.hip -> lili_window.hip (the lidar blocks of the joint window)
 int lili_match_window_records(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const double* t, const double* q, double* d_gram);
 int lili_match_lm_args(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, const lili_lm_options* options, int max_blocks, lili::LmArgs* out);

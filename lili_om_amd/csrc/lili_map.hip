@@ -1,6 +1,7 @@
 // C-ABI of liblili_hip.so, map index part (include/lili_hip.h: lili_map_set*, lili_map_focus, lili_map_info, lili_map_density, lili_map_build_stats).
 // Host code only; the kernels live in lili_s2m.hip.  Replaces pcl::KdTreeFLANN::setInputCloud at L/src/LidarOdometry.cpp:490, L/src/BackendFusion.cpp:1258-1259.
 #include "lili_launch.h"
+#include "lili_device_cloud.h"
 
 #include <cmath>
 #include <cstddef>
@@ -10,6 +11,18 @@
 #include <string>
 #include <vector>
 
+// The three-kernel exclusive scan of n words (tiles of 2048; `out` has n + 1 words and may be `in`: every tile reads its words before it writes them, and nobody else's):
+// the voxel filter's scan of long arrays, the global map's, and the map build's without the look-back scan.  `sums`: one word per tile, grown here.  Asynchronous.
+int lili_scan_exclusive3(lili_ctx* ctx, const int* in, int64_t n, DevBuf& sums, int* out) {
+    const int nb = nblocks(n, 2048);
+    HIPCHK(sums.ensure((size_t)nb * sizeof(int)));
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(kBlock), 0, ctx->stream, in, n, sums.as<int>());
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, ctx->stream, sums.as<int>(), nb);
+    hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(kBlock), 0, ctx->stream, in, n, sums.as<int>(), out);
+    HIPCHK(hipGetLastError());
+    return LILI_OK;
+}
+
 extern "C" {
 // --------------------------------------------------------------------------------------------
 // map index
@@ -17,15 +30,8 @@ extern "C" {
 // Uniform-grid index of the caller's cloud `src` (read where it lies: device memory, or the staging copy of a host cloud) with cells of edge `cell` (grown if the
 // bounding box needs more than max_cells cells): count (one atomic per run of equal cells, the returned value = the point's rank), in-place single-pass scan,
 // atomic-free scatter.
-// scratch words of a map build (ctx->misc): [0, 8192) bounding-box banks, [8192, 16384) density banks, then the sticky error word of the look-back scans
-// then the status words of the two single-pass scans of a build (cell table, super-rows; <= 8192 tiles each).
-// ONE memset arms all of it (round 4: five small fills and a host-to-device copy per build were ~25 us of serialised launches).
-constexpr size_t kMiscBytes = 2 * 64 * 128 + 256;
-constexpr size_t kScanStatusTiles = 8192, kScanStatusBytes = (kScanStatusTiles + 2) * sizeof(unsigned long long) + 112 /* -> a multiple of 128 */;
-constexpr size_t kMiscTotal = kMiscBytes + 2 * kScanStatusBytes;
-static_assert(kMiscTotal == kMiscAlloc, "ctx->misc is allocated in lili_ctx_create");
-static unsigned* scan_err_word(lili_ctx* ctx) { return reinterpret_cast<unsigned*>(ctx->misc.as<char>() + 2 * 64 * 128); }
-static unsigned long long* scan_status(lili_ctx* ctx, int which) { return reinterpret_cast<unsigned long long*>(ctx->misc.as<char>() + kMiscBytes + (size_t)which * kScanStatusBytes); }
+static unsigned* scan_err_word(lili_ctx* ctx) { return reinterpret_cast<unsigned*>(ctx->misc.as<char>() + kMiscErrOff); }
+static unsigned long long* scan_status(lili_ctx* ctx, int which) { return reinterpret_cast<unsigned long long*>(ctx->misc.as<char>() + kMiscStatusOff + (size_t)which * kScanStatusBytes); }
 static int build_grid(lili_ctx* ctx, MapIndex& m, const SrcCloud& src, const double mn[3], const double mx[3], double cell, int reach, DevBuf& sorted, DevBuf& aux_sorted,
                       DevBuf& cell_start, DevBuf& cell_start9, GridView& out, int64_t& n_cells, double& cell_used, unsigned long long* d_rank_sum, bool box_check, float touch_cells, bool narrow /* 8-bit count table (k_cell_count_narrow) */,
                       bool status_armed /* the scans' status words (ctx->misc) are still zero from the build's one memset */, bool want_srows /* super-row copy (if the options and the sizes allow it) */, const void* zeroed_p = nullptr, size_t zeroed_bytes = 0 /* the caller already cleared this much of cell_start (while the bounding box travelled) */) {
@@ -86,9 +92,8 @@ static int build_grid(lili_ctx* ctx, MapIndex& m, const SrcCloud& src, const dou
         if (narrow) hipLaunchKernelGGL(k_scan_lookback_t<true>, dim3(nb_lb), dim3(kBlock), 0, ctx->stream, cell_start.as<int>(), m.cell_tmp.as<unsigned char>(), nc, st, scan_err_word(ctx));
         else hipLaunchKernelGGL(k_scan_lookback_t<false>, dim3(nb_lb), dim3(kBlock), 0, ctx->stream, cell_start.as<int>(), (const unsigned char*)nullptr, nc, st, scan_err_word(ctx));
     } else {
-        hipLaunchKernelGGL(k_scan_block_sums, dim3(nb_scan), dim3(kBlock), 0, ctx->stream, cell_start.as<int>(), nc, m.block_sums.as<int>());
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, ctx->stream, m.block_sums.as<int>(), nb_scan);
-        hipLaunchKernelGGL(k_scan_apply, dim3(nb_scan), dim3(kBlock), 0, ctx->stream, cell_start.as<int>(), nc, m.block_sums.as<int>(), cell_start.as<int>());
+        const int rc = lili_scan_exclusive3(ctx, cell_start.as<int>(), nc, m.block_sums, cell_start.as<int>());
+        if (rc != LILI_OK) return rc;
     }
     if (narrow) hipLaunchKernelGGL(k_scatter_t<unsigned char>, dim3(8 * nblocks(nblocks(n, kBlock), 8)), dim3(kBlock), 0, ctx->stream, src, n, g, m.pt_cell.as<unsigned char>(), cell_start.as<int>(),
                                    sorted.as<float4>(), m.has_aux ? aux_sorted.as<float>() : nullptr);
@@ -151,7 +156,6 @@ int lili_map_set_hinted(lili_ctx* ctx, int kind, const lili_cloud* cloud, double
     ARGCHK(kind == LILI_KIND_SURF || kind == LILI_KIND_EDGE, "map_set: bad kind");
     return map_set_impl(ctx, kind, cloud, max_sq_radius, box6, true);
 }
-static float ord2f(unsigned u) { unsigned b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u; float f; std::memcpy(&f, &b, 4); return f; }
 static int map_set_impl(lili_ctx* ctx, int kind, const lili_cloud* cloud, double max_sq_radius, const unsigned* box6, bool allow_guess) {
     ARGCHK(cloud, "map_set: null cloud");
     ARGCHK(max_sq_radius > 0 && std::isfinite(max_sq_radius), "map_set: max_sq_radius must be positive");
@@ -204,8 +208,8 @@ static int map_set_impl(lili_ctx* ctx, int kind, const lili_cloud* cloud, double
         else source = kBoxGuess;
     }
     // every scratch word of the build — box banks, density banks, the scans' error word and status words, the guess's flags — starts from zero: one fill
-    { const int rl = lili_lazy_sources_clear_of(ctx, ctx->misc.p, kMiscTotal); if (rl != LILI_OK) return rl; }
-    HIPCHK(hipMemsetAsync(ctx->misc.p, 0, kMiscTotal, ctx->stream));
+    { const int rl = lili_lazy_sources_clear_of(ctx, ctx->misc.p, kMiscAlloc); if (rl != LILI_OK) return rl; }
+    HIPCHK(hipMemsetAsync(ctx->misc.p, 0, kMiscAlloc, ctx->stream));
     unsigned banks[64 * 32], mm[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
     const void* zeroed_p = nullptr;
     size_t zeroed_bytes = 0;
@@ -239,7 +243,7 @@ static int map_set_impl(lili_ctx* ctx, int kind, const lili_cloud* cloud, double
     }
     m.has_fine = false; m.fview = GridView{}; m.fbound = 0.f; m.fine_cell = 0; m.mean_occupancy = 0;
     constexpr size_t kRankBanks = 64;                       // k_cell_count: one bank per 128 bytes
-    unsigned long long* d_rank = reinterpret_cast<unsigned long long*>(ctx->misc.as<char>() + 8192);
+    unsigned long long* d_rank = reinterpret_cast<unsigned long long*>(ctx->misc.as<char>() + kMiscDensityOff);
     unsigned scan_err = 0;
     bool err_read = false;
     int rc = build_grid(ctx, m, src, mn, mx, cell, reach, m.sorted, m.aux_sorted, m.cell_start, m.cell_start9, m.view, m.n_cells, m.cell, d_rank, source == kBoxGuess,
@@ -251,9 +255,9 @@ static int map_set_impl(lili_ctx* ctx, int kind, const lili_cloud* cloud, double
     // A map with many points per gate-sized cell gets a second, fine index whose cells hold ~3 points; k_associate_fine searches it first.
     {
         struct Back { unsigned long long rank[kRankBanks * 16]; unsigned err, pad; } back;
-        static_assert(sizeof(Back) == 64 * 128 + 8, "layout of ctx->misc");
+        static_assert(sizeof(Back) == kMiscErrOff - kMiscDensityOff + 8, "layout of ctx->misc");
         {
-            int rb = lili_readback_add(ctx, &back, ctx->misc.as<char>() + 8192, sizeof(back));
+            int rb = lili_readback_add(ctx, &back, ctx->misc.as<char>() + kMiscDensityOff, sizeof(back));
             // the caller's launches and read-backs that want to share this synchronisation (one shot; they must leave ctx->misc + 8192 onwards and the cloud alone)
             int hk = LILI_OK;
             ctx->hook_box_words_zero = source != kBoxMeasure;      // the box banks at the head of ctx->misc: written only by a build that measures its box
@@ -362,7 +366,7 @@ int lili_map_set_begin(lili_ctx* ctx, int kind, const lili_cloud* cloud, double 
     }
     if (!ctx->build_done[kind]) HIPCHK(hipEventCreateWithFlags(&ctx->build_done[kind], hipEventDisableTiming));
     if (!ctx->main_mark[kind]) HIPCHK(hipEventCreateWithFlags(&ctx->main_mark[kind], hipEventDisableTiming));
-    if (ctx->misc_build.ensure(kMiscTotal) != hipSuccess) return ctx->fail(LILI_E_NOMEM, "map_set_begin: scratch allocation failed");
+    if (ctx->misc_build.ensure(kMiscAlloc) != hipSuccess) return ctx->fail(LILI_E_NOMEM, "map_set_begin: scratch allocation failed");
     // the buffers being rebuilt are the ones the index before the current one lived in: everything enqueued up to the swap that retired
     // them (main_mark, recorded by lili_map_set_end) has to be through before they are overwritten — NOT what was enqueued since, which
     // uses the current index and is what the build overlaps with

@@ -997,7 +997,6 @@ static int launch_solve_lm(lili_ctx* ctx, int slot, int kind_mask, const lili_s2
     }
     if (n_all == 0) return ctx->fail(LILI_E_STATE, "solve_lm: no records");
     // workgroups: 512 records each, split between the kinds in proportion, at most max_blocks in total (a kind that is present gets at least one)
-    constexpr int kLmThreads = 512;      // must match lili_s2m_lm.hip
     const int want_s = a.S.n_q > 0 ? nblocks(a.S.n_q, kLmThreads) : 0, want_e = a.E.n_q > 0 ? nblocks(a.E.n_q, kLmThreads) : 0;
     int nb_s = want_s, nb_e = want_e;
     if (want_s > 0 && want_e > 0 && max_blocks < 2)     // every kind present needs a workgroup of its own, and all of them must be resident
@@ -1008,7 +1007,7 @@ static int launch_solve_lm(lili_ctx* ctx, int slot, int kind_mask, const lili_s2
     }
     a.S.nb = nb_s; a.E.nb = nb_e;
     a.nb = nb_s + nb_e;
-    a.ng = a.nb > 16 ? nblocks(a.nb, 16) : 1;       // kLmGroup of lili_s2m_lm.hip
+    a.ng = a.nb > kLmGroup ? nblocks(a.nb, kLmGroup) : 1;
     HIPCHK(sl.lm_part.ensure((size_t)2 * a.nb * kPartialStride * sizeof(double)));
     HIPCHK(sl.lm_gsum.ensure((size_t)2 * a.ng * kPartialStride * sizeof(double)));
     HIPCHK(sl.lm_summary.ensure(sizeof(lili_lm_summary)));
@@ -1067,7 +1066,7 @@ int lili_s2m_solve_lm_window(lili_ctx* ctx, const int* slots, int n_slots, int k
     }
     MatchParams P = to_device_params(params);
     P.no_cost = 0;                              // the robust cost drives the accept / reject decisions
-    hipLaunchKernelGGL(k_solve_lm_window, dim3(nb), dim3(512 /* kLmThreads of lili_s2m_lm.hip */), lds_linearize(512), ctx->stream, W, P);
+    hipLaunchKernelGGL(k_solve_lm_window, dim3(nb), dim3(kLmThreads), lds_linearize(kLmThreads), ctx->stream, W, P);
     HIPCHK(hipGetLastError());
     if (summaries) {
         for (int i = 0; i < n_slots; i++) { const int rb = lili_readback_add(ctx, summaries + i, ctx->slots[slots[i]].lm_summary.p, sizeof(lili_lm_summary)); if (rb != LILI_OK) { (void)lili_readback_finish(ctx); return rb; } }

@@ -12,6 +12,7 @@
 #include <type_traits>
 #include "lili_kernels.h"
 #include "lili_device_math.h"
+#include "lili_device_cloud.h"
 #include "lili_s2m_dev.h"
 
 namespace lili {
@@ -19,16 +20,12 @@ namespace lili {
 // ================================================================================================
 // cloud ingestion: AoS points (stride 32 / 48 B ...) -> float4 (x, y, z, aux)
 // ================================================================================================
-__device__ __forceinline__ unsigned f2ord(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 // `mm` (optional, 64 banks x 32 words, words 0..5 of a bank = ordered-uint min xyz / max xyz): the bounding box of the finite points is reduced in the same pass (the map
 // index needs it before anything else; a separate k_bbox pass re-read the whole cloud) — one atomic set per block.
 __global__ __launch_bounds__(256) void k_cloud_to_f4(const unsigned char* __restrict__ raw, int n, int stride, int aux_off, float4* __restrict__ out, unsigned* __restrict__ mm) {
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float* p = reinterpret_cast<const float*>(raw + (size_t)i * stride);
-        float4 v;
-        v.x = p[0]; v.y = p[1]; v.z = p[2];
-        v.w = aux_off >= 0 ? *reinterpret_cast<const float*>(raw + (size_t)i * stride + aux_off) : 0.f;
+        const float4 v = load_row_f4(raw + (size_t)i * stride, aux_off);
         out[i] = v;
         if (mm && isfinite(v.x) && isfinite(v.y) && isfinite(v.z)) {
             mn[0] = fminf(mn[0], v.x); mn[1] = fminf(mn[1], v.y); mn[2] = fminf(mn[2], v.z);

@@ -306,14 +306,6 @@ template __global__ void k_associate_coop_window<16>(WinAssocArgs, MatchParams);
 // up to the partition of the Gram sum (poses <= 1e-10, tests/test_coop_gpu.py).  All workgroups must be resident (<= 256 of 256 threads);
 // every wait is bounded and ends with gn_status = 2 instead of a hang.
 // ================================================================================================
-struct IterArgs {
-    SlotState* state;
-    double* part;                 // [2 parities][nb][kPartialStride]
-    double* gsum;                 // [2 parities][ng][kPartialStride]
-    double* cpart;                // [2 parities][nb + ng][4]            correspondence counts (surf, edge) as granules
-    int nb, ng, n_iters, derive_assoc;
-    unsigned long long launch;
-};
 struct IterShared {
     double vals[16][40];
     double cvals[16][2];

@@ -780,7 +780,6 @@ struct LaneRec { bool ok; float4 ql, r0, r1; double score; };
 // block writes one 40-double partial; k_reduce_gn adds the partials in a fixed order.
 // ================================================================================================
 constexpr int kRow = 12;          // LDS row: [J0..J6, r | 1, cost, 0, 0]
-constexpr int kLinBlock = 1024;   // linearisation block (16 waves; the launch covers the queries with <= 256 blocks)
 // Gram accumulation on the f64 matrix cores.  Per wave, G += V^T V over its 64 rows v = [a | b | e] with a = (J0..J3),
 // b = (J4, J5, J6, r), e = (1, cost, 0, 0), issued as 16 x v_mfma_f64_4x4x4_4b_f64: ONE instruction contracts four rows (k)
 // into four independent 4x4 blocks — block 0: a a^T, block 1: a b^T, block 2: b b^T, block 3: e e^T (count and cost sum) —

@@ -27,26 +27,8 @@
 // All workgroups must be co-resident (<= one per CU: 512 threads at up to 256 VGPRs, 48 KB LDS); every wait is bounded and ends the launch with
 // termination = LILI_LM_STALLED instead of hanging the GPU.
 #include "lili_s2m_dev.h"
-#include "../../include/lili_hip.h"
 
 namespace lili {
-
-constexpr int kLmThreads = 512;      // 8 waves: the launch may use 256 VGPRs per lane (1024-thread workgroups cap it at 128 and the loop spilled ~150 words)
-constexpr int kLmGroup = 16;      // workgroups per group sum; up to this many workgroups exchange in ONE hop (32: measured slower, one wave polls 1280 granules)
-
-struct LmArgs {
-    LinArgs S, E;                 // records of the two kinds; S.nb / E.nb = workgroups of each kind (either may be 0)
-    SlotState* state;
-    double* part;                 // [2 parities][nb][kPartialStride]   block partials as granules
-    double* gsum;                 // [2 parities][ng][kPartialStride]   group sums as granules
-    int nb, ng;
-    int max_iter;
-    unsigned long long launch;    // host counter: makes the granule keys of this launch unique
-    lili_lm_summary* summary;     // device copy, written by workgroup 0
-    double function_tolerance, gradient_tolerance, parameter_tolerance;
-    double initial_radius, max_radius, min_radius, min_relative_decrease, min_lm_diagonal, max_lm_diagonal;
-};
-struct WinLmArgs { LmArgs a[kWindowMaxSlots]; int first_block[kWindowMaxSlots]; int n; };      // must match lili_launch.h
 
 struct LmShared {
     double vals[kLmGroup][40];

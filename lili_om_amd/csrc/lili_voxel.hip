@@ -9,17 +9,13 @@
 //     PCL's std::sort leaves that order unspecified — oracle mode stable_sort = 1)
 //   * keyframe ring buffer: transformCloud (f64 rotate + translate, stored f32) of each pushed feature cloud,
 //     oldest dropped beyond `width`, commit = concatenate + voxel filter + uniform-grid index (lili_map_set path)
-#include "lili_ctx.h"
+#include "lili_launch.h"
 #include "lili_device_math.h"
+#include "lili_device_cloud.h"
 
 namespace lili_detail { struct ConcatSeg { const float4* src; long long first; }; }      // one keyframe of the ring: its points and where they start in the concatenation
 
 namespace lili {
-__global__ void k_scan_block_sums(const int*, int64_t, int*);
-__global__ void k_scan_sums(int*, int);
-__global__ void k_scan_apply(const int*, int64_t, const int*, int*);
-__global__ void k_bbox(const float4*, int, unsigned*);
-__global__ void k_bbox_dev(const float4*, const int*, int, unsigned*);
 
 constexpr int kSortBlock = 256, kSortItems = 8, kSortTile = kSortBlock * kSortItems;
 
@@ -233,12 +229,11 @@ __global__ void k_vox_key_dev(const float4* __restrict__ pts, int n, float inv_l
                               int bits_guess, unsigned* __restrict__ keys, int* __restrict__ vals, int* __restrict__ res,
                               int* __restrict__ hist0 /*[256][nb] counts of the lowest digit per sort tile, or nullptr*/, int nb, int tile) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    auto dec = [](unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); };
     int min_b[3], div_b[3];
     bool any = true;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        const float mn = dec(zform ? ~mm[k] : mm[k]), mx = dec(mm[3 + k]);
+        const float mn = ord2f(zform ? ~mm[k] : mm[k]), mx = ord2f(mm[3 + k]);
         if (!(mn <= mx)) any = false;
         min_b[k] = (int)floorf(mn * inv_leaf);
         div_b[k] = (int)floorf(mx * inv_leaf) - min_b[k] + 1;
@@ -277,11 +272,10 @@ __global__ void k_vox_key_packed(const float4* __restrict__ pts, int n, float in
                                  unsigned* __restrict__ bad) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    auto dec = [](unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); };
     const float4 p = pts[i];
     vals[i] = i;
     if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) { keys[i] = 0xFFFFFFFFu; return; }
-    const int m0 = (int)floorf(dec(mm[0]) * inv_leaf), m1 = (int)floorf(dec(mm[1]) * inv_leaf), m2 = (int)floorf(dec(mm[2]) * inv_leaf);
+    const int m0 = (int)floorf(ord2f(mm[0]) * inv_leaf), m1 = (int)floorf(ord2f(mm[1]) * inv_leaf), m2 = (int)floorf(ord2f(mm[2]) * inv_leaf);
     const int i0 = (int)floorf(p.x * inv_leaf) - m0, i1 = (int)floorf(p.y * inv_leaf) - m1, i2 = (int)floorf(p.z * inv_leaf) - m2;
     if (i0 < 0 || i0 > 2047 || i1 < 0 || i1 > 2047 || i2 < 0 || i2 > 1022) { *bad = 1u; keys[i] = 0xFFFFFFFEu; return; }
     keys[i] = ((unsigned)i2 << 22) | ((unsigned)i1 << 11) | (unsigned)i0;
@@ -295,7 +289,6 @@ __global__ void k_vox_heads(const unsigned* __restrict__ keys, const int* __rest
     spts[i] = pts[vals[i]];
     flags[i] = (keys[i] != sentinel && (i == 0 || keys[i] != keys[i - 1])) ? 1 : 0;
 }
-__device__ __forceinline__ void wave_lds_order();
 // CentroidPoint over the sorted cloud: float accumulators, members added in sorted (= input) order — the sum itself has to stay sequential, so the launch lasts as long as
 // its fullest voxel (next to the sensor: up to ~600 of a Livox frame's 21 k surf features; nine voxels of ten hold 4 or fewer).  Round 5: the launch is a chain of THREE
 // memory round trips whatever the voxel's size —
@@ -350,35 +343,12 @@ __global__ __launch_bounds__(256) void k_vox_centroid(const unsigned* __restrict
     __syncthreads();
     const int nq = q_n;
     for (int j = wave; j < nq; j += 4) {      // (wave-uniform)
-        int mL = q_m[j];
+        const int mL = q_m[j];
         const int eL = q_end[j], oL = q_o[j];
         // lane c (of every four) carries component c of the sum: ONE dependent addition per member instead of four (the fullest voxel's ~600 members are the launch's tail)
         const int comp = lane & 3;
         float acc = comp == 0 ? q_s[j].x : comp == 1 ? q_s[j].y : comp == 2 ? q_s[j].z : q_s[j].w;
-        const float* st = reinterpret_cast<const float*>(stage[wave]) + comp;
-        while (mL < eL) {
-            const int cnt = min(eL - mL, kStage);
-            float4 reg[kStage / 64];
-#pragma unroll
-            for (int r = 0; r < kStage / 64; r++) reg[r] = spts[min(mL + 64 * r + lane, eL - 1)];      // (no branch: every request leaves before the first answer is awaited; rows behind the end re-read its last point)
-#pragma unroll
-            for (int r = 0; r < kStage / 64; r++) stage[wave][64 * r + lane] = reg[r];
-            wave_lds_order();
-            float p[16];
-#pragma unroll
-            for (int t = 0; t < 16; t++) p[t] = st[4 * t];
-            for (int u = 0; u < cnt; u += 16) {
-                float nx[16];
-#pragma unroll
-                for (int t = 0; t < 16; t++) nx[t] = st[4 * min(u + 16 + t, kStage - 1)];
-#pragma unroll
-                for (int t = 0; t < 16; t++) if (u + t < cnt) acc += p[t];
-#pragma unroll
-                for (int t = 0; t < 16; t++) p[t] = nx[t];
-            }
-            mL += cnt;
-            wave_lds_order();      // the next members overwrite the stage
-        }
+        acc = fold_staged<kStage>(spts, mL, eL, stage[wave], lane, acc);
         const float ax = __shfl(acc, 0), ay = __shfl(acc, 1), az = __shfl(acc, 2), aw = __shfl(acc, 3);
         if (lane == 0) {
             const int len_l = eL - (q_m[j] - kFirst);
@@ -396,8 +366,6 @@ __global__ __launch_bounds__(256) void k_vox_centroid(const unsigned* __restrict
 // in LDS —, members of a voxel summed in input order with float accumulators, non-finite points skipped.  res[0] = number of voxels, res[1] = 1 if the voxel index
 // would not fit 31 bits (the caller then takes the general path, which reports PCL's overflow error), 2 if no point is finite.
 constexpr int kVoxSmallMax = 8192, kVoxSmallThreads = 1024;
-// between two steps of a sort in which a wave reads what only ITS OWN lanes wrote: the LDS serves a wave's accesses in order; the compiler must keep them in order too
-__device__ __forceinline__ void wave_lds_order() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
 __global__ __launch_bounds__(kVoxSmallThreads) void k_voxel_small(const float4* __restrict__ pts, int n, float inv_leaf, float4* __restrict__ out, int* __restrict__ out_cnt,
                                                                    int* __restrict__ res) {
     __shared__ unsigned long long key[kVoxSmallMax];
@@ -511,12 +479,6 @@ __global__ __launch_bounds__(kVoxSmallThreads) void k_voxel_small(const float4* 
 // new ones in one streaming pass (ranks by prefix sum and binary search, no comparison network), and run the centroid pass — the same f32
 // sums over the same members in the same order, so the map is bit-identical to the full rebuild (tests/test_voxel_gpu.py).
 // ------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long abs_voxel_key(float4 p, float inv_leaf) {
-    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) return ~0ull;               // sorts last, never a voxel (voxel_grid.hpp: !isFinite -> skipped)
-    const long long i = (long long)floorf(p.x * inv_leaf) + (1ll << 20), j = (long long)floorf(p.y * inv_leaf) + (1ll << 20), k = (long long)floorf(p.z * inv_leaf) + (1ll << 20);
-    if ((i | j | k) < 0 || i >= (1ll << 21) || j >= (1ll << 21) || k >= (1ll << 21)) return ~0ull - 1ull;      // beyond +-2^20 voxels: the host falls back to the full rebuild (flagged)
-    return ((unsigned long long)k << 42) | ((unsigned long long)j << 21) | (unsigned long long)i;
-}
 // sorted copy of one cloud: out_pt[r] = pts[order[r]], its absolute key and a constant sequence number; *bad is raised if a point lies outside the key range
 __global__ void k_sorted_gather(const float4* __restrict__ pts, const int* __restrict__ order, int n, float inv_leaf, unsigned seq_const, const lili_detail::ConcatSeg* __restrict__ segs,
                                 const unsigned* __restrict__ seg_seq, int n_seg, float4* __restrict__ out_pt, unsigned long long* __restrict__ out_key, unsigned* __restrict__ out_seq,
@@ -529,9 +491,7 @@ __global__ void k_sorted_gather(const float4* __restrict__ pts, const int* __res
     if (key == ~0ull - 1ull) *bad = 1u;
     unsigned sq = seq_const;
     if (segs) {          // the cloud is the concatenation of the ring: the keyframe of a point by bisection over the segments' first positions
-        int lo = 0, hi = n_seg - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first <= (long long)src) lo = mid; else hi = mid - 1; }
-        sq = seg_seq[lo];
+        sq = seg_seq[seg_of(segs, n_seg, src)];
     }
     out_pt[r] = p; out_key[r] = key; out_seq[r] = sq;
 }
@@ -543,7 +503,7 @@ __global__ void k_sorted_gather(const float4* __restrict__ pts, const int* __res
 // into places.  n^2 / 4096 wave tasks of ~1.5 us each on n^2 / 32768 workgroups: ~4 us for the 2 k points of a Livox frame, where a single-workgroup bitonic network
 // took 22-27 us and counting inside n / 64 workgroups 19.
 constexpr int kRankWaves = 8;
-constexpr size_t kRankOff = 2 * 64 * 128 + 256;      // ctx->misc behind the box / density banks (lili_map.hip: kMiscBytes): the scan-status words of a map build
+constexpr size_t kRankOff = kMiscRankOff;      // ctx->misc behind the box / density banks: the scan-status words of a map build
 static_assert(kRankOff + (size_t)kVoxSmallMax * 4 <= kMiscAlloc, "rank words of k_rank_count");
 __global__ __launch_bounds__(64 * kRankWaves) void k_rank_count(const float4* __restrict__ pts, int n, float inv_leaf, int* __restrict__ rank, unsigned* __restrict__ bad) {
     __shared__ int part[kRankWaves][64];
@@ -645,8 +605,7 @@ __global__ void k_rank_scatter_segs(const float4* __restrict__ pts, int n, float
                                     const int* __restrict__ rank, float4* __restrict__ out_pt, unsigned long long* __restrict__ out_key, unsigned* __restrict__ out_seq) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first <= (long long)e) lo = mid; else hi = mid - 1; }
+    const int lo = seg_of(segs, n_seg, e);
     const float4 p = pts[e];
     const int r = rank[e];
     out_pt[r] = p; out_key[r] = abs_voxel_key(p, inv_leaf); out_seq[r] = seg_seq[lo];
@@ -674,7 +633,6 @@ __global__ void k_vox_head_pos(const int* __restrict__ flags, const int* __restr
     if (i < n && flags[i]) head_pos[slot[i]] = (int)i;
 }
 constexpr int kBoxBanks = 32;      // x 128 bytes
-__device__ __forceinline__ unsigned f2ord_v(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }      // order-preserving float -> uint (as lili_s2m.hip)
 // `boxz` (may be null): bounding box of the centroids in the ZERO-INITIALISED form — words 0-2 hold ~ordered(min), words 3-5 ordered(max), all six maximised from zero —
 // so that the fill that arms the commit's other scratch words arms it too (round 5: k_box_init + k_bbox_dev were two launches of the frame pipeline's commit)
 __global__ void k_vox_centroid64(const unsigned long long* __restrict__ keys, const float4* __restrict__ pts, const int* __restrict__ head_pos /*[n_out] = where the voxels end if has_end*/,
@@ -721,7 +679,7 @@ __global__ void k_vox_centroid64(const unsigned long long* __restrict__ keys, co
         float a = smn[0][k], b = smx[0][k];
         for (int w = 1; w < 4; w++) { a = fminf(a, smn[w][k]); b = fmaxf(b, smx[w][k]); }
         unsigned* bank = boxz + (blockIdx.x % kBoxBanks) * 32;
-        if (a <= b) { atomicMax(&bank[k], ~f2ord_v(a)); atomicMax(&bank[3 + k], f2ord_v(b)); }
+        if (a <= b) { atomicMax(&bank[k], ~f2ord(a)); atomicMax(&bank[3 + k], f2ord(b)); }
     }
 }
 
@@ -748,30 +706,24 @@ __global__ void k_transform_cloud_state(const float4* __restrict__ in, int n, co
 }
 
 // lili_localmap_repose: the changed keyframes of both rings re-transformed from their LiDAR-frame rows in ONE launch; thread i finds its keyframe by bisection over the
-// (ascending) first positions of the segment table, as k_concat does
+// (ascending) first positions of the segment table
 struct ReposeSeg { const float4* src; float4* dst; long long first; double t[3], q[4]; };
 __global__ void k_ring_repose(const ReposeSeg* __restrict__ segs, int n_seg, long long total) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first <= i) lo = mid; else hi = mid - 1; }
-    const ReposeSeg& s = segs[lo];
+    const ReposeSeg& s = segs[seg_of(segs, n_seg, i)];
     const long long j = i - s.first;
     s.dst[j] = transform_point(s.src[j], dq{s.q[0], s.q[1], s.q[2], s.q[3]}, d3{s.t[0], s.t[1], s.t[2]});
 }
 
 // lili_loop_cloud: detectLoopClosure's transformCloud + concatenation (L/src/BackendFusion.cpp:2476-2493, 2502-2521) of a caller's keyframe clouds in ONE launch —
-// the rows read where they lie as k_cloud_to_f4 reads them, placed by the same expression as the ring's keyframes; thread i finds its cloud by bisection
+// the rows read where they lie (load_row_f4), placed by the same expression as the ring's keyframes; thread i finds its cloud by bisection
 struct LoopSeg { const unsigned char* src; long long first; int stride, aux_off; double t[3], q[4]; };
 __global__ void k_loop_gather(const LoopSeg* __restrict__ segs, int n_seg, long long total, float4* __restrict__ out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first <= i) lo = mid; else hi = mid - 1; }
-    const LoopSeg& s = segs[lo];
-    const unsigned char* row = s.src + (size_t)(i - s.first) * s.stride;
-    const float* p = reinterpret_cast<const float*>(row);
-    const float4 v = make_float4(p[0], p[1], p[2], s.aux_off >= 0 ? *reinterpret_cast<const float*>(row + s.aux_off) : 0.f);
+    const LoopSeg& s = segs[seg_of(segs, n_seg, i)];
+    const float4 v = load_row_f4(s.src + (size_t)(i - s.first) * s.stride, s.aux_off);
     out[i] = transform_point(v, dq{s.q[0], s.q[1], s.q[2], s.q[3]}, d3{s.t[0], s.t[1], s.t[2]});
 }
 
@@ -836,8 +788,7 @@ struct VoxelBuffers {
 __global__ void k_concat(const lili_detail::ConcatSeg* __restrict__ segs, int n_seg, long long total, float4* __restrict__ out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first <= i) lo = mid; else hi = mid - 1; }
+    const int lo = lili::seg_of(segs, n_seg, i);
     out[i] = segs[lo].src[i - segs[lo].first];
 }
 
@@ -1052,13 +1003,7 @@ static int exclusive_scan(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const int
         HIPCHK(hipGetLastError());
         return LILI_OK;
     }
-    const int nb = nblocks(n, 2048);
-    HIPCHK(V->sums.ensure((size_t)nb * sizeof(int)));
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(256), 0, ctx->stream, in, n, V->sums.as<int>());
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, ctx->stream, V->sums.as<int>(), nb);
-    hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(256), 0, ctx->stream, in, n, V->sums.as<int>(), out);
-    HIPCHK(hipGetLastError());
-    return LILI_OK;
+    return lili_scan_exclusive3(ctx, in, n, V->sums, out);
 }
 
 // sorts (keys_a, vals_a) by the low `bits` bits, stable; result ends in (keys_a, vals_a).  8-bit digits (option sort_digit_bits = 4: the
@@ -1120,12 +1065,11 @@ static int voxel_sort(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const float4*
     hipLaunchKernelGGL(k_bbox, dim3(std::min(nblocks(n, kBlock), 512)), dim3(kBlock), 0, ctx->stream, d_pts, n, d_mm);
     unsigned mm[6];
     { int rb = lili_readback_add(ctx, mm, d_mm, sizeof(mm)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
-    auto dec = [](unsigned u) { unsigned b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u; float f; std::memcpy(&f, &b, 4); return f; };
     P = VoxDev{};
     P.inv_leaf = 1.0f / leaf;
     int div_b[3];
     for (int k = 0; k < 3; k++) {
-        float mn = dec(mm[k]), mx = dec(mm[3 + k]);
+        float mn = ord2f(mm[k]), mx = ord2f(mm[3 + k]);
         if (!(mn <= mx)) { if (status) { *status = 2; return LILI_OK; } return ctx->fail(LILI_E_ARG, "voxel_filter: cloud holds no finite point"); }
         if (box) { box[k] = mn; box[3 + k] = mx; }
         P.min_b[k] = (int)std::floor(mn * P.inv_leaf);
@@ -1613,10 +1557,9 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
             // error a first commit would report.
             bool guard = total > 0 && V->n_out == 0;
             if (!guard && have_box) {
-                auto dec = [](unsigned u) { unsigned b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u; float f; std::memcpy(&f, &b, 4); return f; };
                 const float inv_leaf = 1.0f / leaf;
                 double cells = 1.0;
-                for (int k = 0; k < 3; k++) cells *= (double)((long long)std::floor(dec(V->out_box[3 + k]) * inv_leaf) - (long long)std::floor(dec(V->out_box[k]) * inv_leaf) + 3);
+                for (int k = 0; k < 3; k++) cells *= (double)((long long)std::floor(ord2f(V->out_box[3 + k]) * inv_leaf) - (long long)std::floor(ord2f(V->out_box[k]) * inv_leaf) + 3);
                 guard = !(cells <= 2147483647.0);
             }
             if (guard) { S.valid = false; inc = false; have_box = false; }

@@ -23,7 +23,7 @@
 namespace lili {
 
 constexpr int kWinMaxKf = LILI_WINDOW_MAX_KF, kWinMaxN = 15 * kWinMaxKf, kWinMaxBlocks = 3 * kWinMaxKf;
-constexpr int kWinThreads = 512;      // as k_solve_lm: 8 waves, the launch may use 256 VGPRs per lane
+constexpr int kWinThreads = kLmThreads;      // k_solve_lm's workgroup, for its reason: 8 waves, the launch may use 256 VGPRs per lane
 constexpr int kWinGroup = 16;         // workgroups per slot at most: every slot's partials are gathered in ONE hop
 
 struct WinImuDev {

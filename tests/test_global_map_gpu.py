@@ -269,6 +269,22 @@ def test_int32_guard_over_everything_folded(oracle):
         ctx.close()
 
 
+def test_refuses_a_point_beyond_the_key_range():
+    """one keyframe of 8 points within 1 cm of (2000, 0, 0) at leaf 0.001: the box is a few voxels wide (PCL's int32 guard does not fire), the voxel index 2 * 10^6
+    exceeds the 2^20 the absolute key can hold — an argument error that says so"""
+    ctx = L.Context(0)
+    try:
+        arch = L.KeyframeArchive(ctx)
+        gm = L.GlobalMap(arch)
+        pts = _rows(np.array([2000.0, 0.0, 0.0]) + np.random.default_rng(5).uniform(-0.005, 0.005, (8, 3)), 6)
+        arch.push(None, None, pts, 0.0, np.zeros(3), np.array([1.0, 0, 0, 0]))
+        with pytest.raises(L.LiliError) as e:
+            gm.build(ARCHIVE_FULL, 1, 0.001)
+        assert str(e.value).startswith("lili error -1:") and "2^20 voxels" in str(e.value)      # LILI_E_ARG
+    finally:
+        ctx.close()
+
+
 def test_archive_and_map_calls_leave_the_rest_of_the_context_alone(world):
     """the same local-map / voxel-filter / loop sequence with and without archive and global-map calls interleaved: identical maps, statistics, clouds and registration"""
     ts, qs, full = _small(world, 8, rows=12_000, seed=5)
