@@ -658,17 +658,18 @@ class ScanToMapMatcher:
             setattr(o, k, v)
         return o
 
-    def solve_lm(self, slot, kind_mask=MASK_SURF | MASK_EDGE, options=None, want_summary=True):
+    def solve_lm(self, slot, kind_mask=MASK_SURF | MASK_EDGE, options=None, want_summary=True, summary=None):
         """Levenberg-Marquardt on the records of the last association, one persistent launch (ceres::Solve's loop for the lidar blocks of one
-        keyframe); returns the summary as a dict (blocking) or None (asynchronous)."""
-        s = LmSummary() if want_summary else None
+        keyframe); returns the summary as a dict (blocking) or None (asynchronous).  summary: an LmSummary of the caller's to fill instead of a new one."""
+        s = summary if summary is not None else LmSummary() if want_summary else None
         self.ctx._chk(self.lib.lili_s2m_solve_lm(self.ctx.h, slot, kind_mask, C.byref(self.params), C.byref(options) if options is not None else None,
                                                      C.byref(s) if s is not None else None))
         return s.as_dict() if s is not None else None
 
-    def solve_lm_window(self, slots, kind_mask=MASK_SURF | MASK_EDGE, options=None, want_summary=True):
+    def solve_lm_window(self, slots, kind_mask=MASK_SURF | MASK_EDGE, options=None, want_summary=True, summary=None):
+        """summary: an (LmSummary * len(slots)) array of the caller's to fill instead of a new one"""
         arr = (C.c_int * len(slots))(*slots)
-        s = (LmSummary * len(slots))() if want_summary else None
+        s = summary if summary is not None else (LmSummary * len(slots))() if want_summary else None
         self.ctx._chk(self.lib.lili_s2m_solve_lm_window(self.ctx.h, arr, len(slots), kind_mask, C.byref(self.params),
                                                             C.byref(options) if options is not None else None, s))
         return [x.as_dict() for x in s] if s is not None else None
@@ -1101,11 +1102,11 @@ class WindowSolver:
         self.ctx._chk(self.lib.lili_window_evaluate(self.ctx.h, C.byref(self.problem), C.byref(self.matcher.params), _ptr(s), _ptr(cost), _ptr(g), _ptr(H)))
         return float(cost[0]), g, H
 
-    def solve(self, state, options=None, want_summary=True):
+    def solve(self, state, options=None, want_summary=True, summary=None):
         """ceres::Solve on the window, one persistent launch: (final state (n_kf, 16), summary dict) — or (None, None) asynchronously
-        (want_summary=False; last_state() fetches the state later)."""
+        (want_summary=False; last_state() fetches the state later).  summary: an LmSummary of the caller's to fill instead of a new one."""
         s = self._state(state)
-        sm = LmSummary() if want_summary else None
+        sm = summary if summary is not None else LmSummary() if want_summary else None
         self.ctx._chk(self.lib.lili_window_solve(self.ctx.h, C.byref(self.problem), C.byref(self.matcher.params), C.byref(options) if options is not None else None,
                                                  _ptr(s), C.byref(sm) if sm is not None else None))
         return (s, sm.as_dict()) if sm is not None else (None, None)

@@ -286,7 +286,8 @@ class Problem:
             if want_jac:
                 Jd = np.zeros((len(r), int(sum(sizes))))
                 for n, J in zip(names, Js):
-                    J = np.asarray(J, np.float64).reshape(len(r), -1)
+                    J = np.asarray(J, np.float64)
+                    J = J.reshape(len(r), J.shape[-1] if J.ndim == 2 else -1)      # (a block without rows keeps its columns)
                     if self.kind[n]:
                         J = J @ plus_jacobian(values[n])
                     Jd[:, offs[n]:offs[n] + J.shape[1]] += J

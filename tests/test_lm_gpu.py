@@ -22,15 +22,21 @@ def _angle(qa, qb):
     return 2.0 * np.arctan2(np.linalg.norm(d[1:]), abs(d[0]))
 
 
-def _setup(gpu_ctx, flavour, seed, n_surf, n_edge, off=(0.06, 0.6)):
+def _data(flavour, seed, n_surf, n_edge, off=(0.06, 0.6)):
+    """the room, the association pose and the reflectivities of _setup, without a device (the oracle-only checks need no more)"""
     room = synth.make_room(seed=seed, n_query=n_surf, n_edge_query=n_edge)
     P = L.make_params(flavour)
     tb, qb = L.api.body_pose_from_lidar(room["t_true"], room["q_true"], P)
     t0, q0 = synth.perturbed_pose(tb, qb, np.random.default_rng(seed + 3), *off)
     rng = np.random.default_rng(seed + 7)
     refl = lambda n: rng.uniform(0.0, 0.05, n).astype(np.float32)
-    data = dict(room=room, P=P, t0=np.asarray(t0, np.float64), q0=np.asarray(q0, np.float64), tb=tb, qb=qb,
+    return dict(room=room, P=P, t0=np.asarray(t0, np.float64), q0=np.asarray(q0, np.float64), tb=tb, qb=qb,
                 map_refl=refl(room["map_xyz"].shape[0]), q_refl=refl(room["q_xyz"].shape[0]))
+
+
+def _setup(gpu_ctx, flavour, seed, n_surf, n_edge, off=(0.06, 0.6)):
+    data = _data(flavour, seed, n_surf, n_edge, off)
+    room, P = data["room"], data["P"]
     m = L.ScanToMapMatcher(gpu_ctx, P)
     if flavour == "livox":
         m.set_input_cloud(L.KIND_SURF, np.c_[room["map_xyz"], data["map_refl"]])

@@ -149,13 +149,14 @@ def values_of(state):
     return v
 
 
-def perturbed(state, seed, negate_q=None):
+def perturbed(state, seed, negate_q=None, scale=1):
+    """every sigma times `scale`; the draws and their order do not depend on it"""
     rng = np.random.default_rng(seed)
     s = np.array(state, np.float64)
     for k in range(s.shape[0]):
-        s[k, 0:3] += rng.normal(0, 0.02, 3)
-        s[k, 3:7] = W.quat_plus(s[k, 3:7], rng.normal(0, 0.004, 3))
-        s[k, 7:16] += np.concatenate([rng.normal(0, 0.03, 3), rng.normal(0, 0.002, 3), rng.normal(0, 0.0003, 3)])
+        s[k, 0:3] += rng.normal(0, 0.02 * scale, 3)
+        s[k, 3:7] = W.quat_plus(s[k, 3:7], rng.normal(0, 0.004 * scale, 3))
+        s[k, 7:16] += np.concatenate([rng.normal(0, 0.03 * scale, 3), rng.normal(0, 0.002 * scale, 3), rng.normal(0, 0.0003 * scale, 3)])
     if negate_q is not None:
         s[negate_q, 3:7] = -s[negate_q, 3:7]
     return s
