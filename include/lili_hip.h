@@ -232,7 +232,9 @@ typedef struct lili_livox_params {
  * pcl::PointXYZINormal.  q_imu = the gyro quaternion integrated over the scan (L:129-171, caller side).
  * Outputs are records of 32 B (x,y,z,nx,ny,nz,intensity,curvature; stride 32) or pcl::PointXYZINormal (stride 48):
  *   cutted: every deskewed point with a valid line (/lidar_cloud_cutted), edge: /edge_features (normal = line
- *   direction), surf: /surf_features (normal = plane normal).  Blocking.  The rows are read as they are (one transfer for host memory);
+ *   direction), surf: /surf_features (normal = plane normal).  Blocking.  A valid line is int(intensity) in 0 .. 5: a negative line is skipped as in the
+ *   reference, a line >= 6 (the reference would write outside its grid) and a non-finite intensity (NaN, +-inf: the reference's x86 build converts them to
+ *   INT_MIN and skips the point) are dropped before lidar_cloud_cutted as well.  The rows are read as they are (one transfer for host memory);
  *   a `cutted` buffer in host memory receives min(scan->n, capacity) records while the features are selected — the records behind
  *   cutted->count are unspecified.  `edge` and `surf` buffers in PAGE-LOCKED host memory (lili_host_alloc, 16-byte aligned) are written by the
  *   packing kernel itself, `count` records each, and the call synchronises once; pageable buffers are served by copies after the counts have arrived. */

@@ -63,7 +63,9 @@ __global__ __launch_bounds__(256) void k_livox_prep(const unsigned char* __restr
     }
     bool ok = live && isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && !(p.x * p.x + p.y * p.y + p.z * p.z < P.near_thres * P.near_thres);   // L:225-226
     int scan_id = (int)p.w;                                                                                                          // L:252
-    ok = ok && scan_id >= 0 && scan_id < kLvLines;   // lines >= 6 would index mat[] out of bounds in the reference
+    // lines >= 6 would index mat[] out of bounds in the reference.  A non-finite intensity holds no line: the reference's x86 conversion gives INT_MIN (skipped by
+    // scan_id < 0), this one gives 0 for NaN — the point would pass as line 0 and enter lidar_cloud_cutted as a row of NaN
+    ok = ok && isfinite(p.w) && scan_id >= 0 && scan_id < kLvLines;
     if (live) keep[i] = ok;
     const int nk = __syncthreads_count(ok ? 1 : 0);
     if (threadIdx.x == 0) blk_keep[blockIdx.x] = nk;

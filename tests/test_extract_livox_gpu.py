@@ -6,21 +6,9 @@ import pytest
 
 import lili_om_amd as L
 from lili_om_amd import synth
+from tests.livox_cases import check as _check
 
 pytestmark = pytest.mark.gpu
-
-
-def _check(g, o):
-    assert np.array_equal(g["cut_src"], o["cut_src"])
-    assert np.array_equal(g["cutted"].view(np.uint32), o["cutted"].view(np.uint32))
-    assert np.array_equal(g["cell_src"], o["cell_src"])
-    assert np.array_equal(g["edge_cell"], o["edge_cell"])
-    assert np.array_equal(g["surf_cell"], o["surf_cell"])
-    for k in ("edge", "surf"):
-        a, b = g[k], o[k]
-        assert a.shape == b.shape
-        assert np.array_equal(a[:, [0, 1, 2, 6, 7]].view(np.uint32), b[:, [0, 1, 2, 6, 7]].view(np.uint32))
-        np.testing.assert_allclose(a[:, 3:6], b[:, 3:6], rtol=0, atol=2e-6)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
@@ -44,12 +32,15 @@ def test_livox_extractor_edge_cases(gpu_ctx, oracle):
     P = oracle.livox_params(0.2, 2.0, 0.1)
     scan = synth.make_livox_scan(5)
     bad = scan.copy()
-    bad[100:110, 3] = -0.5        # negative line -> dropped before lidar_cloud_cutted
+    bad[100:110, 3] = -0.5        # int(-0.5) = 0: line 0 with a negative column -> in lidar_cloud_cutted, not in the grid
+    bad[120:130, 3] = -1.5        # negative line -> dropped before lidar_cloud_cutted
     bad[200:210, 3] = 7.25        # line >= 6: rejected (the reference would write out of bounds)
     bad[300:400, :3] *= 50.0      # beyond 200 m: in cutted, not in the grid
     g = ex.extract(bad, debug=True)
     o = oracle.extract_livox(bad, P=P)
     _check(g, o)
+    assert np.isin(np.arange(100, 110), g["cut_src"]).all() and not np.isin(np.arange(100, 110), g["cell_src"]).any()
+    assert not np.isin(np.arange(120, 130), g["cut_src"]).any() and not np.isin(np.arange(200, 210), g["cut_src"]).any()
     g0 = ex.extract(np.zeros((0, 5), np.float32), debug=True)
     assert g0["cutted"].shape[0] == 0 and g0["surf"].shape[0] == 0 and (g0["cell_src"] == -1).all()
 
@@ -66,7 +57,9 @@ def test_livox_extractor_layouts_and_repeats(gpu_ctx, oracle):
     o = oracle.extract_livox(scan)
     _check(ref, o)
     for other in (scan[:5000], np.zeros((0, 5), np.float32), scan[::3], scan):
-        g = ex.extract(np.ascontiguousarray(other), debug=True)
+        other = np.ascontiguousarray(other)
+        g = ex.extract(other, debug=True)
+        _check(g, oracle.extract_livox(other))
     for k in ("cutted", "edge", "surf", "cut_src", "cell_src", "edge_cell", "surf_cell"):
         assert np.array_equal(g[k], ref[k]), k
     n = scan.shape[0]
