@@ -83,6 +83,10 @@ int lili_readback_finish(lili_ctx* ctx, hipStream_t stream) {
     HIPCHK(e);
     return LILI_OK;
 }
+int lili_readback_now(lili_ctx* ctx, void* dst, const void* d_src, size_t bytes, hipStream_t stream) {
+    TRY(lili_readback_add(ctx, dst, d_src, bytes, stream));
+    return lili_readback_finish(ctx, stream);
+}
 
 // copies / converts a described cloud into a device float4 array (x, y, z, aux)
 // The device-side address of a caller's PAGE-LOCKED host buffer (lili_host_alloc / hipHostMalloc / hipHostRegister), or nullptr: pageable memory, or not aligned to

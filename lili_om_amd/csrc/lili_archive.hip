@@ -395,9 +395,7 @@ int fold_batch(lili_ctx* ctx, GlobalMap& G, int total) {
                        G.key[nxt].as<unsigned long long>(), G.sum[nxt].as<float4>(), G.cnt[nxt].as<int>());
     HIPCHK(hipGetLastError());
     int n_new = 0;
-    rc = lili_readback_add(ctx, &n_new, G.new_rank.as<int>() + n_vox, sizeof(int));
-    if (rc == LILI_OK) rc = lili_readback_finish(ctx);
-    if (rc != LILI_OK) return rc;
+    TRY(lili_readback_now(ctx, &n_new, G.new_rank.as<int>() + n_vox, sizeof(int)));
     if (n_new < 0 || n_new > n_vox) return ctx->fail(LILI_E_STATE, "global_map: internal: new-voxel count of a batch out of range");
     G.cur = nxt;
     G.n_tab = (long long)n_tab + n_new;

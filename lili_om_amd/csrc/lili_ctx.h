@@ -235,6 +235,7 @@ struct lili_ctx {
         if (_e != hipSuccess) return ctx->fail(LILI_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 #define ARGCHK(cond, msg) do { if (!(cond)) return ctx->fail(LILI_E_ARG, msg); } while (0)
+#define TRY(expr) do { const int _rc = (expr); if (_rc != LILI_OK) return _rc; } while (0)      // a library call's status, handed on
 
 // PCL's "leaf size is too small for the input dataset": the refusal of lili_voxel_filter, and of lili_global_map for everything it has folded
 constexpr const char* kVoxelOverflowMsg = "voxel_filter: leaf size too small for the cloud extent (voxel index would overflow int32, as in PCL)";
@@ -249,6 +250,7 @@ static inline int nblocks(int64_t n, int per) { return (int)((n + per - 1) / per
 int lili_map_set_hinted(lili_ctx* ctx, int kind, const lili_cloud* cloud, double max_sq_radius, const unsigned* box6, bool in_place);
 int lili_readback_add(lili_ctx* ctx, void* dst, const void* d_src, size_t bytes, hipStream_t stream = nullptr);
 int lili_readback_finish(lili_ctx* ctx, hipStream_t stream = nullptr);
+int lili_readback_now(lili_ctx* ctx, void* dst, const void* d_src, size_t bytes, hipStream_t stream = nullptr);      // one item: add, then finish
 // a lazy read-back reads its device source when the FINISH launches its gather kernel, so nothing enqueued in between may rewrite that source.  Every fill of
 // the shared scratch words (ctx->misc) asks here first: LILI_E_STATE if [p, p + bytes) overlaps the source of a read-back that is still pending (a programming error in
 // the library — a hook or a commit that clears words another stage has yet to deliver), LILI_OK otherwise.  Host-side, a loop over at most twelve items.

@@ -1669,6 +1669,32 @@ static int copy_out_f4(lili_ctx* ctx, const lili_feature_out* o, const float4* d
     return LILI_OK;
 }
 
+static RotDev rot_dev_params(const lili_ctx* ctx, const lili_rot_params* params, const double q_imu[4], const double q_lb[4]) {
+    RotDev P{};
+    P.n_scans = params->n_scans; P.ds_rate = params->ds_rate; P.ds_v = params->ds_v; P.near_thres = params->near_range;
+    P.atan_mode = ctx->rot_atan;
+    for (int i = 0; i < 4; i++) { P.q_imu[i] = q_imu[i]; P.q_lb[i] = q_lb[i]; }
+    return P;
+}
+// the ring stage; `fold` empty: the lists stay per ring and launch_rot_compact follows
+static void launch_rot_ring(lili_ctx* ctx, lili_detail::RotBuffers* R, const RotDev& P, RotState* st, const RotRingScratch& X, const RotFold& fold) {
+    hipLaunchKernelGGL(k_rot_ring, dim3(kMaxRings), dim3(kRotBlock), sizeof(RingLds), ctx->stream, R->full.as<float4>(), R->curv.as<float>(), R->sort_ind.as<int>(), P, st,
+                       R->label.as<int>(), R->ring_edge.as<int>(), R->ring_sharp.as<int>(), R->ring_flat.as<int>(), R->lessflat_tmp.as<int>(),
+                       R->surf_tmp.as<float4>(), R->surf_cnt_tmp.as<int>(), X, fold);
+}
+// the ordered concatenation of the per-ring lists; `mirror`: where the state travels as well (the page-locked copy), or nullptr
+static void launch_rot_compact(lili_ctx* ctx, lili_detail::RotBuffers* R, RotState* st, RotState* mirror) {
+    hipLaunchKernelGGL(k_rot_compact, dim3(kMaxRings), dim3(256), 0, ctx->stream, st, R->full.as<float4>(), R->ring_edge.as<int>(), R->ring_sharp.as<int>(),
+                       R->ring_flat.as<int>(), R->lessflat_tmp.as<int>(), R->surf_tmp.as<float4>(), R->surf_cnt_tmp.as<int>(), R->edge_idx.as<int>(),
+                       R->edge_pts.as<float4>(), R->sharp_idx.as<int>(), R->flat_idx.as<int>(), R->lessflat_idx.as<int>(), R->surf.as<float4>(), R->surf_cnt.as<int>(), mirror);
+}
+// a second pass's end: the concatenation again, and the state it leaves
+static int rot_recompact(lili_ctx* ctx, lili_detail::RotBuffers* R, RotState* st) {
+    launch_rot_compact(ctx, R, st, nullptr);
+    HIPCHK(hipGetLastError());
+    return lili_readback_now(ctx, &R->host, st, sizeof(RotState));
+}
+
 extern "C" {
 
 // The extraction up to (not including) its synchronisation: every kernel of the first pass is on the context's stream, the state travels to the page-locked mirror
@@ -1721,10 +1747,7 @@ static int rot_enqueue(lili_ctx* ctx, const lili_cloud* scan, const double q_imu
         X.sorted_len = R->sorted_len.as<int>();
         R->fold_tag = R->fold_tag >= 0xffffu ? 1u : R->fold_tag + 1u;      // tag of this extraction's status words (k_rot_segments, k_rot_ring)
         X.seg_final = ctx->rot_segment_wait ? R->fold_words.as<unsigned long long>() + kMaxRings : nullptr; X.tag = R->fold_tag;
-        RotDev P{};
-        P.n_scans = params->n_scans; P.ds_rate = params->ds_rate; P.ds_v = params->ds_v; P.near_thres = params->near_range;
-        P.atan_mode = ctx->rot_atan;
-        for (int i = 0; i < 4; i++) { P.q_imu[i] = q_imu[i]; P.q_lb[i] = q_lb[i]; }
+        const RotDev P = rot_dev_params(ctx, params, q_imu, q_lb);
         const float4* in = in_place ? static_cast<const float4*>(scan->data) : R->in.as<float4>();
         // four launches (round 2: nine, rounds 3-5: five): classify | scatter | segments + voxel ordering (7 workgroups per ring) | ring (writes the scan's lists itself since round 6)
         hipLaunchKernelGGL(k_rot_classify, dim3(nb), dim3(kRotBlock), 0, ctx->stream, in, n, P, st, R->scan_id.as<signed char>(), R->ori_raw.as<float>(),
@@ -1750,6 +1773,7 @@ static int rot_enqueue(lili_ctx* ctx, const lili_cloud* scan, const double q_imu
         }
         hipLaunchKernelGGL(k_rot_segments, dim3(kStage3Blocks), dim3(kRotBlock), std::max(sizeof(SegLds), sizeof(OrderLds)), ctx->stream, R->full.as<float4>(), R->vkey.as<unsigned>(), P, st, R->curv.as<float>(),
                            R->sort_ind.as<int>(), R->label.as<int>(), X);
+        if (R->h_state) *reinterpret_cast<volatile int*>(R->h_state + 1) = 0;      // the word a ring raises when its look-back gives up
         if (ctx->rot_fold) {   // the ring stage writes the scan's lists itself (RotFold): four launches
             RotFold F{};
             F.words = R->fold_words.as<unsigned long long>();
@@ -1759,18 +1783,10 @@ static int rot_enqueue(lili_ctx* ctx, const lili_cloud* scan, const double q_imu
             F.mirror = R->h_state_dev;
             F.give_up = R->h_state_dev ? reinterpret_cast<int*>(R->h_state_dev + 1) : nullptr;
             if (sink) { F.q_surf = sink->q_surf; F.cap_surf = sink->cap_surf; F.q_edge = sink->q_edge; F.cap_edge = sink->cap_edge; F.q_state = sink->state; for (int i = 0; i < 7; i++) F.q_pose[i] = sink->pose[i]; }
-            if (R->h_state) *reinterpret_cast<volatile int*>(R->h_state + 1) = 0;
-            hipLaunchKernelGGL(k_rot_ring, dim3(kMaxRings), dim3(kRotBlock), sizeof(RingLds), ctx->stream, R->full.as<float4>(), R->curv.as<float>(), R->sort_ind.as<int>(), P, st,
-                               R->label.as<int>(), R->ring_edge.as<int>(), R->ring_sharp.as<int>(), R->ring_flat.as<int>(), R->lessflat_tmp.as<int>(),
-                               R->surf_tmp.as<float4>(), R->surf_cnt_tmp.as<int>(), X, F);
+            launch_rot_ring(ctx, R, P, st, X, F);
         } else {               // option "rot_fold" = 0 (A/B, and the path a ring's given-up look-back falls back to): per-ring lists, then the concatenation launch of rounds 3-5
-            if (R->h_state) *reinterpret_cast<volatile int*>(R->h_state + 1) = 0;
-            hipLaunchKernelGGL(k_rot_ring, dim3(kMaxRings), dim3(kRotBlock), sizeof(RingLds), ctx->stream, R->full.as<float4>(), R->curv.as<float>(), R->sort_ind.as<int>(), P, st,
-                               R->label.as<int>(), R->ring_edge.as<int>(), R->ring_sharp.as<int>(), R->ring_flat.as<int>(), R->lessflat_tmp.as<int>(),
-                               R->surf_tmp.as<float4>(), R->surf_cnt_tmp.as<int>(), X, RotFold{});
-            hipLaunchKernelGGL(k_rot_compact, dim3(kMaxRings), dim3(256), 0, ctx->stream, st, R->full.as<float4>(), R->ring_edge.as<int>(), R->ring_sharp.as<int>(),
-                               R->ring_flat.as<int>(), R->lessflat_tmp.as<int>(), R->surf_tmp.as<float4>(), R->surf_cnt_tmp.as<int>(), R->edge_idx.as<int>(),
-                               R->edge_pts.as<float4>(), R->sharp_idx.as<int>(), R->flat_idx.as<int>(), R->lessflat_idx.as<int>(), R->surf.as<float4>(), R->surf_cnt.as<int>(), R->h_state_dev);
+            launch_rot_ring(ctx, R, P, st, X, RotFold{});
+            launch_rot_compact(ctx, R, st, R->h_state_dev);
         }
         HIPCHK(hipGetLastError());
         // page-locked feature buffers are written right behind the concatenation, `count` records each, before the host has seen the counts: the state's read-back below
@@ -1802,8 +1818,7 @@ static int rot_complete(lili_ctx* ctx, lili_feature_out* full, lili_feature_out*
     if (!R->pend.on) return ctx->fail(LILI_E_STATE, "extract_rot: nothing enqueued");
     R->pend.on = false;
     const int n = R->n_in;
-    const lili_rot_params* params = &R->pend.params;
-    const double* q_imu = R->pend.q_imu; const double* q_lb = R->pend.q_lb;
+    const RotDev P = rot_dev_params(ctx, &R->pend.params, R->pend.q_imu, R->pend.q_lb);      // (for the second passes)
     RotRingScratch X = R->pend.X;
     const bool full_early = R->pend.full_early;
     bool sent_edge = R->pend.sent_edge, sent_surf = R->pend.sent_surf;
@@ -1814,29 +1829,16 @@ static int rot_complete(lili_ctx* ctx, lili_feature_out* full, lili_feature_out*
         if (!synced) HIPCHK(hipStreamSynchronize(ctx->stream));
         std::memcpy(&R->host, R->h_state, sizeof(RotState));
         if (*reinterpret_cast<volatile int*>(R->h_state + 1)) R->host.fold_failed = 1;
-    } else { int rb = lili_readback_add(ctx, &R->host, st, sizeof(RotState)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+    } else { TRY(lili_readback_now(ctx, &R->host, st, sizeof(RotState))); }
     if (n == 0) { R->host.first_valid = R->host.half_idx = 0x7fffffff; R->host.last_valid = -1; }
     if (n > 0 && (R->host.vox_overflow || R->host.fallback_rings > 0 || R->host.fold_failed)) sent_edge = sent_surf = false;      // the lists are about to change: copied again below
     if (n > 0 && R->host.fold_failed && !R->host.vox_overflow && R->host.fallback_rings == 0) {      // a ring gave up its look-back (never seen): the per-ring lists are complete, concatenate them
-        hipLaunchKernelGGL(k_rot_compact, dim3(kMaxRings), dim3(256), 0, ctx->stream, st, R->full.as<float4>(), R->ring_edge.as<int>(), R->ring_sharp.as<int>(),
-                           R->ring_flat.as<int>(), R->lessflat_tmp.as<int>(), R->surf_tmp.as<float4>(), R->surf_cnt_tmp.as<int>(), R->edge_idx.as<int>(),
-                           R->edge_pts.as<float4>(), R->sharp_idx.as<int>(), R->flat_idx.as<int>(), R->lessflat_idx.as<int>(), R->surf.as<float4>(), R->surf_cnt.as<int>(), nullptr);
-        HIPCHK(hipGetLastError());
-        { int rb = lili_readback_add(ctx, &R->host, st, sizeof(RotState)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+        TRY(rot_recompact(ctx, R, st));
     }
     if (n > 0 && R->host.vox_overflow) {   // voxel coordinates beyond the packed keys: order by the radix pass, then the ring stage and the concatenation again
-        RotDev P{};
-        P.n_scans = params->n_scans; P.ds_rate = params->ds_rate; P.ds_v = params->ds_v; P.near_thres = params->near_range; P.atan_mode = ctx->rot_atan;
-        for (int i = 0; i < 4; i++) { P.q_imu[i] = q_imu[i]; P.q_lb[i] = q_lb[i]; }
         hipLaunchKernelGGL(k_rot_voxel_order, dim3(kMaxRings), dim3(kRotBlock), sizeof(SortLds), ctx->stream, R->full.as<float4>(), P, st, X);
-        hipLaunchKernelGGL(k_rot_ring, dim3(kMaxRings), dim3(kRotBlock), sizeof(RingLds), ctx->stream, R->full.as<float4>(), R->curv.as<float>(), R->sort_ind.as<int>(), P, st,
-                           R->label.as<int>(), R->ring_edge.as<int>(), R->ring_sharp.as<int>(), R->ring_flat.as<int>(), R->lessflat_tmp.as<int>(),
-                           R->surf_tmp.as<float4>(), R->surf_cnt_tmp.as<int>(), X, RotFold{});
-        hipLaunchKernelGGL(k_rot_compact, dim3(kMaxRings), dim3(256), 0, ctx->stream, st, R->full.as<float4>(), R->ring_edge.as<int>(), R->ring_sharp.as<int>(),
-                           R->ring_flat.as<int>(), R->lessflat_tmp.as<int>(), R->surf_tmp.as<float4>(), R->surf_cnt_tmp.as<int>(), R->edge_idx.as<int>(),
-                           R->edge_pts.as<float4>(), R->sharp_idx.as<int>(), R->flat_idx.as<int>(), R->lessflat_idx.as<int>(), R->surf.as<float4>(), R->surf_cnt.as<int>(), nullptr);
-        HIPCHK(hipGetLastError());
-        { int rb = lili_readback_add(ctx, &R->host, st, sizeof(RotState)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+        launch_rot_ring(ctx, R, P, st, X, RotFold{});
+        TRY(rot_recompact(ctx, R, st));
     }
     if (R->host.fallback_rings > 0) {      // rings beyond the LDS working set: second pass with global-memory arrays, then the concatenation again
         const size_t cap = (size_t)std::max(n, 1);
@@ -1851,18 +1853,11 @@ static int rot_complete(lili_ctx* ctx, lili_feature_out* full, lili_feature_out*
         HIPCHK(R->big_rcnt.ensure(std::max<size_t>(off, 1) * 4));
         B.mark = R->big_mark.as<signed char>(); B.vidx = R->big_vidx.as<unsigned>(); B.ord_a = R->big_ord_a.as<unsigned>(); B.ord_b = R->big_ord_b.as<unsigned>();
         B.rcnt = R->big_rcnt.as<int>();
-        RotDev P{};
-        P.n_scans = params->n_scans; P.ds_rate = params->ds_rate; P.ds_v = params->ds_v; P.near_thres = params->near_range; P.atan_mode = ctx->rot_atan;
-        for (int i = 0; i < 4; i++) { P.q_imu[i] = q_imu[i]; P.q_lb[i] = q_lb[i]; }
         hipLaunchKernelGGL(k_rot_rank, dim3(kMaxRings, 6, 12), dim3(256), 0, ctx->stream, R->curv.as<float>(), P, st, R->sort_ind.as<int>());
         hipLaunchKernelGGL(k_rot_select_big, dim3(kMaxRings), dim3(kRotBlock), 0, ctx->stream, R->full.as<float4>(), R->curv.as<float>(), R->sort_ind.as<int>(), P, st,
                            R->label.as<int>(), R->ring_edge.as<int>(), R->ring_sharp.as<int>(), R->ring_flat.as<int>(), R->lessflat_tmp.as<int>(),
                            R->surf_tmp.as<float4>(), R->surf_cnt_tmp.as<int>(), B);
-        hipLaunchKernelGGL(k_rot_compact, dim3(kMaxRings), dim3(256), 0, ctx->stream, st, R->full.as<float4>(), R->ring_edge.as<int>(), R->ring_sharp.as<int>(),
-                           R->ring_flat.as<int>(), R->lessflat_tmp.as<int>(), R->surf_tmp.as<float4>(), R->surf_cnt_tmp.as<int>(), R->edge_idx.as<int>(),
-                           R->edge_pts.as<float4>(), R->sharp_idx.as<int>(), R->flat_idx.as<int>(), R->lessflat_idx.as<int>(), R->surf.as<float4>(), R->surf_cnt.as<int>(), nullptr);
-        HIPCHK(hipGetLastError());
-        { int rb = lili_readback_add(ctx, &R->host, st, sizeof(RotState)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+        TRY(rot_recompact(ctx, R, st));
     }
     R->have = true;
     R->redone = n > 0 && (R->host.vox_overflow || R->host.fallback_rings > 0 || R->host.fold_failed);

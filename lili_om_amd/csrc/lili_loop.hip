@@ -564,9 +564,7 @@ int lili_icp_align(lili_ctx* ctx, const lili_icp_params* p, const double guess[1
         launched += k;
         enqueue_fitness(ctx, L, true, nullptr, DBL_MAX);
         HIPCHK(hipGetLastError());
-        rc = lili_readback_add(ctx, &h, L->dev.p, sizeof(h));
-        if (rc == LILI_OK) rc = lili_readback_finish(ctx);
-        if (rc != LILI_OK) return rc;
+        TRY(lili_readback_now(ctx, &h, L->dev.p, sizeof(h)));
         syncs++;
         if (h.done) break;
         if (launched >= p->max_iterations) return ctx->fail(LILI_E_STATE, "icp_align: internal: the iterations ran out without an end state");
@@ -596,9 +594,7 @@ int lili_icp_fitness(lili_ctx* ctx, const double T[16], double max_range, double
     enqueue_fitness(ctx, L, false, T, max_range);
     HIPCHK(hipGetLastError());
     lili::IcpDev& h = *L->h_dev;
-    rc = lili_readback_add(ctx, &h, L->dev.p, sizeof(h));
-    if (rc == LILI_OK) rc = lili_readback_finish(ctx);
-    if (rc != LILI_OK) return rc;
+    TRY(lili_readback_now(ctx, &h, L->dev.p, sizeof(h)));
     *fitness = h.fitness;
     if (n_used) *n_used = h.n_fit;
     return LILI_OK;

@@ -235,7 +235,7 @@ static int map_set_impl(lili_ctx* ctx, int kind, const lili_cloud* cloud, double
         zeroed_p = table.p;
         zeroed_bytes = table.p ? table.cap : 0;
         if (zeroed_bytes) HIPCHK(hipMemsetAsync(table.p, 0, zeroed_bytes, ctx->stream));
-        int rb = lili_readback_add(ctx, banks, d_mm, sizeof(banks)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb;
+        TRY(lili_readback_now(ctx, banks, d_mm, sizeof(banks)));
         unsigned inv_min[3] = {0u, 0u, 0u};          // the banks hold ~ordered(min) and ordered(max), both maximised from zero (bbox_to_banks)
         for (int b = 0; b < 64; b++) for (int k = 0; k < 3; k++) { inv_min[k] = std::max(inv_min[k], banks[b * 32 + k]); mm[3 + k] = std::max(mm[3 + k], banks[b * 32 + 3 + k]); }
         for (int k = 0; k < 3; k++) mm[k] = ~inv_min[k];
@@ -320,7 +320,7 @@ static int map_set_impl(lili_ctx* ctx, int kind, const lili_cloud* cloud, double
     // no inter-workgroup dependency.
     if (ctx->scan_lookback) {
         if (!err_read) {
-            { int rb = lili_readback_add(ctx, &scan_err, scan_err_word(ctx), sizeof(scan_err)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+            TRY(lili_readback_now(ctx, &scan_err, scan_err_word(ctx), sizeof(scan_err)));
         }
         if (scan_err) {
             ctx->scan_lookback = false;

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 static MatchParams to_device_params(const lili_s2m_params* p) {
@@ -36,13 +37,136 @@ static MatchParams to_device_params(const lili_s2m_params* p) {
     return m;
 }
 
+// --------------------------------------------------------------------------------------------
+// what every entry point and every association launcher below shares: argument checks, poses, eligibility, launch arguments, result landing
+// --------------------------------------------------------------------------------------------
+// `who`: the entry point's name, the head of its message
+static int check_slot(lili_ctx* ctx, int slot, const char* who) {
+    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, std::string(who) + ": bad slot");
+    return LILI_OK;
+}
+static int check_kind_mask(lili_ctx* ctx, int kind_mask, const char* who) {
+    ARGCHK((kind_mask & ~3) == 0 && kind_mask != 0, std::string(who) + ": bad kind mask");
+    return LILI_OK;
+}
+static int check_slot_list(lili_ctx* ctx, const int* slots, int n_slots, const char* who) {
+    ARGCHK(slots && n_slots >= 1 && n_slots <= LILI_MAX_SLOTS, std::string(who) + ": 1..LILI_MAX_SLOTS slots");
+    for (int i = 0; i < n_slots; i++) {
+        TRY(check_slot(ctx, slots[i], who));
+        for (int k = 0; k < i; k++) ARGCHK(slots[k] != slots[i], std::string(who) + ": duplicate slot");
+    }
+    return LILI_OK;
+}
+
+// a pose the host provides ...
+static PoseArg pose_at(const double t[3], const double q[4]) {
+    PoseArg pa{};
+    for (int i = 0; i < 3; i++) pa.t[i] = t[i];
+    for (int i = 0; i < 4; i++) pa.q[i] = q[i];
+    return pa;
+}
+// ... or the slot's pose on the device; `assoc_params`: for an association, which derives its transform from the body pose unless the flavour matches in the body frame
+static int derives_assoc(const lili_s2m_params* params) { return params->variant == LILI_VARIANT_FRONTEND ? 0 : 1; }
+static PoseArg pose_of_slot(lili_ctx* ctx, int slot, const lili_s2m_params* assoc_params = nullptr) {
+    PoseArg pa{};
+    pa.state = ctx->state(slot);
+    pa.derive_assoc = assoc_params ? derives_assoc(assoc_params) : 0;
+    return pa;
+}
+
+// the gate ball lies inside the cells a query's search covers
+static bool gate_fits(const MapIndex& m, int kind, const MatchParams& P) {
+    const double gate = kind == LILI_KIND_SURF ? P.kd_max_radius : P.edge_gate;
+    return std::sqrt(gate) * 1.0099 <= m.cell * (double)m.view.reach;
+}
+// the Livox flavour weighs surf matches by reflectivity: the auxiliary float on the map and on the queries
+static bool livox_aux_ok(const MapIndex& m, const KindSlot& ks, int kind, const MatchParams& P) {
+    return kind != LILI_KIND_SURF || P.variant != LILI_VARIANT_LIVOX || (m.has_aux && ks.has_aux);
+}
+// What every launcher but the plain per-kind one (launch_associate) asks of the kinds in kind_mask: queries, a gate-sized index of at least five points and nothing
+// launch_associate would refuse.  Silent — the caller falls back to launch_associate, which reports the error.  *n_all += the queries of these kinds.
+static bool coop_eligible(lili_ctx* ctx, int slot, int kind_mask, const MatchParams& P, int64_t* n_all) {
+    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
+        const KindSlot& ks = ctx->slots[slot].k[kind];
+        const MapIndex& m = ctx->map[kind];
+        if (!ks.has_queries || !m.valid || ks.n_q == 0 || m.n < 5 || m.has_fine) return false;
+        if (!gate_fits(m, kind, P) || !livox_aux_ok(m, ks, kind, P)) return false;
+        *n_all += ks.n_q;
+    }
+    return true;
+}
+
+// The arguments of one kind of a slot for an association launch of `nb` workgroups on the index `view`, and the slot's books for it: the neighbour lists when
+// lili_set_debug keeps them, one count per workgroup (what a later linearize / solve_lm sums), records present, `launches` more launches.
+static int assoc_args_of(lili_ctx* ctx, int slot, int kind, const GridView& view, int nb, int launches, AssocArgs& a) {
+    KindSlot& ks = ctx->slots[slot].k[kind];
+    const size_t n = (size_t)ks.n_q;
+    a = AssocArgs{};
+    a.queries = ks.q.as<float4>(); a.n_q = (int)n; a.g = view;
+    a.rec0 = ks.rec0.as<float4>(); a.rec1 = ks.rec1.p; a.valid = ks.valid.as<unsigned char>();
+    if (ctx->keep_nn) {
+        HIPCHK(ks.dbg_idx.ensure(n * 5 * sizeof(int)));
+        HIPCHK(ks.dbg_d2.ensure(n * 5 * sizeof(float)));
+        a.dbg_idx = ks.dbg_idx.as<int>(); a.dbg_d2 = ks.dbg_d2.as<float>();
+    }
+    HIPCHK(ks.block_counts.ensure((size_t)nb * sizeof(int)));
+    a.block_counts = ks.block_counts.as<int>(); a.nb = nb;
+    ks.n_assoc_blocks = nb; ks.has_records = true; ks.launches += launches;
+    return LILI_OK;
+}
+// the same for the kinds in kind_mask, L lanes per query (256 / L queries per workgroup); the other kind's arguments stay empty
+static int coop_args_of(lili_ctx* ctx, int slot, int kind_mask, int L, int launches, AssocArgs A[2]) {
+    for (int kind = 0; kind < 2; kind++) {
+        A[kind] = AssocArgs{};
+        if (kind_mask & (1 << kind)) TRY(assoc_args_of(ctx, slot, kind, ctx->map[kind].view, nblocks(ctx->slots[slot].k[kind].n_q, 256 / L), launches, A[kind]));
+    }
+    return LILI_OK;
+}
+
+// run-time lanes per query -> the kernels' template argument: f(std::integral_constant<int, L>); false for an L no kernel is built for
+template <typename F> static bool with_lanes(int L, F&& f) {
+    switch (L) {
+        case 2: f(std::integral_constant<int, 2>{}); return true;
+        case 4: f(std::integral_constant<int, 4>{}); return true;
+        case 8: f(std::integral_constant<int, 8>{}); return true;
+        case 16: f(std::integral_constant<int, 16>{}); return true;
+        default: return false;
+    }
+}
+
+// Page-locked landing area of the blocking calls' results, written by their last kernel across PCIe (a record is 576 bytes): the host reads it after the one
+// synchronisation of the call — no device-to-host copy launch in between (~4 us of GPU time and an API call per blocking evaluation).
+constexpr size_t kHRecordDoubles = (size_t)LILI_MAX_SLOTS * LILI_GRAM_DOUBLES + 2 * LILI_MAX_SLOTS;      // records | 2 x MAX_SLOTS window counts | 2 x MAX_SLOTS per-slot counts (ints)
+constexpr size_t kHWindowCountsOff = (size_t)LILI_MAX_SLOTS * LILI_GRAM_DOUBLES * sizeof(double), kHSlotCountsOff = kHWindowCountsOff + 2 * LILI_MAX_SLOTS * sizeof(int);
+static int ensure_h_records(lili_ctx* ctx) {
+    if (ctx->h_records) return LILI_OK;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_records), kHRecordDoubles * sizeof(double), hipHostMallocDefault));
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, ctx->h_records, 0) != hipSuccess) { (void)hipGetLastError(); d = nullptr; }
+    ctx->h_records_dev = static_cast<double*>(d);
+    return LILI_OK;
+}
+// Where a blocking call's last kernel leaves its result (after ensure_h_records): `off` bytes into the landing area, or — where the device cannot see that
+// memory — the device buffer `fallback`, which then comes back through the read-back queue.
+struct Landing {
+    lili_ctx* ctx; size_t off; void* fallback;
+    bool direct() const { return ctx->h_records_dev != nullptr; }
+    template <class T> T* dev() const { return direct() ? reinterpret_cast<T*>(reinterpret_cast<char*>(ctx->h_records_dev) + off) : static_cast<T*>(fallback); }
+    int fetch(void* host_dst, size_t bytes) const {      // the call's one synchronisation
+        if (!direct()) return lili_readback_now(ctx, host_dst, fallback, bytes);
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        std::memcpy(host_dst, reinterpret_cast<const char*>(ctx->h_records) + off, bytes);
+        return LILI_OK;
+    }
+};
+
 extern "C" {
 // --------------------------------------------------------------------------------------------
 // queries / associate / linearize
 // --------------------------------------------------------------------------------------------
 int lili_s2m_set_queries(lili_ctx* ctx, int slot, int kind, const lili_cloud* cloud) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "set_queries: bad slot");
+    TRY(check_slot(ctx, slot, "set_queries"));
     ARGCHK(kind == 0 || kind == 1, "set_queries: bad kind");
     ARGCHK(cloud, "set_queries: null cloud");
     HIPCHK(hipSetDevice(ctx->device));
@@ -114,57 +238,36 @@ static int launch_associate(lili_ctx* ctx, int slot, int kind, const PoseArg& pa
     if (!ks.has_queries) return ctx->fail(LILI_E_STATE, "associate: set_queries first");
     MapIndex& m = ctx->map[kind];
     if (!m.valid) return ctx->fail(LILI_E_STATE, "associate: map_set first");
-    double gate = kind == LILI_KIND_SURF ? P.kd_max_radius : P.edge_gate;
-    if (m.n > 0 && !(std::sqrt(gate) * 1.0099 <= m.cell * (double)m.view.reach))
-        return ctx->fail(LILI_E_STATE, "associate: gate radius exceeds the radius the map index was built for");
+    if (m.n > 0 && !gate_fits(m, kind, P)) return ctx->fail(LILI_E_STATE, "associate: gate radius exceeds the radius the map index was built for");
     ks.has_records = true;
     if (ks.n_q == 0) return LILI_OK;
     const int n = (int)ks.n_q;
-    int* dbg_i = nullptr; float* dbg_d = nullptr;
-    if (ctx->keep_nn) {
-        HIPCHK(ks.dbg_idx.ensure((size_t)n * 5 * sizeof(int)));
-        HIPCHK(ks.dbg_d2.ensure((size_t)n * 5 * sizeof(float)));
-        dbg_i = ks.dbg_idx.as<int>(); dbg_d = ks.dbg_d2.as<float>();
-    }
-    if (m.n < 5) {   // fewer than 5 map points: the reference reads pt_search_sq_dists[4] out of bounds; we reject all
-        HIPCHK(hipMemsetAsync(ks.valid.p, 0, (size_t)n, ctx->stream));
-        ks.n_assoc_blocks = ks.n_blocks;
-        HIPCHK(hipMemsetAsync(ks.block_counts.p, 0, (size_t)ks.n_blocks * sizeof(int), ctx->stream));
-        if (dbg_i) { HIPCHK(hipMemsetAsync(dbg_i, 0xFF, (size_t)n * 5 * sizeof(int), ctx->stream)); HIPCHK(hipMemsetAsync(dbg_d, 0x7F, (size_t)n * 5 * sizeof(float), ctx->stream)); }
+    const bool too_few = m.n < 5, dense = !too_few && m.has_fine;      // dense map: the fine index alone (lili_s2m_dense.hip)
+    if (dense && !livox_aux_ok(m, ks, kind, P))
+        return ctx->fail(LILI_E_STATE, "associate: Livox variant needs reflectivity (aux_offset) on the surf map and the surf queries");
+    // one wave per workgroup (kAssocBlock): the dispatcher balances the SIMDs wave by wave.  Dense: one lane per query for the queries their inner 27 fine cells
+    // settle, then the wave serves the rest 16 lanes per query — `qpw` queries per wave (see the kernel)
+    const int qpw = dense && ks.n_blocks < std::max(ctx->n_simd, 256) ? 16 : kAssocBlock;
+    AssocArgs a;
+    TRY(assoc_args_of(ctx, slot, kind, dense ? m.fview : m.view, nblocks(n, qpw), too_few ? 0 : 1, a));
+    if (too_few) {   // fewer than 5 map points: the reference reads pt_search_sq_dists[4] out of bounds; we reject all
+        HIPCHK(hipMemsetAsync(a.valid, 0, (size_t)n, ctx->stream));
+        HIPCHK(hipMemsetAsync(a.block_counts, 0, (size_t)a.nb * sizeof(int), ctx->stream));
+        if (a.dbg_idx) { HIPCHK(hipMemsetAsync(a.dbg_idx, 0xFF, (size_t)n * 5 * sizeof(int), ctx->stream)); HIPCHK(hipMemsetAsync(a.dbg_d2, 0x7F, (size_t)n * 5 * sizeof(float), ctx->stream)); }
         return LILI_OK;
     }
-    ks.n_assoc_blocks = ks.n_blocks;
     const bool any_order = pa.wait_key != 0ull;
-    if (m.has_fine) {      // dense map: fine index first, gate-sized index for the queries it cannot settle
-        if (kind == LILI_KIND_SURF && P.variant == LILI_VARIANT_LIVOX && (!m.has_aux || !ks.has_aux))
-            return ctx->fail(LILI_E_STATE, "associate: Livox variant needs reflectivity (aux_offset) on the surf map and the surf queries");
-        // the fine index alone (lili_s2m_dense.hip): one lane per query for the queries their inner 27 fine cells settle, then the wave serves the rest 16 lanes per query
-        AssocArgs a{};
-        a.queries = ks.q.as<float4>(); a.n_q = n; a.g = m.fview;
-        a.rec0 = ks.rec0.as<float4>(); a.rec1 = ks.rec1.p; a.valid = ks.valid.as<unsigned char>();
-        a.dbg_idx = dbg_i; a.dbg_d2 = dbg_d; a.block_counts = ks.block_counts.as<int>(); a.nb = ks.n_blocks;
-        ks.launches++;
+    const dim3 grid(a.nb), block(kAssocBlock);
+    if (dense) {
+        const double gate = kind == LILI_KIND_SURF ? P.kd_max_radius : P.edge_gate;
         const int r_max = std::max(1, (int)std::ceil(std::sqrt(gate) * 1.01 / m.fine_cell));      // fine cells the search has to reach for the gate ball
-        const int qpw = ks.n_blocks < std::max(ctx->n_simd, 256) ? 16 : kAssocBlock;                // queries per wave (see the kernel)
-        const int nb = nblocks(n, qpw);
-        HIPCHK(ks.block_counts.ensure((size_t)nb * sizeof(int)));
-        a.nb = nb; a.block_counts = ks.block_counts.as<int>();
-        ks.n_assoc_blocks = nb;
-        launch_k(ctx->stream, any_order, k_associate_fine, dim3(nb), dim3(kAssocBlock), 0, a, r_max, qpw, kind, pa, P);
-        HIPCHK(hipGetLastError());
-        return LILI_OK;
-    }
-    ks.launches++;
-    // one wave per workgroup (kAssocBlock): the dispatcher balances the SIMDs wave by wave
-    const dim3 grid(ks.n_assoc_blocks);
-    if (kind == LILI_KIND_SURF) {
-        if (P.variant == LILI_VARIANT_LIVOX && !m.has_aux) return ctx->fail(LILI_E_STATE, "associate: Livox variant needs reflectivity (aux_offset) on the surf map");
-        if (P.variant == LILI_VARIANT_LIVOX && !ks.has_aux) return ctx->fail(LILI_E_STATE, "associate: Livox variant needs reflectivity (aux_offset) on the surf queries");
-        launch_k(ctx->stream, any_order, k_associate_surf<kAssocBlock>, grid, dim3(kAssocBlock), 0, (const float4*)ks.q.as<float4>(), n, m.view, pa, P,
-                 ks.rec0.as<float4>(), ks.rec1.as<double>(), ks.valid.as<unsigned char>(), dbg_i, dbg_d, ks.block_counts.as<int>());
+        launch_k(ctx->stream, any_order, k_associate_fine, grid, block, 0, a, r_max, qpw, kind, pa, P);
+    } else if (kind == LILI_KIND_SURF) {
+        if (!livox_aux_ok(m, ks, kind, P))
+            return ctx->fail(LILI_E_STATE, !m.has_aux ? "associate: Livox variant needs reflectivity (aux_offset) on the surf map" : "associate: Livox variant needs reflectivity (aux_offset) on the surf queries");
+        launch_k(ctx->stream, any_order, k_associate_surf<kAssocBlock>, grid, block, 0, a.queries, n, a.g, pa, P, a.rec0, static_cast<double*>(a.rec1), a.valid, a.dbg_idx, a.dbg_d2, a.block_counts);
     } else {
-        launch_k(ctx->stream, any_order, k_associate_edge<kAssocBlock>, grid, dim3(kAssocBlock), 0, (const float4*)ks.q.as<float4>(), n, m.view, pa, P,
-                 ks.rec0.as<float4>(), ks.rec1.as<float4>(), ks.valid.as<unsigned char>(), dbg_i, dbg_d, ks.block_counts.as<int>());
+        launch_k(ctx->stream, any_order, k_associate_edge<kAssocBlock>, grid, block, 0, a.queries, n, a.g, pa, P, a.rec0, static_cast<float4*>(a.rec1), a.valid, a.dbg_idx, a.dbg_d2, a.block_counts);
     }
     HIPCHK(hipGetLastError());
     return LILI_OK;
@@ -184,30 +287,10 @@ static int launch_sum_counts(lili_ctx* ctx, int slot, int kind_mask, int* d_out 
 // Both kinds of a keyframe in one launch (k_associate_both): only the plain direct path — one wave per workgroup, caller's
 // query order, no dispatch-order or binning experiments.  Returns 1 if the slot is not eligible (the caller then launches per kind).
 static int launch_associate_both(lili_ctx* ctx, int slot, const PoseArg& pa, const MatchParams& P) {
+    int64_t n_all = 0;
+    if (!coop_eligible(ctx, slot, LILI_MASK_SURF | LILI_MASK_EDGE, P, &n_all)) return 1;
     AssocArgs A[2];
-    for (int kind = 0; kind < 2; kind++) {
-        KindSlot& ks = ctx->slots[slot].k[kind];
-        MapIndex& m = ctx->map[kind];
-        if (!ks.has_queries || !m.valid || ks.n_q == 0 || m.n < 5 || m.has_fine) return 1;
-        const double gate = kind == LILI_KIND_SURF ? P.kd_max_radius : P.edge_gate;
-        if (!(std::sqrt(gate) * 1.0099 <= m.cell * (double)m.view.reach)) return 1;     // the per-kind path reports the error
-        if (kind == LILI_KIND_SURF && P.variant == LILI_VARIANT_LIVOX && (!m.has_aux || !ks.has_aux)) return 1;
-    }
-    for (int kind = 0; kind < 2; kind++) {
-        KindSlot& ks = ctx->slots[slot].k[kind];
-        const int n = (int)ks.n_q;
-        AssocArgs& a = A[kind];
-        a = AssocArgs{};
-        a.queries = ks.q.as<float4>(); a.n_q = n; a.g = ctx->map[kind].view;
-        a.rec0 = ks.rec0.as<float4>(); a.rec1 = ks.rec1.p; a.valid = ks.valid.as<unsigned char>();
-        if (ctx->keep_nn) {
-            HIPCHK(ks.dbg_idx.ensure((size_t)n * 5 * sizeof(int)));
-            HIPCHK(ks.dbg_d2.ensure((size_t)n * 5 * sizeof(float)));
-            a.dbg_idx = ks.dbg_idx.as<int>(); a.dbg_d2 = ks.dbg_d2.as<float>();
-        }
-        a.block_counts = ks.block_counts.as<int>(); a.nb = ks.n_blocks;
-        ks.n_assoc_blocks = ks.n_blocks; ks.has_records = true; ks.launches++;
-    }
+    for (int kind = 0; kind < 2; kind++) TRY(assoc_args_of(ctx, slot, kind, ctx->map[kind].view, ctx->slots[slot].k[kind].n_blocks, 1, A[kind]));
     launch_k(ctx->stream, pa.wait_key != 0ull, k_associate_both, dim3(A[0].nb + A[1].nb), dim3(kAssocBlock), 0, A[0], A[1], pa, P);
     HIPCHK(hipGetLastError());
     return LILI_OK;
@@ -234,51 +317,28 @@ static int launch_associate_coop(lili_ctx* ctx, int slot, int kind_mask, const P
     if (P.debug & 4096) return 1;
     Slot& sl = ctx->slots[slot];
     int64_t n_all = 0;
-    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-        KindSlot& ks = sl.k[kind];
-        MapIndex& m = ctx->map[kind];
-        if (!ks.has_queries || !m.valid || ks.n_q == 0 || m.n < 5 || m.has_fine) return 1;
-        const double gate = kind == LILI_KIND_SURF ? P.kd_max_radius : P.edge_gate;
-        if (!(std::sqrt(gate) * 1.0099 <= m.cell * (double)m.view.reach)) return 1;     // the per-kind path reports the error
-        if (kind == LILI_KIND_SURF && P.variant == LILI_VARIANT_LIVOX && (!m.has_aux || !ks.has_aux)) return 1;
-        n_all += ks.n_q;
-    }
+    if (!coop_eligible(ctx, slot, kind_mask, P, &n_all)) return 1;
     const bool first = sl.assoc_since_pose == 0;      // the first association after lili_s2m_pose_set / _pose_copy: far from converged
     sl.assoc_since_pose++;
     const int L = coop_lanes(ctx, n_all, first);
     if (L < 2 || n_all == 0) return 1;
-    const int qpb = 256 / L;
     // count-scaled flavours (ROT) may linearise in the association launch only through its in-launch count barrier: small grids
     const bool scaled = P.scale_surf_num > 0 || P.scale_edge_num > 0;
     int cb_blocks = 0;
     if (lin && scaled) {
-        for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) cb_blocks += nblocks((int)sl.k[kind].n_q, qpb);
+        for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) cb_blocks += nblocks((int)sl.k[kind].n_q, 256 / L);
         if (cb_blocks > 256 || !ctx->count_barrier) { sl.assoc_since_pose--; return 1; }      // (the caller's three-launch path calls in again and counts the launch itself)
     }
-    AssocArgs A[2] = {AssocArgs{}, AssocArgs{}};
-    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-        KindSlot& ks = sl.k[kind];
-        const int n = (int)ks.n_q;
-        AssocArgs& a = A[kind];
-        a.queries = ks.q.as<float4>(); a.n_q = n; a.g = ctx->map[kind].view;
-        a.rec0 = ks.rec0.as<float4>(); a.rec1 = ks.rec1.p; a.valid = ks.valid.as<unsigned char>();
-        if (ctx->keep_nn) {
-            HIPCHK(ks.dbg_idx.ensure((size_t)n * 5 * sizeof(int)));
-            HIPCHK(ks.dbg_d2.ensure((size_t)n * 5 * sizeof(float)));
-            a.dbg_idx = ks.dbg_idx.as<int>(); a.dbg_d2 = ks.dbg_d2.as<float>();
-        }
-        a.nb = nblocks(n, qpb);
-        HIPCHK(ks.block_counts.ensure((size_t)a.nb * sizeof(int)));
-        if (lin) HIPCHK(ks.partials_wave.ensure((size_t)a.nb * kPartialStride * sizeof(double)));
-        a.block_counts = ks.block_counts.as<int>();
-        ks.n_assoc_blocks = a.nb; ks.has_records = true; ks.launches++;
-    }
+    AssocArgs A[2];
+    TRY(coop_args_of(ctx, slot, kind_mask, L, 1, A));
+    if (lin) for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) HIPCHK(sl.k[kind].partials_wave.ensure((size_t)A[kind].nb * kPartialStride * sizeof(double)));
     const dim3 grid(A[0].nb + A[1].nb), block(256);
     double* ps = sl.k[0].partials_wave.as<double>(); double* pe = sl.k[1].partials_wave.as<double>();
-#define LILI_COOP_CASE(LL) case LL: if (lin) hipLaunchKernelGGL((k_associate_coop<LL, true>), grid, block, 0, ctx->stream, A[0], A[1], pa, P, ps, pe, ctx->state(slot), cb_blocks); \
-                                    else launch_k(ctx->stream, pa.wait_key != 0ull, (k_associate_coop<LL, false>), grid, block, 0, A[0], A[1], pa, P, ps, pe, ctx->state(slot), 0); break;
-    switch (L) { LILI_COOP_CASE(2) LILI_COOP_CASE(4) LILI_COOP_CASE(8) LILI_COOP_CASE(16) default: return 1; }
-#undef LILI_COOP_CASE
+    if (!with_lanes(L, [&](auto lanes) {
+            constexpr int LL = decltype(lanes)::value;
+            if (lin) hipLaunchKernelGGL((k_associate_coop<LL, true>), grid, block, 0, ctx->stream, A[0], A[1], pa, P, ps, pe, ctx->state(slot), cb_blocks);
+            else launch_k(ctx->stream, pa.wait_key != 0ull, (k_associate_coop<LL, false>), grid, block, 0, A[0], A[1], pa, P, ps, pe, ctx->state(slot), 0);
+        })) return 1;
     if (lin) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, (const double*)ps, A[0].nb, (const double*)pe, A[1].nb, d_out, ctx->state(slot),
                                 1 | (P.debug & 256), P2PView{}, 0ull, (double*)nullptr, ctx->take_state_mirror(slot));
     HIPCHK(hipGetLastError());
@@ -293,21 +353,11 @@ static int launch_associate_coop_window(lili_ctx* ctx, const int* slots, int n_s
     int64_t n_all = 0;
     bool first = false;
     for (int i = 0; i < n_slots; i++) {
-        Slot& sl = ctx->slots[slots[i]];
-        for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-            KindSlot& ks = sl.k[kind];
-            MapIndex& m = ctx->map[kind];
-            if (!ks.has_queries || !m.valid || ks.n_q == 0 || m.n < 5 || m.has_fine) return 1;
-            const double gate = kind == LILI_KIND_SURF ? P.kd_max_radius : P.edge_gate;
-            if (!(std::sqrt(gate) * 1.0099 <= m.cell * (double)m.view.reach)) return 1;     // the per-kind path reports the error
-            if (kind == LILI_KIND_SURF && P.variant == LILI_VARIANT_LIVOX && (!m.has_aux || !ks.has_aux)) return 1;
-            n_all += ks.n_q;
-        }
-        first = first || sl.assoc_since_pose == 0;
+        if (!coop_eligible(ctx, slots[i], kind_mask, P, &n_all)) return 1;
+        first = first || ctx->slots[slots[i]].assoc_since_pose == 0;
     }
     const int L = coop_lanes(ctx, n_all, first);
     if (L < 2 || n_all == 0) return 1;
-    const int qpb = 256 / L;
     WinAssocArgs W{};
     for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) W.g[kind] = ctx->map[kind].view;
     int nb = 0;
@@ -315,25 +365,14 @@ static int launch_associate_coop_window(lili_ctx* ctx, const int* slots, int n_s
         Slot& sl = ctx->slots[slots[i]];
         WinAssocSlot& ws = W.s[i];
         ws = WinAssocSlot{};
-        for (int k = 0; k < 3; k++) ws.pa.t[k] = t_assoc[3 * i + k];
-        for (int k = 0; k < 4; k++) ws.pa.q[k] = q_assoc[4 * i + k];
+        ws.pa = pose_at(t_assoc + 3 * i, q_assoc + 4 * i);
         ws.first_block = nb;
         // (edge workgroups first, then surf: the order of k_associate_coop's grid)
-        for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-            KindSlot& ks = sl.k[kind];
-            const int n = (int)ks.n_q;
-            WinAssocKind& a = ws.k[kind];
-            a.queries = ks.q.as<float4>(); a.n_q = n;
-            a.rec0 = ks.rec0.as<float4>(); a.rec1 = ks.rec1.p; a.valid = ks.valid.as<unsigned char>();
-            if (ctx->keep_nn) {
-                HIPCHK(ks.dbg_idx.ensure((size_t)n * 5 * sizeof(int)));
-                HIPCHK(ks.dbg_d2.ensure((size_t)n * 5 * sizeof(float)));
-                a.dbg_idx = ks.dbg_idx.as<int>(); a.dbg_d2 = ks.dbg_d2.as<float>();
-            }
-            a.nb = nblocks(n, qpb);
-            HIPCHK(ks.block_counts.ensure((size_t)a.nb * sizeof(int)));
-            a.block_counts = ks.block_counts.as<int>();
-            ks.n_assoc_blocks = a.nb; ks.has_records = true; ks.launches++;
+        AssocArgs A[2];
+        TRY(coop_args_of(ctx, slots[i], kind_mask, L, 1, A));
+        for (int kind = 0; kind < 2; kind++) {      // the same fields without the index, which the launch carries once
+            const AssocArgs& a = A[kind];
+            ws.k[kind] = WinAssocKind{a.queries, a.n_q, a.rec0, a.rec1, a.valid, a.dbg_idx, a.dbg_d2, a.block_counts, a.nb};
             nb += a.nb;
         }
         sl.assoc_since_pose++;
@@ -341,13 +380,7 @@ static int launch_associate_coop_window(lili_ctx* ctx, const int* slots, int n_s
     }
     W.n = n_slots;
     const dim3 grid(nb), block(256);
-    switch (L) {
-        case 2: hipLaunchKernelGGL((k_associate_coop_window<2>), grid, block, 0, ctx->stream, W, P); break;
-        case 4: hipLaunchKernelGGL((k_associate_coop_window<4>), grid, block, 0, ctx->stream, W, P); break;
-        case 8: hipLaunchKernelGGL((k_associate_coop_window<8>), grid, block, 0, ctx->stream, W, P); break;
-        case 16: hipLaunchKernelGGL((k_associate_coop_window<16>), grid, block, 0, ctx->stream, W, P); break;
-        default: return 1;
-    }
+    if (!with_lanes(L, [&](auto lanes) { hipLaunchKernelGGL((k_associate_coop_window<decltype(lanes)::value>), grid, block, 0, ctx->stream, W, P); })) return 1;
     HIPCHK(hipGetLastError());
     return LILI_OK;
 }
@@ -363,16 +396,7 @@ static int launch_iterate_persistent(lili_ctx* ctx, int slot, int kind_mask, con
     P.no_cost = 1;
     Slot& sl = ctx->slots[slot];
     int64_t n_all = 0;
-    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-        KindSlot& ks = sl.k[kind];
-        MapIndex& m = ctx->map[kind];
-        if (!ks.has_queries || !m.valid || ks.n_q == 0 || m.n < 5 || m.has_fine) return 1;
-        const double gate = kind == LILI_KIND_SURF ? P.kd_max_radius : P.edge_gate;
-        if (!(std::sqrt(gate) * 1.0099 <= m.cell * (double)m.view.reach)) return 1;
-        if (kind == LILI_KIND_SURF && P.variant == LILI_VARIANT_LIVOX && (!m.has_aux || !ks.has_aux)) return 1;
-        n_all += ks.n_q;
-    }
-    if (n_all == 0) return 1;
+    if (!coop_eligible(ctx, slot, kind_mask, P, &n_all) || n_all == 0) return 1;
     // Lanes per query: one choice for the whole registration (the converged launches decide), halved until the launch has at most 128 workgroups —
     // every workgroup has to be resident, two fit a CU, and up to four such launches may run side by side (lili_s2m_iterate_window).  The bound does
     // not depend on what else runs, so a slot iterated alone and inside a window partitions its Gram sums identically (same bits).
@@ -380,43 +404,21 @@ static int launch_iterate_persistent(lili_ctx* ctx, int slot, int kind_mask, con
     if (L < 2) return 1;
     auto blocks_for = [&](int lanes) { int b = 0; for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) b += nblocks((int)sl.k[kind].n_q, 256 / lanes); return b; };
     while (L > 2 && blocks_for(L) > 128) L /= 2;
-    const int qpb = 256 / L;
-    AssocArgs A[2] = {AssocArgs{}, AssocArgs{}};
     const int nb = blocks_for(L);
     if (nb > 128 || ctx->persistent_off_now) return 1;
-    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-        KindSlot& ks = sl.k[kind];
-        const int n = (int)ks.n_q;
-        AssocArgs& a = A[kind];
-        a.queries = ks.q.as<float4>(); a.n_q = n; a.g = ctx->map[kind].view;
-        a.rec0 = ks.rec0.as<float4>(); a.rec1 = ks.rec1.p; a.valid = ks.valid.as<unsigned char>();
-        if (ctx->keep_nn) {
-            HIPCHK(ks.dbg_idx.ensure((size_t)n * 5 * sizeof(int)));
-            HIPCHK(ks.dbg_d2.ensure((size_t)n * 5 * sizeof(float)));
-            a.dbg_idx = ks.dbg_idx.as<int>(); a.dbg_d2 = ks.dbg_d2.as<float>();
-        }
-        a.nb = nblocks(n, qpb);
-        HIPCHK(ks.block_counts.ensure((size_t)a.nb * sizeof(int)));
-        a.block_counts = ks.block_counts.as<int>();
-        ks.n_assoc_blocks = a.nb; ks.has_records = true; ks.launches += n_iters;
-    }
+    AssocArgs A[2];
+    TRY(coop_args_of(ctx, slot, kind_mask, L, n_iters, A));
     IterArgs it{};
     it.state = ctx->state(slot);
     it.nb = nb; it.ng = nb > 16 ? nblocks(nb, 16) : 1; it.n_iters = n_iters;
-    it.derive_assoc = params->variant == LILI_VARIANT_FRONTEND ? 0 : 1;
+    it.derive_assoc = derives_assoc(params);
     it.launch = ++ctx->lm_launches;
     HIPCHK(sl.lm_part.ensure((size_t)2 * nb * kPartialStride * sizeof(double)));
     HIPCHK(sl.lm_gsum.ensure((size_t)2 * it.ng * kPartialStride * sizeof(double)));
     HIPCHK(sl.lm_cnt.ensure((size_t)2 * (nb + it.ng) * 4 * sizeof(double)));
     it.part = sl.lm_part.as<double>(); it.gsum = sl.lm_gsum.as<double>(); it.cpart = sl.lm_cnt.as<double>();
     const dim3 grid(nb), block(256);
-    switch (L) {
-        case 2: hipLaunchKernelGGL(k_iterate_coop<2>, grid, block, 0, ctx->stream, A[0], A[1], P, it); break;
-        case 4: hipLaunchKernelGGL(k_iterate_coop<4>, grid, block, 0, ctx->stream, A[0], A[1], P, it); break;
-        case 8: hipLaunchKernelGGL(k_iterate_coop<8>, grid, block, 0, ctx->stream, A[0], A[1], P, it); break;
-        case 16: hipLaunchKernelGGL(k_iterate_coop<16>, grid, block, 0, ctx->stream, A[0], A[1], P, it); break;
-        default: return 1;
-    }
+    if (!with_lanes(L, [&](auto lanes) { hipLaunchKernelGGL(k_iterate_coop<decltype(lanes)::value>, grid, block, 0, ctx->stream, A[0], A[1], P, it); })) return 1;
     HIPCHK(hipGetLastError());
     sl.use_global_counts = false; sl.sticky_global_counts = false;
     sl.assoc_since_pose += n_iters;
@@ -447,18 +449,8 @@ static int launch_associate_lin_reduce(lili_ctx* ctx, int slot, int kind_mask, c
     if (ctx->fuse_tail || (P.debug & 4096)) return 1;
     const bool scaled = P.scale_surf_num > 0 || P.scale_edge_num > 0;      // ROT: only through the count barrier of the cooperative kernel (small launches)
     Slot& sl = ctx->slots[slot];
-    AssocArgs A[2] = {AssocArgs{}, AssocArgs{}};
-    int n_kinds = 0;
-    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-        KindSlot& ks = sl.k[kind];
-        MapIndex& m = ctx->map[kind];
-        if (!ks.has_queries || !m.valid || ks.n_q == 0 || m.n < 5 || m.has_fine) return 1;
-        const double gate = kind == LILI_KIND_SURF ? P.kd_max_radius : P.edge_gate;
-        if (!(std::sqrt(gate) * 1.0099 <= m.cell * (double)m.view.reach)) return 1;     // the per-kind path reports the error
-        if (kind == LILI_KIND_SURF && P.variant == LILI_VARIANT_LIVOX && (!m.has_aux || !ks.has_aux)) return 1;
-        n_kinds++;
-    }
-    if (n_kinds == 0) return 1;
+    int64_t n_all = 0;
+    if (!coop_eligible(ctx, slot, kind_mask, P, &n_all) || n_all == 0) return 1;
     {   // small launches: several lanes per query (k_associate_coop, which linearises as well)
         const int rc = launch_associate_coop(ctx, slot, kind_mask, pa, P, true, d_out);
         if (rc != 1) return rc;
@@ -472,20 +464,11 @@ static int launch_associate_lin_reduce(lili_ctx* ctx, int slot, int kind_mask, c
     // separate linearisation launch (which runs on otherwise idle SIMDs at four waves each).
     if (waves > 1600 && !ctx->fuse_lin_block) return 1;
     const int bs = ctx->fuse_lin_block ? ctx->fuse_lin_block : (waves <= 800 ? kAssocBlock : kBlock);
+    AssocArgs A[2] = {AssocArgs{}, AssocArgs{}};
     for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
         KindSlot& ks = sl.k[kind];
-        const int n = (int)ks.n_q;
-        AssocArgs& a = A[kind];
-        a.queries = ks.q.as<float4>(); a.n_q = n; a.g = ctx->map[kind].view;
-        a.rec0 = ks.rec0.as<float4>(); a.rec1 = ks.rec1.p; a.valid = ks.valid.as<unsigned char>();
-        if (ctx->keep_nn) {
-            HIPCHK(ks.dbg_idx.ensure((size_t)n * 5 * sizeof(int)));
-            HIPCHK(ks.dbg_d2.ensure((size_t)n * 5 * sizeof(float)));
-            a.dbg_idx = ks.dbg_idx.as<int>(); a.dbg_d2 = ks.dbg_d2.as<float>();
-        }
-        HIPCHK(ks.partials_wave.ensure((size_t)ks.n_blocks * kPartialStride * sizeof(double)));
-        a.block_counts = ks.block_counts.as<int>(); a.nb = nblocks(n, bs);
-        ks.n_assoc_blocks = a.nb; ks.has_records = true; ks.launches++;
+        TRY(assoc_args_of(ctx, slot, kind, ctx->map[kind].view, nblocks(ks.n_q, bs), 1, A[kind]));
+        HIPCHK(ks.partials_wave.ensure((size_t)ks.n_blocks * kPartialStride * sizeof(double)));      // (n_blocks >= nb: bs is kAssocBlock or larger)
     }
     // k_associate_lin: blocks [0, E.nb) edge, the rest surf
     if (bs == kAssocBlock) hipLaunchKernelGGL(k_associate_lin<kAssocBlock>, dim3(A[0].nb + A[1].nb), dim3(kAssocBlock), 0, ctx->stream, A[0], A[1], pa, P,
@@ -538,49 +521,27 @@ static int launch_linearize_reduce(lili_ctx* ctx, int slot, int kind_mask, const
     return LILI_OK;
 }
 
-// Page-locked landing area of the blocking calls' results, written by their last kernel across PCIe (a record is 576 bytes): the host reads it after the one
-// synchronisation of the call — no device-to-host copy launch in between (~4 us of GPU time and an API call per blocking evaluation).
-constexpr size_t kHRecordDoubles = (size_t)LILI_MAX_SLOTS * LILI_GRAM_DOUBLES + 2 * LILI_MAX_SLOTS;      // records | 2 x MAX_SLOTS window counts | 2 x MAX_SLOTS per-slot counts (ints)
-static int ensure_h_records(lili_ctx* ctx) {
-    if (ctx->h_records) return LILI_OK;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_records), kHRecordDoubles * sizeof(double), hipHostMallocDefault));
-    void* d = nullptr;
-    if (hipHostGetDevicePointer(&d, ctx->h_records, 0) != hipSuccess) { (void)hipGetLastError(); d = nullptr; }
-    ctx->h_records_dev = static_cast<double*>(d);
-    return LILI_OK;
-}
-
 int lili_s2m_associate(lili_ctx* ctx, int slot, int kind, const double t_assoc[3], const double q_assoc[4],
                        const lili_s2m_params* params, int* n_res) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "associate: bad slot");
+    TRY(check_slot(ctx, slot, "associate"));
     ARGCHK(kind == 0 || kind == 1, "associate: bad kind");
     ARGCHK(t_assoc && q_assoc && params, "associate: null argument");
     HIPCHK(hipSetDevice(ctx->device));
-    PoseArg pa{};
-    for (int i = 0; i < 3; i++) pa.t[i] = t_assoc[i];
-    for (int i = 0; i < 4; i++) pa.q[i] = q_assoc[i];
-    pa.state = nullptr; pa.derive_assoc = 0;
+    const PoseArg pa = pose_at(t_assoc, q_assoc);
     MatchParams P = to_device_params(params);
     ctx->slots[slot].use_global_counts = false; ctx->slots[slot].sticky_global_counts = false;
     int rc = launch_associate_coop(ctx, slot, 1 << kind, pa, P, false, nullptr);
     if (rc == 1) rc = launch_associate(ctx, slot, kind, pa, P);
     if (rc != LILI_OK) return rc;
     if (n_res) {
-        if ((rc = ensure_h_records(ctx)) != LILI_OK) return rc;
-        if (ctx->h_records_dev) {              // k_sum_counts writes the two counts into page-locked memory itself: no copy launch before the synchronisation
-            const size_t off = (size_t)LILI_MAX_SLOTS * LILI_GRAM_DOUBLES * sizeof(double) + (size_t)(2 * LILI_MAX_SLOTS + 2 * slot) * sizeof(int);
-            rc = launch_sum_counts(ctx, slot, 1 << kind, reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->h_records_dev) + off));
-            if (rc != LILI_OK) return rc;
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            *n_res = reinterpret_cast<const int*>(reinterpret_cast<const char*>(ctx->h_records) + off)[kind];
-        } else {
-            rc = launch_sum_counts(ctx, slot, 1 << kind);
-            if (rc != LILI_OK) return rc;
-            rc = lili_readback_add(ctx, n_res, &ctx->state(slot)->n_res[kind], sizeof(int));
-            if (rc == LILI_OK) rc = lili_readback_finish(ctx);
-            if (rc != LILI_OK) return rc;
-        }
+        TRY(ensure_h_records(ctx));
+        // k_sum_counts writes the two counts into page-locked memory itself (no copy launch before the synchronisation), else into the slot's state alone
+        const Landing land{ctx, kHSlotCountsOff + (size_t)2 * slot * sizeof(int), ctx->state(slot)->n_res};
+        TRY(launch_sum_counts(ctx, slot, 1 << kind, land.direct() ? land.dev<int>() : nullptr));
+        int counts[2];
+        TRY(land.fetch(counts, sizeof(counts)));
+        *n_res = counts[kind];
     }
     return LILI_OK;
 }
@@ -593,12 +554,9 @@ int lili_s2m_associate_window(lili_ctx* ctx, const int* slots, int n_slots, int 
                               const lili_s2m_params* params, int* n_res /*2 per slot: surf, edge; optional*/) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(slots && n_slots >= 1 && n_slots <= LILI_MAX_SLOTS, "associate_window: 1..LILI_MAX_SLOTS slots");
-    ARGCHK((kind_mask & ~3) == 0 && kind_mask != 0, "associate_window: bad kind mask");
+    TRY(check_kind_mask(ctx, kind_mask, "associate_window"));
     ARGCHK(t_assoc && q_assoc && params, "associate_window: null argument");
-    for (int i = 0; i < n_slots; i++) {
-        ARGCHK(slots[i] >= 0 && slots[i] < LILI_MAX_SLOTS, "associate_window: bad slot");
-        for (int k = 0; k < i; k++) ARGCHK(slots[k] != slots[i], "associate_window: duplicate slot");
-    }
+    TRY(check_slot_list(ctx, slots, n_slots, "associate_window"));      // (the launches below index the slots: not left to window_args)
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t main_stream = ctx->stream;
     const MatchParams P = to_device_params(params);
@@ -617,9 +575,7 @@ int lili_s2m_associate_window(lili_ctx* ctx, const int* slots, int n_slots, int 
             HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->fork_ev, 0));
             ctx->stream = ctx->side[i];
         }
-        PoseArg pa{};
-        for (int k = 0; k < 3; k++) pa.t[k] = t_assoc[3 * i + k];
-        for (int k = 0; k < 4; k++) pa.q[k] = q_assoc[4 * i + k];
+        const PoseArg pa = pose_at(t_assoc + 3 * i, q_assoc + 4 * i);
         ctx->slots[slots[i]].use_global_counts = false; ctx->slots[slots[i]].sticky_global_counts = false;
         rc = launch_associate_coop(ctx, slots[i], kind_mask, pa, P, false, nullptr);
         if (rc == 1 && kind_mask == (LILI_MASK_SURF | LILI_MASK_EDGE) && ctx->merge_kinds) rc = launch_associate_both(ctx, slots[i], pa, P);
@@ -641,23 +597,14 @@ int lili_s2m_associate_window(lili_ctx* ctx, const int* slots, int n_slots, int 
         // the counts of every slot in ONE launch (k_window_counts: [surf, edge] per slot, also left in the slots' states) and ONE read-back
         // through the page-locked scratch — it was one k_sum_counts + one copy per slot on the forked streams
         WindowArgs w;
-        if ((rc = window_args(ctx, slots, n_slots, kind_mask, w, "associate_window")) != LILI_OK) return rc;
-        if ((rc = ensure_h_records(ctx)) != LILI_OK) return rc;
+        TRY(window_args(ctx, slots, n_slots, kind_mask, w, "associate_window"));
+        TRY(ensure_h_records(ctx));
+        if (!ctx->h_records_dev) HIPCHK(ctx->win_counts.ensure(sizeof(int) * 2 * LILI_MAX_SLOTS));
+        const Landing land{ctx, kHWindowCountsOff, ctx->win_counts.p};
+        hipLaunchKernelGGL(k_window_counts, dim3(1), dim3(kBlock), 0, ctx->stream, w, land.dev<int>(), P2PView{});
+        HIPCHK(hipGetLastError());
         int host[2 * LILI_MAX_SLOTS];
-        if (ctx->h_records_dev) {          // the counts land in page-locked memory straight from the kernel
-            int* d_out = reinterpret_cast<int*>(ctx->h_records_dev + (size_t)LILI_MAX_SLOTS * LILI_GRAM_DOUBLES);
-            hipLaunchKernelGGL(k_window_counts, dim3(1), dim3(kBlock), 0, ctx->stream, w, d_out, P2PView{});
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            std::memcpy(host, ctx->h_records + (size_t)LILI_MAX_SLOTS * LILI_GRAM_DOUBLES, sizeof(int) * 2 * n_slots);
-        } else {
-            HIPCHK(ctx->win_counts.ensure(sizeof(int) * 2 * LILI_MAX_SLOTS));
-            hipLaunchKernelGGL(k_window_counts, dim3(1), dim3(kBlock), 0, ctx->stream, w, ctx->win_counts.as<int>(), P2PView{});
-            HIPCHK(hipGetLastError());
-            rc = lili_readback_add(ctx, host, ctx->win_counts.p, sizeof(int) * 2 * n_slots);
-            if (rc == LILI_OK) rc = lili_readback_finish(ctx);
-            if (rc != LILI_OK) return rc;
-        }
+        TRY(land.fetch(host, sizeof(int) * 2 * n_slots));
         for (int i = 0; i < n_slots; i++) {
             n_res[2 * i] = (kind_mask & LILI_MASK_SURF) ? host[2 * i] : 0;
             n_res[2 * i + 1] = (kind_mask & LILI_MASK_EDGE) ? host[2 * i + 1] : 0;
@@ -678,25 +625,15 @@ int lili_s2m_linearize_window(lili_ctx* ctx, const int* slots, int n_slots, int 
                               const lili_s2m_params* params, double* gram /*64 per slot*/, double* cost /*1 per slot, optional*/, int* counts /*2 per slot, optional*/) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(slots && n_slots >= 1 && n_slots <= LILI_MAX_SLOTS, "linearize_window: 1..LILI_MAX_SLOTS slots");
-    ARGCHK((kind_mask & ~3) == 0 && kind_mask != 0, "linearize_window: bad kind mask");
+    TRY(check_kind_mask(ctx, kind_mask, "linearize_window"));
     ARGCHK(t && q && params && gram, "linearize_window: null argument");
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = ensure_h_records(ctx);
-    if (rc != LILI_OK) return rc;
+    TRY(ensure_h_records(ctx));
+    if (!ctx->h_records_dev) HIPCHK(ctx->win_rec.ensure(sizeof(double) * LILI_GRAM_DOUBLES * LILI_MAX_SLOTS));
+    const Landing land{ctx, 0, ctx->win_rec.p};      // k_window_reduce writes the n records
+    TRY(linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, nullptr, nullptr, land.dev<double>(), 0));
     double host[LILI_GRAM_DOUBLES * LILI_MAX_SLOTS];
-    if (ctx->h_records_dev) {              // k_window_reduce writes the n records into page-locked memory itself
-        rc = linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, nullptr, nullptr, ctx->h_records_dev, 0);
-        if (rc != LILI_OK) return rc;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        std::memcpy(host, ctx->h_records, sizeof(double) * LILI_GRAM_DOUBLES * n_slots);
-    } else {
-        HIPCHK(ctx->win_rec.ensure(sizeof(double) * LILI_GRAM_DOUBLES * LILI_MAX_SLOTS));
-        rc = linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, nullptr, nullptr, ctx->win_rec.as<double>(), 0);
-        if (rc != LILI_OK) return rc;
-        rc = lili_readback_add(ctx, host, ctx->win_rec.p, sizeof(double) * LILI_GRAM_DOUBLES * n_slots);
-        if (rc == LILI_OK) rc = lili_readback_finish(ctx);
-        if (rc != LILI_OK) return rc;
-    }
+    TRY(land.fetch(host, sizeof(double) * LILI_GRAM_DOUBLES * n_slots));
     for (int i = 0; i < n_slots; i++) {
         const double* h = host + (size_t)i * LILI_GRAM_DOUBLES;
         std::memcpy(gram + (size_t)64 * i, h, 64 * sizeof(double));
@@ -709,30 +646,16 @@ int lili_s2m_linearize_window(lili_ctx* ctx, const int* slots, int n_slots, int 
 int lili_s2m_linearize(lili_ctx* ctx, int slot, int kind_mask, const double t[3], const double q[4],
                        const lili_s2m_params* params, double gram[64], double* cost, int counts[2]) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "linearize: bad slot");
-    ARGCHK((kind_mask & ~3) == 0 && kind_mask != 0, "linearize: bad kind mask");
+    TRY(check_slot(ctx, slot, "linearize"));
+    TRY(check_kind_mask(ctx, kind_mask, "linearize"));
     ARGCHK(t && q && params && gram, "linearize: null argument");
     HIPCHK(hipSetDevice(ctx->device));
-    PoseArg pa{};
-    for (int i = 0; i < 3; i++) pa.t[i] = t[i];
-    for (int i = 0; i < 4; i++) pa.q[i] = q[i];
     MatchParams P = to_device_params(params);
-    int rc = ensure_h_records(ctx);
-    if (rc != LILI_OK) return rc;
+    TRY(ensure_h_records(ctx));
+    const Landing land{ctx, (size_t)slot * LILI_GRAM_DOUBLES * sizeof(double), ctx->gram_of(slot)};      // k_reduce_partials writes the record
+    TRY(launch_linearize_reduce(ctx, slot, kind_mask, pose_at(t, q), P, land.dev<double>(), 0));
     double host[LILI_GRAM_DOUBLES];
-    if (ctx->h_records_dev) {              // k_reduce_partials writes the record into page-locked memory itself
-        double* d_out = ctx->h_records_dev + (size_t)slot * LILI_GRAM_DOUBLES;
-        rc = launch_linearize_reduce(ctx, slot, kind_mask, pa, P, d_out, 0);
-        if (rc != LILI_OK) return rc;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        std::memcpy(host, ctx->h_records + (size_t)slot * LILI_GRAM_DOUBLES, sizeof(host));
-    } else {
-        rc = launch_linearize_reduce(ctx, slot, kind_mask, pa, P, ctx->gram_of(slot), 0);
-        if (rc != LILI_OK) return rc;
-        rc = lili_readback_add(ctx, host, ctx->gram_of(slot), sizeof(host));
-        if (rc == LILI_OK) rc = lili_readback_finish(ctx);
-        if (rc != LILI_OK) return rc;
-    }
+    TRY(land.fetch(host, sizeof(host)));
     std::memcpy(gram, host, 64 * sizeof(double));
     if (cost) *cost = host[64];
     if (counts) { counts[0] = (int)host[65]; counts[1] = (int)host[66]; }
@@ -745,7 +668,7 @@ int lili_s2m_linearize(lili_ctx* ctx, int slot, int kind_mask, const double t[3]
 int lili_s2m_get_surf_records(lili_ctx* ctx, int slot, size_t capacity, int32_t* query_index, float* cur_pt, float* normal,
                               float* neg_oa_dot_norm, double* score, size_t* n_out) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "get_surf_records: bad slot");
+    TRY(check_slot(ctx, slot, "get_surf_records"));
     KindSlot& ks = ctx->slots[slot].k[0];
     if (!ks.has_records) return ctx->fail(LILI_E_STATE, "get_surf_records: associate first");
     HIPCHK(hipSetDevice(ctx->device));
@@ -777,7 +700,7 @@ int lili_s2m_get_surf_records(lili_ctx* ctx, int slot, size_t capacity, int32_t*
 int lili_s2m_get_edge_records(lili_ctx* ctx, int slot, size_t capacity, int32_t* query_index, float* cur_pt, float* pt_a, float* pt_b,
                               float* s, size_t* n_out) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "get_edge_records: bad slot");
+    TRY(check_slot(ctx, slot, "get_edge_records"));
     KindSlot& ks = ctx->slots[slot].k[1];
     if (!ks.has_records) return ctx->fail(LILI_E_STATE, "get_edge_records: associate first");
     HIPCHK(hipSetDevice(ctx->device));
@@ -841,10 +764,10 @@ int lili_s2m_pose_set(lili_ctx* ctx, int slot, const double t[3], const double q
 
 int lili_s2m_pose_get(lili_ctx* ctx, int slot, double t[3], double q[4], int* gn_status) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "pose_get: bad slot");
+    TRY(check_slot(ctx, slot, "pose_get"));
     HIPCHK(hipSetDevice(ctx->device));
     SlotState s{};
-    { int rb = lili_readback_add(ctx, &s, ctx->state(slot), sizeof(s)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+    TRY(lili_readback_now(ctx, &s, ctx->state(slot), sizeof(s)));
     if (t) for (int i = 0; i < 3; i++) t[i] = s.pose[i];
     if (q) for (int i = 0; i < 4; i++) q[i] = s.pose[3 + i];
     if (gn_status) *gn_status = s.gn_status;
@@ -858,10 +781,10 @@ int lili_s2m_pose_get(lili_ctx* ctx, int slot, double t[3], double q[4], int* gn
 // lili_s2m_linearize + its own trust region as include/lili_ceres_adapter.h does).
 int lili_s2m_last_step(lili_ctx* ctx, int slot, double delta[6], int* n_updates, int* gn_status) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "last_step: bad slot");
+    TRY(check_slot(ctx, slot, "last_step"));
     HIPCHK(hipSetDevice(ctx->device));
     SlotState s{};
-    { int rb = lili_readback_add(ctx, &s, ctx->state(slot), sizeof(s)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+    TRY(lili_readback_now(ctx, &s, ctx->state(slot), sizeof(s)));
     if (delta) for (int i = 0; i < 6; i++) delta[i] = s.last_delta[i];
     if (n_updates) *n_updates = s.iters;
     if (gn_status) *gn_status = s.gn_status;
@@ -874,7 +797,7 @@ int lili_s2m_debug_times(lili_ctx* ctx, int slot, long long out[16]) {
     ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS && out, "debug_times: bad argument");
     HIPCHK(hipSetDevice(ctx->device));
     SlotState s{};
-    { int rb = lili_readback_add(ctx, &s, ctx->state(slot), sizeof(s)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+    TRY(lili_readback_now(ctx, &s, ctx->state(slot), sizeof(s)));
     for (int i = 0; i < 16; i++) out[i] = s.tprof[i];
     return LILI_OK;
 }
@@ -885,15 +808,13 @@ int lili_s2m_associate_dev(lili_ctx* ctx, int slot, int kind_mask, const lili_s2
 // the granules that kernel publishes (load_assoc_pose / wait_published_pose)
 static int associate_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, unsigned long long wait_key) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "associate_dev: bad slot");
-    ARGCHK((kind_mask & ~3) == 0 && kind_mask != 0, "associate_dev: bad kind mask");
+    TRY(check_slot(ctx, slot, "associate_dev"));
+    TRY(check_kind_mask(ctx, kind_mask, "associate_dev"));
     ARGCHK(params, "associate_dev: null argument");
     HIPCHK(hipSetDevice(ctx->device));
     Slot& s = ctx->slots[slot];
     s.use_global_counts = false; s.sticky_global_counts = false;
-    PoseArg pa{};
-    pa.state = ctx->state(slot);
-    pa.derive_assoc = params->variant == LILI_VARIANT_FRONTEND ? 0 : 1;
+    PoseArg pa = pose_of_slot(ctx, slot, params);
     pa.wait_key = wait_key;
     pa.pub = ctx->pub_of(slot);
     MatchParams P = to_device_params(params);
@@ -930,16 +851,13 @@ int lili_s2m_counts_import(lili_ctx* ctx, int slot, const int32_t* d_counts) {
 
 static int linearize_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, double* d_gram, int do_gn, int want_cost = 0, unsigned long long* pub_key = nullptr) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "linearize_dev: bad slot");
-    ARGCHK((kind_mask & ~3) == 0 && kind_mask != 0, "linearize_dev: bad kind mask");
+    TRY(check_slot(ctx, slot, "linearize_dev"));
+    TRY(check_kind_mask(ctx, kind_mask, "linearize_dev"));
     ARGCHK(params && d_gram, "linearize_dev: null argument");
     HIPCHK(hipSetDevice(ctx->device));
-    PoseArg pa{};
-    pa.state = ctx->state(slot);
     MatchParams P = to_device_params(params);
     if (do_gn && d_gram == ctx->gram_of(slot) && !want_cost) P.no_cost = 1;   // lili_s2m_iterate*: the record stays inside the library, only the GN step is used
-    int rc = launch_linearize_reduce(ctx, slot, kind_mask, pa, P, d_gram, do_gn, nullptr, pub_key);
-    if (rc != LILI_OK) return rc;
+    TRY(launch_linearize_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot), P, d_gram, do_gn, nullptr, pub_key));
     ctx->slots[slot].use_global_counts = false;
     return LILI_OK;
 }
@@ -954,7 +872,7 @@ int lili_s2m_linearize_dev(lili_ctx* ctx, int slot, int kind_mask, const lili_s2
 int lili_s2m_iterate_inner(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, int n_iters, int want_cost) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(n_iters >= 0, "iterate_inner: negative n_iters");
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "iterate_inner: bad slot");
+    TRY(check_slot(ctx, slot, "iterate_inner"));
     for (int it = 0; it < n_iters; it++) {
         int rc = linearize_dev_impl(ctx, slot, kind_mask, params, ctx->gram_of(slot), 1, want_cost);
         if (rc != LILI_OK) return rc;
@@ -975,8 +893,8 @@ void lili_lm_default_options(lili_lm_options* o) {      // Ceres 2.0 Solver::Opt
 
 // enqueues the persistent launch of one slot on ctx->stream; max_blocks bounds the grid (all workgroups have to be resident)
 static int launch_solve_lm(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, const lili_lm_options* options, int max_blocks, LmArgs* prepared = nullptr /* fill the arguments only: the caller launches (k_solve_lm_window) */) {
-    ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS, "solve_lm: bad slot");
-    ARGCHK((kind_mask & ~3) == 0 && kind_mask != 0, "solve_lm: bad kind mask");
+    TRY(check_slot(ctx, slot, "solve_lm"));
+    TRY(check_kind_mask(ctx, kind_mask, "solve_lm"));
     ARGCHK(params, "solve_lm: null params");
     lili_lm_options opt;
     if (options) opt = *options; else lili_lm_default_options(&opt);
@@ -1036,22 +954,14 @@ int lili_s2m_solve_lm(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_par
     const int max_blocks = std::max(1, std::min(ctx->n_simd / 4 - 16, 240));     // one workgroup per CU, a few CUs left to whatever else runs
     int rc = launch_solve_lm(ctx, slot, kind_mask, params, options, max_blocks);
     if (rc != LILI_OK) return rc;
-    if (summary) {
-        rc = lili_readback_add(ctx, summary, ctx->slots[slot].lm_summary.p, sizeof(lili_lm_summary));
-        if (rc == LILI_OK) rc = lili_readback_finish(ctx);
-        if (rc != LILI_OK) return rc;
-    }
+    if (summary) TRY(lili_readback_now(ctx, summary, ctx->slots[slot].lm_summary.p, sizeof(lili_lm_summary)));
     return LILI_OK;
 }
 
 int lili_s2m_solve_lm_window(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const lili_lm_options* options,
                              lili_lm_summary* summaries) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slots && n_slots >= 1 && n_slots <= LILI_MAX_SLOTS, "solve_lm_window: 1..LILI_MAX_SLOTS slots");
-    for (int i = 0; i < n_slots; i++) {
-        ARGCHK(slots[i] >= 0 && slots[i] < LILI_MAX_SLOTS, "solve_lm_window: bad slot");
-        for (int k = 0; k < i; k++) ARGCHK(slots[k] != slots[i], "solve_lm_window: duplicate slot");
-    }
+    TRY(check_slot_list(ctx, slots, n_slots, "solve_lm_window"));
     HIPCHK(hipSetDevice(ctx->device));
     // ONE launch for all slots (round 6: k_solve_lm_window); every slot needs all its workgroups resident: the CUs are shared out
     const int max_blocks = std::max(1, std::min(ctx->n_simd / 4 - 16, 240) / n_slots);
@@ -1107,12 +1017,9 @@ int lili_s2m_pose_copy(lili_ctx* ctx, int dst_slot, int src_slot) {
 // one outer iteration through k_associate_lin (see launch_associate_lin_reduce); 1 = not eligible
 static int iterate_fused_lin(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params) {
     if (!ctx->fuse_lin) return 1;
-    PoseArg pa{};
-    pa.state = ctx->state(slot);
-    pa.derive_assoc = params->variant == LILI_VARIANT_FRONTEND ? 0 : 1;
     MatchParams P = to_device_params(params);
     P.no_cost = 1;             // the record stays inside the library, only the GN step is used
-    return launch_associate_lin_reduce(ctx, slot, kind_mask, pa, P, ctx->gram_of(slot));
+    return launch_associate_lin_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot, params), P, ctx->gram_of(slot));
 }
 static int iterate_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, int n_iters, int restart_every, int restart_slot, float* assoc_ms) {
     if (!ctx) return LILI_E_ARG;
@@ -1190,11 +1097,9 @@ int lili_s2m_iterate_sharded(lili_ctx* ctx, int slot, int kind_mask, const lili_
                 if ((rc = launch_sum_counts(ctx, slot, LILI_MASK_SURF | LILI_MASK_EDGE, d_counts, &v)) != LILI_OK) return rc;
                 if ((rc = lili_s2m_counts_import(ctx, slot, d_counts)) != LILI_OK) return rc;
             }
-            PoseArg pa{};
-            pa.state = ctx->state(slot);
             const MatchParams P = to_device_params(params);
             const P2PView v = lili_p2p_next_view(p2p);
-            if ((rc = launch_linearize_reduce(ctx, slot, kind_mask, pa, P, d_gram, 1, &v)) != LILI_OK) return rc;
+            if ((rc = launch_linearize_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot), P, d_gram, 1, &v)) != LILI_OK) return rc;
             ctx->slots[slot].use_global_counts = false;
             continue;
         }
@@ -1217,12 +1122,11 @@ int lili_s2m_iterate_sharded(lili_ctx* ctx, int slot, int kind_mask, const lili_
 // --------------------------------------------------------------------------------------------
 static int window_args(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, WindowArgs& w, const char* who) {
     ARGCHK(slots && n_slots >= 1 && n_slots <= LILI_MAX_SLOTS, std::string(who) + ": 1..LILI_MAX_SLOTS slots");
-    ARGCHK((kind_mask & ~3) == 0 && kind_mask != 0, std::string(who) + ": bad kind mask");
+    TRY(check_kind_mask(ctx, kind_mask, who));
+    TRY(check_slot_list(ctx, slots, n_slots, who));
     w = WindowArgs{};
     w.n = n_slots;
     for (int i = 0; i < n_slots; i++) {
-        ARGCHK(slots[i] >= 0 && slots[i] < LILI_MAX_SLOTS, std::string(who) + ": bad slot");
-        for (int k = 0; k < i; k++) ARGCHK(slots[k] != slots[i], std::string(who) + ": duplicate slot");
         Slot& sl = ctx->slots[slots[i]];
         WindowSlot& ws = w.s[i];
         ws.state = ctx->state(slots[i]);
@@ -1258,10 +1162,7 @@ static int launch_linearize_only(lili_ctx* ctx, int slot, int kind_mask, const P
 // slot (host poses), or both null for the slots' device poses.  Bit-identical to launch_linearize_only slot by slot (same bodies, same block geometry).
 static int launch_linearize_window(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const double* t, const double* q, const MatchParams& P) {
     if (n_slots == 1) {
-        PoseArg pa{};
-        if (t && q) { for (int k = 0; k < 3; k++) pa.t[k] = t[k]; for (int k = 0; k < 4; k++) pa.q[k] = q[k]; }
-        else pa.state = ctx->state(slots[0]);
-        return launch_linearize_only(ctx, slots[0], kind_mask, pa, P);
+        return launch_linearize_only(ctx, slots[0], kind_mask, t && q ? pose_at(t, q) : pose_of_slot(ctx, slots[0]), P);
     }
     WinLinArgs W{};
     int nb = 0;
@@ -1278,8 +1179,7 @@ static int launch_linearize_window(lili_ctx* ctx, const int* slots, int n_slots,
             n_kinds++;
         }
         if (n_kinds == 0) continue;             // nothing to linearise for this slot: k_window_reduce sees nb = 0 and writes a zero record
-        if (t && q) { for (int k = 0; k < 3; k++) ws.pa.t[k] = t[3 * i + k]; for (int k = 0; k < 4; k++) ws.pa.q[k] = q[4 * i + k]; }
-        else ws.pa.state = ctx->state(slots[i]);
+        ws.pa = t && q ? pose_at(t + 3 * i, q + 4 * i) : pose_of_slot(ctx, slots[i]);
         ws.state = ctx->state(slots[i]);
         ws.n_global = s.use_global_counts ? s.global_counts : nullptr;
         ws.first_block = nb;
@@ -1486,11 +1386,7 @@ int lili_s2m_iterate_window_gather(lili_ctx* ctx, const int* slots, int n_slots,
 // association of another.  Results are identical to calling lili_s2m_iterate slot after slot.
 int lili_s2m_iterate_window(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, int n_iters) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(slots && n_slots >= 1 && n_slots <= LILI_MAX_SLOTS, "iterate_window: 1..LILI_MAX_SLOTS slots");
-    for (int i = 0; i < n_slots; i++) {
-        ARGCHK(slots[i] >= 0 && slots[i] < LILI_MAX_SLOTS, "iterate_window: bad slot");
-        for (int k = 0; k < i; k++) ARGCHK(slots[k] != slots[i], "iterate_window: duplicate slot");
-    }
+    TRY(check_slot_list(ctx, slots, n_slots, "iterate_window"));
     HIPCHK(hipSetDevice(ctx->device));
     if (!ctx->fork_ev) HIPCHK(hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(ctx->fork_ev, ctx->stream));

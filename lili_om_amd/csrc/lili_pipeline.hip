@@ -276,7 +276,7 @@ static int frame_impl(lili_ctx* ctx, const FrameExtractor& ex, const lili_s2m_pa
     //      lili_frontend_flush).
     SlotState st{};
     if (matched) rc = read_pose_after_iterate(ctx, slot, &st);
-    else { rc = lili_readback_add(ctx, &st, ctx->state(slot), sizeof(st)); if (rc == LILI_OK) rc = lili_readback_finish(ctx); }
+    else rc = lili_readback_now(ctx, &st, ctx->state(slot), sizeof(st));
     if (rc != LILI_OK) return rc;
     if (!ext_map) {
         rc = lili_localmap_push_dev(ctx, LILI_KIND_SURF, ctx->slots[slot].k[LILI_KIND_SURF].q.as<float4>(), (opt->flags & LILI_FRAME_PUSH_EMPTY) ? 0 : n_q, ctx->state(slot), opt->width);

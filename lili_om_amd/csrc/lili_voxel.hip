@@ -1064,7 +1064,7 @@ static int voxel_sort(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const float4*
     hipLaunchKernelGGL(k_box_init, dim3(1), dim3(64), 0, ctx->stream, d_mm);
     hipLaunchKernelGGL(k_bbox, dim3(std::min(nblocks(n, kBlock), 512)), dim3(kBlock), 0, ctx->stream, d_pts, n, d_mm);
     unsigned mm[6];
-    { int rb = lili_readback_add(ctx, mm, d_mm, sizeof(mm)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+    TRY(lili_readback_now(ctx, mm, d_mm, sizeof(mm)));
     P = VoxDev{};
     P.inv_leaf = 1.0f / leaf;
     int div_b[3];
@@ -1115,7 +1115,7 @@ static int voxel_filter_measured(lili_ctx* ctx, lili_detail::VoxelBuffers* V, co
     rc = voxel_filter_tail(ctx, V, d_pts, n, P.sentinel, alt);
     if (rc != LILI_OK) return rc;
     int& n_out = alt ? V->qn_out : V->n_out;
-    { int rb = lili_readback_add(ctx, &n_out, V->slots.as<int>() + n, sizeof(int)); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+    TRY(lili_readback_now(ctx, &n_out, V->slots.as<int>() + n, sizeof(int)));
     return LILI_OK;
 }
 
@@ -1598,7 +1598,7 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
                                S.seq[0].as<unsigned>(), d_bad);
             HIPCHK(hipGetLastError());
             unsigned bad = 0;
-            { int rb = lili_readback_add(ctx, &bad, d_bad, 4); if (rb == LILI_OK) rb = lili_readback_finish(ctx); if (rb != LILI_OK) return rb; }
+            TRY(lili_readback_now(ctx, &bad, d_bad, 4));
             S.cur = 0; S.n = (long long)total; S.leaf = leaf; S.valid = bad == 0;
             S.members.clear();
             for (auto* k : ring) S.members.push_back({k->seq, k->n});
