@@ -63,6 +63,7 @@ struct FuseTail {
     double* out;
     SlotState* state;
     int debug;                 // LILI_DEBUG bits (256: phase stamps of the reducer block)
+    const SlotState* pose_src; // mode 2: the slot whose pose the Gauss-Newton step starts from (the first step after a restart), or nullptr = state
 };
 
 

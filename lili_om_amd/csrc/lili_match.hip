@@ -67,9 +67,11 @@ static PoseArg pose_at(const double t[3], const double q[4]) {
 }
 // ... or the slot's pose on the device; `assoc_params`: for an association, which derives its transform from the body pose unless the flavour matches in the body frame
 static int derives_assoc(const lili_s2m_params* params) { return params->variant == LILI_VARIANT_FRONTEND ? 0 : 1; }
-static PoseArg pose_of_slot(lili_ctx* ctx, int slot, const lili_s2m_params* assoc_params = nullptr) {
+// pose_slot >= 0: the first step after a restart reads the pose of the slot that holds the initial guess (no copy launch: the reduction + GN kernel of that step
+// writes the slot's own state from it)
+static PoseArg pose_of_slot(lili_ctx* ctx, int slot, const lili_s2m_params* assoc_params = nullptr, int pose_slot = -1) {
     PoseArg pa{};
-    pa.state = ctx->state(slot);
+    pa.state = ctx->state(pose_slot >= 0 ? pose_slot : slot);
     pa.derive_assoc = assoc_params ? derives_assoc(assoc_params) : 0;
     return pa;
 }
@@ -340,7 +342,7 @@ static int launch_associate_coop(lili_ctx* ctx, int slot, int kind_mask, const P
             else launch_k(ctx->stream, pa.wait_key != 0ull, (k_associate_coop<LL, false>), grid, block, 0, A[0], A[1], pa, P, ps, pe, ctx->state(slot), 0);
         })) return 1;
     if (lin) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, (const double*)ps, A[0].nb, (const double*)pe, A[1].nb, d_out, ctx->state(slot),
-                                1 | (P.debug & 256), P2PView{}, 0ull, (double*)nullptr, ctx->take_state_mirror(slot));
+                                1 | (P.debug & 256), P2PView{}, 0ull, (double*)nullptr, ctx->take_state_mirror(slot), pa.state);
     HIPCHK(hipGetLastError());
     sl.use_global_counts = false;
     return LILI_OK;
@@ -388,7 +390,8 @@ static int launch_associate_coop_window(lili_ctx* ctx, const int* slots, int n_s
 // n_iters outer iterations of a SMALL scan as ONE persistent launch (k_iterate_coop, lili_s2m_coop.hip): every workgroup keeps the pose in LDS,
 // the workgroups exchange counts and Gram partials inside the launch and each applies the same Gauss-Newton step.  Returns 1 if not eligible
 // (the caller then iterates launch by launch).  Eligible: the configurations of launch_associate_coop with at most 256 workgroups.
-static int launch_iterate_persistent(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, int n_iters) {
+// pose_slot != slot: a restart — this launch keeps the pose in LDS and reads it from its own slot, so the copy launch stays here (enqueued once the launch is certain)
+static int launch_iterate_persistent(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, int n_iters, int pose_slot) {
     if (!ctx->persistent_iterate || n_iters < 2 || n_iters > 2000) return 1;
     if (ctx->fuse_tail) return 1;
     MatchParams P = to_device_params(params);
@@ -418,6 +421,7 @@ static int launch_iterate_persistent(lili_ctx* ctx, int slot, int kind_mask, con
     HIPCHK(sl.lm_cnt.ensure((size_t)2 * (nb + it.ng) * 4 * sizeof(double)));
     it.part = sl.lm_part.as<double>(); it.gsum = sl.lm_gsum.as<double>(); it.cpart = sl.lm_cnt.as<double>();
     const dim3 grid(nb), block(256);
+    if (pose_slot != slot) { const int saved = sl.assoc_since_pose; TRY(lili_s2m_pose_copy(ctx, slot, pose_slot)); sl.assoc_since_pose = saved; }
     if (!with_lanes(L, [&](auto lanes) { hipLaunchKernelGGL(k_iterate_coop<decltype(lanes)::value>, grid, block, 0, ctx->stream, A[0], A[1], P, it); })) return 1;
     HIPCHK(hipGetLastError());
     sl.use_global_counts = false; sl.sticky_global_counts = false;
@@ -476,7 +480,7 @@ static int launch_associate_lin_reduce(lili_ctx* ctx, int slot, int kind_mask, c
     else hipLaunchKernelGGL(k_associate_lin<kBlock>, dim3(A[0].nb + A[1].nb), dim3(kBlock), 0, ctx->stream, A[0], A[1], pa, P,
                             sl.k[0].partials_wave.as<double>(), sl.k[1].partials_wave.as<double>());
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, (const double*)sl.k[0].partials_wave.as<double>(), A[0].nb,
-                       (const double*)sl.k[1].partials_wave.as<double>(), A[1].nb, d_out, ctx->state(slot), 1 | (P.debug & 256), P2PView{}, 0ull, (double*)nullptr, ctx->take_state_mirror(slot));
+                       (const double*)sl.k[1].partials_wave.as<double>(), A[1].nb, d_out, ctx->state(slot), 1 | (P.debug & 256), P2PView{}, 0ull, (double*)nullptr, ctx->take_state_mirror(slot), pa.state);
     HIPCHK(hipGetLastError());
     sl.use_global_counts = false;
     return LILI_OK;
@@ -499,7 +503,7 @@ static int launch_linearize_reduce(lili_ctx* ctx, int slot, int kind_mask, const
     const int* ng = s.use_global_counts ? s.global_counts : nullptr;
     FuseTail fz{};
     fz.mode = (ctx->fuse_tail && n_kinds > 0 && !xv) ? (do_gn ? 2 : 1) : 0;     // the exchange across ranks lives in k_reduce_partials
-    fz.out = d_out; fz.state = ctx->state(slot); fz.debug = P.debug;
+    fz.out = d_out; fz.state = ctx->state(slot); fz.debug = P.debug; fz.pose_src = pa.state;
     fz.part_surf = A[0].partials; fz.nb_surf = A[0].nb; fz.part_edge = A[1].partials; fz.nb_edge = A[1].nb;
     const FuseTail off{};
     const size_t lds = lds_linearize(kLinBlock);
@@ -514,7 +518,7 @@ static int launch_linearize_reduce(lili_ctx* ctx, int slot, int kind_mask, const
     HIPCHK(hipGetLastError());
     if (!fz.mode) {
         hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, fz.part_surf, fz.nb_surf, fz.part_edge, fz.nb_edge, d_out, ctx->state(slot), (do_gn ? 1 : 0) | (P.debug & 256),
-                           xv ? *xv : P2PView{}, (pub_key && do_gn) ? *pub_key : 0ull, ctx->pub_of(slot), do_gn ? ctx->take_state_mirror(slot) : nullptr);
+                           xv ? *xv : P2PView{}, (pub_key && do_gn) ? *pub_key : 0ull, ctx->pub_of(slot), do_gn ? ctx->take_state_mirror(slot) : nullptr, pa.state);
         HIPCHK(hipGetLastError());
     } else if (pub_key) *pub_key = 0ull;
     if (pub_key && !do_gn) *pub_key = 0ull;
@@ -802,11 +806,11 @@ int lili_s2m_debug_times(lili_ctx* ctx, int slot, long long out[16]) {
     return LILI_OK;
 }
 
-static int associate_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, unsigned long long wait_key);
+static int associate_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, unsigned long long wait_key, int pose_slot = -1);
 int lili_s2m_associate_dev(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params) { return associate_dev_impl(ctx, slot, kind_mask, params, 0ull); }
 // wait_key != 0 (iterate_impl, option "overlap_gn"): the launch carries no barrier against the reduction + GN kernel enqueued right before it and takes the pose from
 // the granules that kernel publishes (load_assoc_pose / wait_published_pose)
-static int associate_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, unsigned long long wait_key) {
+static int associate_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, unsigned long long wait_key, int pose_slot) {
     if (!ctx) return LILI_E_ARG;
     TRY(check_slot(ctx, slot, "associate_dev"));
     TRY(check_kind_mask(ctx, kind_mask, "associate_dev"));
@@ -814,7 +818,7 @@ static int associate_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili
     HIPCHK(hipSetDevice(ctx->device));
     Slot& s = ctx->slots[slot];
     s.use_global_counts = false; s.sticky_global_counts = false;
-    PoseArg pa = pose_of_slot(ctx, slot, params);
+    PoseArg pa = pose_of_slot(ctx, slot, params, pose_slot);
     pa.wait_key = wait_key;
     pa.pub = ctx->pub_of(slot);
     MatchParams P = to_device_params(params);
@@ -849,7 +853,8 @@ int lili_s2m_counts_import(lili_ctx* ctx, int slot, const int32_t* d_counts) {
     return LILI_OK;
 }
 
-static int linearize_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, double* d_gram, int do_gn, int want_cost = 0, unsigned long long* pub_key = nullptr) {
+static int linearize_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, double* d_gram, int do_gn, int want_cost = 0, unsigned long long* pub_key = nullptr,
+                              int pose_slot = -1) {
     if (!ctx) return LILI_E_ARG;
     TRY(check_slot(ctx, slot, "linearize_dev"));
     TRY(check_kind_mask(ctx, kind_mask, "linearize_dev"));
@@ -857,7 +862,7 @@ static int linearize_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili
     HIPCHK(hipSetDevice(ctx->device));
     MatchParams P = to_device_params(params);
     if (do_gn && d_gram == ctx->gram_of(slot) && !want_cost) P.no_cost = 1;   // lili_s2m_iterate*: the record stays inside the library, only the GN step is used
-    TRY(launch_linearize_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot), P, d_gram, do_gn, nullptr, pub_key));
+    TRY(launch_linearize_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot, nullptr, pose_slot), P, d_gram, do_gn, nullptr, pub_key));
     ctx->slots[slot].use_global_counts = false;
     return LILI_OK;
 }
@@ -991,14 +996,15 @@ int lili_s2m_accumulate(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_p
     return lili_s2m_linearize_dev(ctx, slot, kind_mask, params, d_gram);
 }
 
-int lili_s2m_gn_update(lili_ctx* ctx, int slot, const double* d_gram) {
+static int gn_update_impl(lili_ctx* ctx, int slot, const double* d_gram, int pose_slot) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS && d_gram, "gn_update: bad argument");
     HIPCHK(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_gn_update, dim3(1), dim3(64), 0, ctx->stream, d_gram, ctx->state(slot));
+    hipLaunchKernelGGL(k_gn_update, dim3(1), dim3(64), 0, ctx->stream, d_gram, ctx->state(slot), (const SlotState*)(pose_slot >= 0 ? ctx->state(pose_slot) : nullptr));
     HIPCHK(hipGetLastError());
     return LILI_OK;
 }
+int lili_s2m_gn_update(lili_ctx* ctx, int slot, const double* d_gram) { return gn_update_impl(ctx, slot, d_gram, -1); }
 
 int lili_s2m_pose_copy(lili_ctx* ctx, int dst_slot, int src_slot) {
     if (!ctx) return LILI_E_ARG;
@@ -1011,15 +1017,17 @@ int lili_s2m_pose_copy(lili_ctx* ctx, int dst_slot, int src_slot) {
 }
 
 // n_iters outer iterations; if restart_every > 0 the pose of `slot` is re-initialised from `restart_slot` before
-// iterations 0, restart_every, 2*restart_every, ... (device-to-device, async) — "one registration = restart_every
-// GN iterations".  If assoc_ms is non-NULL the association launches are bracketed by HIP events on the context's
+// iterations 0, restart_every, 2*restart_every, ... — "one registration = restart_every GN iterations".  No copy launch: the
+// kernels of such an iteration read the pose from the restart slot's state, and its reduction + GN kernel writes the updated
+// pose (the restart pose itself if the step is rejected) into the slot's own state (only the persistent launch of small scans,
+// which reads its own slot, is still preceded by k_pose_copy).  If assoc_ms is non-NULL the association launches are bracketed by HIP events on the context's
 // stream and their total duration is returned (this variant synchronises at the end).
 // one outer iteration through k_associate_lin (see launch_associate_lin_reduce); 1 = not eligible
-static int iterate_fused_lin(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params) {
+static int iterate_fused_lin(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, int pose_slot) {
     if (!ctx->fuse_lin) return 1;
     MatchParams P = to_device_params(params);
     P.no_cost = 1;             // the record stays inside the library, only the GN step is used
-    return launch_associate_lin_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot, params), P, ctx->gram_of(slot));
+    return launch_associate_lin_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot, params, pose_slot), P, ctx->gram_of(slot));
 }
 static int iterate_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, int n_iters, int restart_every, int restart_slot, float* assoc_ms) {
     if (!ctx) return LILI_E_ARG;
@@ -1039,20 +1047,22 @@ static int iterate_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_p
     ctx->state_mirror_want = false; ctx->state_mirror_armed = false;
     for (int it = 0; it < n_iters; it++) {   // 3 launches per outer iteration: associate, linearise, reduce+GN
         ctx->state_mirror_armed = want_mirror && it == n_iters - 1;
-        if (restart_every > 0 && it % restart_every == 0) { int rc = lili_s2m_pose_copy(ctx, slot, restart_slot); if (rc != LILI_OK) return rc; wait_key = 0ull; }
+        const bool restart = restart_every > 0 && it % restart_every == 0;
+        const int pose_slot = restart ? restart_slot : slot;      // where this iteration's kernels read the pose
+        if (restart) { TRY(check_slot(ctx, slot, "iterate")); ctx->slots[slot].assoc_since_pose = 0; wait_key = 0ull; }
         if (!assoc_ms) {        // small scans: the whole registration (up to the next restart) as ONE persistent launch
             const int seg = restart_every > 0 ? std::min(restart_every - it % restart_every, n_iters - it) : n_iters - it;
-            const int rcp = launch_iterate_persistent(ctx, slot, kind_mask, params, seg);
+            const int rcp = launch_iterate_persistent(ctx, slot, kind_mask, params, seg, pose_slot);
             if (rcp == LILI_OK) { it += seg - 1; wait_key = 0ull; continue; }
             if (rcp != 1) return rcp;
         }
         if (!assoc_ms) {        // flavours without count scaling: association + linearisation in one launch (2 launches per iteration)
-            int rc2 = iterate_fused_lin(ctx, slot, kind_mask, params);
+            int rc2 = iterate_fused_lin(ctx, slot, kind_mask, params, pose_slot);
             if (rc2 == LILI_OK) { wait_key = 0ull; continue; }
             if (rc2 != 1) return rc2;
         }
         if (assoc_ms) HIPCHK(hipEventRecord(ev[2 * it], ctx->stream));
-        int rc = associate_dev_impl(ctx, slot, kind_mask, params, wait_key);
+        int rc = associate_dev_impl(ctx, slot, kind_mask, params, wait_key, pose_slot);
         if (rc != LILI_OK) return rc;
         if (assoc_ms) HIPCHK(hipEventRecord(ev[2 * it + 1], ctx->stream));
         // Round 5, "overlap_gn": when the NEXT thing on the stream is this slot's next association, the reduction + GN kernel publishes the new pose as keyed granules and
@@ -1060,7 +1070,7 @@ static int iterate_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_p
         // reduction still runs — two barriers and one flag hop per iteration instead of three barriers.  Keys never repeat within a context.
         unsigned long long pub_key = 0ull;
         if (ctx->overlap_gn && !assoc_ms && it + 1 < n_iters && !(restart_every > 0 && (it + 1) % restart_every == 0)) pub_key = (++ctx->gn_seq) * 0x9E3779B97F4A7C15ull;
-        rc = linearize_dev_impl(ctx, slot, kind_mask, params, ctx->gram_of(slot), 1, 0, &pub_key);
+        rc = linearize_dev_impl(ctx, slot, kind_mask, params, ctx->gram_of(slot), 1, 0, &pub_key, pose_slot);
         if (rc != LILI_OK) return rc;
         wait_key = pub_key;
     }
@@ -1088,8 +1098,10 @@ int lili_s2m_iterate_sharded(lili_ctx* ctx, int slot, int kind_mask, const lili_
         return ctx->fail(LILI_E_STATE, "iterate_sharded: the lili_p2p communicator has failed (a peer's record did not arrive within its timeout); SlotState gn_status is 2 on the ranks that noticed");
     for (int it = 0; it < n_iters; it++) {
         int rc;
-        if (restart_every > 0 && it % restart_every == 0 && (rc = lili_s2m_pose_copy(ctx, slot, restart_slot)) != LILI_OK) return rc;
-        if ((rc = lili_s2m_associate_dev(ctx, slot, kind_mask, params)) != LILI_OK) return rc;
+        const bool restart = restart_every > 0 && it % restart_every == 0;
+        const int pose_slot = restart ? restart_slot : slot;      // (as in iterate_impl: no copy launch)
+        if (restart) { TRY(check_slot(ctx, slot, "iterate_sharded")); ctx->slots[slot].assoc_since_pose = 0; }
+        if ((rc = associate_dev_impl(ctx, slot, kind_mask, params, 0ull, pose_slot)) != LILI_OK) return rc;
         if (p2p) {
             ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS && (kind_mask & ~3) == 0 && kind_mask != 0, "iterate_sharded: bad slot / kind mask");
             if (count_scaled) {
@@ -1099,7 +1111,7 @@ int lili_s2m_iterate_sharded(lili_ctx* ctx, int slot, int kind_mask, const lili_
             }
             const MatchParams P = to_device_params(params);
             const P2PView v = lili_p2p_next_view(p2p);
-            if ((rc = launch_linearize_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot), P, d_gram, 1, &v)) != LILI_OK) return rc;
+            if ((rc = launch_linearize_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot, nullptr, pose_slot), P, d_gram, 1, &v)) != LILI_OK) return rc;
             ctx->slots[slot].use_global_counts = false;
             continue;
         }
@@ -1109,10 +1121,10 @@ int lili_s2m_iterate_sharded(lili_ctx* ctx, int slot, int kind_mask, const lili_
                 return ctx->fail(LILI_E_HIP, "iterate_sharded: all-reduce of the correspondence counts failed");
             if ((rc = lili_s2m_counts_import(ctx, slot, d_counts)) != LILI_OK) return rc;
         }
-        if ((rc = lili_s2m_linearize_dev(ctx, slot, kind_mask, params, d_gram)) != LILI_OK) return rc;
+        if ((rc = linearize_dev_impl(ctx, slot, kind_mask, params, d_gram, 0, 0, nullptr, pose_slot)) != LILI_OK) return rc;
         if (allreduce && allreduce(d_gram, d_gram, LILI_GRAM_DOUBLES, /*ncclFloat64*/ 8, /*ncclSum*/ 0, comm, (void*)ctx->stream) != 0)
             return ctx->fail(LILI_E_HIP, "iterate_sharded: all-reduce of the Gram record failed");
-        if ((rc = lili_s2m_gn_update(ctx, slot, d_gram)) != LILI_OK) return rc;
+        if ((rc = gn_update_impl(ctx, slot, d_gram, pose_slot)) != LILI_OK) return rc;
     }
     return LILI_OK;
 }

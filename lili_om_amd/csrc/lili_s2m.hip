@@ -786,12 +786,13 @@ template __global__ void k_associate_edge<kAssocBlock>(const float4*, int, GridV
 template <bool XCHG>
 __device__ __forceinline__ void reduce_partials_block(const double* part_surf, int nb_surf, const double* part_edge, int nb_edge,
                                                       double* __restrict__ out, SlotState* __restrict__ state, int do_gn, unsigned long long key, const P2PView& xv,
-                                                      unsigned long long pub_key = 0ull, double* pub = nullptr, SlotState* __restrict__ mirror = nullptr);   // defined below
+                                                      unsigned long long pub_key = 0ull, double* pub = nullptr, SlotState* __restrict__ mirror = nullptr,
+                                                      const SlotState* __restrict__ pose_src = nullptr);   // defined below
 __device__ __forceinline__ void fused_tail(const FuseTail& fz, unsigned long long key) {
     if (fz.mode != 1 && fz.mode != 2) return;      // 0: plain partials for k_reduce_partials; 3: publish only (the per-kind launches of merge_kinds = 0: the second launch reduces)
     if (blockIdx.x != gridDim.x - 1) return;
     P2PView none{};       // the fused tail is the single-GPU structure: no exchange (seq = 0)
-    reduce_partials_block<false>(fz.part_surf, fz.nb_surf, fz.part_edge, fz.nb_edge, fz.out, fz.state, (fz.mode == 2 ? 1 : 0) | (fz.debug & 256), key, none);
+    reduce_partials_block<false>(fz.part_surf, fz.nb_surf, fz.part_edge, fz.nb_edge, fz.out, fz.state, (fz.mode == 2 ? 1 : 0) | (fz.debug & 256), key, none, 0ull, nullptr, nullptr, fz.pose_src);
 }
 
 
@@ -866,19 +867,136 @@ __global__ __launch_bounds__(BS) void k_associate_lin(AssocArgs S, AssocArgs E, 
 template __global__ void k_associate_lin<kAssocBlock>(AssocArgs, AssocArgs, PoseArg, MatchParams, double*, double*);
 template __global__ void k_associate_lin<kBlock>(AssocArgs, AssocArgs, PoseArg, MatchParams, double*, double*);
 
-// xq: the quaternion of state->pose, loaded by the caller at kernel start (its latency hides behind the partial loads).
-// Must be called by exactly ONE wave (lanes 0..63 of it).
+// What the Gauss-Newton tail reads of the slots' states, REQUESTED AT KERNEL START by its caller (the round trips hide behind the partial loads): the pose the step
+// starts from — `src`, which is the slot itself or, for the first step after a restart, the slot that holds the initial guess (no copy launch in between) — and the
+// update counter of the slot that receives the result.  After these loads the tail only computes and stores.
+struct GnIn {
+    double pose[7];
+    int iters;
+};
+__device__ __forceinline__ GnIn gn_load(const SlotState* __restrict__ state, const SlotState* __restrict__ src) {
+    const SlotState* ps = src ? src : state;
+    GnIn in;
+#pragma unroll
+    for (int i = 0; i < 7; i++) in.pose[i] = ps->pose[i];
+    in.iters = state->iters;
+    return in;
+}
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b & 0xffffffffull), lane);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+// 6x6 LDL^T solve of H d = g entirely in registers (all indices are compile-time constants after unrolling): six dependent
+// divisions (1/d_j) instead of the 6 square roots + 27 divisions of a Cholesky with per-element divides — the
+// f64 divide / sqrt sequences dominated this kernel's critical path.  d: g on entry, the solution on return; false = a pivot
+// was not positive or the solution holds a NaN.  Every lane that calls it runs all 36 updates one after the other.
+__device__ __forceinline__ bool ldlt6_solve_lane0(const double (*H)[6], double d[6]) {
+    double L[6][6], W[6][6], dinv[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+#pragma unroll
+        for (int j = 0; j <= i; j++) L[i][j] = H[i][j];
+    }
+    bool okc = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double dj = L[j][j];
+#pragma unroll
+        for (int k = 0; k < j; k++) dj -= L[j][k] * W[j][k];     // W[j][k] = L[j][k] * d_k
+        if (!(dj > 0)) okc = false;
+        dinv[j] = 1.0 / dj;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double sv = L[i][j];
+#pragma unroll
+            for (int k = 0; k < j; k++) sv -= L[i][k] * W[j][k];
+            W[i][j] = sv;
+            L[i][j] = sv * dinv[j];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) {          // L z = g
+        double sv = d[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) sv -= L[i][k] * d[k];
+        d[i] = sv;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) d[i] = d[i] * dinv[i];   // D y = z
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {         // L^T x = y
+        double sv = d[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; k++) sv -= L[k][i] * d[k];
+        d[i] = sv;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) if (!(d[i] == d[i])) okc = false;
+    return okc;
+}
+// The same factorisation with lane i of the wave on row i: in column j every lane forms its own W[i][j] = H[i][j] - sum_{k<j} L[i][k] W[j][k] (k ascending, a
+// multiplication and a subtraction each: the operations of ldlt6_solve_lane0 on the same operands in the same order, so the same bits), lane j's value is the pivot,
+// and row j's W entries reach the other lanes by v_readlane.  The five rows of a column no longer queue up behind each other on one lane.  The substitutions run on
+// the wave-uniform L[i][k] = W[i][k] * dinv[k] (the product each lane formed for itself) in every lane alike.  Must be called by ALL lanes of one wave.
+__device__ __forceinline__ bool ldlt6_solve_lanes(const double (*H)[6], int tid, double d[6]) {
+    const int r = tid < 6 ? tid : 5;       // (lanes 6..63 repeat row 5: no divergence, nothing of theirs is read)
+    double Hr[6], Lr[6], Wr[6], Wu[6][6], dinv[6];
+#pragma unroll
+    for (int j = 0; j < 6; j++) Hr[j] = H[r][j];
+    bool okc = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double sv = Hr[j];
+#pragma unroll
+        for (int k = 0; k < j; k++) sv -= Lr[k] * Wu[j][k];
+        const double dj = readlane_f64(sv, j);
+        if (!(dj > 0)) okc = false;
+        dinv[j] = 1.0 / dj;
+        Wr[j] = sv;
+        Lr[j] = sv * dinv[j];
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) Wu[i][j] = readlane_f64(sv, i);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) {          // L z = g
+        double sv = d[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) sv -= (Wu[i][k] * dinv[k]) * d[k];
+        d[i] = sv;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) d[i] = d[i] * dinv[i];   // D y = z
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {         // L^T x = y
+        double sv = d[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; k++) sv -= (Wu[k][i] * dinv[i]) * d[k];
+        d[i] = sv;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) if (!(d[i] == d[i])) okc = false;
+    return okc;
+}
+
+// in: the start pose and the update counter, loaded by the caller at kernel start (gn_load) — this function loads nothing of `state`.
+// Must be called by exactly ONE wave (lanes 0..63 of it).  LANES: the factorisation on six lanes (ldlt6_solve_lanes), else on one (ldlt6_solve_lane0: k_gn_update,
+// the split / multi-GPU path) — two implementations of one sequence of operations, which tests/test_gn_tail_gpu.py sets against each other bit for bit.
+// Every lane computes the (wave-uniform) step; lane 0 then issues all stores back to back, none of which depends on a load: pose (the start pose if the step was
+// rejected — with a restart that is what initialises the slot), last_delta (accepted steps only), gn_status, iters.
 // pub_key != 0: the resulting pose (the unchanged one if the step was rejected) is also PUBLISHED as seven keyed granules, kPubReplicas copies (lane l writes copy l), for
 // an association launch that is already running behind this kernel (wait_published_pose, option "overlap_gn").
 // `mirror` (optional): a page-locked copy of the slot's state as the device sees it — the lane that updates the pose writes pose and status there as well, so that a caller
 // whose next step is "read the pose" synchronises without a copy launch in between (lili_pipeline.hip; gn_status there stays at the host's sentinel if this function is
 // not reached).
-__device__ void gn_update_block(const double* gram /*LDS or global, 64+*/, SlotState* __restrict__ state, const double xq[4], unsigned long long pub_key = 0ull, double* pub = nullptr,
+template <bool LANES>
+__device__ void gn_update_block(const double* gram /*LDS or global, 64+*/, SlotState* __restrict__ state, const GnIn& in, unsigned long long pub_key = 0ull, double* pub = nullptr,
                                 SlotState* __restrict__ mirror = nullptr) {
     __shared__ double H[6][6];
     __shared__ double gvec[6];
     int tid = threadIdx.x & 63;
-    const double x0 = xq[0], x1 = xq[1], x2 = xq[2], x3 = xq[3];
+    const double x0 = in.pose[3], x1 = in.pose[4], x2 = in.pose[5], x3 = in.pose[6];
     // plus-Jacobian Jq (4x3) of ceres::QuaternionParameterization, rows [-x1 -x2 -x3; x0 x3 -x2; -x3 x0 x1; x2 -x1 x0]; every lane
     // builds the column(s) it needs in registers.  H = P^T G77 P and g = -P^T G7r with P = blockdiag(I3, Jq), evaluated as
     // M = G P (4-term sums, left to right) and H = P^T M exactly like round 1's three LDS-staged steps — one step now.
@@ -903,88 +1021,42 @@ __device__ void gn_update_block(const double* gram /*LDS or global, 64+*/, SlotS
         if (tid < 36) H[a][b] = v; else gvec[a] = -v;
     }
     LILI_WAVE_SYNC();
-    double pz[7] = {0, 0, 0, x0, x1, x2, x3};
+    double d[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) d[i] = gvec[i];
+    const bool okc = LANES ? ldlt6_solve_lanes(H, tid, d) : ldlt6_solve_lane0(H, d);
+    double pz[7] = {in.pose[0], in.pose[1], in.pose[2], x0, x1, x2, x3};
+    if (okc) {
+        pz[0] += d[0]; pz[1] += d[1]; pz[2] += d[2];
+        const double nd2 = d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
+        if (nd2 > 0.0) {
+            double sbd, cw;
+            if (nd2 < 0.25) sinc_cos_small(nd2, sbd, cw);
+            else { const double nd = sqrt(nd2); sbd = sin(nd) / nd; cw = cos(nd); }
+            dq qd{cw, sbd * d[3], sbd * d[4], sbd * d[5]};
+            dq r = qmul(qd, dq{x0, x1, x2, x3});
+            pz[3] = r.w; pz[4] = r.x; pz[5] = r.y; pz[6] = r.z;
+        }
+    }
     if (tid == 0) {
-        // 6x6 LDL^T solve entirely in registers (all indices are compile-time constants after unrolling): six dependent
-        // divisions (1/d_j) instead of the 6 square roots + 27 divisions of a Cholesky with per-element divides — the
-        // f64 divide / sqrt sequences dominated this kernel's critical path
-        double L[6][6], W[6][6], dinv[6], d[6];
+        const int status = okc ? 0 : 1;
 #pragma unroll
-        for (int i = 0; i < 6; i++) {
-            d[i] = gvec[i];
-#pragma unroll
-            for (int j = 0; j <= i; j++) L[i][j] = H[i][j];
-        }
-        bool okc = true;
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-            double dj = L[j][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) dj -= L[j][k] * W[j][k];     // W[j][k] = L[j][k] * d_k
-            if (!(dj > 0)) okc = false;
-            dinv[j] = 1.0 / dj;
-#pragma unroll
-            for (int i = j + 1; i < 6; i++) {
-                double sv = L[i][j];
-#pragma unroll
-                for (int k = 0; k < j; k++) sv -= L[i][k] * W[j][k];
-                W[i][j] = sv;
-                L[i][j] = sv * dinv[j];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 6; i++) {          // L z = g
-            double sv = d[i];
-#pragma unroll
-            for (int k = 0; k < i; k++) sv -= L[i][k] * d[k];
-            d[i] = sv;
-        }
-#pragma unroll
-        for (int i = 0; i < 6; i++) d[i] = d[i] * dinv[i];   // D y = z
-#pragma unroll
-        for (int i = 5; i >= 0; i--) {         // L^T x = y
-            double sv = d[i];
-#pragma unroll
-            for (int k = i + 1; k < 6; k++) sv -= L[k][i] * d[k];
-            d[i] = sv;
-        }
-#pragma unroll
-        for (int i = 0; i < 6; i++) if (!(d[i] == d[i])) okc = false;
-        if (pub_key) { pz[0] = state->pose[0]; pz[1] = state->pose[1]; pz[2] = state->pose[2]; }
+        for (int i = 0; i < 7; i++) state->pose[i] = pz[i];
         if (okc) {
-            if (pub_key) { pz[0] += d[0]; pz[1] += d[1]; pz[2] += d[2]; state->pose[0] = pz[0]; state->pose[1] = pz[1]; state->pose[2] = pz[2]; }
-            else if (mirror) {
-                const double p0 = state->pose[0] + d[0], p1 = state->pose[1] + d[1], p2 = state->pose[2] + d[2];
-                state->pose[0] = p0; state->pose[1] = p1; state->pose[2] = p2; mirror->pose[0] = p0; mirror->pose[1] = p1; mirror->pose[2] = p2;
-            } else { state->pose[0] += d[0]; state->pose[1] += d[1]; state->pose[2] += d[2]; }
-            const double nd2 = d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
-            if (nd2 > 0.0) {
-                double sbd, cw;
-                if (nd2 < 0.25) sinc_cos_small(nd2, sbd, cw);
-                else { const double nd = sqrt(nd2); sbd = sin(nd) / nd; cw = cos(nd); }
-                dq qd{cw, sbd * d[3], sbd * d[4], sbd * d[5]};
-                dq r = qmul(qd, dq{x0, x1, x2, x3});
-                state->pose[3] = r.w; state->pose[4] = r.x; state->pose[5] = r.y; state->pose[6] = r.z;
-                pz[3] = r.w; pz[4] = r.x; pz[5] = r.y; pz[6] = r.z;
-                if (mirror) { mirror->pose[3] = r.w; mirror->pose[4] = r.x; mirror->pose[5] = r.y; mirror->pose[6] = r.z; }
-            } else if (mirror) { mirror->pose[3] = x0; mirror->pose[4] = x1; mirror->pose[5] = x2; mirror->pose[6] = x3; }
 #pragma unroll
             for (int i = 0; i < 6; i++) state->last_delta[i] = d[i];
-            state->gn_status = 0;
-            if (mirror) mirror->gn_status = 0;
-        } else {
-            state->gn_status = 1;
-            if (mirror) { for (int i = 0; i < 3; i++) mirror->pose[i] = state->pose[i]; mirror->pose[3] = x0; mirror->pose[4] = x1; mirror->pose[5] = x2; mirror->pose[6] = x3; mirror->gn_status = 1; }
         }
-        state->iters += 1;
-    }
-    if (pub_key) {          // lane 0's result to every lane, then one copy per lane: 7 x 64 sixteen-byte write-through stores
+        state->gn_status = status;
+        state->iters = in.iters + 1;
+        if (mirror) {
 #pragma unroll
-        for (int k = 0; k < 7; k++) {
-            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)__double_as_longlong(pz[k]) & 0xffffffffull));
-            const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)__double_as_longlong(pz[k]) >> 32));
-            store_granule(pub + (size_t)tid * kPubStride + 2 * k, __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)), pub_key);
+            for (int i = 0; i < 7; i++) mirror->pose[i] = pz[i];
+            mirror->gn_status = status;
         }
+    }
+    if (pub_key) {          // the result to one copy per lane: 7 x 64 sixteen-byte write-through stores
+#pragma unroll
+        for (int k = 0; k < 7; k++) store_granule(pub + (size_t)tid * kPubStride + 2 * k, pz[k], pub_key);
     }
 }
 
@@ -1038,10 +1110,12 @@ __device__ __forceinline__ bool sum_partial_chunk(const double* part, int nb, in
 template <bool XCHG>
 __device__ __forceinline__ void reduce_partials_block(const double* part_surf, int nb_surf, const double* part_edge, int nb_edge,
                                                       double* __restrict__ out, SlotState* __restrict__ state, int do_gn, unsigned long long key, const P2PView& xv,
-                                                      unsigned long long pub_key, double* pub, SlotState* __restrict__ mirror) {
+                                                      unsigned long long pub_key, double* pub, SlotState* __restrict__ mirror, const SlotState* __restrict__ pose_src) {
     tstamp(state, do_gn, (int)blockIdx.x, 8);
     const unsigned long long was_dead = XCHG ? p2p_dead_word(xv) : 0ull;      // requested first: the round trip hides behind the partial loads
-    const double xq[4] = {state->pose[3], state->pose[4], state->pose[5], state->pose[6]};
+    // ... and everything the tail reads of the slots' states: no load of `state` after the first partial load
+    const GnIn gin = gn_load(state, pose_src);
+    const unsigned long long epoch0 = key ? state->epoch : 0ull;
     constexpr int kGroups = kReduceThreads / 40;   // 25 groups of 40 lanes, group g adds partials g, g+25, ...
     __shared__ double acc[kGroups][2][40];
     __shared__ double tri[40];
@@ -1073,7 +1147,7 @@ __device__ __forceinline__ void reduce_partials_block(const double* part_surf, i
         if (!key && nb_edge > 8 * kGroups) { for (int c = 0; c * 32 * kGroups < nb_edge; c++) sum_partial_wide(part_edge, nb_edge, c, g, e, kGroups, s2); }
         else for (int c = 0; c * 8 * kGroups < nb_edge && ok; c++) ok = sum_partial_chunk(part_edge, nb_edge, c, g, e, kGroups, key, s2);
         if (!ok) {           // uniform
-            if (threadIdx.x == 0) { state->gn_status = 2; state->epoch = state->epoch + 1ull; }
+            if (threadIdx.x == 0) { state->gn_status = 2; state->epoch = epoch0 + 1ull; }
             return;
         }
         if (g < kGroups) { acc[g][0][e] = s; acc[g][1][e] = s2; }
@@ -1109,18 +1183,19 @@ __device__ __forceinline__ void reduce_partials_block(const double* part_surf, i
     }
     out[lane] = full[lane];
     if (lane < 8) out[64 + lane] = full[64 + lane];
-    if (key && lane == 0) state->epoch = state->epoch + 1ull;      // the next fused launch of this slot gets a new key (stream order)
+    if (key && lane == 0) state->epoch = epoch0 + 1ull;      // the next fused launch of this slot gets a new key (stream order)
     if (lane == 0) state->cnt_word = 0ull;                          // re-arms the count barrier of k_associate_coop (the next association of this slot comes after this launch)
     tstamp(state, do_gn, (int)blockIdx.x, 10);
-    if (do_gn & 1) gn_update_block(full, state, xq, pub_key, pub, mirror);
+    if (do_gn & 1) gn_update_block<true>(full, state, gin, pub_key, pub, mirror);
     tstamp(state, do_gn, (int)blockIdx.x, 11);
 }
 
 __global__ __launch_bounds__(kReduceThreads) void k_reduce_partials(const double* __restrict__ part_surf, int nb_surf,
                                                             const double* __restrict__ part_edge, int nb_edge,
                                                             double* __restrict__ out, SlotState* __restrict__ state, int do_gn, P2PView v, unsigned long long pub_key, double* pub,
-                                                            SlotState* __restrict__ mirror /*page-locked copy of the pose and status for the host, or nullptr*/) {
-    reduce_partials_block<true>(part_surf, nb_surf, part_edge, nb_edge, out, state, do_gn, 0ull, v, pub_key, pub, mirror);
+                                                            SlotState* __restrict__ mirror /*page-locked copy of the pose and status for the host, or nullptr*/,
+                                                            const SlotState* __restrict__ pose_src /*the slot whose pose the step starts from (a restart), or nullptr = state*/) {
+    reduce_partials_block<true>(part_surf, nb_surf, part_edge, nb_edge, out, state, do_gn, 0ull, v, pub_key, pub, mirror, pose_src);
 }
 
 // ================================================================================================
@@ -1162,9 +1237,10 @@ __device__ __forceinline__ void reduce_partials_plain(const double* part_surf, i
 }
 __global__ __launch_bounds__(kReduceThreads) void k_window_reduce(WindowArgs w, double* __restrict__ out /*n x 72*/, int do_gn, P2PView v) {
     __shared__ double rec[kWindowMaxSlots * 72];
-    __shared__ double xq[kWindowMaxSlots][4];
+    __shared__ double pose0[kWindowMaxSlots][7];      // what the tail reads of the slots' states, requested before the partial loads
+    __shared__ int iters0[kWindowMaxSlots];
     const unsigned long long was_dead = p2p_dead_word(v);      // requested first: the round trip hides behind the partial loads
-    for (int i = 0; i < w.n; i++) if (threadIdx.x < 4) xq[i][threadIdx.x] = w.s[i].state->pose[3 + threadIdx.x];
+    for (int i = 0; i < w.n; i++) { if (threadIdx.x < 7) pose0[i][threadIdx.x] = w.s[i].state->pose[threadIdx.x]; else if (threadIdx.x == 7) iters0[i] = w.s[i].state->iters; }
     for (int i = 0; i < w.n; i++) reduce_partials_plain(w.s[i].part_surf, w.s[i].nb_surf, w.s[i].part_edge, w.s[i].nb_edge, rec + 72 * i);
     if (threadIdx.x >= 64) return;
     const int lane = threadIdx.x, count = 72 * w.n;
@@ -1178,13 +1254,30 @@ __global__ __launch_bounds__(kReduceThreads) void k_window_reduce(WindowArgs w, 
         LILI_WAVE_SYNC();
     }
     for (int i = lane; i < count; i += 64) out[i] = rec[i];
-    if (do_gn) for (int i = 0; i < w.n; i++) { gn_update_block(rec + 72 * i, w.s[i].state, xq[i]); LILI_WAVE_SYNC(); }
+    if (do_gn)
+#pragma unroll 1
+    for (int i = 0; i < w.n; i++) {
+        GnIn in;
+#pragma unroll
+        for (int k = 0; k < 7; k++) in.pose[k] = pose0[i][k];
+        in.iters = iters0[i];
+        gn_update_block<true>(rec + 72 * i, w.s[i].state, in);
+        LILI_WAVE_SYNC();
+    }
 }
 // the Gauss-Newton update of every slot from its (all-reduced) record: the generic-collective form of k_window_reduce's tail
 __global__ __launch_bounds__(64) void k_window_gn(WindowArgs w, const double* __restrict__ gram /*n x 72*/) {
+    __shared__ double pose0[kWindowMaxSlots][7];      // every slot's loads in flight at once, before the first update
+    __shared__ int iters0[kWindowMaxSlots];
+    for (int i = 0; i < w.n; i++) { if (threadIdx.x < 7) pose0[i][threadIdx.x] = w.s[i].state->pose[threadIdx.x]; else if (threadIdx.x == 7) iters0[i] = w.s[i].state->iters; }
+    LILI_WAVE_SYNC();
+#pragma unroll 1
     for (int i = 0; i < w.n; i++) {
-        const double xq[4] = {w.s[i].state->pose[3], w.s[i].state->pose[4], w.s[i].state->pose[5], w.s[i].state->pose[6]};
-        gn_update_block(gram + 72 * i, w.s[i].state, xq);
+        GnIn in;
+#pragma unroll
+        for (int k = 0; k < 7; k++) in.pose[k] = pose0[i][k];
+        in.iters = iters0[i];
+        gn_update_block<true>(gram + 72 * i, w.s[i].state, in);
         LILI_WAVE_SYNC();
     }
 }
@@ -1220,9 +1313,10 @@ __global__ void k_pose_copy(SlotState* __restrict__ dst, const SlotState* __rest
     if (threadIdx.x < 7) dst->pose[threadIdx.x] = src->pose[threadIdx.x];
 }
 
-__global__ void k_gn_update(const double* __restrict__ gram, SlotState* __restrict__ state) {
-    const double xq[4] = {state->pose[3], state->pose[4], state->pose[5], state->pose[6]};
-    gn_update_block(gram, state, xq);
+// pose_src: the slot whose pose the step starts from (the first step after a restart), or nullptr = state
+__global__ void k_gn_update(const double* __restrict__ gram, SlotState* __restrict__ state, const SlotState* __restrict__ pose_src) {
+    const GnIn in = gn_load(state, pose_src);
+    gn_update_block<false>(gram, state, in);
 }
 
 }  // namespace lili
