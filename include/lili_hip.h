@@ -39,7 +39,8 @@ enum {
     LILI_E_HIP = -2,      /* HIP runtime error (message in lili_last_error) */
     LILI_E_STATE = -3,    /* call order violated (e.g. associate before map_set) */
     LILI_E_NOMEM = -4,
-    LILI_E_NODEVICE = -5  /* no usable gfx950 device: there is no CPU fallback */
+    LILI_E_NODEVICE = -5, /* no usable gfx950 device: there is no CPU fallback */
+    LILI_E_NUMERIC = -6   /* a bounded iteration did not converge (lili_marg_schur, lili_window_marginalize); nothing was written */
 };
 enum { LILI_KIND_SURF = 0, LILI_KIND_EDGE = 1 };
 enum { LILI_MASK_SURF = 1, LILI_MASK_EDGE = 2 };
@@ -610,9 +611,10 @@ int lili_gram_to_factor(const double gram[64], double cost, double residuals[9],
  * with QuaternionParameterization, speed-bias[9] = v, ba, bg), the lidar blocks of every keyframe (the records of the slots' last association,
  * robustified by params->loss; correspondences stay fixed), one IMU factor between consecutive keyframes (ImuFactor.h:18-144), and either the
  * marginalisation prior (MarginalizationFactor::Evaluate) or the speed-bias priors (PriorFactor.h:13-23); the last three enter without a loss.
- * What stays with the caller: the IMU pre-integration, building the marginalisation prior (Schur complement, eigen-decomposition), the
- * write-back gates and the quaternion sign unification — their RESULTS are handed in as the plain arrays below (host memory, copied once per
- * call).  A state is n_kf x 16 doubles: t[3], q[4], speed-bias[9] per keyframe; "local" means 15 per keyframe: t, the 3 quaternion-plus
+ * The prior of the NEXT window (MarginalizationInfo::PreMarginalize + Marginalize: the factors again at the solved state, Schur complement over the
+ * oldest keyframe, two eigen-decompositions) is lili_window_marginalize below: a keyframe cycle is prepare -> solve -> marginalise.
+ * What stays with the caller: the IMU pre-integration, the write-back gates and the quaternion sign unification — their RESULTS are handed in as
+ * the plain arrays below (host memory, copied once per call).  A state is n_kf x 16 doubles: t[3], q[4], speed-bias[9] per keyframe; "local" means 15 per keyframe: t, the 3 quaternion-plus
  * coordinates, speed-bias. */
 #define LILI_WINDOW_MAX_KF 4          /* 15 * n_kf <= 60 local dimensions: every matrix of the solve stays in LDS */
 #define LILI_WINDOW_STATE_DOUBLES 16
@@ -656,6 +658,46 @@ int lili_window_solve(lili_ctx* ctx, const lili_window_problem* problem, const l
                       double* state, lili_lm_summary* summary);
 /* the final state of the last lili_window_solve of this context (n_kf x 16 doubles).  Blocking. */
 int lili_window_state_get(lili_ctx* ctx, int n_kf, double* state);
+
+/* ---- the window's next prior (MarginalizationInfo::Marginalize, L/src/MarginalizationFactor.cpp:128-202) ----
+ * Schur complement and square-root prior of a GIVEN system, MarginalizationFactor.cpp:176-201 in f64 on the device (one workgroup, everything in
+ * LDS): A is pos x pos (leading dimension ld, symmetric, 2 <= pos <= 60), b has pos entries, the first m dimensions (1 <= m < pos) go, n = pos - m.
+ *   Amm = (Amm + Amm^T) / 2, eigen-decomposition, pseudo-inverse with the reference's ABSOLUTE threshold 1e-8 (eigenvalues > 1e-8 are inverted, the
+ *   others become 0);  S = Arr - Arm Amm^+ Amr,  bs = brr - Arm Amm^+ bmm;  eigen-decomposition of S;  J0 = diag(sqrt(lambda+)) V^T (n x n row-major),
+ *   r0 = diag(sqrt(1 / lambda)+) V^T bs;  rows whose eigenvalue is <= 1e-8 are exactly zero;  *rank = the number of the others.
+ * The eigen-solver is a cyclic Jacobi method with fixed sums and a fixed order of rotations: two calls give identical bits.  Rows are ordered by
+ * ascending eigenvalue and each eigenvector has its largest-magnitude component positive (the first such on ties) — Eigen's order is the same, its
+ * signs are arbitrary; J0 and r0 are unique only up to an orthogonal transform of the rows, and nothing may depend on either choice (J0^T J0, J0^T r0,
+ * r0^T r0 and the rank do not).  Blocking, host pointers.  LILI_E_ARG (bad sizes, a null pointer, a non-finite entry) and LILI_E_NUMERIC (the sweep
+ * cap was reached) write nothing. */
+int lili_marg_schur(lili_ctx* ctx, const double* A, size_t ld, const double* b, int pos, int m, double* J0, double* r0, int* rank);
+
+/* A marginalisation prior with its storage: `prior` points into the arrays of the SAME object, so the object is not to be copied or moved once
+ * filled; &storage->prior goes to the next lili_window_solve / lili_window_evaluate as lili_window_problem::prior. */
+typedef struct lili_window_prior_storage {
+    lili_window_prior prior;
+    int32_t block_kind[3 * LILI_WINDOW_MAX_KF], block_keyframe[3 * LILI_WINDOW_MAX_KF];
+    int32_t rank;                     /* rows of J0 that are not zero */
+    int32_t sweeps_mm, sweeps_s;      /* Jacobi sweeps the two eigen-decompositions (Amm, Schur complement) took: diagnosis only */
+    int32_t reserved_;
+    double x0[LILI_WINDOW_STATE_DOUBLES * LILI_WINDOW_MAX_KF];
+    double r0[15 * LILI_WINDOW_MAX_KF];
+    double J0[15 * LILI_WINDOW_MAX_KF * 15 * LILI_WINDOW_MAX_KF];
+} lili_window_prior_storage;
+/* The prior of the next window from this window's problem and its solved `state` (n_kf x 16): what PreMarginalize + Marginalize leave in
+ * last_marginalization_info (L/src/BackendFusion.cpp:1009-1184).  Exactly the reference's factor set is evaluated at `state`, correspondences fixed,
+ * every quaternion block by the LAST THREE of its four global columns (MarginalizationFactor.cpp:9-17):
+ *   problem->prior, if present (MarginalizationFactor::Evaluate);  a speed-bias prior for every row of problem->sb_prior that is present, with the
+ *   mean as given;  the IMU factor between keyframes 0 and 1 ONLY (further entries of problem->imu are ignored, as in the reference);  the lidar
+ *   blocks of every keyframe, kinds problem->kind_mask, linearised at `state` by the launches of lili_window_evaluate.
+ * Keyframe 0's blocks are marginalised; the blocks of the later keyframes that at least one factor touches are kept, in (keyframe, kind) order —
+ * with the reference's set and n_kf = 3 the last keyframe's speed-bias is touched by nothing and is no block of the prior (21 columns).  `out` lists
+ * each kept block with its keyframe index SHIFTED BY -1 (addr_shift, L:1170-1177: the next window's numbering) and x0 = its value in `state`;
+ * n_rows = n_cols, rows beyond out->rank are zero.  The lidar launches, then one single-workgroup launch (assembly + the code of lili_marg_schur);
+ * blocking, one synchronisation.  Refusals — those of lili_window_evaluate, a state that is not finite, no factor on keyframe 0 or on the others,
+ * LILI_E_NUMERIC — leave `out` and the slots' poses untouched. */
+int lili_window_marginalize(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const double* state,
+                            lili_window_prior_storage* out);
 
 /* ---- callers / data formats either side of the path ------------------------- */
 

@@ -97,6 +97,12 @@ class WindowPrior(C.Structure):
                 ("block_keyframe", C.POINTER(C.c_int32)), ("x0", C.POINTER(C.c_double)), ("J0", C.POINTER(C.c_double)), ("r0", C.POINTER(C.c_double))]
 
 
+class WindowPriorStorage(C.Structure):
+    """lili_window_prior_storage: `prior` points into the arrays of the same object (do not copy it once filled)."""
+    _fields_ = [("prior", WindowPrior), ("block_kind", C.c_int32 * 12), ("block_keyframe", C.c_int32 * 12), ("rank", C.c_int32), ("sweeps_mm", C.c_int32), ("sweeps_s", C.c_int32), ("reserved_", C.c_int32),
+                ("x0", C.c_double * 64), ("r0", C.c_double * 60), ("J0", C.c_double * 3600)]
+
+
 class WindowProblem(C.Structure):
     _fields_ = [("n_kf", C.c_int32), ("kind_mask", C.c_int32), ("slots", C.POINTER(C.c_int32)), ("imu", C.POINTER(WindowImu)), ("prior", C.POINTER(WindowPrior)),
                 ("sb_prior", C.POINTER(C.c_double)), ("q_lb", C.c_double * 4), ("t_lb", C.c_double * 3)]
@@ -280,6 +286,8 @@ _SIGS = {
     "lili_window_evaluate": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_window_solve": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.POINTER(LmOptions), C.c_void_p, C.POINTER(LmSummary)]),
     "lili_window_state_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "lili_marg_schur": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "lili_window_marginalize": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.c_void_p, C.POINTER(WindowPriorStorage)]),
 }
 
 
@@ -1115,6 +1123,37 @@ class WindowSolver:
         s = np.zeros((self.problem.n_kf, 16))
         self.ctx._chk(self.lib.lili_window_state_get(self.ctx.h, self.problem.n_kf, _ptr(s)))
         return s
+
+    def marginalize(self, state, storage=None):
+        """The NEXT window's prior from this problem at the solved `state` (lili_window_marginalize: keyframe 0 marginalised, the reference's factor
+        set): the dict set_problem(prior=...) takes — block_kind, block_keyframe (already in the next window's numbering), x0 (list per block), J0, r0 —
+        plus rank and sweeps (of the two Jacobi decompositions).  storage: a WindowPriorStorage of the caller's to fill (its .prior is the C view); untouched when the call is refused."""
+        s = self._state(state)
+        st = storage if storage is not None else WindowPriorStorage()
+        self.ctx._chk(self.lib.lili_window_marginalize(self.ctx.h, C.byref(self.problem), C.byref(self.matcher.params), _ptr(s), C.byref(st)))
+        n, nb = st.prior.n_cols, st.prior.n_blocks
+        kind = [int(st.block_kind[b]) for b in range(nb)]
+        x0_all, x0, off = np.array(st.x0[:], np.float64), [], 0
+        for k in kind:
+            gs = (3, 4, 9)[k]
+            x0.append(x0_all[off:off + gs].copy())
+            off += gs
+        return dict(block_kind=kind, block_keyframe=[int(st.block_keyframe[b]) for b in range(nb)], x0=x0,
+                    J0=np.array(st.J0[:n * n], np.float64).reshape(n, n), r0=np.array(st.r0[:n], np.float64), rank=int(st.rank), sweeps=(int(st.sweeps_mm), int(st.sweeps_s)))
+
+
+def marg_schur(ctx, A, b, m):
+    """(J0 (n, n), r0 (n), rank) of lili_marg_schur: the first m dimensions of the symmetric system A (pos, pos), b are marginalised on the device, n = pos - m
+    (MarginalizationFactor.cpp:176-201).  Only J0^T J0, J0^T r0, r0^T r0 and the rank are independent of the eigenvector basis."""
+    A = np.ascontiguousarray(A, np.float64)
+    b = np.ascontiguousarray(b, np.float64).reshape(-1)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or b.shape[0] != A.shape[0]:
+        raise LiliError("marg_schur: A must be square and b as long")
+    pos, m = A.shape[0], int(m)
+    n = max(pos - m, 0) if m >= 0 else 0
+    J0, r0, rank = np.full((n, n), np.nan), np.full(n, np.nan), C.c_int(-1)
+    ctx._chk(ctx.lib.lili_marg_schur(ctx.h, _ptr(A), pos, _ptr(b), pos, m, _ptr(J0) if n else None, _ptr(r0) if n else None, C.byref(rank)))
+    return J0, r0, rank.value
 
 
 def gn_step_host(gram, t, q):

@@ -141,6 +141,7 @@ struct lili_ctx {
     DevBuf win_rec;      // lili_s2m_linearize_window: the n x LILI_GRAM_DOUBLES records of one evaluation of the window (k_window_reduce's output)
     DevBuf win_prob, win_out;   // lili_window_evaluate / lili_window_solve: the uploaded problem block; cost, gradient, J^T J or the final state + summary
     std::vector<unsigned char> win_host;   // the problem block as the host packs it
+    DevBuf win_marg, win_marg_in;   // lili_window_marginalize / lili_marg_schur: the kernel's output (status, rank, r0, J0); the uploaded host system of lili_marg_schur
     DevBuf win_counts;   // lili_s2m_associate_window: [surf, edge] counts of every slot (k_window_counts' output)
     DevBuf misc;         // bbox words etc.
     // Small device-to-host reads (counts, boxes, states) land in a page-locked scratch and are copied out after the synchronisation: a D2H into

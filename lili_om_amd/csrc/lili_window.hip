@@ -13,11 +13,17 @@
 //                          is broadcast.  Partial buffers are double-buffered by the evaluation's parity as in k_solve_lm; every wait is bounded
 //                          (xchg_gather) and ends the launch with LILI_LM_STALLED.
 //
+//   lili_window_marginalize  the NEXT window's prior (MarginalizationInfo::PreMarginalize + Marginalize, L/src/BackendFusion.cpp:1009-1184): the lidar launches of
+//                          lili_window_evaluate, then k_window_marg (ONE workgroup): win_build<true> forms the reference's factor set with the "last three columns"
+//                          convention, marg_schur takes the Schur complement over keyframe 0 and the square-root form through two Jacobi eigen-decompositions
+//                          in LDS.  lili_marg_schur uploads a host system into the same kernel.
+//
 // The factors are restated from the semantics SURVEY records; the checker's restatement (tests/test_window_solve_gpu.py) is the referee.
 #include "lili_s2m_dev.h"
 #include "lili_launch.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 namespace lili {
@@ -88,7 +94,9 @@ __device__ __forceinline__ d3 m3v(const double* m, d3 v) {
 }
 __device__ __forceinline__ double d3c(d3 v, int i) { return i == 0 ? v.x : i == 1 ? v.y : v.z; }
 
-// ImuFactor::Evaluate of ONE factor by ONE lane, un-whitened, Jacobians in local coordinates: J[15][31] (zeroed by the caller), column 30 = residual
+// ImuFactor::Evaluate of ONE factor by ONE lane, un-whitened, Jacobians in local coordinates: J[15][31] (zeroed by the caller), column 30 = residual.
+// kLast3: the quaternion blocks enter by the last three of their four global columns (MarginalizationFactor.cpp:9-17) instead of through Ceres' plus-Jacobian
+template <bool kLast3>
 __device__ __noinline__ void win_imu_raw(const WinImuDev& f, const double* xi, const double* xj, double (*J)[31]) {
     const d3 Pi{xi[0], xi[1], xi[2]}, Pj{xj[0], xj[1], xj[2]};
     const dq Qi = qnormalized(dq{xi[3], xi[4], xi[5], xi[6]}), Qj = qnormalized(dq{xj[3], xj[4], xj[5], xj[6]});
@@ -131,8 +139,10 @@ __device__ __noinline__ void win_imu_raw(const WinImuDev& f, const double* xi, c
                 m[i][1 + c] = 2.0 * ((((i == c ? uv : 0.0) + d3c(u, i) * d3c(v, c)) - d3c(v, i) * d3c(u, c)) - Qi.w * sk);
             }
         }
-        for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++)
-            J[r0 + i][3 + c] = ((m[i][0] * Pq_i[0][c] + m[i][1] * Pq_i[1][c]) + m[i][2] * Pq_i[2][c]) + m[i][3] * Pq_i[3][c];
+        for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++) {
+            if constexpr (kLast3) J[r0 + i][3 + c] = m[i][1 + c];
+            else J[r0 + i][3 + c] = ((m[i][0] * Pq_i[0][c] + m[i][1] * Pq_i[1][c]) + m[i][2] * Pq_i[2][c]) + m[i][3] * Pq_i[3][c];
+        }
     };
     dq_block(tmp, 0);
     dq_block(tmp1, 6);
@@ -159,7 +169,10 @@ __device__ __noinline__ void win_imu_raw(const WinImuDev& f, const double* xi, c
         for (int i = 0; i < 3; i++) {
             double m[4];
             for (int c = 0; c < 4; c++) m[c] = -2.0 * (((L[i][0] * R[0][c] + L[i][1] * R[1][c]) + L[i][2] * R[2][c]) + L[i][3] * R[3][c]);
-            for (int c = 0; c < 3; c++) J[3 + i][3 + c] = ((m[0] * Pq_i[0][c] + m[1] * Pq_i[1][c]) + m[2] * Pq_i[2][c]) + m[3] * Pq_i[3][c];
+            for (int c = 0; c < 3; c++) {
+                if constexpr (kLast3) J[3 + i][3 + c] = m[1 + c];
+                else J[3 + i][3 + c] = ((m[0] * Pq_i[0][c] + m[1] * Pq_i[1][c]) + m[2] * Pq_i[2][c]) + m[3] * Pq_i[3][c];
+            }
         }
     }
     {   // d r_q / d Bgi = -LeftQuatMatrix(Qj^-1 Qi cq)[0:3, 0:3] dq_dbg,  [0:3, 0:3] = w I + [v]x
@@ -171,13 +184,17 @@ __device__ __noinline__ void win_imu_raw(const WinImuDev& f, const double* xi, c
     {   // d r_q / d Qj = 2 Qleft(cq^-1 Qi^-1) rows 1..3, times the plus-Jacobian of Qj
         double L[3][4];
         qleft_rows(qmul(qinv(cq), Qi_inv), L);
-        for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++)
-            J[3 + i][18 + c] = 2.0 * (((L[i][0] * Pq_j[0][c] + L[i][1] * Pq_j[1][c]) + L[i][2] * Pq_j[2][c]) + L[i][3] * Pq_j[3][c]);
+        for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++) {
+            if constexpr (kLast3) J[3 + i][18 + c] = 2.0 * L[i][1 + c];
+            else J[3 + i][18 + c] = 2.0 * (((L[i][0] * Pq_j[0][c] + L[i][1] * Pq_j[1][c]) + L[i][2] * Pq_j[2][c]) + L[i][3] * Pq_j[3][c]);
+        }
     }
 }
 
 // MarginalizationFactor::Evaluate, block b by ONE lane: dx of the block, and for a quaternion block T = +-2 Qleft(q0^-1)[1:4, :] * plus(q) — the reference's own
-// Jacobian of dx in global columns times Ceres' plus-Jacobian, not the derivative of the normalised expression
+// Jacobian of dx in global columns times Ceres' plus-Jacobian, not the derivative of the normalised expression.  kLast3: the last three of those four
+// global columns instead (what MarginalizationInfo takes of every quaternion block)
+template <bool kLast3>
 __device__ __noinline__ void win_prior_block(const WinDev* pb, WinSys& s, int b) {
     const int kind = pb->blk_kind[b], kf = pb->blk_kf[b], col = pb->blk_col[b];
     const double* x0 = pb->x0 + pb->blk_x0[b];
@@ -192,17 +209,22 @@ __device__ __noinline__ void win_prior_block(const WinDev* pb, WinSys& s, int b)
         double L[3][4], Pq[4][3];
         qleft_rows(q0i, L);
         plus_jac(&s.x[kf][3], Pq);
-        for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++)
-            s.T[b][3 * i + c] = sg * (((L[i][0] * Pq[0][c] + L[i][1] * Pq[1][c]) + L[i][2] * Pq[2][c]) + L[i][3] * Pq[3][c]);
+        for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++) {
+            if constexpr (kLast3) s.T[b][3 * i + c] = sg * L[i][1 + c];
+            else s.T[b][3 * i + c] = sg * (((L[i][0] * Pq[0][c] + L[i][1] * Pq[1][c]) + L[i][2] * Pq[2][c]) + L[i][3] * Pq[3][c]);
+        }
     }
 }
 __device__ __forceinline__ int win_blk_local(const WinDev* pb, int b) { return 15 * pb->blk_kf[b] + (pb->blk_kind[b] == 0 ? 0 : pb->blk_kind[b] == 1 ? 3 : 6); }
 
 // The local system of the window at s.x by ONE wave (all 64 lanes call it, control flow uniform): s.H = J^T J, s.g = J^T r, s.cost.  Every sum runs in a
 // fixed order, so every workgroup of the solve holds the same bits.
+// kMarg: the system MarginalizationInfo::PreMarginalize + ThreadsConstructA form at s.x instead (L/src/BackendFusion.cpp:1009-1165) — every quaternion block by the
+// last three of its four global columns, and of the IMU factors only the one between keyframes 0 and 1; s.cost is then without meaning.
+template <bool kMarg>
 __device__ __noinline__ void win_build(const WinDev* __restrict__ pb, WinSys& s) {
     const int lane = threadIdx.x & 63;
-    const int n_kf = pb->n_kf, N = 15 * n_kf, n_imu = pb->n_imu;
+    const int n_kf = pb->n_kf, N = 15 * n_kf, n_imu = kMarg ? (pb->n_imu < 1 ? pb->n_imu : 1) : pb->n_imu;
     for (int e = lane; e < N * N; e += 64) s.H[e] = 0.0;
     if (lane < N) s.g[lane] = 0.0;
     for (int e = lane; e < n_imu * 15 * 31; e += 64) (&s.Jraw[0][0][0])[e] = 0.0;
@@ -228,7 +250,8 @@ __device__ __noinline__ void win_build(const WinDev* __restrict__ pb, WinSys& s)
                 return ((gram[i * 8 + 3] * jb[0] + gram[i * 8 + 4] * jb[1]) + gram[i * 8 + 5] * jb[2]) + gram[i * 8 + 6] * jb[3];
             };
             double v;
-            if (a < 3) v = Mrow(a);
+            if constexpr (kMarg) v = gram[(a < 3 ? a : a + 1) * 8 + (b < 3 || b == 7 ? b : b + 1)];      // rows / columns {0,1,2}, {4,5,6} and column 7, as lili_marg_add_lidar takes them
+            else if (a < 3) v = Mrow(a);
             else v = ((ja[0] * Mrow(3) + ja[1] * Mrow(4)) + ja[2] * Mrow(5)) + ja[3] * Mrow(6);
             if (lane < 36) s.H[(15 * k + a) * N + 15 * k + b] = v; else s.g[15 * k + a] = v;
         }
@@ -247,7 +270,7 @@ __device__ __noinline__ void win_build(const WinDev* __restrict__ pb, WinSys& s)
         s.pr[lane] = r;
     }
     // ---- IMU factors, raw: one lane per factor
-    if (lane < n_imu) win_imu_raw(pb->imu[lane], s.x[lane], s.x[lane + 1], s.Jraw[lane]);
+    if (lane < n_imu) win_imu_raw<kMarg>(pb->imu[lane], s.x[lane], s.x[lane + 1], s.Jraw[lane]);
     LILI_WAVE_SYNC();
     {
         double c = 0.0;
@@ -283,7 +306,7 @@ __device__ __noinline__ void win_build(const WinDev* __restrict__ pb, WinSys& s)
     if (pb->has_prior) {
         const int n_rows = pb->n_rows, n_cols = pb->n_cols, n_blocks = pb->n_blocks;
         LILI_WAVE_SYNC();
-        if (lane < n_blocks) win_prior_block(pb, s, lane);
+        if (lane < n_blocks) win_prior_block<kMarg>(pb, s, lane);
         LILI_WAVE_SYNC();
         if (lane < n_rows) {
             double r = pb->r0[lane];
@@ -337,7 +360,7 @@ __global__ __launch_bounds__(64) void k_window_evaluate(const WinDev* __restrict
     for (int e = lane; e < 16 * n_kf; e += 64) s.x[e / 16][e % 16] = pb->state[e];
     for (int e = lane; e < 72 * n_kf; e += 64) s.lid[e / 72][e % 72] = rec ? rec[e] : 0.0;
     LILI_WAVE_SYNC();
-    win_build(pb, s);
+    win_build<false>(pb, s);
     if (lane == 0) out[0] = s.cost;
     if (lane < N) out[1 + lane] = s.g[lane];
     if (want_h) for (int e = lane; e < N * N; e += 64) out[1 + N + e] = s.H[e];
@@ -528,7 +551,7 @@ __global__ __launch_bounds__(kWinThreads) void k_window_solve(WinSolveArgs W, Ma
                 if (lane == 0) sh.sys.lid[k][64] = sh.tot[k][36];
             }
             LILI_WAVE_SYNC();
-            win_build(pb, sh.sys);
+            win_build<false>(pb, sh.sys);
             // ---- step logic, identical in every workgroup
             if (eval == 0) {
                 for (int e = threadIdx.x; e < N * N; e += 64) sh.H[e] = sh.sys.H[e];
@@ -596,6 +619,216 @@ __global__ __launch_bounds__(kWinThreads) void k_window_solve(WinSolveArgs W, Ma
             W.summary->n_surf = sh.counts[0]; W.summary->n_edge = sh.counts[1];
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The window's next prior (include/lili_hip.h: lili_marg_schur, lili_window_marginalize): MarginalizationInfo::Marginalize
+// (L/src/MarginalizationFactor.cpp:176-201) in f64 by ONE workgroup — no other workgroup exists, nothing is waited for, every loop is bounded.
+//   k_window_marg   wave 0 forms the system of the reference's factor set at the solved state (win_build<true>) and the workgroup picks the touched columns,
+//                   or the workgroup loads a system the host uploaded (lili_marg_schur); then marg_schur: Amm = (Amm + Amm^T) / 2, its eigen-decomposition,
+//                   the pseudo-inverse with the ABSOLUTE threshold 1e-8, the Schur complement, its eigen-decomposition, J0 = sqrt(S) V^T, r0 = sqrt(S^-1) V^T b.
+//   marg_jacobi     the eigen-solver: cyclic two-sided Jacobi, parallel round-robin ordering (n - 1 rounds of n / 2 disjoint pairs per sweep).  A round
+//                   writes every entry of J^T A J from the previous round's matrix into a second buffer (upper triangle computed, mirrored: the matrix stays
+//                   symmetric bit for bit), so nothing in it depends on which wave runs first; sums and the order of rotations are fixed: two calls give
+//                   the same bits.  At most kMargMaxSweeps sweeps; a cap that is reached is reported and nothing is written.
+// LDS: the assembly's WinSys (49 288 B; its H is the eigen-solver's second buffer afterwards) + three 60 x 60 f64 matrices (system, matrix under rotation,
+// eigenvectors: 3 x 28 800 B) + 3 840 B of vectors = 139 528 B = 136.3 KiB of the CU's 160 KiB: one workgroup per CU, which is all this launch has.
+// Rows come out by ascending eigenvalue, each eigenvector with its largest-magnitude component positive (the first one on ties); nothing may depend on either.
+constexpr int kMargThreads = 256;
+constexpr int kMargMaxSweeps = 30;            // f64 Jacobi converges quadratically: 4 .. 6 sweeps per decomposition measured on the harness windows (reported in lili_window_prior_storage)
+constexpr double kMargEps = 1e-8;             // MarginalizationInfo::eps
+// converged: sum of squares above the diagonal <= (1e-20)^2 x the matrix' squared Frobenius norm.  Far below the rounding of the diagonal on purpose: what is left
+// above the diagonal turns the eigenvectors by (entry / eigenvalue gap), and the gaps here are small against the norm (eigenvalues 2e2 beside 5e7, clusters such as a
+// ninefold 225) — at 1e-20 no gap above 1e-4 of an ulp of the norm matters.  Reachable because annihilated entries are set to exactly 0 and the others only ever shrink
+// quadratically; it costs at most one sweep over a bound of 1e-32.
+constexpr double kMargTol2 = 1e-40;
+
+struct MargArgs { int pos, m; int sel[kWinMaxN]; };      // window mode: column sel[i] of the 15 n_kf local columns is dimension i of the system (dropped first)
+struct MargOut {
+    int status /* 0, 1 = sweep cap reached */, rank, sweeps[2];
+    double r0[kWinMaxN];
+    double J0[kWinMaxN * kWinMaxN];           // n x n, tight
+};
+struct MargShared {
+    WinSys sys;
+    double A[kWinMaxN * kWinMaxN], M[kWinMaxN * kWinMaxN], V[kWinMaxN * kWinMaxN];
+    double b[kWinMaxN], w[kWinMaxN], bs[kWinMaxN], red[kWinMaxN];
+    double cs[kWinMaxN], bt[kWinMaxN], dd[kWinMaxN];      // this round, per index: cosine, coefficient of the partner's row / column, change of the diagonal entry
+    int partner[kWinMaxN], pp[kWinMaxN / 2], qq[kWinMaxN / 2];
+};
+
+// sum of squares of the n x n matrix A (or of its part above the diagonal) in a fixed order; every thread returns the same bits
+__device__ __forceinline__ double marg_sumsq(MargShared& sh, const double* A, const int n, const bool upper) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    if (tid < n) {
+        double v = 0.0;
+        for (int j = upper ? tid + 1 : 0; j < n; j++) v += A[tid * n + j] * A[tid * n + j];
+        sh.red[tid] = v;
+    }
+    __syncthreads();
+    double t = 0.0;
+    for (int i = 0; i < n; i++) t += sh.red[i];
+    return t;
+}
+
+// Eigen-decomposition of the symmetric n x n matrix in A0 (tight) by the whole workgroup: on return A0 holds the rotated matrix (eigenvalues on its diagonal),
+// V the eigenvectors as columns; A1 is scratch of the same size.  Returns the number of sweeps, or -1 when kMargMaxSweeps did not suffice (uniform).
+__device__ __noinline__ int marg_jacobi(MargShared& sh, double* A0, double* A1, double* V, const int n) {
+    const int tid = threadIdx.x;
+    const int np = n + (n & 1), hp = np >> 1;      // an odd n plays with a bye: the pair that holds index n rests
+    for (int e = tid; e < n * n; e += kMargThreads) V[e] = (e / n == e % n) ? 1.0 : 0.0;
+    double* cur = A0;
+    double* nxt = A1;
+    const double tot2 = marg_sumsq(sh, cur, n, false);
+    int sweeps = -1;
+    for (int sweep = 0; sweep <= kMargMaxSweeps; sweep++) {
+        const double off2 = marg_sumsq(sh, cur, n, true);
+        if (off2 <= kMargTol2 * tot2) { sweeps = sweep; break; }
+        if (sweep == kMargMaxSweeps) break;
+        for (int r = 0; r < np - 1; r++) {
+            // ---- the round's pairs (circle method: index np - 1 stays, the others turn) and their rotations, from the matrix as the last round left it
+            if (tid < hp) {
+                const int a = tid == 0 ? r : (r + tid) % (np - 1), b = tid == 0 ? np - 1 : (r + (np - 1) - tid) % (np - 1);
+                const int p = a < b ? a : b, q = a < b ? b : a;
+                double c = 1.0, s = 0.0, d = 0.0;
+                bool rot = false;
+                if (q < n) {
+                    const double apq = cur[p * n + q];
+                    if (apq != 0.0) {
+                        const double th = (cur[q * n + q] - cur[p * n + p]) / (2.0 * apq);
+                        const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+                        c = 1.0 / sqrt(t * t + 1.0); s = t * c; d = t * apq; rot = true;
+                    }
+                    sh.cs[q] = c; sh.bt[q] = s; sh.dd[q] = d; sh.partner[q] = p;
+                }
+                sh.cs[p] = c; sh.bt[p] = -s; sh.dd[p] = -d; sh.partner[p] = q < n ? q : p;
+                sh.pp[tid] = p; sh.qq[tid] = rot ? q : -1;
+            }
+            __syncthreads();
+            // ---- J^T A J, entry by entry: new row / column i = cs[i] * old i + bt[i] * old partner[i]
+            for (int e = tid; e < n * n; e += kMargThreads) {
+                const int i = e / n, j = e - i * n;
+                if (i > j) continue;
+                const int pi = sh.partner[i], pj = sh.partner[j];
+                double v;
+                if (i == j) v = cur[e] + sh.dd[i];          // a_pp - t a_pq, a_qq + t a_pq
+                else if (pi == j) v = 0.0;                  // the entry the rotation annihilates
+                else {
+                    const double ci = sh.cs[i], bi = sh.bt[i], cj = sh.cs[j], bj = sh.bt[j];
+                    v = ci * (cj * cur[i * n + j] + bj * cur[i * n + pj]) + bi * (cj * cur[pi * n + j] + bj * cur[pi * n + pj]);
+                }
+                nxt[i * n + j] = v; nxt[j * n + i] = v;
+            }
+            // ---- V J: both columns of a pair by one thread per row
+            for (int e = tid; e < n * hp; e += kMargThreads) {
+                const int i = e / hp, k = e - i * hp;
+                const int q = sh.qq[k];
+                if (q < 0) continue;
+                const int p = sh.pp[k];
+                const double c = sh.cs[p], s = sh.bt[q], vp = V[i * n + p], vq = V[i * n + q];
+                V[i * n + p] = c * vp - s * vq; V[i * n + q] = s * vp + c * vq;
+            }
+            __syncthreads();
+            double* t = cur; cur = nxt; nxt = t;
+        }
+    }
+    if (cur != A0) {
+        __syncthreads();
+        for (int e = tid; e < n * n; e += kMargThreads) A0[e] = cur[e];
+    }
+    __syncthreads();
+    return sweeps;
+}
+
+// MarginalizationFactor.cpp:176-201 on sh.A (pos x pos, tight), sh.b: the first m dimensions go.  `work`: pos x pos doubles of scratch.
+__device__ __noinline__ void marg_schur(MargShared& sh, double* work, const int pos, const int m, MargOut* __restrict__ out) {
+    const int tid = threadIdx.x;
+    const int n = pos - m;
+    const double* A = sh.A;
+    double* M = sh.M;
+    double* V = sh.V;
+    for (int e = tid; e < m * m; e += kMargThreads) { const int i = e / m, j = e - i * m; M[e] = 0.5 * (A[i * pos + j] + A[j * pos + i]); }
+    const int sw1 = marg_jacobi(sh, M, work, V, m);
+    if (sw1 < 0) { if (tid == 0) { out->status = 1; out->rank = 0; out->sweeps[0] = sw1; out->sweeps[1] = 0; } return; }
+    if (tid < m) { const double l = M[tid * m + tid]; sh.w[tid] = l > kMargEps ? 1.0 / l : 0.0; }
+    __syncthreads();
+    for (int e = tid; e < m * m; e += kMargThreads) {                  // Amm^+ = V diag(1 / lambda, 0 where lambda <= eps) V^T
+        const int i = e / m, j = e - i * m;
+        double v = 0.0;
+        for (int k = 0; k < m; k++) v += (V[i * m + k] * sh.w[k]) * V[j * m + k];
+        M[e] = v;
+    }
+    __syncthreads();
+    double* W = work;                                                   // Amm^+ [Amr | bmm], m x (n + 1)
+    for (int e = tid; e < m * (n + 1); e += kMargThreads) {
+        const int i = e / (n + 1), c = e - i * (n + 1);
+        double v = 0.0;
+        for (int j = 0; j < m; j++) v += M[i * m + j] * (c < n ? A[j * pos + m + c] : sh.b[j]);
+        W[e] = v;
+    }
+    __syncthreads();
+    for (int e = tid; e < n * n; e += kMargThreads) {                  // S = Arr - Arm Amm^+ Amr: the lower triangle, mirrored (an eigen-solver reads one triangle)
+        const int i = e / n, j = e - i * n;
+        if (i < j) continue;
+        double v = 0.0;
+        for (int k = 0; k < m; k++) v += A[(m + i) * pos + k] * W[k * (n + 1) + j];
+        v = A[(m + i) * pos + m + j] - v;
+        M[i * n + j] = v; M[j * n + i] = v;
+    }
+    if (tid < n) {
+        double v = 0.0;
+        for (int k = 0; k < m; k++) v += A[(m + tid) * pos + k] * W[k * (n + 1) + n];
+        sh.bs[tid] = sh.b[m + tid] - v;
+    }
+    const int sw2 = marg_jacobi(sh, M, work, V, n);
+    if (sw2 < 0) { if (tid == 0) { out->status = 1; out->rank = 0; out->sweeps[0] = sw1; out->sweeps[1] = sw2; } return; }
+    if (tid < n) sh.w[tid] = M[tid * n + tid];
+    __syncthreads();
+    if (tid < n) {
+        const double l = sh.w[tid];
+        int row = 0, big = 0;
+        for (int j = 0; j < n; j++) row += (sh.w[j] < l || (sh.w[j] == l && j < tid)) ? 1 : 0;      // ascending eigenvalue, ties by index
+        for (int c = 1; c < n; c++) if (fabs(V[c * n + tid]) > fabs(V[big * n + tid])) big = c;
+        const double sg = V[big * n + tid] < 0.0 ? -1.0 : 1.0;
+        const bool keep = l > kMargEps;
+        const double sq = keep ? sqrt(l) : 0.0, sqi = keep ? sqrt(1.0 / l) : 0.0;
+        double d = 0.0;
+        for (int c = 0; c < n; c++) d += (sg * V[c * n + tid]) * sh.bs[c];
+        out->r0[row] = keep ? sqi * d : 0.0;
+        for (int c = 0; c < n; c++) out->J0[row * n + c] = keep ? sq * (sg * V[c * n + tid]) : 0.0;
+    }
+    if (tid == 0) {
+        int rank = 0;
+        for (int j = 0; j < n; j++) rank += sh.w[j] > kMargEps ? 1 : 0;
+        out->status = 0; out->rank = rank; out->sweeps[0] = sw1; out->sweeps[1] = sw2;
+    }
+}
+
+// pb != nullptr: the window's system at pb->state (rec: the n_kf lidar records of k_window_reduce, or nullptr), dimensions a.sel; pb == nullptr: the system
+// the host uploaded (sys_in: pos x pos tight, then b).  One workgroup.
+__global__ __launch_bounds__(kMargThreads) void k_window_marg(const WinDev* __restrict__ pb, const double* __restrict__ rec, const double* __restrict__ sys_in, MargArgs a,
+                                                              MargOut* __restrict__ out) {
+    __shared__ MargShared sh;
+    const int tid = threadIdx.x;
+    const int pos = a.pos;
+    if (pb) {
+        const int n_kf = pb->n_kf, N = 15 * n_kf;
+        if (tid < 64) {
+            for (int e = tid; e < 16 * n_kf; e += 64) sh.sys.x[e / 16][e % 16] = pb->state[e];
+            for (int e = tid; e < 72 * n_kf; e += 64) sh.sys.lid[e / 72][e % 72] = rec ? rec[e] : 0.0;
+            LILI_WAVE_SYNC();
+            win_build<true>(pb, sh.sys);
+        }
+        __syncthreads();
+        for (int e = tid; e < pos * pos; e += kMargThreads) { const int i = e / pos, j = e - i * pos; sh.A[e] = sh.sys.H[a.sel[i] * N + a.sel[j]]; }
+        if (tid < pos) sh.b[tid] = sh.sys.g[a.sel[tid]];
+    } else {
+        for (int e = tid; e < pos * pos; e += kMargThreads) sh.A[e] = sys_in[e];
+        if (tid < pos) sh.b[tid] = sys_in[pos * pos + tid];
+    }
+    __syncthreads();
+    marg_schur(sh, sh.sys.H, pos, a.m, out);
 }
 
 }  // namespace lili
@@ -716,6 +949,20 @@ static lili_s2m_params window_params(const lili_window_problem* pr, const lili_s
     return p;
 }
 
+// launches k_window_marg on what the caller put into ctx->win_prob (window mode) or ctx->win_marg_in (a host system) and fetches its MargOut: ONE synchronisation
+static int marg_run(lili_ctx* ctx, const WinDev* d_prob, const double* d_rec, const double* d_sys, const MargArgs& a, MargOut* h_out, const char* who) {
+    HIPCHK(ctx->win_marg.ensure(sizeof(MargOut)));
+    hipLaunchKernelGGL(k_window_marg, dim3(1), dim3(kMargThreads), 0, ctx->stream, d_prob, d_rec, d_sys, a, ctx->win_marg.as<MargOut>());
+    HIPCHK(hipGetLastError());
+    const int n = a.pos - a.m;
+    const MargOut* d = ctx->win_marg.as<MargOut>();
+    int rc = lili_readback_add(ctx, h_out, d, offsetof(MargOut, J0) + sizeof(double) * n * n);
+    if (rc != LILI_OK) { (void)lili_readback_finish(ctx); return rc; }
+    if ((rc = lili_readback_finish(ctx)) != LILI_OK) return rc;
+    if (h_out->status != 0) return ctx->fail(LILI_E_NUMERIC, std::string(who) + ": the Jacobi eigen-solver reached its sweep cap without converging");
+    return LILI_OK;
+}
+
 extern "C" {
 
 int lili_window_sqrt_info(const double covariance[225], double sqrt_info[225]) {
@@ -802,6 +1049,91 @@ int lili_window_state_get(lili_ctx* ctx, int n_kf, double* state) {
     const int rc = lili_readback_add(ctx, state, ctx->win_out.p, sizeof(double) * 16 * n_kf);
     if (rc != LILI_OK) { (void)lili_readback_finish(ctx); return rc; }
     return lili_readback_finish(ctx);
+}
+
+int lili_marg_schur(lili_ctx* ctx, const double* A, size_t ld, const double* b, int pos, int m, double* J0, double* r0, int* rank) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(A && b && J0 && r0 && rank, "marg_schur: null argument");
+    ARGCHK(pos >= 2 && pos <= kWinMaxN && m >= 1 && m < pos && ld >= (size_t)pos, "marg_schur: need 2 <= pos <= 60, 1 <= m < pos, ld >= pos");
+    std::vector<double> sys((size_t)pos * pos + pos);
+    for (int i = 0; i < pos; i++) {
+        for (int j = 0; j < pos; j++) { const double v = A[(size_t)i * ld + j]; ARGCHK(std::isfinite(v), "marg_schur: A is not finite"); sys[(size_t)i * pos + j] = v; }
+        ARGCHK(std::isfinite(b[i]), "marg_schur: b is not finite");
+        sys[(size_t)pos * pos + i] = b[i];
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(ctx->win_marg_in.ensure(sizeof(double) * sys.size()));
+    HIPCHK(hipMemcpyAsync(ctx->win_marg_in.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice, ctx->stream));
+    MargArgs a{};
+    a.pos = pos; a.m = m;
+    std::vector<unsigned char> buf(sizeof(MargOut));
+    MargOut* o = reinterpret_cast<MargOut*>(buf.data());
+    const int rc = marg_run(ctx, nullptr, nullptr, ctx->win_marg_in.as<double>(), a, o, "marg_schur");
+    if (rc != LILI_OK) return rc;
+    const int n = pos - m;
+    std::memcpy(J0, o->J0, sizeof(double) * n * n);
+    std::memcpy(r0, o->r0, sizeof(double) * n);
+    *rank = o->rank;
+    return LILI_OK;
+}
+
+int lili_window_marginalize(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const double* state, lili_window_prior_storage* out) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(params && out, "window_marginalize: null argument");
+    int rc = window_pack(ctx, problem, state, false, "window_marginalize");
+    if (rc != LILI_OK) return rc;
+    const int n_kf = problem->n_kf;
+    // ---- the blocks the reference's factor set touches (L/src/BackendFusion.cpp:1009-1165), in (keyframe, kind) order: keyframe 0's go, the others stay
+    // read from the PACKED problem, the words win_build<true> itself branches on (has_prior, sb_has, n_imu) — so the columns picked here are the ones it fills
+    const WinDev& D = *reinterpret_cast<const WinDev*>(ctx->win_host.data());
+    bool touched[kWinMaxKf][3] = {};
+    if (D.has_prior) for (int b = 0; b < D.n_blocks; b++) touched[D.blk_kf[b]][D.blk_kind[b]] = true;
+    for (int k = 0; k < n_kf; k++) if (D.sb_has[k]) touched[k][2] = true;
+    if (D.n_imu >= 1) for (int k = 0; k < 2; k++) for (int kind = 0; kind < 3; kind++) touched[k][kind] = true;      // the factor between keyframes 0 and 1 only
+    if (problem->kind_mask) for (int k = 0; k < n_kf; k++) touched[k][0] = touched[k][1] = true;                      // rec != nullptr below
+    MargArgs a{};
+    int kind_of[kWinMaxBlocks], kf_of[kWinMaxBlocks], n_blocks = 0;
+    for (int k = 0; k < n_kf; k++) for (int kind = 0; kind < 3; kind++) {
+        if (!touched[k][kind]) continue;
+        const int first = 15 * k + (kind == 0 ? 0 : kind == 1 ? 3 : 6), size = kind == 2 ? 9 : 3;
+        for (int i = 0; i < size; i++) a.sel[a.pos++] = first + i;
+        if (k == 0) a.m = a.pos;
+        else { kind_of[n_blocks] = kind; kf_of[n_blocks] = k; n_blocks++; }
+    }
+    ARGCHK(a.m >= 1, "window_marginalize: no factor touches keyframe 0");
+    ARGCHK(a.pos > a.m, "window_marginalize: no factor touches a keyframe that stays");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(ctx->win_prob.ensure(sizeof(WinDev)));
+    const double* rec = nullptr;
+    if (problem->kind_mask) {      // the launches of lili_window_evaluate: every slot linearised at `state`
+        double t[3 * kWinMaxKf], q[4 * kWinMaxKf];
+        for (int k = 0; k < n_kf; k++) { std::memcpy(t + 3 * k, state + 16 * k, 3 * sizeof(double)); std::memcpy(q + 4 * k, state + 16 * k + 3, 4 * sizeof(double)); }
+        const lili_s2m_params p = window_params(problem, params);
+        HIPCHK(ctx->win_rec.ensure(sizeof(double) * LILI_GRAM_DOUBLES * LILI_MAX_SLOTS));
+        if ((rc = lili_match_window_records(ctx, problem->slots, n_kf, problem->kind_mask, &p, t, q, ctx->win_rec.as<double>())) != LILI_OK) return rc;
+        rec = ctx->win_rec.as<double>();
+    }
+    HIPCHK(hipMemcpyAsync(ctx->win_prob.p, ctx->win_host.data(), sizeof(WinDev), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<unsigned char> buf(sizeof(MargOut));
+    MargOut* o = reinterpret_cast<MargOut*>(buf.data());
+    if ((rc = marg_run(ctx, ctx->win_prob.as<WinDev>(), rec, nullptr, a, o, "window_marginalize")) != LILI_OK) return rc;
+    // ---- the prior as the NEXT window sees it: keyframe k is its keyframe k - 1 (addr_shift, L:1170-1177), x0 = the block's value in `state`
+    const int n = a.pos - a.m;
+    std::memset(out, 0, sizeof *out);
+    int off = 0;
+    for (int b = 0; b < n_blocks; b++) {
+        const int kind = kind_of[b], gs = kind == 0 ? 3 : kind == 1 ? 4 : 9;
+        out->block_kind[b] = kind; out->block_keyframe[b] = kf_of[b] - 1;
+        std::memcpy(out->x0 + off, state + 16 * kf_of[b] + (kind == 0 ? 0 : kind == 1 ? 3 : 7), sizeof(double) * gs);
+        off += gs;
+    }
+    std::memcpy(out->J0, o->J0, sizeof(double) * n * n);
+    std::memcpy(out->r0, o->r0, sizeof(double) * n);
+    out->rank = o->rank; out->sweeps_mm = o->sweeps[0]; out->sweeps_s = o->sweeps[1];
+    out->prior.n_rows = n; out->prior.n_cols = n; out->prior.n_blocks = n_blocks;
+    out->prior.block_kind = out->block_kind; out->prior.block_keyframe = out->block_keyframe;
+    out->prior.x0 = out->x0; out->prior.J0 = out->J0; out->prior.r0 = out->r0;
+    return LILI_OK;
 }
 
 }  // extern "C"
