@@ -120,7 +120,8 @@ int lili_set_debug(lili_ctx* ctx, int keep_neighbors);
  *                 matcher behind the extractor for GUESSED feature counts — the previous scan's plus a margin, padding rows select nothing — and synchronises once;
  *                 a scan with more features than guessed is matched again the plain way; results identical either way; not taken with persistent_iterate; default 1), "frame_extract_stream" (1 = a frame whose
  *                 local map is still to be built runs its extraction on a stream of its own, next to the ring merge instead of in front of it: 15-30 us per frame faster in a
- *                 process with one context, ~100 us SLOWER in a process that holds many streams (they share the runtime's few hardware queues); default 0).
+ *                 process with one context, ~100 us SLOWER in a process that holds many streams (they share the runtime's few hardware queues); default 0), "imu_time" (1 = lili_imu_preintegrate brackets its kernel with
+ *                 two events for lili_imu_kernel_ms; default 0).
  *   extraction    "rot_fold" (1 = the ring stage of lili_extract_rot writes the scan's feature lists itself, four launches; 0 = per-ring lists and a concatenation
  *                 launch, also the fallback of a look-back that gave up; default 1), "rot_segment_wait" (1 = a segment whose pick may lie under marks of the
  *                 segment before it waits for them inside the segment stage; 0 = the ring stage repeats such a segment; default 1).
@@ -613,8 +614,8 @@ int lili_gram_to_factor(const double gram[64], double cost, double residuals[9],
  * marginalisation prior (MarginalizationFactor::Evaluate) or the speed-bias priors (PriorFactor.h:13-23); the last three enter without a loss.
  * The prior of the NEXT window (MarginalizationInfo::PreMarginalize + Marginalize: the factors again at the solved state, Schur complement over the
  * oldest keyframe, two eigen-decompositions) is lili_window_marginalize below: a keyframe cycle is prepare -> solve -> marginalise.
- * What stays with the caller: the IMU pre-integration, the write-back gates and the quaternion sign unification — their RESULTS are handed in as
- * the plain arrays below (host memory, copied once per call).  A state is n_kf x 16 doubles: t[3], q[4], speed-bias[9] per keyframe; "local" means 15 per keyframe: t, the 3 quaternion-plus
+ * The IMU factors' records come from lili_imu_preintegrate below (raw samples in, lili_window_imu out).  What stays with the caller: the write-back
+ * gates and the quaternion sign unification — their RESULTS are handed in as the plain arrays below (host memory, copied once per call).  A state is n_kf x 16 doubles: t[3], q[4], speed-bias[9] per keyframe; "local" means 15 per keyframe: t, the 3 quaternion-plus
  * coordinates, speed-bias. */
 #define LILI_WINDOW_MAX_KF 4          /* 15 * n_kf <= 60 local dimensions: every matrix of the solve stays in LDS */
 #define LILI_WINDOW_STATE_DOUBLES 16
@@ -698,6 +699,47 @@ typedef struct lili_window_prior_storage {
  * LILI_E_NUMERIC — leave `out` and the slots' poses untouched. */
 int lili_window_marginalize(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const double* state,
                             lili_window_prior_storage* out);
+
+/* ---- IMU pre-integration on the device (lili_imu.hip) ---------------------------------------------
+ * What the constructor plus one push_back(dt, acc, gyr) per sample leave in a Preintegration object (L/include/factors/Preintegration.h:27-173): the
+ * mid-point step of (delta_p, delta_q, delta_v) with delta_q.normalize() after every sample, sum_dt, jacobian = F ... F I and covariance
+ * P <- F P F^T + V N V^T from 1e-4 I, F / V with the reference's literal coefficients, N from its four noise constants.  f64, no contraction: the eleven
+ * state values are the bits a build of the reference header produces; Jacobian and covariance agree with it to rounding.
+ * One segment = one IMU factor (the samples between two keyframes); segments are independent, one workgroup each, so every factor of a window — or
+ * the same samples at new linearisation biases, Preintegration::Repropagate — goes in ONE call.  out[i] can be used as lili_window_problem::imu[i].
+ * With predict != 0 a segment also carries processIMU's state propagation (L/src/BackendFusion.cpp:815-821) from (P0, R0, V0) — R0 a row-major 3 x 3
+ * that is multiplied on, never re-normalised, as in the reference — with the same biases; processIMU's own g, subtracted from the rotated accelerations,
+ * is the negative of the segment's g (g_vec_ = -g, L:807): pred[i] = the next keyframe's initial guess.  pred may be NULL when no segment predicts; entries of segments with predict == 0 are not written.
+ * One packed upload from page-locked staging, one launch, one synchronisation; blocking.  LILI_E_ARG — a null pointer, n_seg outside
+ * 1 .. LILI_IMU_MAX_SEGMENTS, n outside 0 .. LILI_IMU_MAX_SAMPLES, a sample / bias / g / start state that is not finite, a negative dt, a predicting
+ * segment without pred — leaves out and pred untouched. */
+#define LILI_IMU_MAX_SAMPLES 4096     /* per segment */
+#define LILI_IMU_MAX_SEGMENTS 64
+typedef struct lili_imu_segment {
+    const double* dt; const double* acc; const double* gyr;   /* n, n x 3, n x 3: the arguments of push_back, host memory (may be NULL when n == 0) */
+    int32_t n, predict;                                       /* n >= 0; predict != 0: P0 / R0 / V0 are read, P1 / R1 / V1 written */
+    double acc0[3], gyr0[3], lin_ba[3], lin_bg[3], g[3];      /* constructor arguments; g = the factor's gravity (g_vec_), copied to out[i].g */
+    double P0[3], R0[9], V0[3];
+} lili_imu_segment;
+typedef struct lili_imu_prediction { double P1[3], R1[9], V1[3]; } lili_imu_prediction;
+int lili_imu_preintegrate(lili_ctx* ctx, const lili_imu_segment* seg, int n_seg, lili_window_imu* out, lili_imu_prediction* pred);
+/* Device time of the last lili_imu_preintegrate's kernel in milliseconds, taken with two events around the launch when option "imu_time" is 1
+ * (measurement aid, tools/preint_time.py); LILI_E_STATE when there is none. */
+int lili_imu_kernel_ms(lili_ctx* ctx, float* ms);
+
+/* The sample slicing of saveKeyFramesAndFactors for one keyframe (L/src/BackendFusion.cpp:1700-1771), host code without a context: the samples with
+ * stamp < t_kf from st->idx on are consumed — dt from the running st->t_cur (< 0: unset, the first dt is then 0), accelerations clamped to +-15 / +-15 /
+ * +-18 —, then, if a sample is left, ONE boundary sample at t_kf interpolated with w1 = dt2 / (dt1 + dt2), w2 = dt1 / (dt1 + dt2) between the last
+ * consumed values (zeros when none was consumed, as in the reference) and the next sample, clamped again; st->t_cur = t_kf, st->idx = the first sample
+ * not consumed.  The rows written (dt_out n, acc_out / gyr_out n x 3; *n_out of them) are the push_back arguments of the keyframe's segment.
+ * st->acc0 / gyr0 on entry are the segment's constructor arguments, on exit the next segment's (the last row written).  A state that is all zero (or
+ * after lili_imu_kf_reset) takes acc0 / gyr0 from the first sample as it is, unclamped (imuHandler, L:636-662), before anything else: read them after
+ * the call in that case, they are unchanged by a call that consumes nothing.  LILI_E_ARG — a null pointer, or cap smaller than the rows to write —
+ * writes nothing and leaves the state as it was.  n = 0 or st->idx >= n: no rows, st->t_cur = t_kf. */
+typedef struct lili_imu_kf_state { int64_t idx; double t_cur; double acc0[3], gyr0[3]; int32_t first, reserved; } lili_imu_kf_state;
+void lili_imu_kf_reset(lili_imu_kf_state* st);
+int lili_imu_keyframe_samples(lili_imu_kf_state* st, const double* stamps, const double* acc, const double* gyr, size_t n, double t_kf,
+                              double* dt_out, double* acc_out, double* gyr_out, size_t cap, size_t* n_out);
 
 /* ---- callers / data formats either side of the path ------------------------- */
 

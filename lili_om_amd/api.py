@@ -92,6 +92,20 @@ class WindowImu(C.Structure):
                 ("lin_ba", C.c_double * 3), ("lin_bg", C.c_double * 3), ("jacobian", C.c_double * 225), ("covariance", C.c_double * 225)]
 
 
+class ImuSegment(C.Structure):
+    _fields_ = [("dt", C.POINTER(C.c_double)), ("acc", C.POINTER(C.c_double)), ("gyr", C.POINTER(C.c_double)), ("n", C.c_int32), ("predict", C.c_int32),
+                ("acc0", C.c_double * 3), ("gyr0", C.c_double * 3), ("lin_ba", C.c_double * 3), ("lin_bg", C.c_double * 3), ("g", C.c_double * 3),
+                ("P0", C.c_double * 3), ("R0", C.c_double * 9), ("V0", C.c_double * 3)]
+
+
+class ImuPrediction(C.Structure):
+    _fields_ = [("P1", C.c_double * 3), ("R1", C.c_double * 9), ("V1", C.c_double * 3)]
+
+
+class ImuKfState(C.Structure):
+    _fields_ = [("idx", C.c_int64), ("t_cur", C.c_double), ("acc0", C.c_double * 3), ("gyr0", C.c_double * 3), ("first", C.c_int32), ("reserved", C.c_int32)]
+
+
 class WindowPrior(C.Structure):
     _fields_ = [("n_rows", C.c_int32), ("n_cols", C.c_int32), ("n_blocks", C.c_int32), ("reserved_", C.c_int32), ("block_kind", C.POINTER(C.c_int32)),
                 ("block_keyframe", C.POINTER(C.c_int32)), ("x0", C.POINTER(C.c_double)), ("J0", C.POINTER(C.c_double)), ("r0", C.POINTER(C.c_double))]
@@ -256,6 +270,11 @@ _SIGS = {
     "lili_livox_custom_to_cloud": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_int]),
     "lili_imu_reset": (None, [C.c_void_p]),
     "lili_imu_integrate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p]),
+    "lili_imu_preintegrate": (C.c_int, [C.c_void_p, C.POINTER(ImuSegment), C.c_int, C.POINTER(WindowImu), C.POINTER(ImuPrediction)]),
+    "lili_imu_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "lili_imu_kf_reset": (None, [C.c_void_p]),
+    "lili_imu_keyframe_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]),
     "lili_marg_add_lidar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
     "lili_gn_step_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_gram_to_factor": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
@@ -1270,6 +1289,88 @@ class ImuIntegrator:
         if rc != 0:
             raise LiliError(f"lili_imu_integrate failed ({rc})")
         return q
+
+
+IMU_MAX_SAMPLES, IMU_MAX_SEGMENTS = 4096, 64
+
+
+class ImuPreintegrator:
+    """IMU pre-integration on the device (lili_imu_preintegrate) and the keyframe sample slicing in front of it (lili_imu_keyframe_samples, host code).
+    A segment is a dict: dt (n), acc (n, 3), gyr (n, 3) — push_back's arguments —, acc0, gyr0, ba, bg — the constructor's —, optionally g (default
+    (0, 0, -9.805)) and, for a prediction, P0 (3), R0 (3, 3), V0 (3).  ctx may be None for keyframe_samples alone."""
+
+    def __init__(self, ctx=None):
+        self.ctx, self.lib = ctx, ctx.lib if ctx is not None else load_library()
+        self.state = ImuKfState()
+        self.lib.lili_imu_kf_reset(C.byref(self.state))
+
+    def reset(self):
+        self.lib.lili_imu_kf_reset(C.byref(self.state))
+
+    def keyframe_samples(self, stamps, acc, gyr, t_kf, cap=None):
+        """The segment of the keyframe stamped t_kf from the sample buffer (stamps (n), acc / gyr (n, 3); the running state remembers what is consumed):
+        dict(dt, acc, gyr, acc0, gyr0) — preintegrate's segment once ba / bg are added.  cap: rows the outputs may hold (default: enough)."""
+        st = np.ascontiguousarray(stamps, np.float64).reshape(-1)
+        a = np.ascontiguousarray(acc, np.float64).reshape(-1, 3)
+        g = np.ascontiguousarray(gyr, np.float64).reshape(-1, 3)
+        if not (st.shape[0] == a.shape[0] == g.shape[0]):
+            raise LiliError("keyframe_samples: stamps, acc and gyr differ in length")
+        cap = int(cap if cap is not None else max(st.shape[0] - int(self.state.idx), 0) + 1)
+        dt_o, a_o, g_o = np.zeros(cap), np.zeros((cap, 3)), np.zeros((cap, 3))
+        n_out = C.c_size_t(0)
+        was_first = bool(self.state.first)
+        acc0, gyr0 = np.array(self.state.acc0[:]), np.array(self.state.gyr0[:])
+        rc = self.lib.lili_imu_keyframe_samples(C.byref(self.state), _ptr(st) if st.size else None, _ptr(a) if a.size else None, _ptr(g) if g.size else None, st.shape[0],
+                                                float(t_kf), _ptr(dt_o), _ptr(a_o), _ptr(g_o), cap, C.byref(n_out))
+        if rc != 0:
+            raise LiliError(f"lili_imu_keyframe_samples failed ({rc})")
+        if not was_first and st.size:      # a fresh state took the constructor's pair from the first sample
+            acc0, gyr0 = a[0].copy(), g[0].copy()
+        n = int(n_out.value)
+        return dict(dt=dt_o[:n].copy(), acc=a_o[:n].copy(), gyr=g_o[:n].copy(), acc0=acc0, gyr0=gyr0)
+
+    def _pack(self, segments, predict=False):
+        """(ctypes array of lili_imu_segment, the arrays it points into, per-segment predict flags); a segment's own "predict" key overrides the argument"""
+        n_seg = len(segments)
+        segs = (ImuSegment * max(n_seg, 1))()
+        keep, flags = [], []
+        for s, d in zip(segs, segments):
+            dt = np.ascontiguousarray(d["dt"], np.float64).reshape(-1)
+            a = np.ascontiguousarray(d["acc"], np.float64).reshape(-1, 3)
+            g = np.ascontiguousarray(d["gyr"], np.float64).reshape(-1, 3)
+            if not (dt.shape[0] == a.shape[0] == g.shape[0]):
+                raise LiliError("preintegrate: dt, acc and gyr differ in length")
+            keep += [dt, a, g]
+            flags.append(bool(d.get("predict", predict)))
+            s.n, s.predict = dt.shape[0], 1 if flags[-1] else 0
+            if dt.size:
+                s.dt, s.acc, s.gyr = (x.ctypes.data_as(C.POINTER(C.c_double)) for x in (dt, a, g))
+            for name, key, size, default in (("acc0", "acc0", 3, None), ("gyr0", "gyr0", 3, None), ("lin_ba", "ba", 3, None), ("lin_bg", "bg", 3, None), ("g", "g", 3, (0.0, 0.0, -9.805)),
+                                             ("P0", "P0", 3, (0.0,) * 3), ("R0", "R0", 9, (1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0)), ("V0", "V0", 3, (0.0,) * 3)):
+                v = np.asarray(d[key] if default is None else d.get(key, default), np.float64).reshape(-1)
+                if v.size != size:
+                    raise LiliError(f"preintegrate: {key} has {v.size} values, expected {size}")
+                getattr(s, name)[:] = v.tolist()
+        return segs, keep, flags
+
+    def preintegrate(self, segments, predict=False):
+        """WindowImu array (one per segment, what WindowSolver.set_problem(imu=...) takes) — and, if any segment predicts, the list of
+        (P1 (3), R1 (3, 3), V1 (3)) per segment (None where a segment does not)."""
+        if self.ctx is None:
+            raise LiliError("ImuPreintegrator: preintegrate needs a context")
+        n_seg = len(segments)
+        segs, keep, flags = self._pack(segments, predict)
+        out = (WindowImu * max(n_seg, 1))()
+        pred = (ImuPrediction * max(n_seg, 1))() if any(flags) else None
+        self.ctx._chk(self.lib.lili_imu_preintegrate(self.ctx.h, segs, n_seg, out, pred))
+        if pred is None:
+            return out
+        return out, [(np.array(p.P1[:]), np.array(p.R1[:]).reshape(3, 3), np.array(p.V1[:])) if f else None for p, f in zip(pred, flags)]
+
+    def kernel_ms(self):
+        ms = C.c_float(0)
+        self.ctx._chk(self.lib.lili_imu_kernel_ms(self.ctx.h, C.byref(ms)))
+        return float(ms.value)
 
 
 def marg_add_lidar(gram, A, b, idx_t, idx_q):

@@ -215,6 +215,9 @@ struct lili_ctx {
     void (*ext_loop_free)(void*) = nullptr;
     void* ext_archive = nullptr;             // keyframe archive and global map (lili_archive.hip)
     void (*ext_archive_free)(void*) = nullptr;
+    void* ext_imu = nullptr;                 // IMU pre-integration: page-locked staging, device buffers, timing events (lili_imu.hip)
+    void (*ext_imu_free)(void*) = nullptr;
+    bool imu_time = false;                   // option "imu_time": events around k_imu_preintegrate (lili_imu_kernel_ms)
     int archive_max_mb = 0;                  // bound on the archive's slab pool (0: none)
     int archive_slab_mb = 64;
     int global_map_batch_points = 1 << 21;   // points lili_global_map places, sorts and folds at a time

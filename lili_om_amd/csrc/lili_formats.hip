@@ -122,6 +122,74 @@ int lili_imu_integrate(lili_imu_state* st, const double* stamps, const double* g
     return LILI_OK;
 }
 
+void lili_imu_kf_reset(lili_imu_kf_state* st) {
+    if (!st) return;
+    std::memset(st, 0, sizeof(*st));
+    st->t_cur = -1.0;
+}
+
+static void imu_kf_clamp(double a[3]) {                          // L:1717-1723, 1758-1764
+    if (a[0] > 15.0) a[0] = 15.0;
+    if (a[1] > 15.0) a[1] = 15.0;
+    if (a[2] > 18.0) a[2] = 18.0;
+    if (a[0] < -15.0) a[0] = -15.0;
+    if (a[1] < -15.0) a[1] = -15.0;
+    if (a[2] < -18.0) a[2] = -18.0;
+}
+
+int lili_imu_keyframe_samples(lili_imu_kf_state* st, const double* stamps, const double* acc, const double* gyr, size_t n, double t_kf,
+                              double* dt_out, double* acc_out, double* gyr_out, size_t cap, size_t* n_out) {
+    if (!st || !n_out || (n > 0 && (!stamps || !acc || !gyr))) return LILI_E_ARG;
+    lili_imu_kf_state s = *st;                                // the caller's state changes only when the call succeeds
+    if (s.idx == 0 && s.first == 0 && s.t_cur == 0.0) s.t_cur = -1.0;   // zero-initialised state
+    if (s.idx < 0) return LILI_E_ARG;
+    if (n > 0 && !s.first) {                                  // imuHandler, L:636-662: the first message ever, as it is
+        s.first = 1;
+        for (int k = 0; k < 3; k++) { s.acc0[k] = acc[k]; s.gyr0[k] = gyr[k]; }
+    }
+    for (int pass = 0; pass < 2; pass++) {                    // pass 0 counts the rows, pass 1 writes them
+        double t_cur = s.t_cur, a[3] = {0.0, 0.0, 0.0}, r[3] = {0.0, 0.0, 0.0};      // dx .. rz, L:1700
+        size_t i = (size_t)s.idx, rows = 0;
+        auto emit = [&](double dt) {
+            if (pass) { dt_out[rows] = dt; for (int k = 0; k < 3; k++) { acc_out[3 * rows + k] = a[k]; gyr_out[3 * rows + k] = r[k]; } }
+            rows++;
+        };
+        if (i < n) {
+            while (stamps[i] < t_kf) {                        // L:1707-1737
+                const double t = stamps[i];
+                if (t_cur < 0) t_cur = t;
+                const double dt = t - t_cur;
+                t_cur = stamps[i];
+                for (int k = 0; k < 3; k++) { a[k] = acc[3 * i + k]; r[k] = gyr[3 * i + k]; }
+                imu_kf_clamp(a);
+                emit(dt);
+                i++;
+                if (i >= n) break;
+            }
+            if (i < n) {                                      // L:1741-1770: one sample interpolated at the keyframe's stamp
+                const double dt1 = t_kf - t_cur;
+                const double dt2 = stamps[i] - t_kf;
+                const double w1 = dt2 / (dt1 + dt2);
+                const double w2 = dt1 / (dt1 + dt2);
+                for (int k = 0; k < 3; k++) a[k] = w1 * a[k] + w2 * acc[3 * i + k];
+                imu_kf_clamp(a);
+                for (int k = 0; k < 3; k++) r[k] = w1 * r[k] + w2 * gyr[3 * i + k];
+                emit(dt1);
+            }
+        }
+        if (pass == 0) {
+            if (rows > cap || (rows > 0 && (!dt_out || !acc_out || !gyr_out))) return LILI_E_ARG;
+            continue;
+        }
+        if (rows > 0) for (int k = 0; k < 3; k++) { s.acc0[k] = a[k]; s.gyr0[k] = r[k]; }      // processIMU, L:825-826
+        s.t_cur = t_kf;                                       // L:1771
+        s.idx = (int64_t)i;
+        *n_out = rows;
+    }
+    *st = s;
+    return LILI_OK;
+}
+
 int lili_marg_add_lidar(const double gram[64], double* A, size_t ld, double* b, size_t pos, size_t idx_t, size_t idx_q) {
     if (!gram || !A || !b) return LILI_E_ARG;
     if (ld < pos || idx_t + 3 > pos || idx_q + 3 > pos) return LILI_E_ARG;

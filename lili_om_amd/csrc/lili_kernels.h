@@ -174,4 +174,20 @@ struct IterArgs {
     unsigned long long launch;
 };
 
+// IMU pre-integration (k_imu_preintegrate in lili_imu.hip): one workgroup per segment.  The packed upload is the table of segment headers followed by the sample
+// rows of every segment, 7 doubles each (dt, acc[3], gyr[3]); a segment owns n + 1 rows, row 0 = (0, acc0, gyr0), the constructor's pair.
+constexpr int kImuThreads = 256;     // 225 of them own one entry of the 15 x 15 matrices
+constexpr int kImuChunk = 64;        // samples whose state chain and F / V blocks are prepared at a time
+constexpr int kImuRow = 7;
+struct ImuSegDev {
+    long long first_row;             // of the segment in the sample rows
+    int n, predict;
+    double ba[3], bg[3], g[3];
+    double P0[3], R0[9], V0[3];
+};
+struct ImuOutDev {                   // lili_window_imu's numbers, then the prediction
+    double sum_dt, g[3], delta_p[3], delta_q[4], delta_v[3], lin_ba[3], lin_bg[3], jacobian[225], covariance[225];
+    double P1[3], R1[9], V1[3];
+};
+
 }  // namespace lili

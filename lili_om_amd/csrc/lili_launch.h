@@ -43,6 +43,8 @@ __global__ void k_solve_lm_window(WinLmArgs, MatchParams);
 template <int L, bool LIN> __global__ void k_associate_coop(AssocArgs, AssocArgs, PoseArg, MatchParams, double*, double*, SlotState*, int);
 template <int L> __global__ void k_associate_coop_window(WinAssocArgs, MatchParams);
 template <int L> __global__ void k_iterate_coop(AssocArgs, AssocArgs, MatchParams, IterArgs);
+// lili_imu.hip: IMU pre-integration, one workgroup per segment
+__global__ void k_imu_preintegrate(const ImuSegDev*, const double*, ImuOutDev*);
 }  // namespace lili
 
 // lili_map.hip: the three-kernel exclusive scan (k_scan_block_sums, k_scan_sums, k_scan_apply) of n words into out[0 .. n]; in == out is allowed
