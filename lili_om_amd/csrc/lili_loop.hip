@@ -274,6 +274,12 @@ __global__ __launch_bounds__(kIcpBlock) void k_icp_step(IcpStepArgs a) {
         for (int k = 0; k < 3; k++) { pm[k] = S[1 + k] / n; qm[k] = S[4 + k] / n; }
         for (int r = 0; r < 3; r++)
             for (int s = 0; s < 3; s++) H[3 * r + s] = S[7 + 3 * r + s] - n * pm[r] * qm[s];
+        // rank 0 (every accepted source point the same point, or every partner): what the subtraction leaves is the rounding of the sums (about one ulp of
+        // them, whatever n: they are tree sums) — no rotation can be read from it, and icp_rotation would make one of the noise.  H = 0 gives R = I.
+        double hmax = 0.0, smax = 0.0;
+        for (int k = 0; k < 9; k++) { hmax = fmax(hmax, fabs(H[k])); smax = fmax(smax, fabs(S[7 + k])); }
+        if (hmax <= 64.0 * DBL_EPSILON * smax)
+            for (int k = 0; k < 9; k++) H[k] = 0.0;
         icp_rotation(H, R);
         double t[3];
         for (int r = 0; r < 3; r++) {
