@@ -42,6 +42,35 @@ __device__ __forceinline__ dq qinv(dq q) {
     if (n2 > 0) return {q.w / n2, -q.x / n2, -q.y / n2, -q.z / n2};
     return {0, 0, 0, 0};
 }
+// Eigen 3.3 QuaternionBase::toRotationMatrix (row-major 3x3), q = (w, x, y, z), not normalised inside
+__device__ __forceinline__ void quat_to_mat(const double q[4], double R[9]) {
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
+}
+// Eigen 3.3 slerp of Identity towards b, in two parts: what depends on b alone (the angle and its sine: one acos and one sin, the same for every
+// point of a scan — computed once per workgroup by both extractors) and what depends on t.
+struct SlerpConst { double theta, sin_theta; int linear; };
+__device__ __forceinline__ SlerpConst qslerp_prepare(dq b) {
+    const double one = 1.0 - 2.220446049250313e-16;
+    const double absD = fabs(b.w);
+    SlerpConst c{0.0, 1.0, 1};
+    if (!(absD >= one)) { c.theta = acos(absD); c.sin_theta = sin(c.theta); c.linear = 0; }
+    return c;
+}
+__device__ __forceinline__ dq qslerp_identity(double t, dq b, SlerpConst c) {
+    double s0, s1;
+    if (c.linear) { s0 = 1.0 - t; s1 = t; }
+    else {
+        s0 = sin((1.0 - t) * c.theta) / c.sin_theta;
+        s1 = sin(t * c.theta) / c.sin_theta;
+    }
+    if (b.w < 0) s1 = -s1;
+    return dq{s0 + s1 * b.w, s1 * b.x, s1 * b.y, s1 * b.z};
+}
 // d(q*v)/dq for the expression above, as a 3x4 matrix [d/dw | d/dx d/dy d/dz]:
 //   d/dw = 2 (u x v);   d/du = -2 w [v]x + 2 ((u.v) I + u v^T - 2 v u^T)
 // rowK(g) returns g^T * D (1x4) for a 3-vector g, which is all the factors need.

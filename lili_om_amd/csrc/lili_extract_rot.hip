@@ -145,26 +145,6 @@ __device__ float fd_atan2f(float y, float x) {
 __device__ __forceinline__ float atan_r(float v, int mode) { return mode == 2 ? fd_atanf(v) : (float)atan((double)v); }
 __device__ __forceinline__ float atan2_r(float y, float x, int mode) { return mode == 2 ? fd_atan2f(y, x) : (float)atan2((double)y, (double)x); }
 
-// Eigen 3.3 slerp of Identity towards b, in two parts: what depends on b alone (the angle and its sine: one acos and one sin, the same for every
-// point of a scan — computed once per workgroup) and what depends on t.
-struct SlerpConst { double theta, sin_theta; int linear; };
-__device__ __forceinline__ SlerpConst qslerp_prepare(dq b) {
-    const double one = 1.0 - 2.220446049250313e-16;
-    const double absD = fabs(b.w);
-    SlerpConst c{0.0, 1.0, 1};
-    if (!(absD >= one)) { c.theta = acos(absD); c.sin_theta = sin(c.theta); c.linear = 0; }
-    return c;
-}
-__device__ __forceinline__ dq qslerp_identity(double t, dq b, SlerpConst c) {
-    double s0, s1;
-    if (c.linear) { s0 = 1.0 - t; s1 = t; }
-    else {
-        s0 = sin((1.0 - t) * c.theta) / c.sin_theta;
-        s1 = sin(t * c.theta) / c.sin_theta;
-    }
-    if (b.w < 0) s1 = -s1;
-    return dq{s0 + s1 * b.w, s1 * b.x, s1 * b.y, s1 * b.z};
-}
 __device__ __forceinline__ float range2(float4 p) { return p.x * p.x + p.y * p.y + p.z * p.z; }
 __device__ __forceinline__ bool rot_point_ok(float4 p, float thres) {      // R:131-134: finite and not inside the near range
     return isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && !(p.x * p.x + p.y * p.y + p.z * p.z < thres * thres);

@@ -15,6 +15,7 @@
 // Every sum runs in ascending index order and leaves out only terms whose factor is a structural zero of F, V or N — the order of the reference's own
 // products compiled with textbook loops.  The state values therefore come out of the same IEEE operations in the same order as on the host.
 #include "lili_launch.h"
+#include "lili_device_math.h"
 
 #include <cmath>
 #include <cstddef>
@@ -56,14 +57,6 @@ __device__ const int kImuVRow[5][4] = {{kV00, kV03, kV06, kV03}, {kVZero, kVHalf
                                        {kVZero, kVZero, kVZero, kVZero}};
 
 // Eigen 3.3's formulas, as the reference's build evaluates them
-__device__ __forceinline__ void imu_quat_to_mat(const double q[4], double R[9]) {      // QuaternionBase::toRotationMatrix, q = (w, x, y, z), not normalised inside
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
-}
 __device__ __forceinline__ void imu_quat_rotate(const double q[4], const double v[3], double o[3]) {      // QuaternionBase::_transformVector
     const double u0 = q[1], u1 = q[2], u2 = q[3];
     double c0 = u1 * v[2] - u2 * v[1], c1 = u2 * v[0] - u0 * v[2], c2 = u0 * v[1] - u1 * v[0];
@@ -102,15 +95,15 @@ __device__ __forceinline__ void imu_store(double* dst, const double A[9]) {
 // MidPointIntegration's F and V blocks (Preintegration.h:98-143) and the state increments of one sample; rec holds dt, delta_q and the un-normalised result
 __device__ void imu_blocks(double* rec, const double* prev, const double* cur, const double ba[3], const double bg[3]) {
     const double dt = rec[kRecDt];
-    double dq[4], rq[4];
+    double dqv[4], rq[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) { dq[i] = rec[kRecDq + i]; rq[i] = rec[kRecRq + i]; }
+    for (int i = 0; i < 4; i++) { dqv[i] = rec[kRecDq + i]; rq[i] = rec[kRecRq + i]; }
     double a0[3], a1[3], w[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) { a0[i] = prev[1 + i] - ba[i]; a1[i] = cur[1 + i] - ba[i]; w[i] = 0.5 * (prev[4 + i] + cur[4 + i]) - bg[i]; }
     // the state: un_acc = 0.5 (delta_q a0 + result_delta_q a1); delta_p + delta_v dt + [0.5 un_acc dt dt]; delta_v + [un_acc dt]
     double u0[3], u1[3];
-    imu_quat_rotate(dq, a0, u0);
+    imu_quat_rotate(dqv, a0, u0);
     imu_quat_rotate(rq, a1, u1);
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -119,8 +112,8 @@ __device__ void imu_blocks(double* rec, const double* prev, const double* cur, c
         rec[kRecIncV + i] = ua * dt;
     }
     double Rd[9], Rr[9], A0[9], A1[9], W[9], IW[9], T[9], U[9], X[9];
-    imu_quat_to_mat(dq, Rd);
-    imu_quat_to_mat(rq, Rr);
+    quat_to_mat(dqv, Rd);
+    quat_to_mat(rq, Rr);
     imu_skew(a0, A0); imu_skew(a1, A1); imu_skew(w, W);
     const double ndt = -dt;
     rec[kC0] = 0.0; rec[kC1] = 1.0; rec[kCNegDt] = ndt; rec[kCHalfDt] = 0.5 * dt;      // 1, -1 dt, (0.5 * 1) dt: the diagonal entries of F and V that are no stored block
@@ -249,7 +242,7 @@ __global__ __launch_bounds__(kImuThreads) void k_imu_preintegrate(const ImuSegDe
                 for (int i = 0; i < 3; i++) u0[i] = ((pR[3 * i] * v[0] + pR[3 * i + 1] * v[1]) + pR[3 * i + 2] * v[2]) - g[i];
                 const double hq[4] = {1.0, rec[kRecHalf], rec[kRecHalf + 1], rec[kRecHalf + 2]};      // deltaQ(un_gyr * dt)
                 double M[9], Rn[9];
-                imu_quat_to_mat(hq, M);
+                quat_to_mat(hq, M);
                 imu_mul(pR, M, Rn);
 #pragma unroll
                 for (int i = 0; i < 9; i++) pR[i] = Rn[i];

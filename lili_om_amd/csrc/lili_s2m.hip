@@ -13,7 +13,7 @@
 #include "lili_kernels.h"
 #include "lili_device_math.h"
 #include "lili_device_cloud.h"
-#include "lili_s2m_dev.h"
+#include "lili_solve_dev.h"
 
 namespace lili {
 
@@ -997,27 +997,10 @@ __device__ void gn_update_block(const double* gram /*LDS or global, 64+*/, SlotS
     __shared__ double gvec[6];
     int tid = threadIdx.x & 63;
     const double x0 = in.pose[3], x1 = in.pose[4], x2 = in.pose[5], x3 = in.pose[6];
-    // plus-Jacobian Jq (4x3) of ceres::QuaternionParameterization, rows [-x1 -x2 -x3; x0 x3 -x2; -x3 x0 x1; x2 -x1 x0]; every lane
-    // builds the column(s) it needs in registers.  H = P^T G77 P and g = -P^T G7r with P = blockdiag(I3, Jq), evaluated as
-    // M = G P (4-term sums, left to right) and H = P^T M exactly like round 1's three LDS-staged steps — one step now.
-    auto jcol = [&](int c, double o[4]) {
-        o[0] = c == 0 ? -x1 : c == 1 ? -x2 : -x3;
-        o[1] = c == 0 ? x0 : c == 1 ? x3 : -x2;
-        o[2] = c == 0 ? -x3 : c == 1 ? x0 : x1;
-        o[3] = c == 0 ? x2 : c == 1 ? -x1 : x0;
-    };
+    // H = P^T G77 P and g = -P^T G7r with P = blockdiag(I3, plus-Jacobian of the quaternion): one lane per entry, its columns of P built in registers
     if (tid < 42) {
         const int a = tid < 36 ? tid / 6 : tid - 36, b = tid < 36 ? tid % 6 : 7;   // b == 7: the J^T r column
-        double jb[4] = {0, 0, 0, 0}, ja[4] = {0, 0, 0, 0};
-        if (b >= 3 && b < 6) jcol(b - 3, jb);
-        if (a >= 3) jcol(a - 3, ja);
-        auto Mrow = [&](int i) -> double {      // (G P)[i][b];  for b == 7 the plain column G[i][7]
-            if (b < 3 || b == 7) return gram[i * 8 + b];
-            return ((gram[i * 8 + 3] * jb[0] + gram[i * 8 + 4] * jb[1]) + gram[i * 8 + 5] * jb[2]) + gram[i * 8 + 6] * jb[3];
-        };
-        double v;
-        if (a < 3) v = Mrow(a);
-        else v = ((ja[0] * Mrow(3) + ja[1] * Mrow(4)) + ja[2] * Mrow(5)) + ja[3] * Mrow(6);
+        const double v = pose_local_entry(gram, in.pose + 3, a, b);
         if (tid < 36) H[a][b] = v; else gvec[a] = -v;
     }
     LILI_WAVE_SYNC();
@@ -1028,15 +1011,11 @@ __device__ void gn_update_block(const double* gram /*LDS or global, 64+*/, SlotS
     double pz[7] = {in.pose[0], in.pose[1], in.pose[2], x0, x1, x2, x3};
     if (okc) {
         pz[0] += d[0]; pz[1] += d[1]; pz[2] += d[2];
-        const double nd2 = d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
-        if (nd2 > 0.0) {
-            double sbd, cw;
+        // (libm's sin / cos above 0.5 rad, not sinc_cos_halving: see quat_plus)
+        quat_plus(pz + 3, d + 3, pz + 3, [](double nd2, double& sbd, double& cw) {
             if (nd2 < 0.25) sinc_cos_small(nd2, sbd, cw);
             else { const double nd = sqrt(nd2); sbd = sin(nd) / nd; cw = cos(nd); }
-            dq qd{cw, sbd * d[3], sbd * d[4], sbd * d[5]};
-            dq r = qmul(qd, dq{x0, x1, x2, x3});
-            pz[3] = r.w; pz[4] = r.x; pz[5] = r.y; pz[6] = r.z;
-        }
+        });
     }
     if (tid == 0) {
         const int status = okc ? 0 : 1;

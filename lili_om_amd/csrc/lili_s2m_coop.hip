@@ -14,7 +14,7 @@
 //
 // Reference behaviour replaced: the same as lili_s2m.hip (findCorrespondingSurfFeatures L/src/BackendFusion.cpp:1601-1681,
 // R/src/BackendFusion.cpp:1464-1520, L/src/LidarOdometry.cpp:352-413; findCorrespondingCornerFeatures L:1531-1599, R:1394-1462).
-#include "lili_s2m_dev.h"
+#include "lili_solve_dev.h"
 
 namespace lili {
 
@@ -307,8 +307,8 @@ template __global__ void k_associate_coop_window<16>(WinAssocArgs, MatchParams);
 // every wait is bounded and ends with gn_status = 2 instead of a hang.
 // ================================================================================================
 struct IterShared {
-    double vals[16][40];
-    double cvals[16][2];
+    double vals[kLmGroup][40];
+    double cvals[kLmGroup][2];
     double tot[40];
     double ctot[2];
     double full[64];
@@ -318,7 +318,11 @@ struct IterShared {
     int status;                   // 0 ok, 1 = normal matrix not positive definite (pose kept), 2 = an exchange gave up
     int n_updates;
 };
-// H d = g (no damping) on 42 lanes as in lili_s2m_lm.hip: returns false if a pivot is not positive or the step is not finite
+// H d = g (no damping) on 42 lanes: returns false if a pivot is not positive or the step is not finite.
+// k_iterate_coop sits at its register limit (256 VGPRs, scratch): it keeps its OWN text of the elimination (solve6_wave of lili_solve_dev.h), of the two-hop
+// exchange (xchg_total of lili_s2m_dev.h) and of the quaternion update (quat_plus with sinc_cos_halving) — calling the shared definitions re-schedules the
+// kernel and measured 0.1 - 0.4 us per iteration slower (profiles/EXPERIMENTS.md); only the local system and the tri-to-full step are shared.  Same
+// expression trees, same bits: a change to one of the shared definitions must be repeated here.
 __device__ __forceinline__ bool gn_solve_wave(const double (*H)[6], const double* g, double d[6]) {
     const int lane = threadIdx.x & 63;
     const int ri = lane / 7, cj = lane - 7 * ri;
@@ -409,11 +413,11 @@ __global__ __launch_bounds__(kCoopBlock, 2) void k_iterate_coop(AssocArgs S, Ass
                 store_granule(cpart + (size_t)b * 4 + 2, edge ? c : 0.0, ckey);
             }
             if (wave0) {
-                bool okx = true;
+                bool okx = true;      // (xchg_total of lili_s2m_dev.h, written out: see gn_solve_wave)
                 if (a.ng > 1) {
-                    if (b % 16 == 0) {
-                        okx = xchg_gather<2>(cpart + (size_t)b * 4, min(16, a.nb - b), ckey, sh.cvals, sh.ctot, 4);
-                        if ((threadIdx.x & 63) < 2) store_granule(cpart + (size_t)(a.nb + b / 16) * 4 + 2 * (threadIdx.x & 63), sh.ctot[threadIdx.x & 63], ckey);
+                    if (b % kLmGroup == 0) {
+                        okx = xchg_gather<2>(cpart + (size_t)b * 4, min(kLmGroup, a.nb - b), ckey, sh.cvals, sh.ctot, 4);
+                        if ((threadIdx.x & 63) < 2) store_granule(cpart + (size_t)(a.nb + b / kLmGroup) * 4 + 2 * (threadIdx.x & 63), sh.ctot[threadIdx.x & 63], ckey);
                     }
                     okx = xchg_gather<2>(cpart + (size_t)a.nb * 4, a.ng, ckey, sh.cvals, sh.ctot, 4) && okx;
                 } else okx = xchg_gather<2>(cpart, a.nb, ckey, sh.cvals, sh.ctot, 4);
@@ -443,44 +447,22 @@ __global__ __launch_bounds__(kCoopBlock, 2) void k_iterate_coop(AssocArgs S, Ass
         ga.add_rows(Jr, cost, rec.ok, lds);
         ga.finish(lds, part + (size_t)b * kPartialStride, key);
         if (wave0) {
-            bool okx = true;
+            bool okx = true;          // (xchg_total of lili_s2m_dev.h, written out: see gn_solve_wave)
             if (a.ng > 1) {
-                if (b % 16 == 0) {
-                    okx = xchg_gather<40>(part + (size_t)b * kPartialStride, min(16, a.nb - b), key, sh.vals, sh.tot);
-                    if ((threadIdx.x & 63) < 40) store_granule(gsum + (size_t)(b / 16) * kPartialStride + 2 * (threadIdx.x & 63), sh.tot[threadIdx.x & 63], key);
+                if (b % kLmGroup == 0) {
+                    okx = xchg_gather<40>(part + (size_t)b * kPartialStride, min(kLmGroup, a.nb - b), key, sh.vals, sh.tot);
+                    if ((threadIdx.x & 63) < 40) store_granule(gsum + (size_t)(b / kLmGroup) * kPartialStride + 2 * (threadIdx.x & 63), sh.tot[threadIdx.x & 63], key);
                 }
                 okx = xchg_gather<40>(gsum, a.ng, key, sh.vals, sh.tot) && okx;
             } else okx = xchg_gather<40>(part, a.nb, key, sh.vals, sh.tot);
             // ---- the Gauss-Newton step, identically in every workgroup: H = P^T G77 P, g = -P^T G7r, H d = g, x (+) d
-            {
-                const int lane = threadIdx.x;
-                const int r = lane >> 3, c = lane & 7;
-                const int aa = r < c ? r : c, bb = r < c ? c : r;
-                sh.full[lane] = sh.tot[aa * 8 - aa * (aa - 1) / 2 + (bb - aa)];
-            }
+            gram_tri_to_full(sh.tot, sh.full);
             LILI_WAVE_SYNC();
             {
                 const int tid = threadIdx.x;
-                const double x0 = sh.pose[3], x1 = sh.pose[4], x2 = sh.pose[5], x3 = sh.pose[6];
-                auto jcol = [&](int c, double o[4]) {
-                    o[0] = c == 0 ? -x1 : c == 1 ? -x2 : -x3;
-                    o[1] = c == 0 ? x0 : c == 1 ? x3 : -x2;
-                    o[2] = c == 0 ? -x3 : c == 1 ? x0 : x1;
-                    o[3] = c == 0 ? x2 : c == 1 ? -x1 : x0;
-                };
                 if (tid < 42) {
                     const int ar = tid < 36 ? tid / 6 : tid - 36, bc = tid < 36 ? tid % 6 : 7;
-                    double jb[4] = {0, 0, 0, 0}, ja[4] = {0, 0, 0, 0};
-                    if (bc >= 3 && bc < 6) jcol(bc - 3, jb);
-                    if (ar >= 3) jcol(ar - 3, ja);
-                    const double* gram = sh.full;
-                    auto Mrow = [&](int ii) -> double {
-                        if (bc < 3 || bc == 7) return gram[ii * 8 + bc];
-                        return ((gram[ii * 8 + 3] * jb[0] + gram[ii * 8 + 4] * jb[1]) + gram[ii * 8 + 5] * jb[2]) + gram[ii * 8 + 6] * jb[3];
-                    };
-                    double v;
-                    if (ar < 3) v = Mrow(ar);
-                    else v = ((ja[0] * Mrow(3) + ja[1] * Mrow(4)) + ja[2] * Mrow(5)) + ja[3] * Mrow(6);
+                    const double v = pose_local_entry(sh.full, sh.pose + 3, ar, bc);
                     if (tid < 36) sh.H[ar][bc] = v; else sh.gv[ar] = -v;
                 }
             }
@@ -493,6 +475,7 @@ __global__ __launch_bounds__(kCoopBlock, 2) void k_iterate_coop(AssocArgs S, Ass
                 else {
                     sh.status = 0;
                     sh.pose[0] += d[0]; sh.pose[1] += d[1]; sh.pose[2] += d[2];
+                    // (quat_plus with sinc_cos_halving of lili_solve_dev.h, written out: see gn_solve_wave)
                     const double nd2 = d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
                     if (nd2 > 0.0) {
                         double sbd, cw;

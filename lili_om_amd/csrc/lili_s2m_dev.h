@@ -1067,5 +1067,20 @@ __device__ __forceinline__ bool xchg_gather(const double* src, int count, unsign
     __builtin_amdgcn_wave_barrier();
     return ok;
 }
+// ONE wave of workgroup b of nb: tot[e] = sum of the nb partials at `part` (granules, `stride` doubles each), the same bits in every workgroup.  Up to kLmGroup
+// workgroups (ng == 1): one hop — everybody adds all partials in index order.  More: two hops — the first workgroup of every group of kLmGroup adds its members'
+// partials in index order and publishes the group sum at `gsum` (ng of them, same stride); everybody then adds the group sums in index order.
+// `vals` = LDS scratch [kLmGroup][NE].  Returns false if a (bounded) wait gave up.
+template <int NE>
+__device__ __forceinline__ bool xchg_total(const double* part, double* gsum, int b, int nb, int ng, unsigned long long key, double (*vals)[NE], double* tot,
+                                           int stride = kPartialStride) {
+    if (ng <= 1) return xchg_gather<NE>(part, nb, key, vals, tot, stride);
+    bool ok = true;
+    if (b % kLmGroup == 0) {
+        ok = xchg_gather<NE>(part + (size_t)b * stride, min(kLmGroup, nb - b), key, vals, tot, stride);
+        if ((threadIdx.x & 63) < NE) store_granule(gsum + (size_t)(b / kLmGroup) * stride + 2 * (threadIdx.x & 63), tot[threadIdx.x & 63], key);
+    }
+    return xchg_gather<NE>(gsum, ng, key, vals, tot, stride) && ok;
+}
 
 }  // namespace lili

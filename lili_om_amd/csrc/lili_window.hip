@@ -19,7 +19,7 @@
 //                          in LDS.  lili_marg_schur uploads a host system into the same kernel.
 //
 // The factors are restated from the semantics SURVEY records; the checker's restatement (tests/test_window_solve_gpu.py) is the referee.
-#include "lili_s2m_dev.h"
+#include "lili_solve_dev.h"
 #include "lili_launch.h"
 
 #include <cmath>
@@ -82,13 +82,6 @@ __device__ __forceinline__ void plus_jac(const double* q, double m[4][3]) {
     m[2][0] = -z; m[2][1] = w; m[2][2] = x;
     m[3][0] = y; m[3][1] = -x; m[3][2] = w;
 }
-__device__ __forceinline__ void qmat3(dq q, double R[3][3]) {      // Eigen toRotationMatrix
-    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
-    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w, txx = tx * q.x, txy = ty * q.x, txz = tz * q.x, tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-    R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
-    R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
-    R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
-}
 __device__ __forceinline__ d3 m3v(const double* m, d3 v) {
     return {m[0] * v.x + m[1] * v.y + m[2] * v.z, m[3] * v.x + m[4] * v.y + m[5] * v.z, m[6] * v.x + m[7] * v.y + m[8] * v.z};
 }
@@ -120,8 +113,9 @@ __device__ __noinline__ void win_imu_raw(const WinImuDev& f, const double* xi, c
         J[i][30] = d3c(rp, i); J[3 + i][30] = 2.0 * (i == 0 ? rq.x : i == 1 ? rq.y : rq.z); J[6 + i][30] = d3c(rv, i);
         J[9 + i][30] = d3c(rba, i); J[12 + i][30] = d3c(rbg, i);
     }
-    double Ri[3][3];
-    qmat3(Qi_inv, Ri);
+    const double qi[4] = {Qi_inv.w, Qi_inv.x, Qi_inv.y, Qi_inv.z};
+    double Ri[9];
+    quat_to_mat(qi, Ri);
     double Pq_i[4][3], Pq_j[4][3];
     plus_jac(xi + 3, Pq_i);
     plus_jac(xj + 3, Pq_j);
@@ -147,17 +141,17 @@ __device__ __noinline__ void win_imu_raw(const WinImuDev& f, const double* xi, c
     dq_block(tmp, 0);
     dq_block(tmp1, 6);
     for (int i = 0; i < 3; i++) for (int c = 0; c < 3; c++) {
-        J[i][c] = -Ri[i][c];                    // d r_p / d Pi
-        J[i][6 + c] = -Ri[i][c] * s;            // d r_p / d Vi
+        J[i][c] = -Ri[3 * i + c];                    // d r_p / d Pi
+        J[i][6 + c] = -Ri[3 * i + c] * s;            // d r_p / d Vi
         J[i][9 + c] = -f.dp_dba[3 * i + c];
         J[i][12 + c] = -f.dp_dbg[3 * i + c];
-        J[6 + i][6 + c] = -Ri[i][c];            // d r_v / d Vi
+        J[6 + i][6 + c] = -Ri[3 * i + c];            // d r_v / d Vi
         J[6 + i][9 + c] = -f.dv_dba[3 * i + c];
         J[6 + i][12 + c] = -f.dv_dbg[3 * i + c];
         J[9 + i][9 + c] = i == c ? -1.0 : 0.0;
         J[12 + i][12 + c] = i == c ? -1.0 : 0.0;
-        J[i][15 + c] = Ri[i][c];                // d r_p / d Pj
-        J[6 + i][21 + c] = Ri[i][c];            // d r_v / d Vj
+        J[i][15 + c] = Ri[3 * i + c];                // d r_p / d Pj
+        J[6 + i][21 + c] = Ri[3 * i + c];            // d r_v / d Vj
         J[9 + i][24 + c] = i == c ? 1.0 : 0.0;
         J[12 + i][27 + c] = i == c ? 1.0 : 0.0;
     }
@@ -230,29 +224,14 @@ __device__ __noinline__ void win_build(const WinDev* __restrict__ pb, WinSys& s)
     for (int e = lane; e < n_imu * 15 * 31; e += 64) (&s.Jraw[0][0][0])[e] = 0.0;
     LILI_WAVE_SYNC();
     double cost = 0.0;      // lane 0's is the one that counts
-    // ---- lidar: H_kk = P^T G77 P, g_k = P^T G7r with P = diag(I3, plus-Jacobian(q_k)) (lm_local_system of lili_s2m_lm.hip)
+    // ---- lidar: H_kk = P^T G77 P, g_k = P^T G7r with P = diag(I3, plus-Jacobian(q_k)) (pose_local_entry)
     for (int k = 0; k < n_kf; k++) {
         const double* gram = s.lid[k];
-        const double x0 = s.x[k][3], x1 = s.x[k][4], x2 = s.x[k][5], x3 = s.x[k][6];
-        auto jcol = [&](int c, double o[4]) {
-            o[0] = c == 0 ? -x1 : c == 1 ? -x2 : -x3;
-            o[1] = c == 0 ? x0 : c == 1 ? x3 : -x2;
-            o[2] = c == 0 ? -x3 : c == 1 ? x0 : x1;
-            o[3] = c == 0 ? x2 : c == 1 ? -x1 : x0;
-        };
         if (lane < 42) {
             const int a = lane < 36 ? lane / 6 : lane - 36, b = lane < 36 ? lane % 6 : 7;
-            double jb[4] = {0, 0, 0, 0}, ja[4] = {0, 0, 0, 0};
-            if (b >= 3 && b < 6) jcol(b - 3, jb);
-            if (a >= 3) jcol(a - 3, ja);
-            auto Mrow = [&](int i) -> double {
-                if (b < 3 || b == 7) return gram[i * 8 + b];
-                return ((gram[i * 8 + 3] * jb[0] + gram[i * 8 + 4] * jb[1]) + gram[i * 8 + 5] * jb[2]) + gram[i * 8 + 6] * jb[3];
-            };
             double v;
             if constexpr (kMarg) v = gram[(a < 3 ? a : a + 1) * 8 + (b < 3 || b == 7 ? b : b + 1)];      // rows / columns {0,1,2}, {4,5,6} and column 7, as lili_marg_add_lidar takes them
-            else if (a < 3) v = Mrow(a);
-            else v = ((ja[0] * Mrow(3) + ja[1] * Mrow(4)) + ja[2] * Mrow(5)) + ja[3] * Mrow(6);
+            else v = pose_local_entry(gram, s.x[k] + 3, a, b);
             if (lane < 36) s.H[(15 * k + a) * N + 15 * k + b] = v; else s.g[15 * k + a] = v;
         }
         cost += gram[64];
@@ -381,33 +360,29 @@ struct WinShared {
     double x[kWinMaxKf][16];       // accepted point
     double vals[kWinGroup][40];
     double tot[kWinMaxKf][40];
-    double cost, radius, decrease, model_change, step_norm;
-    int it, n_ok, term, go, n_invalid, stalled, take, max_iter;
+    LmTrust t;                     // trust-region state and options (those of W.a[0])
     int counts[2];
-    double function_tolerance, gradient_tolerance, parameter_tolerance;
-    double max_radius, min_radius, min_relative_decrease, min_lm_diagonal, max_lm_diagonal;
 };
 
-// The trust-region step from the accepted point by ONE wave (lm_propose of lili_s2m_lm.hip on N dimensions): returns with sh.go = 1 and sh.sys.x = candidate,
-// or sh.go = 0.  (H_s + D^2) d = -g_s by a left-looking Cholesky factorisation, lane = row; a non-positive pivot is an INVALID step like a model that does
+// The trust-region step from the accepted point by ONE wave (lm_propose of lili_s2m_lm.hip on N dimensions, the same LmTrust bookkeeping): returns with sh.t.go = 1 and
+// sh.sys.x = candidate, or sh.t.go = 0.  (H_s + D^2) d = -g_s by a left-looking Cholesky factorisation, lane = row; a non-positive pivot is an INVALID step like a model that does
 // not descend (radius halved, five in a row end the solve with LILI_LM_NUMERICAL_FAILURE).
 __device__ __noinline__ void win_propose(WinShared& sh, const int n_kf) {
     const int lane = threadIdx.x & 63;
     const int N = 15 * n_kf;
     const bool in = lane < N;
     double* A = sh.sys.H;
+    LmTrust& t = sh.t;
     for (;;) {
-        const int it = sh.it;
-        if (it >= sh.max_iter) { if (lane == 0) { sh.term = LILI_LM_MAX_ITERATIONS; sh.go = 0; } return; }
+        const int it = t.it;
         double gmax = 0.0;
         for (int i = 0; i < N; i++) gmax = fmax(gmax, fabs(sh.g[i]));
-        if (gmax <= sh.gradient_tolerance) { if (lane == 0) { sh.term = LILI_LM_GRADIENT_TOLERANCE; sh.it = it + 1; sh.go = 0; } return; }
-        const double radius = sh.radius;
-        if (!(radius > sh.min_radius)) { if (lane == 0) { sh.term = LILI_LM_MIN_RADIUS; sh.go = 0; } return; }
+        if (!lm_trust_gate(t, gmax, lane)) return;
+        const double radius = t.radius;
         for (int e = lane; e < N * N; e += 64) {
             const int i = e / N, j = e - N * i;
             double v = sh.H[e] * sh.scale[i] * sh.scale[j];
-            if (i == j) v += fmin(fmax(v, sh.min_lm_diagonal), sh.max_lm_diagonal) / radius;      // D^2 = clamp(diag H_s) / radius
+            if (i == j) v += fmin(fmax(v, t.min_lm_diagonal), t.max_lm_diagonal) / radius;      // D^2 = clamp(diag H_s) / radius
             A[e] = v;
         }
         LILI_WAVE_SYNC();
@@ -447,12 +422,7 @@ __device__ __noinline__ void win_propose(WinShared& sh, const int n_kf) {
         for (int i = 0; i < N; i++) mc += sh.tr[i];
         mc = -mc;
         if (!okc || !(mc > 0.0)) {
-            // Ceres' INVALID step (TrustRegionMinimizer::HandleInvalidStep): the iteration counts, nothing is evaluated, the radius is halved
-            const int n_inv = sh.n_invalid + 1;
-            LILI_WAVE_SYNC();
-            if (lane == 0) { sh.n_invalid = n_inv; sh.radius = radius * 0.5; sh.it = it + 1; }
-            if (n_inv >= 5) { if (lane == 0) { sh.term = LILI_LM_NUMERICAL_FAILURE; sh.go = 0; } return; }
-            LILI_WAVE_SYNC();
+            if (!lm_trust_invalid(t, radius, it, lane)) return;
             continue;
         }
         if (in) sh.d[lane] = bv * sh.scale[lane];          // delta in the unscaled local coordinates
@@ -463,28 +433,13 @@ __device__ __noinline__ void win_propose(WinShared& sh, const int n_kf) {
             double* xn = sh.sys.x[lane];
             for (int i = 0; i < 3; i++) xn[i] = x[i] + d[i];
             for (int i = 0; i < 9; i++) xn[7 + i] = x[7 + i] + d[6 + i];
-            const double nd2 = d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
-            if (nd2 > 0.0) {      // ceres::QuaternionParameterization::Plus; sin / cos as lm_propose takes them
-                double sbd, cw;
-                if (nd2 < 0.25) sinc_cos_small(nd2, sbd, cw);
-                else {
-                    double h2 = nd2; int k = 0;
-                    while (h2 >= 0.25 && k < 60) { h2 *= 0.25; k++; }
-                    double sc, c;
-                    sinc_cos_small(h2, sc, c);
-                    double sn = sc * sqrt(h2);
-                    for (int i = 0; i < k; i++) { const double s2 = 2.0 * sn * c, c2 = c * c - sn * sn; sn = s2; c = c2; }
-                    sbd = sn / sqrt(nd2); cw = c;
-                }
-                const dq r = qmul(dq{cw, sbd * d[3], sbd * d[4], sbd * d[5]}, dq{x[3], x[4], x[5], x[6]});
-                xn[3] = r.w; xn[4] = r.x; xn[5] = r.y; xn[6] = r.z;
-            } else { xn[3] = x[3]; xn[4] = x[4]; xn[5] = x[5]; xn[6] = x[6]; }
+            quat_plus(x + 3, d + 3, xn + 3, sinc_cos_halving);
         }
         if (lane == 0) {
             double n2 = 0.0;
             for (int i = 0; i < N; i++) n2 += sh.d[i] * sh.d[i];
-            sh.model_change = mc; sh.n_invalid = 0; sh.step_norm = sqrt(n2);
-            sh.go = 1;
+            t.model_change = mc; t.n_invalid = 0; t.step_norm = sqrt(n2);
+            t.go = 1;
         }
         return;
     }
@@ -511,14 +466,8 @@ __global__ __launch_bounds__(kWinThreads) void k_window_solve(WinSolveArgs W, Ma
         const int n_e = (a.E.n_q > 0 && a.E.block_counts) ? sum_block_counts(a.E.block_counts, a.E.n_bc) : 0;
         for (int e = threadIdx.x; e < 16 * n_kf; e += blockDim.x) { sh.x[e / 16][e % 16] = pb->state[e]; sh.sys.x[e / 16][e % 16] = pb->state[e]; }
         if (threadIdx.x == 0) {
-            const LmArgs& o = W.a[0];
             sh.counts[0] = n_s; sh.counts[1] = n_e;
-            sh.max_iter = o.max_iter;
-            sh.function_tolerance = o.function_tolerance; sh.gradient_tolerance = o.gradient_tolerance; sh.parameter_tolerance = o.parameter_tolerance;
-            sh.max_radius = o.max_radius; sh.min_radius = o.min_radius; sh.min_relative_decrease = o.min_relative_decrease;
-            sh.min_lm_diagonal = o.min_lm_diagonal; sh.max_lm_diagonal = o.max_lm_diagonal;
-            sh.radius = o.initial_radius; sh.decrease = 2.0; sh.it = 0; sh.n_ok = 0; sh.term = LILI_LM_MAX_ITERATIONS; sh.go = 1; sh.stalled = 0; sh.take = 0; sh.n_invalid = 0;
-            sh.cost = 0.0; sh.model_change = 0.0; sh.step_norm = 0.0;
+            lm_trust_init(sh.t, W.a[0]);
         }
         __syncthreads();
     }
@@ -543,12 +492,10 @@ __global__ __launch_bounds__(kWinThreads) void k_window_solve(WinSolveArgs W, Ma
             bool ok = true;
             for (int k = 0; k < n_kf; k++)
                 ok = xchg_gather<40>(W.a[k].part + (size_t)par * W.a[k].nb * kPartialStride, W.a[k].nb, key, sh.vals, sh.tot[k]) && ok;
-            if (!ok && threadIdx.x == 0) sh.stalled = 1;
+            if (!ok && threadIdx.x == 0) sh.t.stalled = 1;
             for (int k = 0; k < n_kf; k++) {
-                const int lane = threadIdx.x, r = lane >> 3, c = lane & 7;
-                const int lo = r < c ? r : c, hi = r < c ? c : r;
-                sh.sys.lid[k][lane] = sh.tot[k][lo * 8 - lo * (lo - 1) / 2 + (hi - lo)];
-                if (lane == 0) sh.sys.lid[k][64] = sh.tot[k][36];
+                gram_tri_to_full(sh.tot[k], sh.sys.lid[k]);
+                if (threadIdx.x == 0) sh.sys.lid[k][64] = sh.tot[k][36];
             }
             LILI_WAVE_SYNC();
             win_build<false>(pb, sh.sys);
@@ -556,52 +503,26 @@ __global__ __launch_bounds__(kWinThreads) void k_window_solve(WinSolveArgs W, Ma
             if (eval == 0) {
                 for (int e = threadIdx.x; e < N * N; e += 64) sh.H[e] = sh.sys.H[e];
                 if (threadIdx.x < N) { sh.g[threadIdx.x] = sh.sys.g[threadIdx.x]; sh.scale[threadIdx.x] = 1.0 / (1.0 + sqrt(sh.sys.H[threadIdx.x * N + threadIdx.x])); }      // Jacobi scaling, kept for the whole solve
-                if (threadIdx.x == 0) { sh.cost = sh.sys.cost; cost0 = sh.cost; if (sh.stalled) { sh.term = LILI_LM_STALLED; sh.go = 0; } }
+                if (threadIdx.x == 0) { sh.t.cost = sh.sys.cost; cost0 = sh.t.cost; if (sh.t.stalled) { sh.t.term = LILI_LM_STALLED; sh.t.go = 0; } }
             } else {
                 if (threadIdx.x == 0) {
-                    int accepted = 0, stop = 0;
-                    const double new_cost = sh.sys.cost;
-                    const double rho = (sh.cost - new_cost) / sh.model_change;
-                    if (boss && W.summary && n_log < LILI_LM_MAX_LOG) {
-                        lili_lm_iteration& L = W.summary->it[n_log];
-                        L.cost = sh.cost; L.new_cost = new_cost; L.rho = rho; L.radius = sh.radius; L.step_norm = sh.step_norm; L.accepted = 0; L.iteration = sh.it;
-                    }
                     double xn2 = 0.0;
                     for (int k = 0; k < n_kf; k++) for (int i = 0; i < 16; i++) xn2 += sh.x[k][i] * sh.x[k][i];
-                    const double xnorm = sqrt(xn2);
-                    if (sh.stalled) { sh.term = LILI_LM_STALLED; stop = 1; }
-                    // Ceres returns from ParameterToleranceReached / FunctionToleranceReached BEFORE HandleSuccessfulStep: that candidate is never taken
-                    else if (sh.step_norm <= sh.parameter_tolerance * (xnorm + sh.parameter_tolerance)) { sh.term = LILI_LM_PARAMETER_TOLERANCE; stop = 1; }
-                    else if (fabs(sh.cost - new_cost) <= sh.function_tolerance * sh.cost) { sh.term = LILI_LM_FUNCTION_TOLERANCE; stop = 1; }
-                    else if (rho > sh.min_relative_decrease) {
-                        accepted = 1;
-                        const double f = 2.0 * rho - 1.0;
-                        sh.radius = fmin(sh.max_radius, sh.radius / fmax(1.0 / 3.0, 1.0 - f * f * f));
-                        sh.decrease = 2.0;
-                    } else {
-                        sh.radius = sh.radius / sh.decrease; sh.decrease *= 2.0;      // LevenbergMarquardtStrategy::StepRejected
-                        if (!(sh.radius > sh.min_radius)) { sh.term = sh.it + 1 >= sh.max_iter ? LILI_LM_MAX_ITERATIONS : LILI_LM_MIN_RADIUS; stop = 1; }
-                    }
-                    if (accepted) { sh.cost = new_cost; sh.n_ok++; }
-                    if (boss && W.summary && n_log < LILI_LM_MAX_LOG) W.summary->it[n_log].accepted = accepted;
-                    n_log++;
-                    sh.it++;
-                    sh.go = stop ? 0 : 1;
-                    sh.take = accepted;
+                    lm_trust_judge(sh.t, sh.sys.cost, sqrt(xn2), W.summary, n_log, boss);
                 }
                 LILI_WAVE_SYNC();
-                if (sh.take) {
+                if (sh.t.take) {
                     for (int e = threadIdx.x; e < N * N; e += 64) sh.H[e] = sh.sys.H[e];
                     if (threadIdx.x < N) sh.g[threadIdx.x] = sh.sys.g[threadIdx.x];
                     for (int e = threadIdx.x; e < 16 * n_kf; e += 64) sh.x[e / 16][e % 16] = sh.sys.x[e / 16][e % 16];
                 }
             }
             LILI_WAVE_SYNC();
-            if (sh.go) win_propose(sh, n_kf);      // the next candidate (or the end), from the accepted point
+            if (sh.t.go) win_propose(sh, n_kf);      // the next candidate (or the end), from the accepted point
             LILI_WAVE_SYNC();
         }
         __syncthreads();
-        if (!sh.go) break;
+        if (!sh.t.go) break;
     }
     if (bid == 0 && threadIdx.x < 64) {
         const int lane = threadIdx.x;
@@ -609,15 +530,10 @@ __global__ __launch_bounds__(kWinThreads) void k_window_solve(WinSolveArgs W, Ma
         if (lane < n_kf) {
             SlotState* st = W.a[lane].state;
             for (int i = 0; i < 7; i++) st->pose[i] = sh.x[lane][i];
-            st->gn_status = (sh.term == LILI_LM_STALLED || sh.term == LILI_LM_NUMERICAL_FAILURE) ? 1 : 0;
-            st->iters += sh.n_ok;
+            st->gn_status = (sh.t.term == LILI_LM_STALLED || sh.t.term == LILI_LM_NUMERICAL_FAILURE) ? 1 : 0;
+            st->iters += sh.t.n_ok;
         }
-        if (lane == 0 && W.summary) {
-            W.summary->iterations = sh.it; W.summary->successful_steps = sh.n_ok; W.summary->termination = sh.term;
-            W.summary->initial_cost = cost0; W.summary->final_cost = sh.cost; W.summary->final_radius = sh.radius;
-            W.summary->n_logged = n_log < LILI_LM_MAX_LOG ? n_log : LILI_LM_MAX_LOG;
-            W.summary->n_surf = sh.counts[0]; W.summary->n_edge = sh.counts[1];
-        }
+        if (lane == 0 && W.summary) lm_write_summary(W.summary, sh.t, cost0, n_log, sh.counts);
     }
 }
 
