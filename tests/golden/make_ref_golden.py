@@ -5,6 +5,8 @@ tests/golden/{s2m,extract}_*.npz, which come from the oracle — pin the oracle 
 
   ref_rot.npz      LiLi-OM-ROT/src/Preprocessing.cpp driven with 4 clouds + a 200 Hz gyro stream: the three published
                    clouds of the 2 processed scans (/lidar_cloud_cutted, /edge_features, /surf_features)
+  ref_rot_cases.npz the same node on the designed scans of tests/rot_cases.py (16 / 32 / 64 rings, their ds_rate and extrinsic), one case per run
+                   with two filler scans behind it: per published cloud the row count, a sha-256 and the rows themselves (every 8 k-th row of a large cloud)
   ref_livox.npz    LiLi-OM/src/Preprocessing.cpp, same protocol (large clouds stored as sha256 + every 8th row)
   ref_frontend.npz LiLi-OM/src/LidarOdometry.cpp (the whole front-end node) fed with the Livox node's output for 6 frames of a
                    moving synthetic sequence; ceres::Solve = the documented one-GN-step stand-in (oracle/refshim/ref_lo.cpp):
@@ -61,10 +63,15 @@ def rot_inputs():
         w = synth.make_workload(n_map=200_000, n_az=200, half_extent=(150.0, 150.0), seed=synth.SEED_SCENE + 40 + s)
         refl = np.random.default_rng(40 + s).integers(1, 255, w["scan_xyz"].shape[0]).astype(np.float32)
         scans.append(np.concatenate([w["scan_xyz"], refl[:, None]], 1).astype(np.float32))
+    return (scans,) + rot_gyro()
+
+
+def rot_gyro():
+    """Scan stamps and the 200 Hz gyro stream of rot_inputs()."""
     stamps = 100.0 + 0.1 * np.arange(N_SCANS_IN)
     imu_t = 99.95 + 0.005 * np.arange(100)
     gyr = 0.2 * np.random.default_rng(5).standard_normal((100, 3)) + np.array([0.1, -0.05, 0.3])
-    return scans, stamps, imu_t, gyr
+    return stamps, imu_t, gyr
 
 
 def livox_inputs():
@@ -108,6 +115,57 @@ def run_rot(params=None, inputs=None):
         assert len(key) == full.shape[0], "duplicate rows in the reference's full cloud"
         edge = np.ascontiguousarray(d[f"edge{k}"], np.float32).view(np.uint32)
         d[f"edge_src{k}"] = np.array([key[row.tobytes()] for row in edge], np.int32)
+    return d
+
+
+# ---- the designed scans of tests/rot_cases.py through the reference's ROT node -> ref_rot_cases.npz
+ROT_CASES_FULL_ROWS = 512      # a published cloud of up to this many rows is stored whole; a larger one as sha-256 + every `stride`-th row, stride a multiple of 8
+
+
+def rot_cases():
+    """The cases whose parameters the node can express (line_num, ds_rate, the extrinsic; near range 3 m and the 0.6 m leaf are fixed in the reference)."""
+    sys.path.insert(0, ROOT)
+    from tests import rot_cases as RC
+    return [c for c in RC.all_cases() if c["ref"]]
+
+
+def rot_case_inputs(c):
+    """One case as the node needs it: the scan, then two filler scans (the node holds back two clouds), the stamps and the gyro stream of rot_inputs()
+    — q_imu is whatever the node integrates up to the second stamp, not the case's own."""
+    from tests import rot_cases as RC
+    stamps, imu_t, gyr = rot_gyro()
+    filler = RC.scene_scan(0.8, 2 * np.pi, 60, "vlp16")[0]
+    return [c["raw"], filler, filler], stamps[:3], imu_t, gyr
+
+
+def rot_case_params(c):
+    q = c["q_lb"]
+    return dict(ROT_PARAMS, **{"/preprocessing/line_num": c["n_scans"], "/preprocessing/ds_rate": c["ds_rate"], "/backend_fusion/ql2b_w": q[0],
+                               "/backend_fusion/ql2b_x": q[1], "/backend_fusion/ql2b_y": q[2], "/backend_fusion/ql2b_z": q[3]})
+
+
+def cloud_stride(n):
+    return 1 if n <= ROT_CASES_FULL_ROWS else 8 * max(1, -(-n // 2048))
+
+
+def run_rot_cases():
+    d = {}
+    for c in rot_cases():
+        scans, stamps, imu_t, gyr = rot_case_inputs(c)
+        out = R.run_scans("rot", rot_case_params(c), scans, stamps, imu_t, gyr)
+        assert len(out) == 1 and out[0]["stamp"] == stamps[0], c["name"]
+        k = c["name"]
+        for name in ("cutted", "edge", "surf"):
+            a = np.ascontiguousarray(out[0][name][:, PAYLOAD_ROT], np.float32)
+            d[f"{k}/{name}_n"] = a.shape[0]
+            d[f"{k}/{name}_sha"] = sha(a)
+            d[f"{k}/{name}_rows"] = a[::cloud_stride(a.shape[0])]
+        # the indices the reference pushed, where a row of its full cloud names one point (see run_rot); scans with repeated rows go without
+        full = np.ascontiguousarray(out[0]["cutted"][:, PAYLOAD_ROT], np.float32).view(np.uint32)
+        key = {row.tobytes(): i for i, row in enumerate(full)}
+        if len(key) == full.shape[0] and out[0]["edge"].shape[0] <= 4 * ROT_CASES_FULL_ROWS:
+            edge = np.ascontiguousarray(out[0]["edge"][:, PAYLOAD_ROT], np.float32).view(np.uint32)
+            d[f"{k}/edge_src"] = np.array([key[row.tobytes()] for row in edge], np.int32)
     return d
 
 
@@ -396,6 +454,7 @@ def main():
     if not R.build():
         raise SystemExit("/root/reference is not present: the reference fixtures can only be generated in the build container")
     np.savez_compressed(os.path.join(HERE, "ref_rot.npz"), **run_rot())
+    np.savez_compressed(os.path.join(HERE, "ref_rot_cases.npz"), **run_rot_cases())
     np.savez_compressed(os.path.join(HERE, "ref_livox.npz"), **run_livox())
     np.savez_compressed(os.path.join(HERE, "ref_factors.npz"), **run_factors())
     np.savez_compressed(os.path.join(HERE, "ref_frontend.npz"), **run_frontend())
@@ -405,7 +464,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "ref_marg.npz"), **run_marg())
     np.savez_compressed(os.path.join(HERE, "ref_localmap.npz"), **run_localmap())
     np.savez_compressed(os.path.join(HERE, "ref_cfg2.npz"), **run_cfg2())
-    for f in ("ref_cfg2.npz", "ref_rot.npz", "ref_livox.npz", "ref_factors.npz", "ref_frontend.npz", "ref_frontend_R.npz", "ref_backend.npz", "ref_format.npz", "ref_marg.npz", "ref_localmap.npz"):
+    for f in ("ref_cfg2.npz", "ref_rot.npz", "ref_rot_cases.npz", "ref_livox.npz", "ref_factors.npz", "ref_frontend.npz", "ref_frontend_R.npz", "ref_backend.npz", "ref_format.npz", "ref_marg.npz", "ref_localmap.npz"):
         print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")
 
 

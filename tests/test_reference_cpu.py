@@ -41,11 +41,11 @@ def _same_npz(d, g):
 
 
 # ------------------------------------------------------------------ the reference build itself
-@pytest.mark.parametrize("which", ["rot", "livox", "factors", "frontend", "frontend_R", "backend", "format", "marg", "localmap"])
+@pytest.mark.parametrize("which", ["rot", "rot_cases", "livox", "factors", "frontend", "frontend_R", "backend", "format", "marg", "localmap"])
 def test_reference_build_reproduces_fixtures(which):
     if not M.R.available():
         pytest.skip("oracle/_ref not built (needs /root/reference; build container only)")
-    d = {"rot": M.run_rot, "livox": M.run_livox, "factors": M.run_factors, "frontend": M.run_frontend, "frontend_R": M.run_frontend_rot, "backend": M.run_backend, "format": M.run_format,
+    d = {"rot": M.run_rot, "rot_cases": M.run_rot_cases, "livox": M.run_livox, "factors": M.run_factors, "frontend": M.run_frontend, "frontend_R": M.run_frontend_rot, "backend": M.run_backend, "format": M.run_format,
          "marg": M.run_marg, "localmap": M.run_localmap}[which]()
     _same_npz(d, np.load(os.path.join(G, f"ref_{which}.npz")))
 
@@ -86,6 +86,37 @@ def test_oracle_equals_reference_rot(oracle):
         for key in ("full", "surf"):
             assert np.array_equal(_bits(f[key]), _bits(r[key])), key
         assert np.array_equal(f["edge_idx"], r["edge_idx"]) and np.array_equal(f["label"], r["label"])
+
+
+def test_oracle_equals_reference_rot_cases(oracle):
+    """The designed scans of tests/rot_cases.py — both endOri corrections, the four wrap branches, early and missing latches, relTime outside [0, 1], the three ring
+    tables at every id boundary, rings of 0 .. 24 600 points, picks at their caps and across segment borders, voxels, the slerp's branches — as the reference's own
+    Preprocessing.cpp published them (tests/golden/ref_rot_cases.npz): the oracle's literal mode gives every cloud bit for bit, and where no two curvatures of a
+    segment are equal, the definition the HIP extractor follows (glibc's float atan / atan2 restated, index tie-break, in-order centroids) picks the same features."""
+    g = np.load(os.path.join(G, "ref_rot_cases.npz"))
+    cases = M.rot_cases()
+    assert len(cases) >= 50 and {k.split("/")[0] for k in g.files} == {c["name"] for c in cases}
+    n_src = 0
+    for c in cases:
+        _, stamps, imu_t, gyr = M.rot_case_inputs(c)
+        q_imu = _q_imu_per_scan(oracle.ImuIntegrator(), stamps, imu_t, gyr, 0)      # every case is a run of its own
+        assert abs(np.linalg.norm(q_imu[1:])) > 1e-3            # the deskew is exercised
+        P = dict(n_scans=c["n_scans"], ds_rate=c["ds_rate"])
+        r = oracle.extract_rot(c["raw"], q_imu, c["q_lb"], oracle.rot_params(atan_mode=0, stable_sort=0, **P))
+        k = c["name"]
+        for name, a in (("cutted", r["full"]), ("edge", r["full"][r["edge_idx"]]), ("surf", r["surf"])):     # /lidar_cloud_cutted, /edge_features, /surf_features
+            assert a.shape[0] == int(g[f"{k}/{name}_n"]), (k, name)
+            assert np.array_equal(_bits(a[::M.cloud_stride(a.shape[0])]), _bits(g[f"{k}/{name}_rows"])), (k, name)
+            assert _sha(np.ascontiguousarray(a, np.float32)) == str(g[f"{k}/{name}_sha"]), (k, name)
+        if f"{k}/edge_src" in g.files:                           # the indices the reference run pushed
+            assert np.array_equal(r["edge_idx"], g[f"{k}/edge_src"]), k
+            n_src += 1
+        if r["n_ties"] == 0:
+            d = oracle.extract_rot(c["raw"], q_imu, c["q_lb"], oracle.rot_params(atan_mode=2, stable_sort=1, **P))
+            assert np.array_equal(_bits(d["full"]), _bits(r["full"])) and np.array_equal(d["full_src"], r["full_src"]), k
+            assert np.array_equal(d["edge_idx"], r["edge_idx"]) and np.array_equal(d["label"], r["label"]) and np.array_equal(d["surf_cnt"], r["surf_cnt"]), k
+            np.testing.assert_allclose(d["surf"], r["surf"], rtol=2e-6, atol=2e-5)
+    assert n_src >= 50
 
 
 def test_oracle_equals_reference_livox(oracle):
