@@ -40,7 +40,7 @@ enum {
     LILI_E_STATE = -3,    /* call order violated (e.g. associate before map_set) */
     LILI_E_NOMEM = -4,
     LILI_E_NODEVICE = -5, /* no usable gfx950 device: there is no CPU fallback */
-    LILI_E_NUMERIC = -6   /* a bounded iteration did not converge (lili_marg_schur, lili_window_marginalize); nothing was written */
+    LILI_E_NUMERIC = -6   /* a bounded iteration did not converge (lili_marg_schur, lili_window_marginalize, lili_window_cycle); nothing was written */
 };
 enum { LILI_KIND_SURF = 0, LILI_KIND_EDGE = 1 };
 enum { LILI_MASK_SURF = 1, LILI_MASK_EDGE = 2 };
@@ -613,9 +613,10 @@ int lili_gram_to_factor(const double gram[64], double cost, double residuals[9],
  * robustified by params->loss; correspondences stay fixed), one IMU factor between consecutive keyframes (ImuFactor.h:18-144), and either the
  * marginalisation prior (MarginalizationFactor::Evaluate) or the speed-bias priors (PriorFactor.h:13-23); the last three enter without a loss.
  * The prior of the NEXT window (MarginalizationInfo::PreMarginalize + Marginalize: the factors again at the solved state, Schur complement over the
- * oldest keyframe, two eigen-decompositions) is lili_window_marginalize below: a keyframe cycle is prepare -> solve -> marginalise.
- * The IMU factors' records come from lili_imu_preintegrate below (raw samples in, lili_window_imu out).  What stays with the caller: the write-back
- * gates and the quaternion sign unification — their RESULTS are handed in as the plain arrays below (host memory, copied once per call).  A state is n_kf x 16 doubles: t[3], q[4], speed-bias[9] per keyframe; "local" means 15 per keyframe: t, the 3 quaternion-plus
+ * oldest keyframe, two eigen-decompositions) is lili_window_marginalize below; lili_window_cycle does solve, sign unification, that prior and the
+ * write-back gates in one call and keeps the prior on the device: a keyframe cycle is prepare -> pre-integrate -> cycle.
+ * The IMU factors' records come from lili_imu_preintegrate below (raw samples in, lili_window_imu out).  With the separate calls the write-back
+ * gates and the quaternion sign unification stay with the caller — their RESULTS are handed in as the plain arrays below (host memory, copied once per call).  A state is n_kf x 16 doubles: t[3], q[4], speed-bias[9] per keyframe; "local" means 15 per keyframe: t, the 3 quaternion-plus
  * coordinates, speed-bias. */
 #define LILI_WINDOW_MAX_KF 4          /* 15 * n_kf <= 60 local dimensions: every matrix of the solve stays in LDS */
 #define LILI_WINDOW_STATE_DOUBLES 16
@@ -699,6 +700,53 @@ typedef struct lili_window_prior_storage {
  * LILI_E_NUMERIC — leave `out` and the slots' poses untouched. */
 int lili_window_marginalize(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const double* state,
                             lili_window_prior_storage* out);
+
+/* ---- the window cycle in one call: solve, sign unification, next prior, write-back gates (DESIGN.md §7h "The cycle") ----
+ * lili_window_cycle is the chain
+ *   1. lili_window_solve(problem, state_in);
+ *   2. every keyframe's q with w < 0 negated (unifyQuaternion, L/src/BackendFusion.cpp:994-1006; -0.0 and NaN are left alone, as `< 0` leaves them);
+ *   3. lili_window_marginalize(problem, the unified state), every PRESENT row of problem->sb_prior replaced by that keyframe's solved speed-bias, as the
+ *      reference hands it in (L:1045-1057: the first marginalisation's speed-bias priors have residual 0 and information 225 I) — the prior stays in
+ *      device memory, in a buffer of the context no other call writes (the RESIDENT prior); lili_window_prior_get copies it out;
+ *   4. the write-back gates of L:1187-1284 between state_in and the unified state,
+ * as one upload, the solve launch, a single-wave write-back launch, the lidar launches at the slots' DEVICE poses, the marginalisation launch, one
+ * synchronisation and one read-back.  With use_resident_prior = 1 the problem's prior is the resident one — the prior step 3 of the previous cycle
+ * left, or the one lili_window_prior_set seeded — and reaches the kernels by a device-to-device copy.  The same kernels run on the same doubles:
+ * summary, `solved` and the prior are the chain's bits.
+ * Gates (strict '<' accepts; a NaN refuses):  pnorm = sqrt(d0*d0 + d1*d1 + d2*d2) of state_in - solved, summed left to right, likewise vnorm;
+ * qnorm = |vec(inverse(normalized(q_solved)) * q_in)| with normalized = q / sqrt(x*x + y*y + z*z + w*w), inverse = conjugate / squared norm and
+ * Eigen's product; the six bias components one by one, |d| < gate.  A refused component keeps the value of state_in.  next_state's q is, where the
+ * q gate accepts, Eigen 3.3's Quaterniond(normalized(q).toRotationMatrix()) (all four branches of the conversion), else state_in's q.  Only + - * /
+ * and sqrt, compiled without contraction: the bits of a plain IEEE restatement (tests/cycle_model.py).
+ * Returns and refuses what the chain returns and refuses (LILI_E_ARG, LILI_E_STATE, LILI_E_NUMERIC of lili_window_marginalize included), and:
+ * use_resident_prior = 1 together with problem->prior is LILI_E_ARG, without a resident prior LILI_E_STATE.  A refused cycle enqueues nothing; one that fails behind the solve's
+ * launches (LILI_E_NUMERIC, a launch or read-back error) puts the slots' states back and drains the stream: either way the resident prior, `out` and the
+ * slots' device poses are as they were.  A solve that ends LILI_LM_STALLED marginalises nothing (prior_updated = 0, the
+ * resident prior stays); one that ends LILI_LM_NUMERICAL_FAILURE goes on at the unchanged state, as the reference does.  Afterwards the slots'
+ * device poses are the unified (t, q) of `solved`. */
+typedef struct lili_window_cycle_options {
+    double gate_p, gate_q, gate_v, gate_ba, gate_bg;  /* 10, 10, 10, 22, 22: the literals of L:1215-1283; strict '<' accepts */
+    int32_t use_resident_prior;   /* 0: problem->prior (may be NULL) as today; 1: the prior the previous cycle left in this context */
+    int32_t reserved_;
+} lili_window_cycle_options;     /* NULL = the defaults, use_resident_prior = 0 */
+typedef struct lili_window_cycle_result {
+    lili_lm_summary summary;
+    double solved[16 * LILI_WINDOW_MAX_KF];      /* the solve's final state after sign unification (tmpTrans / tmpQuat / tmpSpeedBias) */
+    double abs_state[16 * LILI_WINDOW_MAX_KF];   /* after the gates: abs_poses (raw unified q), Ps, Vs / para_speed_bias */
+    double next_state[16 * LILI_WINDOW_MAX_KF];  /* abs_state with q replaced by Quaterniond(Rs): what the next "eigen to double" reads */
+    uint32_t refused[LILI_WINDOW_MAX_KF];        /* bit 0 p, 1 q, 2 v, 3..5 ba, 6..8 bg */
+    int32_t prior_updated, prior_n, prior_blocks, rank, sweeps_mm, sweeps_s;
+} lili_window_cycle_result;      /* rows of keyframes >= n_kf and summary rows that were not logged are zero */
+int lili_window_cycle(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const lili_lm_options* options,
+                      const lili_window_cycle_options* cycle_options, const double* state_in, lili_window_cycle_result* out);
+/* drops the resident prior (loop closure: L:2635-2638, marg = false) */
+int lili_window_cycle_reset(lili_ctx* ctx);
+/* copy of the resident prior (blocking); LILI_E_STATE when there is none.  rank / sweeps: those of the cycle that built it; after
+ * lili_window_prior_set the number of non-zero rows and 0, 0. */
+int lili_window_prior_get(lili_ctx* ctx, lili_window_prior_storage* out);
+/* seeds the resident prior from host memory (restart from a saved prior): validated as lili_window_problem::prior is, except that its keyframes
+ * are checked against LILI_WINDOW_MAX_KF here and against n_kf by the cycle that uses it.  A refusal leaves the resident prior as it was. */
+int lili_window_prior_set(lili_ctx* ctx, const lili_window_prior* prior);
 
 /* ---- IMU pre-integration on the device (lili_imu.hip) ---------------------------------------------
  * What the constructor plus one push_back(dt, acc, gyr) per sample leave in a Preintegration object (L/include/factors/Preintegration.h:27-173): the

@@ -117,6 +117,20 @@ class WindowPriorStorage(C.Structure):
                 ("x0", C.c_double * 64), ("r0", C.c_double * 60), ("J0", C.c_double * 3600)]
 
 
+class WindowCycleOptions(C.Structure):
+    """lili_window_cycle_options; the defaults are the literals of the reference's write-back gates."""
+    _fields_ = [("gate_p", C.c_double), ("gate_q", C.c_double), ("gate_v", C.c_double), ("gate_ba", C.c_double), ("gate_bg", C.c_double),
+                ("use_resident_prior", C.c_int32), ("reserved_", C.c_int32)]
+
+    def __init__(self, gate_p=10.0, gate_q=10.0, gate_v=10.0, gate_ba=22.0, gate_bg=22.0, use_resident_prior=0):
+        super().__init__(gate_p, gate_q, gate_v, gate_ba, gate_bg, int(use_resident_prior), 0)
+
+
+class WindowCycleResult(C.Structure):
+    _fields_ = [("summary", LmSummary), ("solved", C.c_double * 64), ("abs_state", C.c_double * 64), ("next_state", C.c_double * 64), ("refused", C.c_uint32 * 4),
+                ("prior_updated", C.c_int32), ("prior_n", C.c_int32), ("prior_blocks", C.c_int32), ("rank", C.c_int32), ("sweeps_mm", C.c_int32), ("sweeps_s", C.c_int32)]
+
+
 class WindowProblem(C.Structure):
     _fields_ = [("n_kf", C.c_int32), ("kind_mask", C.c_int32), ("slots", C.POINTER(C.c_int32)), ("imu", C.POINTER(WindowImu)), ("prior", C.POINTER(WindowPrior)),
                 ("sb_prior", C.POINTER(C.c_double)), ("q_lb", C.c_double * 4), ("t_lb", C.c_double * 3)]
@@ -307,6 +321,11 @@ _SIGS = {
     "lili_window_state_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "lili_marg_schur": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "lili_window_marginalize": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.c_void_p, C.POINTER(WindowPriorStorage)]),
+    "lili_window_cycle": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.POINTER(LmOptions), C.POINTER(WindowCycleOptions), C.c_void_p,
+                                    C.POINTER(WindowCycleResult)]),
+    "lili_window_cycle_reset": (C.c_int, [C.c_void_p]),
+    "lili_window_prior_get": (C.c_int, [C.c_void_p, C.POINTER(WindowPriorStorage)]),
+    "lili_window_prior_set": (C.c_int, [C.c_void_p, C.POINTER(WindowPrior)]),
 }
 
 
@@ -1069,6 +1088,33 @@ def pack_preintegration(pre, g=None):
     return w
 
 
+def _pack_prior(prior):
+    """(lili_window_prior, the arrays it points into) from the dict WindowSolver.set_problem(prior=...) takes"""
+    wp = WindowPrior()
+    kind = np.ascontiguousarray(prior["block_kind"], np.int32)
+    kf = np.ascontiguousarray(prior["block_keyframe"], np.int32)
+    x0 = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float64).reshape(-1) for v in prior["x0"]]) if isinstance(prior["x0"], (list, tuple)) else prior["x0"], np.float64)
+    J0 = np.ascontiguousarray(prior["J0"], np.float64)
+    r0 = np.ascontiguousarray(prior["r0"], np.float64)
+    wp.n_rows, wp.n_cols, wp.n_blocks = J0.shape[0], int(prior.get("n_cols", J0.shape[1])), len(kind)
+    wp.block_kind = kind.ctypes.data_as(C.POINTER(C.c_int32)); wp.block_keyframe = kf.ctypes.data_as(C.POINTER(C.c_int32))
+    wp.x0 = x0.ctypes.data_as(C.POINTER(C.c_double)); wp.J0 = J0.ctypes.data_as(C.POINTER(C.c_double)); wp.r0 = r0.ctypes.data_as(C.POINTER(C.c_double))
+    return wp, [kind, kf, x0, J0, r0]
+
+
+def _prior_dict(st):
+    """the dict set_problem(prior=...) takes, plus rank and sweeps, from a filled WindowPriorStorage"""
+    rows, n, nb = st.prior.n_rows, st.prior.n_cols, st.prior.n_blocks
+    kind = [int(st.block_kind[b]) for b in range(nb)]
+    x0_all, x0, off = np.array(st.x0[:], np.float64), [], 0
+    for k in kind:
+        gs = (3, 4, 9)[k]
+        x0.append(x0_all[off:off + gs].copy())
+        off += gs
+    return dict(block_kind=kind, block_keyframe=[int(st.block_keyframe[b]) for b in range(nb)], x0=x0,
+                J0=np.array(st.J0[:rows * n], np.float64).reshape(rows, n), r0=np.array(st.r0[:rows], np.float64), rank=int(st.rank), sweeps=(int(st.sweeps_mm), int(st.sweeps_s)))
+
+
 class WindowSolver:
     """The joint keyframe window on the device (lili_window_evaluate / lili_window_solve): lidar blocks of the matcher's slots + IMU factors + the
     marginalisation prior or the speed-bias priors.  A state is (n_kf, 16): t[3], q[4] (w x y z), speed-bias[9] per keyframe."""
@@ -1096,16 +1142,8 @@ class WindowSolver:
             keep.append(arr)
             pr.imu = arr
         if prior is not None:
-            wp = WindowPrior()
-            kind = np.ascontiguousarray(prior["block_kind"], np.int32)
-            kf = np.ascontiguousarray(prior["block_keyframe"], np.int32)
-            x0 = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float64).reshape(-1) for v in prior["x0"]]) if isinstance(prior["x0"], (list, tuple)) else prior["x0"], np.float64)
-            J0 = np.ascontiguousarray(prior["J0"], np.float64)
-            r0 = np.ascontiguousarray(prior["r0"], np.float64)
-            wp.n_rows, wp.n_cols, wp.n_blocks = J0.shape[0], int(prior.get("n_cols", J0.shape[1])), len(kind)
-            wp.block_kind = kind.ctypes.data_as(C.POINTER(C.c_int32)); wp.block_keyframe = kf.ctypes.data_as(C.POINTER(C.c_int32))
-            wp.x0 = x0.ctypes.data_as(C.POINTER(C.c_double)); wp.J0 = J0.ctypes.data_as(C.POINTER(C.c_double)); wp.r0 = r0.ctypes.data_as(C.POINTER(C.c_double))
-            keep += [wp, kind, kf, x0, J0, r0]
+            wp, held = _pack_prior(prior)
+            keep += [wp] + held
             pr.prior = C.pointer(wp)
         if sb_prior is not None:
             sb = np.ascontiguousarray(np.asarray(sb_prior, np.float64).reshape(n_kf, 9))
@@ -1150,15 +1188,41 @@ class WindowSolver:
         s = self._state(state)
         st = storage if storage is not None else WindowPriorStorage()
         self.ctx._chk(self.lib.lili_window_marginalize(self.ctx.h, C.byref(self.problem), C.byref(self.matcher.params), _ptr(s), C.byref(st)))
-        n, nb = st.prior.n_cols, st.prior.n_blocks
-        kind = [int(st.block_kind[b]) for b in range(nb)]
-        x0_all, x0, off = np.array(st.x0[:], np.float64), [], 0
-        for k in kind:
-            gs = (3, 4, 9)[k]
-            x0.append(x0_all[off:off + gs].copy())
-            off += gs
-        return dict(block_kind=kind, block_keyframe=[int(st.block_keyframe[b]) for b in range(nb)], x0=x0,
-                    J0=np.array(st.J0[:n * n], np.float64).reshape(n, n), r0=np.array(st.r0[:n], np.float64), rank=int(st.rank), sweeps=(int(st.sweeps_mm), int(st.sweeps_s)))
+        return _prior_dict(st)
+
+    def cycle(self, state, options=None, gates=None, use_resident_prior=False, result=None):
+        """One keyframe's solve, sign unification, next prior and write-back gates in one call (lili_window_cycle).  gates: a WindowCycleOptions or a dict of
+        gate_p / gate_q / gate_v / gate_ba / gate_bg (default: the reference's 10, 10, 10, 22, 22); use_resident_prior: the problem's prior is the one the previous
+        cycle left on the device (set_problem then carries none).  Returns dict(summary, solved, abs_state, next_state (each (n_kf, 16)), refused (n_kf bit masks:
+        bit 0 p, 1 q, 2 v, 3..5 ba, 6..8 bg), prior_updated, prior_n, prior_blocks, rank, sweeps).  result: a WindowCycleResult of the caller's to fill; untouched
+        when the call is refused."""
+        s = self._state(state)
+        co = gates if isinstance(gates, WindowCycleOptions) else WindowCycleOptions(**(gates or {}))
+        co.use_resident_prior = 1 if use_resident_prior else 0
+        res = result if result is not None else WindowCycleResult()
+        self.ctx._chk(self.lib.lili_window_cycle(self.ctx.h, C.byref(self.problem), C.byref(self.matcher.params), C.byref(options) if options is not None else None,
+                                                 C.byref(co), _ptr(s), C.byref(res)))
+        n = s.shape[0]
+        return dict(summary=res.summary.as_dict(), solved=np.array(res.solved[:16 * n], np.float64).reshape(n, 16), abs_state=np.array(res.abs_state[:16 * n], np.float64).reshape(n, 16),
+                    next_state=np.array(res.next_state[:16 * n], np.float64).reshape(n, 16), refused=[int(res.refused[k]) for k in range(n)],
+                    prior_updated=bool(res.prior_updated), prior_n=int(res.prior_n), prior_blocks=int(res.prior_blocks), rank=int(res.rank),
+                    sweeps=(int(res.sweeps_mm), int(res.sweeps_s)))
+
+    def reset_cycle(self):
+        """drops the resident prior (after a loop closure the reference starts again without one)"""
+        self.ctx._chk(self.lib.lili_window_cycle_reset(self.ctx.h))
+
+    def resident_prior(self, storage=None):
+        """a copy of the resident prior as marginalize() returns one; LiliError when there is none"""
+        st = storage if storage is not None else WindowPriorStorage()
+        self.ctx._chk(self.lib.lili_window_prior_get(self.ctx.h, C.byref(st)))
+        return _prior_dict(st)
+
+    def set_resident_prior(self, prior):
+        """seeds the resident prior from a dict as set_problem(prior=...) takes (a restart from a saved prior)"""
+        wp, held = _pack_prior(prior)
+        self.ctx._chk(self.lib.lili_window_prior_set(self.ctx.h, C.byref(wp)))
+        del held
 
 
 def marg_schur(ctx, A, b, m):

@@ -231,6 +231,15 @@ struct lili_ctx {
     bool state_mirror_want = false, state_mirror_armed = false;
     lili::SlotState* take_state_mirror(int slot) { if (!state_mirror_armed || !h_state_mirror_dev) return nullptr; state_mirror_armed = false; return h_state_mirror_dev + slot; }
     double* pub_of(int slot) { return pose_pub.as<double>() + (size_t)slot * kPubReplicas * kPubStride; }      // option overlap_gn: the slot's published-pose copies
+    // lili_window_cycle (behind every older member, whose offsets stay what they were): the RESIDENT prior (x0, r0, J0, A0 as WinDev lays them out; set by
+    // lili_window_prior_set or by a successful cycle, which has k_window_marg_cycle write win_res_nxt and then swaps the two — no other call touches either), the cycle's
+    // device result, the slots' states as they were before the solve (put back when the cycle fails behind it)
+    DevBuf win_res, win_res_nxt, win_cyc, win_state_bak;
+    struct WinResidentTable {      // what the host knows of the resident prior without a read-back: the kept-block table, the sizes, and the rank / sweeps the cycle read back
+        bool valid = false;
+        int n_rows = 0, n_cols = 0, n_blocks = 0, rank = 0, sweeps[2] = {0, 0};
+        int32_t kind[3 * LILI_WINDOW_MAX_KF] = {}, kf[3 * LILI_WINDOW_MAX_KF] = {};
+    } win_res_tab;
 };
 
 #define HIPCHK(expr)                                                                                         \

@@ -1520,7 +1520,8 @@ int lili_gram_to_factor(const double gram[64], double cost, double residuals[9],
 
 }  // extern "C"
 
-// lili_window.hip builds the joint window on what this file already does for the lidar blocks: the slots' Gram records at host poses
+// lili_window.hip builds the joint window on what this file already does for the lidar blocks: the slots' Gram records at host poses — or, with t and q null, at
+// the slots' DEVICE poses as lili_s2m_iterate reads them (lili_window_cycle: same kernel bodies, same fixed-order reduction, so the same bytes at the same doubles) —
 // (lili_s2m_linearize_window's launches, records left in d_gram), the arguments of a slot's share of a persistent LM launch, the device parameters.
 int lili_match_window_records(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const double* t, const double* q, double* d_gram) {
     return linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, nullptr, nullptr, d_gram, 0);

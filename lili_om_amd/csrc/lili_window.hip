@@ -89,7 +89,7 @@ __device__ __forceinline__ double d3c(d3 v, int i) { return i == 0 ? v.x : i == 
 
 // ImuFactor::Evaluate of ONE factor by ONE lane, un-whitened, Jacobians in local coordinates: J[15][31] (zeroed by the caller), column 30 = residual.
 // kLast3: the quaternion blocks enter by the last three of their four global columns (MarginalizationFactor.cpp:9-17) instead of through Ceres' plus-Jacobian
-template <bool kLast3>
+template <bool kLast3, int kWho = 0>
 __device__ __noinline__ void win_imu_raw(const WinImuDev& f, const double* xi, const double* xj, double (*J)[31]) {
     const d3 Pi{xi[0], xi[1], xi[2]}, Pj{xj[0], xj[1], xj[2]};
     const dq Qi = qnormalized(dq{xi[3], xi[4], xi[5], xi[6]}), Qj = qnormalized(dq{xj[3], xj[4], xj[5], xj[6]});
@@ -188,7 +188,7 @@ __device__ __noinline__ void win_imu_raw(const WinImuDev& f, const double* xi, c
 // MarginalizationFactor::Evaluate, block b by ONE lane: dx of the block, and for a quaternion block T = +-2 Qleft(q0^-1)[1:4, :] * plus(q) — the reference's own
 // Jacobian of dx in global columns times Ceres' plus-Jacobian, not the derivative of the normalised expression.  kLast3: the last three of those four
 // global columns instead (what MarginalizationInfo takes of every quaternion block)
-template <bool kLast3>
+template <bool kLast3, int kWho = 0>
 __device__ __noinline__ void win_prior_block(const WinDev* pb, WinSys& s, int b) {
     const int kind = pb->blk_kind[b], kf = pb->blk_kf[b], col = pb->blk_col[b];
     const double* x0 = pb->x0 + pb->blk_x0[b];
@@ -215,7 +215,8 @@ __device__ __forceinline__ int win_blk_local(const WinDev* pb, int b) { return 1
 // fixed order, so every workgroup of the solve holds the same bits.
 // kMarg: the system MarginalizationInfo::PreMarginalize + ThreadsConstructA form at s.x instead (L/src/BackendFusion.cpp:1009-1165) — every quaternion block by the
 // last three of its four global columns, and of the IMU factors only the one between keyframes 0 and 1; s.cost is then without meaning.
-template <bool kMarg>
+// kWho: whose copy this is (0: the kernels up to k_window_marg, 1: k_window_marg_cycle's own — see there); it changes nothing in the code
+template <bool kMarg, int kWho = 0>
 __device__ __noinline__ void win_build(const WinDev* __restrict__ pb, WinSys& s) {
     const int lane = threadIdx.x & 63;
     const int n_kf = pb->n_kf, N = 15 * n_kf, n_imu = kMarg ? (pb->n_imu < 1 ? pb->n_imu : 1) : pb->n_imu;
@@ -249,7 +250,7 @@ __device__ __noinline__ void win_build(const WinDev* __restrict__ pb, WinSys& s)
         s.pr[lane] = r;
     }
     // ---- IMU factors, raw: one lane per factor
-    if (lane < n_imu) win_imu_raw<kMarg>(pb->imu[lane], s.x[lane], s.x[lane + 1], s.Jraw[lane]);
+    if (lane < n_imu) win_imu_raw<kMarg, kWho>(pb->imu[lane], s.x[lane], s.x[lane + 1], s.Jraw[lane]);
     LILI_WAVE_SYNC();
     {
         double c = 0.0;
@@ -285,7 +286,7 @@ __device__ __noinline__ void win_build(const WinDev* __restrict__ pb, WinSys& s)
     if (pb->has_prior) {
         const int n_rows = pb->n_rows, n_cols = pb->n_cols, n_blocks = pb->n_blocks;
         LILI_WAVE_SYNC();
-        if (lane < n_blocks) win_prior_block<kMarg>(pb, s, lane);
+        if (lane < n_blocks) win_prior_block<kMarg, kWho>(pb, s, lane);
         LILI_WAVE_SYNC();
         if (lane < n_rows) {
             double r = pb->r0[lane];
@@ -590,6 +591,7 @@ __device__ __forceinline__ double marg_sumsq(MargShared& sh, const double* A, co
 
 // Eigen-decomposition of the symmetric n x n matrix in A0 (tight) by the whole workgroup: on return A0 holds the rotated matrix (eigenvalues on its diagonal),
 // V the eigenvectors as columns; A1 is scratch of the same size.  Returns the number of sweeps, or -1 when kMargMaxSweeps did not suffice (uniform).
+template <int kWho = 0>
 __device__ __noinline__ int marg_jacobi(MargShared& sh, double* A0, double* A1, double* V, const int n) {
     const int tid = threadIdx.x;
     const int np = n + (n & 1), hp = np >> 1;      // an odd n plays with a bye: the pair that holds index n rests
@@ -658,6 +660,7 @@ __device__ __noinline__ int marg_jacobi(MargShared& sh, double* A0, double* A1, 
 }
 
 // MarginalizationFactor.cpp:176-201 on sh.A (pos x pos, tight), sh.b: the first m dimensions go.  `work`: pos x pos doubles of scratch.
+template <int kWho = 0>
 __device__ __noinline__ void marg_schur(MargShared& sh, double* work, const int pos, const int m, MargOut* __restrict__ out) {
     const int tid = threadIdx.x;
     const int n = pos - m;
@@ -665,7 +668,7 @@ __device__ __noinline__ void marg_schur(MargShared& sh, double* work, const int 
     double* M = sh.M;
     double* V = sh.V;
     for (int e = tid; e < m * m; e += kMargThreads) { const int i = e / m, j = e - i * m; M[e] = 0.5 * (A[i * pos + j] + A[j * pos + i]); }
-    const int sw1 = marg_jacobi(sh, M, work, V, m);
+    const int sw1 = marg_jacobi<kWho>(sh, M, work, V, m);
     if (sw1 < 0) { if (tid == 0) { out->status = 1; out->rank = 0; out->sweeps[0] = sw1; out->sweeps[1] = 0; } return; }
     if (tid < m) { const double l = M[tid * m + tid]; sh.w[tid] = l > kMargEps ? 1.0 / l : 0.0; }
     __syncthreads();
@@ -697,7 +700,7 @@ __device__ __noinline__ void marg_schur(MargShared& sh, double* work, const int 
         for (int k = 0; k < m; k++) v += A[(m + tid) * pos + k] * W[k * (n + 1) + n];
         sh.bs[tid] = sh.b[m + tid] - v;
     }
-    const int sw2 = marg_jacobi(sh, M, work, V, n);
+    const int sw2 = marg_jacobi<kWho>(sh, M, work, V, n);
     if (sw2 < 0) { if (tid == 0) { out->status = 1; out->rank = 0; out->sweeps[0] = sw1; out->sweeps[1] = sw2; } return; }
     if (tid < n) sh.w[tid] = M[tid * n + tid];
     __syncthreads();
@@ -747,6 +750,159 @@ __global__ __launch_bounds__(kMargThreads) void k_window_marg(const WinDev* __re
     marg_schur(sh, sh.sys.H, pos, a.m, out);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The cycle (include/lili_hip.h: lili_window_cycle): behind k_window_solve on the same stream, k_window_writeback (sign unification, gates), the lidar launches at the
+// slots' device poses, k_window_marg_cycle (the next prior, left in the context's resident buffer).  Nothing here waits for another workgroup; every loop is bounded.
+// ------------------------------------------------------------------------------------------------------------------------------------
+struct WinPriorDev { double x0[16 * kWinMaxKf], r0[kWinMaxN], J0[kWinMaxN * kWinMaxN], A0[kWinMaxN * kWinMaxN]; };      // the resident prior: WinDev's members x0 .. A0, one device-to-device copy apart
+static_assert(offsetof(WinDev, r0) - offsetof(WinDev, x0) == offsetof(WinPriorDev, r0) && offsetof(WinDev, J0) - offsetof(WinDev, x0) == offsetof(WinPriorDev, J0) &&
+              offsetof(WinDev, A0) - offsetof(WinDev, x0) == offsetof(WinPriorDev, A0) && offsetof(WinDev, imu) - offsetof(WinDev, x0) == sizeof(WinPriorDev),
+              "WinPriorDev is the run of WinDev from x0 to A0");
+struct WinWbArgs { SlotState* st[kWinMaxKf]; int n, summary_words; double gate_p, gate_q, gate_v, gate_ba, gate_bg; };
+struct WinCycleMargArgs { MargArgs a; int n_blocks, kind[kWinMaxBlocks], kf[kWinMaxBlocks]; };
+
+// Eigen's quaternion product, sums left to right
+__device__ __forceinline__ void wb_qmul(const double* a, const double* b, double* o) {
+    o[0] = ((a[0] * b[0] - a[1] * b[1]) - a[2] * b[2]) - a[3] * b[3];
+    o[1] = ((a[0] * b[1] + a[1] * b[0]) + a[2] * b[3]) - a[3] * b[2];
+    o[2] = ((a[0] * b[2] + a[2] * b[0]) + a[3] * b[1]) - a[1] * b[3];
+    o[3] = ((a[0] * b[3] + a[3] * b[0]) + a[1] * b[2]) - a[2] * b[1];
+}
+// the general branch of Eigen 3.3's matrix -> quaternion for the largest diagonal entry i (j, k its successors): returns w, writes the three vector components
+__device__ __forceinline__ double wb_branch(double Rii, double Rjj, double Rkk, double Rkj, double Rjk, double Rji, double Rij, double Rki, double Rik, double& qi, double& qj, double& qk) {
+    double t = sqrt(((Rii - Rjj) - Rkk) + 1.0);
+    qi = 0.5 * t;
+    t = 0.5 / t;
+    qj = (Rji + Rij) * t;
+    qk = (Rki + Rik) * t;
+    return (Rkj - Rjk) * t;
+}
+// Quaterniond(q.toRotationMatrix()) of a normalised q (w x y z): the formulas lili_om_amd/loop.py restates (_matrix_from_quat, quat_from_matrix)
+__device__ __forceinline__ void wb_round_trip(const double* q, double* o) {
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    const double R00 = 1.0 - 2.0 * (y * y + z * z), R01 = 2.0 * (x * y - w * z), R02 = 2.0 * (x * z + w * y);
+    const double R10 = 2.0 * (x * y + w * z), R11 = 1.0 - 2.0 * (x * x + z * z), R12 = 2.0 * (y * z - w * x);
+    const double R20 = 2.0 * (x * z - w * y), R21 = 2.0 * (y * z + w * x), R22 = 1.0 - 2.0 * (x * x + y * y);
+    const double tr = (R00 + R11) + R22;
+    if (tr > 0.0) {
+        double t = sqrt(tr + 1.0);
+        o[0] = 0.5 * t;
+        t = 0.5 / t;
+        o[1] = (R21 - R12) * t; o[2] = (R02 - R20) * t; o[3] = (R10 - R01) * t;
+        return;
+    }
+    int i = 0;
+    if (R11 > R00) i = 1;
+    if (R22 > (i == 0 ? R00 : R11)) i = 2;
+    if (i == 0) o[0] = wb_branch(R00, R11, R22, R21, R12, R10, R01, R20, R02, o[1], o[2], o[3]);
+    else if (i == 1) o[0] = wb_branch(R11, R22, R00, R02, R20, R21, R12, R01, R10, o[2], o[3], o[1]);
+    else o[0] = wb_branch(R22, R00, R11, R10, R01, R02, R20, R12, R21, o[3], o[1], o[2]);
+}
+
+// ONE wave behind k_window_solve: lane k < n unifies keyframe k's q where the solve left it (`state`, in place) and in its slot's device pose, moves the mean of its
+// speed-bias prior (if it has one) to the solved speed-bias for the marginalisation behind it, then applies the
+// gates of L/src/BackendFusion.cpp:1187-1284 against pb->state; the wave copies the solve's summary into the result and clears the prior's fields (k_window_marg_cycle sets them)
+__global__ __launch_bounds__(64) void k_window_writeback(WinDev* __restrict__ pb, double* __restrict__ state, const lili_lm_summary* __restrict__ summary, WinWbArgs a,
+                                                         lili_window_cycle_result* __restrict__ out) {
+    const int lane = threadIdx.x;
+    {
+        const double* s = reinterpret_cast<const double*>(summary);
+        double* d = reinterpret_cast<double*>(&out->summary);
+        for (int e = lane; e < a.summary_words; e += 64) d[e] = s[e];
+    }
+    if (lane == 0) { out->prior_updated = 0; out->prior_n = 0; out->prior_blocks = 0; out->rank = 0; out->sweeps_mm = 0; out->sweeps_s = 0; }
+    if (lane >= a.n) return;
+    double x[16], in[16];
+    for (int i = 0; i < 16; i++) { x[i] = state[16 * lane + i]; in[i] = pb->state[16 * lane + i]; }
+    if (x[3] < 0.0) {
+        for (int i = 3; i < 7; i++) { x[i] = -x[i]; state[16 * lane + i] = x[i]; }
+    }
+    for (int i = 3; i < 7; i++) a.st[lane]->pose[i] = x[i];
+    // the marginalisation's speed-bias priors take the SOLVED speed-bias as their mean (L/src/BackendFusion.cpp:1045-1057: residual 0, information 225 I); the solve is over,
+    // so the uploaded problem block is this launch's to change
+    if (pb->sb_has[lane]) for (int i = 0; i < 9; i++) pb->sb_mean[9 * lane + i] = x[7 + i];
+    const double dp0 = in[0] - x[0], dp1 = in[1] - x[1], dp2 = in[2] - x[2];
+    const double pnorm = sqrt((dp0 * dp0 + dp1 * dp1) + dp2 * dp2);
+    const double dv0 = in[7] - x[7], dv1 = in[8] - x[8], dv2 = in[9] - x[9];
+    const double vnorm = sqrt((dv0 * dv0 + dv1 * dv1) + dv2 * dv2);
+    double qn[4], qi[4], dq[4];
+    {
+        const double n = sqrt(((x[4] * x[4] + x[5] * x[5]) + x[6] * x[6]) + x[3] * x[3]);
+        for (int i = 0; i < 4; i++) qn[i] = x[3 + i] / n;
+        const double n2 = ((qn[1] * qn[1] + qn[2] * qn[2]) + qn[3] * qn[3]) + qn[0] * qn[0];
+        qi[0] = qn[0] / n2; qi[1] = -qn[1] / n2; qi[2] = -qn[2] / n2; qi[3] = -qn[3] / n2;
+        wb_qmul(qi, in + 3, dq);
+    }
+    const double qnorm = sqrt((dq[1] * dq[1] + dq[2] * dq[2]) + dq[3] * dq[3]);
+    unsigned refused = 0;
+    if (!(pnorm < a.gate_p)) refused |= 1u;
+    if (!(qnorm < a.gate_q)) refused |= 2u;
+    if (!(vnorm < a.gate_v)) refused |= 4u;
+    for (int i = 0; i < 3; i++) {
+        if (!(fabs(in[10 + i] - x[10 + i]) < a.gate_ba)) refused |= 8u << i;
+        if (!(fabs(in[13 + i] - x[13 + i]) < a.gate_bg)) refused |= 64u << i;
+    }
+    double ab[16], nx[16];
+    for (int i = 0; i < 3; i++) ab[i] = (refused & 1u) ? in[i] : x[i];
+    for (int i = 3; i < 7; i++) ab[i] = (refused & 2u) ? in[i] : x[i];
+    for (int i = 7; i < 10; i++) ab[i] = (refused & 4u) ? in[i] : x[i];
+    for (int i = 0; i < 3; i++) {
+        ab[10 + i] = (refused & (8u << i)) ? in[10 + i] : x[10 + i];
+        ab[13 + i] = (refused & (64u << i)) ? in[13 + i] : x[13 + i];
+    }
+    for (int i = 0; i < 16; i++) nx[i] = ab[i];
+    if (!(refused & 2u)) wb_round_trip(qn, nx + 3);
+    for (int i = 0; i < 16; i++) { out->solved[16 * lane + i] = x[i]; out->abs_state[16 * lane + i] = ab[i]; out->next_state[16 * lane + i] = nx[i]; }
+    out->refused[lane] = refused;
+}
+
+// k_window_marg in cycle mode (a second entry point: k_window_marg stays the code it was — its callees too: win_build<true, 1>, marg_schur<1> are this kernel's own copies,
+// because a second caller of one copy ends the compiler's specialisation to the single call site and changes the instructions k_window_marg runs): the state is the one k_window_writeback left in `state`, a solve that stalled
+// marginalises nothing, and after marg_schur the workgroup writes the resident prior — J0, r0, x0 = the kept blocks' values of that state, and A0 = J0^T J0 with the row
+// index ascending per entry (window_pack's order on the host), computed from a copy of J0 in sh.A, which the Schur step no longer needs.  A sweep cap that is reached
+// leaves the resident prior as it was (out->status tells the host).
+__global__ __launch_bounds__(kMargThreads) void k_window_marg_cycle(const WinDev* __restrict__ pb, const double* __restrict__ rec, const double* __restrict__ state,
+                                                                    const lili_lm_summary* __restrict__ summary, WinCycleMargArgs c, MargOut* out, WinPriorDev* __restrict__ res,
+                                                                    lili_window_cycle_result* __restrict__ cyc) {
+    __shared__ MargShared sh;
+    const int tid = threadIdx.x;
+    const int pos = c.a.pos, m = c.a.m, n = pos - m;
+    if (summary->termination == LILI_LM_STALLED) { if (tid == 0) out->status = 0; return; }
+    {
+        const int n_kf = pb->n_kf, N = 15 * n_kf;
+        if (tid < 64) {
+            for (int e = tid; e < 16 * n_kf; e += 64) sh.sys.x[e / 16][e % 16] = state[e];
+            for (int e = tid; e < 72 * n_kf; e += 64) sh.sys.lid[e / 72][e % 72] = rec ? rec[e] : 0.0;
+            LILI_WAVE_SYNC();
+            win_build<true, 1>(pb, sh.sys);
+        }
+        __syncthreads();
+        for (int e = tid; e < pos * pos; e += kMargThreads) { const int i = e / pos, j = e - i * pos; sh.A[e] = sh.sys.H[c.a.sel[i] * N + c.a.sel[j]]; }
+        if (tid < pos) sh.b[tid] = sh.sys.g[c.a.sel[tid]];
+    }
+    __syncthreads();
+    marg_schur<1>(sh, sh.sys.H, pos, m, out);
+    __threadfence();
+    __syncthreads();
+    if (*reinterpret_cast<volatile int*>(&out->status) != 0) return;      // uniform: written by thread 0 before the barrier
+    for (int e = tid; e < n * n; e += kMargThreads) { const double v = out->J0[e]; sh.A[e] = v; res->J0[e] = v; }
+    if (tid < n) res->r0[tid] = out->r0[tid];
+    if (tid < c.n_blocks) {
+        int off = 0;
+        for (int b = 0; b < tid; b++) off += c.kind[b] == 0 ? 3 : c.kind[b] == 1 ? 4 : 9;
+        const int kind = c.kind[tid], gs = kind == 0 ? 3 : kind == 1 ? 4 : 9, first = kind == 0 ? 0 : kind == 1 ? 3 : 7;
+        for (int i = 0; i < gs; i++) res->x0[off + i] = sh.sys.x[c.kf[tid]][first + i];
+    }
+    __syncthreads();
+    for (int e = tid; e < n * n; e += kMargThreads) {
+        const int a = e / n, b = e - a * n;
+        double v = 0.0;
+        for (int r = 0; r < n; r++) v += sh.A[r * n + a] * sh.A[r * n + b];
+        res->A0[e] = v;
+    }
+    if (tid == 0) { cyc->prior_updated = 1; cyc->rank = out->rank; cyc->sweeps_mm = out->sweeps[0]; cyc->sweeps_s = out->sweeps[1]; }
+}
+
 }  // namespace lili
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -794,8 +950,41 @@ static bool window_sqrt_info(const double* cov, double* out) {
     return true;
 }
 
+// A0 = J0^T J0 (n_cols x n_cols, tight), the row index ascending per entry: the order k_window_marg_cycle uses on the device
+static void window_prior_gram(const double* J0, int n_rows, int n_cols, double* A0) {
+    for (int a = 0; a < n_cols; a++) for (int b = 0; b < n_cols; b++) {
+        double v = 0.0;
+        for (int r = 0; r < n_rows; r++) v += J0[r * n_cols + a] * J0[r * n_cols + b];
+        A0[a * n_cols + b] = v;
+    }
+}
+
+// the block table of a prior, checked (sizes, kinds, keyframes below kf_bound, no block twice, n_cols = the blocks' local sizes) and, with D, written into the packed
+// problem's blk_* / col_blk tables; *x0_doubles = the length of x0.  One definition for window_pack and lili_window_prior_set.
+static int window_prior_table(lili_ctx* ctx, const lili_window_prior& p, int kf_bound, const std::string& w, WinDev* D, int* x0_doubles) {
+    ARGCHK(p.n_blocks >= 1 && p.n_blocks <= kWinMaxBlocks && p.block_kind && p.block_keyframe, w + ": bad prior");
+    ARGCHK(p.n_rows >= 1 && p.n_rows <= kWinMaxN && p.n_cols >= 1 && p.n_cols <= kWinMaxN, w + ": prior size out of range");
+    int col = 0, off = 0;
+    for (int b = 0; b < p.n_blocks; b++) {
+        const int kind = p.block_kind[b], kf = p.block_keyframe[b];
+        ARGCHK(kind >= 0 && kind <= 2 && kf >= 0 && kf < kf_bound, w + ": bad prior block");
+        for (int k = 0; k < b; k++) ARGCHK(!(p.block_kind[k] == kind && p.block_keyframe[k] == kf), w + ": duplicate prior block");
+        const int ls = kind == 2 ? 9 : 3, gs = kind == 0 ? 3 : kind == 1 ? 4 : 9;
+        if (D) {
+            D->blk_kind[b] = kind; D->blk_kf[b] = kf; D->blk_col[b] = col; D->blk_x0[b] = off;
+            for (int i = 0; i < ls && col + i < kWinMaxN; i++) D->col_blk[col + i] = b;
+        }
+        col += ls; off += gs;
+    }
+    ARGCHK(col == p.n_cols, w + ": n_cols of the prior does not match its blocks");
+    *x0_doubles = off;
+    return LILI_OK;
+}
+
 // validates the problem and packs it (with `state`) into ctx->win_host; nothing is enqueued
-static int window_pack(lili_ctx* ctx, const lili_window_problem* pr, const double* state, bool solve, const char* who) {
+// resident: the problem's prior is the context's resident one — has_prior, the sizes and the blk_* / col_blk tables come from the host's kept-block table, and x0, r0, J0, A0
+// stay zero here (the caller copies them over the uploaded block on the device)
+static int window_pack(lili_ctx* ctx, const lili_window_problem* pr, const double* state, bool solve, const char* who, bool resident = false) {
     const std::string w(who);
     ARGCHK(pr && state, w + ": null argument");
     ARGCHK(pr->n_kf >= 2 && pr->n_kf <= LILI_WINDOW_MAX_KF, w + ": n_kf must be in 2..LILI_WINDOW_MAX_KF");
@@ -832,29 +1021,24 @@ static int window_pack(lili_ctx* ctx, const lili_window_problem* pr, const doubl
         D.sb_has[k] = std::isnan(pr->sb_prior[9 * k]) ? 0 : 1;
         if (D.sb_has[k]) for (int i = 0; i < 9; i++) { ARGCHK(std::isfinite(pr->sb_prior[9 * k + i]), w + ": speed-bias prior is not finite"); D.sb_mean[9 * k + i] = pr->sb_prior[9 * k + i]; }
     }
-    if (pr->prior) {
-        const lili_window_prior& p = *pr->prior;
-        ARGCHK(p.n_blocks >= 1 && p.n_blocks <= kWinMaxBlocks && p.block_kind && p.block_keyframe && p.x0 && p.J0 && p.r0, w + ": bad prior");
-        ARGCHK(p.n_rows >= 1 && p.n_rows <= kWinMaxN && p.n_cols >= 1 && p.n_cols <= kWinMaxN, w + ": prior size out of range");
-        int col = 0, off = 0;
-        for (int b = 0; b < p.n_blocks; b++) {
-            const int kind = p.block_kind[b], kf = p.block_keyframe[b];
-            ARGCHK(kind >= 0 && kind <= 2 && kf >= 0 && kf < n_kf, w + ": bad prior block");
-            for (int k = 0; k < b; k++) ARGCHK(!(p.block_kind[k] == kind && p.block_keyframe[k] == kf), w + ": duplicate prior block");
-            D.blk_kind[b] = kind; D.blk_kf[b] = kf; D.blk_col[b] = col; D.blk_x0[b] = off;
-            const int ls = kind == 2 ? 9 : 3, gs = kind == 0 ? 3 : kind == 1 ? 4 : 9;
-            for (int i = 0; i < ls && col + i < kWinMaxN; i++) D.col_blk[col + i] = b;
-            col += ls; off += gs;
+    if (pr->prior || resident) {
+        int rc_tab;
+        lili_window_prior p{};
+        if (resident) {
+            const lili_ctx::WinResidentTable& rt = ctx->win_res_tab;
+            p.n_rows = rt.n_rows; p.n_cols = rt.n_cols; p.n_blocks = rt.n_blocks; p.block_kind = rt.kind; p.block_keyframe = rt.kf;
+        } else {
+            p = *pr->prior;
+            ARGCHK(p.x0 && p.J0 && p.r0, w + ": bad prior");
         }
-        ARGCHK(col == p.n_cols, w + ": n_cols of the prior does not match its blocks");
+        int off = 0;
+        if ((rc_tab = window_prior_table(ctx, p, n_kf, w, &D, &off)) != LILI_OK) return rc_tab;
         D.has_prior = 1; D.n_rows = p.n_rows; D.n_cols = p.n_cols; D.n_blocks = p.n_blocks;
-        std::memcpy(D.x0, p.x0, sizeof(double) * off);
-        std::memcpy(D.r0, p.r0, sizeof(double) * p.n_rows);
-        std::memcpy(D.J0, p.J0, sizeof(double) * p.n_rows * p.n_cols);
-        for (int a = 0; a < p.n_cols; a++) for (int b = 0; b < p.n_cols; b++) {
-            double v = 0.0;
-            for (int r = 0; r < p.n_rows; r++) v += p.J0[r * p.n_cols + a] * p.J0[r * p.n_cols + b];
-            D.A0[a * p.n_cols + b] = v;
+        if (!resident) {
+            std::memcpy(D.x0, p.x0, sizeof(double) * off);
+            std::memcpy(D.r0, p.r0, sizeof(double) * p.n_rows);
+            std::memcpy(D.J0, p.J0, sizeof(double) * p.n_rows * p.n_cols);
+            window_prior_gram(p.J0, p.n_rows, p.n_cols, D.A0);
         }
     }
     return LILI_OK;
@@ -876,6 +1060,30 @@ static int marg_run(lili_ctx* ctx, const WinDev* d_prob, const double* d_rec, co
     if (rc != LILI_OK) { (void)lili_readback_finish(ctx); return rc; }
     if ((rc = lili_readback_finish(ctx)) != LILI_OK) return rc;
     if (h_out->status != 0) return ctx->fail(LILI_E_NUMERIC, std::string(who) + ": the Jacobi eigen-solver reached its sweep cap without converging");
+    return LILI_OK;
+}
+
+// the blocks the reference's factor set touches (L/src/BackendFusion.cpp:1009-1165), in (keyframe, kind) order: keyframe 0's go, the others stay
+// read from the PACKED problem, the words win_build<true> itself branches on (has_prior, sb_has, n_imu) — so the columns picked here are the ones it fills
+static int window_marg_table(lili_ctx* ctx, const lili_window_problem* problem, const char* who, WinCycleMargArgs& c) {
+    const int n_kf = problem->n_kf;
+    const WinDev& D = *reinterpret_cast<const WinDev*>(ctx->win_host.data());
+    bool touched[kWinMaxKf][3] = {};
+    if (D.has_prior) for (int b = 0; b < D.n_blocks; b++) touched[D.blk_kf[b]][D.blk_kind[b]] = true;
+    for (int k = 0; k < n_kf; k++) if (D.sb_has[k]) touched[k][2] = true;
+    if (D.n_imu >= 1) for (int k = 0; k < 2; k++) for (int kind = 0; kind < 3; kind++) touched[k][kind] = true;      // the factor between keyframes 0 and 1 only
+    if (problem->kind_mask) for (int k = 0; k < n_kf; k++) touched[k][0] = touched[k][1] = true;                      // rec != nullptr below
+    c = WinCycleMargArgs{};
+    MargArgs& a = c.a;
+    for (int k = 0; k < n_kf; k++) for (int kind = 0; kind < 3; kind++) {
+        if (!touched[k][kind]) continue;
+        const int first = 15 * k + (kind == 0 ? 0 : kind == 1 ? 3 : 6), size = kind == 2 ? 9 : 3;
+        for (int i = 0; i < size; i++) a.sel[a.pos++] = first + i;
+        if (k == 0) a.m = a.pos;
+        else { c.kind[c.n_blocks] = kind; c.kf[c.n_blocks] = k; c.n_blocks++; }
+    }
+    ARGCHK(a.m >= 1, std::string(who) + ": no factor touches keyframe 0");
+    ARGCHK(a.pos > a.m, std::string(who) + ": no factor touches a keyframe that stays");
     return LILI_OK;
 }
 
@@ -918,22 +1126,19 @@ int lili_window_evaluate(lili_ctx* ctx, const lili_window_problem* problem, cons
     return lili_readback_finish(ctx);
 }
 
-int lili_window_solve(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const lili_lm_options* options,
-                      double* state, lili_lm_summary* summary) {
-    if (!ctx) return LILI_E_ARG;
-    ARGCHK(params, "window_solve: null params");
-    int rc = window_pack(ctx, problem, state, true, "window_solve");
-    if (rc != LILI_OK) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+// the packed problem (ctx->win_host) uploaded and k_window_solve enqueued behind it; resident: the resident prior copied over the uploaded block's x0 .. A0 in between,
+// device to device.  Every refusal comes before the first enqueue.  state_bak (the cycle): the slots' states are copied there first, and *enqueued tells the caller that from here
+// on a failure has poses to put back.
+static int window_solve_enqueue(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params& p, const lili_lm_options* options, bool resident, WinSolveArgs& W,
+                                void* state_bak = nullptr, bool* enqueued = nullptr) {
     const int n_kf = problem->n_kf;
-    const lili_s2m_params p = window_params(problem, params);
     // every workgroup has to be resident: the share of the CUs lili_s2m_solve_lm_window gives a slot, and at most kWinGroup per slot (one exchange hop)
     const int max_blocks = std::max(1, std::min(std::min(ctx->n_simd / 4 - 16, 240) / n_kf, kWinGroup));
     HIPCHK(ctx->win_prob.ensure(sizeof(WinDev)));
     HIPCHK(ctx->win_out.ensure(sizeof(double) * (1 + kWinMaxN + kWinMaxN * kWinMaxN) + sizeof(lili_lm_summary)));
-    WinSolveArgs W{};
+    W = WinSolveArgs{};
     W.n = n_kf;
-    int nb = 0;
+    int nb = 0, rc;
     for (int i = 0; i < n_kf; i++) {
         if ((rc = lili_match_lm_args(ctx, problem->slots[i], problem->kind_mask, &p, options, max_blocks, &W.a[i])) != LILI_OK) return rc;
         if (W.a[i].nb > kWinGroup) return ctx->fail(LILI_E_STATE, "window_solve: internal: too many workgroups for one exchange hop");
@@ -945,9 +1150,28 @@ int lili_window_solve(lili_ctx* ctx, const lili_window_problem* problem, const l
     W.summary = reinterpret_cast<lili_lm_summary*>(ctx->win_out.as<double>() + 1 + kWinMaxN + kWinMaxN * kWinMaxN);
     MatchParams P = lili_match_device_params(&p);
     P.no_cost = 0;                              // the robust cost drives the accept / reject decisions
+    if (state_bak) {
+        HIPCHK(hipMemcpyAsync(state_bak, ctx->states.p, sizeof(SlotState) * LILI_MAX_SLOTS, hipMemcpyDeviceToDevice, ctx->stream));
+        *enqueued = true;
+    }
     HIPCHK(hipMemcpyAsync(ctx->win_prob.p, ctx->win_host.data(), sizeof(WinDev), hipMemcpyHostToDevice, ctx->stream));
+    if (resident) HIPCHK(hipMemcpyAsync(reinterpret_cast<unsigned char*>(ctx->win_prob.p) + offsetof(WinDev, x0), ctx->win_res.p, sizeof(WinPriorDev), hipMemcpyDeviceToDevice, ctx->stream));
     hipLaunchKernelGGL(k_window_solve, dim3(nb), dim3(kWinThreads), lds_linearize(kWinThreads), ctx->stream, W, P);
     HIPCHK(hipGetLastError());
+    return LILI_OK;
+}
+
+int lili_window_solve(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const lili_lm_options* options,
+                      double* state, lili_lm_summary* summary) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(params, "window_solve: null params");
+    int rc = window_pack(ctx, problem, state, true, "window_solve");
+    if (rc != LILI_OK) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int n_kf = problem->n_kf;
+    const lili_s2m_params p = window_params(problem, params);
+    WinSolveArgs W;
+    if ((rc = window_solve_enqueue(ctx, problem, p, options, false, W)) != LILI_OK) return rc;
     if (summary) {
         rc = lili_readback_add(ctx, summary, W.summary, sizeof(lili_lm_summary));
         if (rc == LILI_OK) rc = lili_readback_add(ctx, state, W.state_out, sizeof(double) * 16 * n_kf);
@@ -999,25 +1223,12 @@ int lili_window_marginalize(lili_ctx* ctx, const lili_window_problem* problem, c
     int rc = window_pack(ctx, problem, state, false, "window_marginalize");
     if (rc != LILI_OK) return rc;
     const int n_kf = problem->n_kf;
-    // ---- the blocks the reference's factor set touches (L/src/BackendFusion.cpp:1009-1165), in (keyframe, kind) order: keyframe 0's go, the others stay
-    // read from the PACKED problem, the words win_build<true> itself branches on (has_prior, sb_has, n_imu) — so the columns picked here are the ones it fills
-    const WinDev& D = *reinterpret_cast<const WinDev*>(ctx->win_host.data());
-    bool touched[kWinMaxKf][3] = {};
-    if (D.has_prior) for (int b = 0; b < D.n_blocks; b++) touched[D.blk_kf[b]][D.blk_kind[b]] = true;
-    for (int k = 0; k < n_kf; k++) if (D.sb_has[k]) touched[k][2] = true;
-    if (D.n_imu >= 1) for (int k = 0; k < 2; k++) for (int kind = 0; kind < 3; kind++) touched[k][kind] = true;      // the factor between keyframes 0 and 1 only
-    if (problem->kind_mask) for (int k = 0; k < n_kf; k++) touched[k][0] = touched[k][1] = true;                      // rec != nullptr below
-    MargArgs a{};
-    int kind_of[kWinMaxBlocks], kf_of[kWinMaxBlocks], n_blocks = 0;
-    for (int k = 0; k < n_kf; k++) for (int kind = 0; kind < 3; kind++) {
-        if (!touched[k][kind]) continue;
-        const int first = 15 * k + (kind == 0 ? 0 : kind == 1 ? 3 : 6), size = kind == 2 ? 9 : 3;
-        for (int i = 0; i < size; i++) a.sel[a.pos++] = first + i;
-        if (k == 0) a.m = a.pos;
-        else { kind_of[n_blocks] = kind; kf_of[n_blocks] = k; n_blocks++; }
-    }
-    ARGCHK(a.m >= 1, "window_marginalize: no factor touches keyframe 0");
-    ARGCHK(a.pos > a.m, "window_marginalize: no factor touches a keyframe that stays");
+    WinCycleMargArgs c{};
+    if ((rc = window_marg_table(ctx, problem, "window_marginalize", c)) != LILI_OK) return rc;
+    const MargArgs& a = c.a;
+    const int n_blocks = c.n_blocks;
+    const int* kind_of = c.kind;
+    const int* kf_of = c.kf;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(ctx->win_prob.ensure(sizeof(WinDev)));
     const double* rec = nullptr;
@@ -1049,6 +1260,163 @@ int lili_window_marginalize(lili_ctx* ctx, const lili_window_problem* problem, c
     out->prior.n_rows = n; out->prior.n_cols = n; out->prior.n_blocks = n_blocks;
     out->prior.block_kind = out->block_kind; out->prior.block_keyframe = out->block_keyframe;
     out->prior.x0 = out->x0; out->prior.J0 = out->J0; out->prior.r0 = out->r0;
+    return LILI_OK;
+}
+
+// lili_window_cycle without its clean-up: *enqueued is set once the solve's launches are on the stream (the slots' states saved in win_state_bak just before).  The next prior
+// is written into win_res_nxt and becomes the resident one (a swap of the two buffers) only when everything, the read-back included, has succeeded.
+static int window_cycle_body(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const lili_lm_options* options,
+                             const lili_window_cycle_options* cycle_options, const double* state_in, lili_window_cycle_result* out, bool* enqueued) {
+    ARGCHK(params && out, "window_cycle: null argument");
+    lili_window_cycle_options co{10.0, 10.0, 10.0, 22.0, 22.0, 0, 0};
+    if (cycle_options) co = *cycle_options;
+    const bool resident = co.use_resident_prior != 0;
+    ARGCHK(!(resident && problem && problem->prior), "window_cycle: use_resident_prior together with a prior of the problem");
+    // ---- every refusal of the chain, before anything of the cycle is enqueued (a context's first cycle clears its two new prior buffers on the way): the solve's, then the marginalisation's (its factor set is the packed problem's)
+    int rc = window_pack(ctx, problem, state_in, true, "window_cycle", resident && ctx->win_res_tab.valid);
+    if (rc != LILI_OK) return rc;
+    if (resident && !ctx->win_res_tab.valid) return ctx->fail(LILI_E_STATE, "window_cycle: no resident prior (no cycle has left one, or lili_window_cycle_reset dropped it)");
+    const int n_kf = problem->n_kf;
+    WinCycleMargArgs c{};
+    if ((rc = window_marg_table(ctx, problem, "window_cycle", c)) != LILI_OK) return rc;
+    lili_lm_options opt;
+    if (options) opt = *options; else lili_lm_default_options(&opt);
+    HIPCHK(hipSetDevice(ctx->device));
+    for (DevBuf* b : {&ctx->win_res, &ctx->win_res_nxt})
+        if (!b->p) { HIPCHK(b->ensure(sizeof(WinPriorDev))); HIPCHK(hipMemsetAsync(b->p, 0, sizeof(WinPriorDev), ctx->stream)); }
+    HIPCHK(ctx->win_cyc.ensure(sizeof(lili_window_cycle_result)));
+    HIPCHK(ctx->win_state_bak.ensure(sizeof(SlotState) * LILI_MAX_SLOTS));
+    HIPCHK(ctx->win_marg.ensure(sizeof(MargOut)));
+    HIPCHK(ctx->win_rec.ensure(sizeof(double) * LILI_GRAM_DOUBLES * LILI_MAX_SLOTS));
+    const lili_s2m_params p = window_params(problem, params);
+    // ---- the solve (its own refusals still come before its first enqueue)
+    WinSolveArgs W;
+    if ((rc = window_solve_enqueue(ctx, problem, p, options, resident, W, ctx->win_state_bak.p, enqueued)) != LILI_OK) return rc;
+    // ---- unification and gates, one wave
+    const int rows = std::min(std::max(opt.max_iterations, 0), LILI_LM_MAX_LOG);      // the log has a row per judged candidate: at most max_iterations of them
+    const size_t summary_bytes = offsetof(lili_lm_summary, it) + sizeof(lili_lm_iteration) * rows;
+    WinWbArgs wb{};
+    wb.n = n_kf; wb.summary_words = (int)(summary_bytes / sizeof(double));
+    for (int k = 0; k < n_kf; k++) wb.st[k] = ctx->state(problem->slots[k]);
+    wb.gate_p = co.gate_p; wb.gate_q = co.gate_q; wb.gate_v = co.gate_v; wb.gate_ba = co.gate_ba; wb.gate_bg = co.gate_bg;
+    lili_window_cycle_result* d_cyc = ctx->win_cyc.as<lili_window_cycle_result>();
+    hipLaunchKernelGGL(k_window_writeback, dim3(1), dim3(64), 0, ctx->stream, ctx->win_prob.as<WinDev>(), W.state_out, (const lili_lm_summary*)W.summary, wb, d_cyc);
+    HIPCHK(hipGetLastError());
+    // ---- the lidar records at the slots' device poses (the unified state), then the next prior into the resident buffer
+    if ((rc = lili_match_window_records(ctx, problem->slots, n_kf, problem->kind_mask, &p, nullptr, nullptr, ctx->win_rec.as<double>())) != LILI_OK) return rc;
+    MargOut* d_marg = ctx->win_marg.as<MargOut>();
+    hipLaunchKernelGGL(k_window_marg_cycle, dim3(1), dim3(kMargThreads), 0, ctx->stream, (const WinDev*)W.prob, (const double*)ctx->win_rec.as<double>(), (const double*)W.state_out,
+                       (const lili_lm_summary*)W.summary, c, d_marg, ctx->win_res_nxt.as<WinPriorDev>(), d_cyc);
+    HIPCHK(hipGetLastError());
+    // ---- one synchronisation, one read-back: the summary's rows that can be written, n_kf rows of the three states, the gates' and the prior's words
+    std::vector<unsigned char> buf(sizeof(lili_window_cycle_result), 0);
+    lili_window_cycle_result* h = reinterpret_cast<lili_window_cycle_result*>(buf.data());
+    int marg_status[4] = {0, 0, 0, 0};
+    const size_t row_bytes = sizeof(double) * 16 * n_kf, tail = offsetof(lili_window_cycle_result, refused);
+    rc = lili_readback_add(ctx, &h->summary, &d_cyc->summary, summary_bytes);
+    if (rc == LILI_OK) rc = lili_readback_add(ctx, h->solved, d_cyc->solved, row_bytes);
+    if (rc == LILI_OK) rc = lili_readback_add(ctx, h->abs_state, d_cyc->abs_state, row_bytes);
+    if (rc == LILI_OK) rc = lili_readback_add(ctx, h->next_state, d_cyc->next_state, row_bytes);
+    if (rc == LILI_OK) rc = lili_readback_add(ctx, buf.data() + tail, reinterpret_cast<const unsigned char*>(d_cyc) + tail, sizeof(lili_window_cycle_result) - tail);
+    if (rc == LILI_OK) rc = lili_readback_add(ctx, marg_status, d_marg, sizeof marg_status);
+    if (rc != LILI_OK) { (void)lili_readback_finish(ctx); return rc; }
+    if ((rc = lili_readback_finish(ctx)) != LILI_OK) return rc;
+    if (marg_status[0] != 0)      // the sweep cap: nothing was written into win_res_nxt; the caller puts the slots' states back
+        return ctx->fail(LILI_E_NUMERIC, "window_cycle: the Jacobi eigen-solver reached its sweep cap without converging");
+    for (int k = n_kf; k < kWinMaxKf; k++) h->refused[k] = 0;
+    for (int r = std::max(h->summary.n_logged, 0); r < LILI_LM_MAX_LOG; r++) std::memset(&h->summary.it[r], 0, sizeof(lili_lm_iteration));
+    if (h->prior_updated) {
+        ctx->win_res.swap(ctx->win_res_nxt);
+        lili_ctx::WinResidentTable& rt = ctx->win_res_tab;
+        rt.valid = true; rt.n_rows = rt.n_cols = c.a.pos - c.a.m; rt.n_blocks = c.n_blocks;
+        rt.rank = h->rank; rt.sweeps[0] = h->sweeps_mm; rt.sweeps[1] = h->sweeps_s;
+        for (int b = 0; b < c.n_blocks; b++) { rt.kind[b] = c.kind[b]; rt.kf[b] = c.kf[b] - 1; }      // the next window's numbering (addr_shift, L:1170-1177)
+        h->prior_n = rt.n_cols; h->prior_blocks = rt.n_blocks;
+    }
+    std::memcpy(out, h, sizeof *out);
+    return LILI_OK;
+}
+
+int lili_window_cycle(lili_ctx* ctx, const lili_window_problem* problem, const lili_s2m_params* params, const lili_lm_options* options,
+                      const lili_window_cycle_options* cycle_options, const double* state_in, lili_window_cycle_result* out) {
+    if (!ctx) return LILI_E_ARG;
+    bool enqueued = false;
+    const int rc = window_cycle_body(ctx, problem, params, options, cycle_options, state_in, out, &enqueued);
+    if (rc != LILI_OK && enqueued) {
+        // a failure behind the solve's launches — the sweep cap, a launch, the read-back: the slots get the states they had before the solve, and the stream is drained so
+        // that nothing of the failed cycle is still running when the call returns.  The message of the failure stays; an error of this clean-up is not reported on top of it.
+        const std::string msg = ctx->err;
+        (void)lili_readback_finish(ctx);
+        (void)hipMemcpyAsync(ctx->states.p, ctx->win_state_bak.p, sizeof(SlotState) * LILI_MAX_SLOTS, hipMemcpyDeviceToDevice, ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->err = msg;
+    }
+    return rc;
+}
+
+int lili_window_cycle_reset(lili_ctx* ctx) {
+    if (!ctx) return LILI_E_ARG;
+    ctx->win_res_tab = lili_ctx::WinResidentTable{};
+    return LILI_OK;
+}
+
+int lili_window_prior_get(lili_ctx* ctx, lili_window_prior_storage* out) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(out, "window_prior_get: null argument");
+    const lili_ctx::WinResidentTable& rt = ctx->win_res_tab;
+    if (!rt.valid) return ctx->fail(LILI_E_STATE, "window_prior_get: no resident prior");
+    HIPCHK(hipSetDevice(ctx->device));
+    int off = 0;
+    for (int b = 0; b < rt.n_blocks; b++) off += rt.kind[b] == 0 ? 3 : rt.kind[b] == 1 ? 4 : 9;
+    std::vector<double> x0(off), r0(rt.n_rows), J0((size_t)rt.n_rows * rt.n_cols);
+    const WinPriorDev* d = ctx->win_res.as<WinPriorDev>();
+    // three plain copies, then the synchronisation (36 KB at most: more than the page-locked scratch's lazy items take)
+    HIPCHK(hipMemcpyAsync(x0.data(), d->x0, sizeof(double) * x0.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(r0.data(), d->r0, sizeof(double) * r0.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(J0.data(), d->J0, sizeof(double) * J0.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::memset(out, 0, sizeof *out);
+    for (int b = 0; b < rt.n_blocks; b++) { out->block_kind[b] = rt.kind[b]; out->block_keyframe[b] = rt.kf[b]; }
+    std::memcpy(out->x0, x0.data(), sizeof(double) * x0.size());
+    std::memcpy(out->r0, r0.data(), sizeof(double) * r0.size());
+    std::memcpy(out->J0, J0.data(), sizeof(double) * J0.size());
+    out->rank = rt.rank; out->sweeps_mm = rt.sweeps[0]; out->sweeps_s = rt.sweeps[1];
+    out->prior.n_rows = rt.n_rows; out->prior.n_cols = rt.n_cols; out->prior.n_blocks = rt.n_blocks;
+    out->prior.block_kind = out->block_kind; out->prior.block_keyframe = out->block_keyframe;
+    out->prior.x0 = out->x0; out->prior.J0 = out->J0; out->prior.r0 = out->r0;
+    return LILI_OK;
+}
+
+int lili_window_prior_set(lili_ctx* ctx, const lili_window_prior* prior) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(prior, "window_prior_set: null argument");
+    const lili_window_prior& p = *prior;
+    ARGCHK(p.x0 && p.J0 && p.r0, "window_prior_set: bad prior");
+    int off = 0;
+    const int rc_tab = window_prior_table(ctx, p, kWinMaxKf, "window_prior_set", nullptr, &off);
+    if (rc_tab != LILI_OK) return rc_tab;
+    for (int i = 0; i < off; i++) ARGCHK(std::isfinite(p.x0[i]), "window_prior_set: x0 is not finite");
+    for (int i = 0; i < p.n_rows; i++) ARGCHK(std::isfinite(p.r0[i]), "window_prior_set: r0 is not finite");
+    for (int i = 0; i < p.n_rows * p.n_cols; i++) ARGCHK(std::isfinite(p.J0[i]), "window_prior_set: J0 is not finite");
+    std::vector<unsigned char> buf(sizeof(WinPriorDev), 0);
+    WinPriorDev& h = *reinterpret_cast<WinPriorDev*>(buf.data());
+    std::memcpy(h.x0, p.x0, sizeof(double) * off);
+    std::memcpy(h.r0, p.r0, sizeof(double) * p.n_rows);
+    std::memcpy(h.J0, p.J0, sizeof(double) * p.n_rows * p.n_cols);
+    window_prior_gram(p.J0, p.n_rows, p.n_cols, h.A0);
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(ctx->win_res.ensure(sizeof(WinPriorDev)));
+    HIPCHK(hipMemcpyAsync(ctx->win_res.p, buf.data(), sizeof(WinPriorDev), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // `buf` is pageable and goes out of scope
+    lili_ctx::WinResidentTable& rt = ctx->win_res_tab;
+    rt = lili_ctx::WinResidentTable{};
+    rt.valid = true; rt.n_rows = p.n_rows; rt.n_cols = p.n_cols; rt.n_blocks = p.n_blocks;
+    for (int b = 0; b < p.n_blocks; b++) { rt.kind[b] = p.block_kind[b]; rt.kf[b] = p.block_keyframe[b]; }
+    for (int r = 0; r < p.n_rows; r++) {
+        bool nz = false;
+        for (int cc = 0; cc < p.n_cols; cc++) nz = nz || p.J0[r * p.n_cols + cc] != 0.0;
+        rt.rank += nz ? 1 : 0;
+    }
     return LILI_OK;
 }
 
