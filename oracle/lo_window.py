@@ -169,13 +169,15 @@ class Preintegration:
         return r
 
 
-def imu_factor(pre, Pi, Qi, SBi, Pj, Qj, SBj):
-    """ImuFactor::Evaluate (ImuFactor.h:18-144): residual[15] and the six Jacobian blocks (15x3, 15x4, 15x9, 15x3, 15x4, 15x9)."""
+def imu_factor(pre, Pi, Qi, SBi, Pj, Qj, SBj, sqrt_info=None):
+    """ImuFactor::Evaluate (ImuFactor.h:18-144): residual[15] and the six Jacobian blocks (15x3, 15x4, 15x9, 15x3, 15x4, 15x9).
+    sqrt_info: a given 15x15 square-root information instead of LLT(covariance^-1) in f64 (for covariances whose f64 inverse loses the digits a test looks at)."""
     Pi, Pj, SBi, SBj = (np.asarray(a, np.float64) for a in (Pi, Pj, SBi, SBj))
     Qi, Qj = qnormalized(np.asarray(Qi, np.float64)), qnormalized(np.asarray(Qj, np.float64))
     Vi, Bai, Bgi, Vj, Baj, Bgj = SBi[0:3], SBi[3:6], SBi[6:9], SBj[0:3], SBj[3:6], SBj[6:9]
     residual = pre.evaluate(Pi, Qi, Vi, Bai, Bgi, Pj, Qj, Vj, Baj, Bgj)
-    sqrt_info = np.linalg.cholesky(np.linalg.inv(pre.covariance)).T                          # LLT(cov^-1).matrixL().transpose()
+    if sqrt_info is None:
+        sqrt_info = np.linalg.cholesky(np.linalg.inv(pre.covariance)).T                      # LLT(cov^-1).matrixL().transpose()
     residual = sqrt_info @ residual
     s, g, J = pre.sum_dt, pre.g_vec, pre.jacobian
     dp_dba, dp_dbg, dq_dbg, dv_dba, dv_dbg = J[O_P:O_P + 3, O_BA:O_BA + 3], J[O_P:O_P + 3, O_BG:O_BG + 3], J[O_R:O_R + 3, O_BG:O_BG + 3], \

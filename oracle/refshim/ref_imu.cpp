@@ -51,4 +51,24 @@ int ref_imu_factor(int n, const double* dt, const double* acc, const double* gyr
     return f.Evaluate(blocks, residual, jac ? jb : nullptr) ? 0 : 1;
 }
 
+// The factor on a GIVEN record instead of an integration: a Preintegration is built, its public members are overwritten from `rec` — the 470 doubles of
+// lili_window_imu (include/lili_hip.h): sum_dt, g[3], delta_p[3], delta_q[4] w x y z, delta_v[3], lin_ba[3], lin_bg[3], jacobian[225], covariance[225] —
+// and ImuFactor::Evaluate runs on it.  With covariance = I the reference's inverse and LLT are exact: residual and blocks come out un-whitened.
+int ref_imu_factor_record(const double rec[470], const double params[32], double residual[15], double jac[480]) {
+    const double zero[3] = {0.0, 0.0, 0.0};
+    std::unique_ptr<Preintegration> p(new Preintegration(v3(zero), v3(zero), v3(rec + 14), v3(rec + 17)));
+    p->sum_dt_ = rec[0];
+    p->g_vec_ = v3(rec + 1);
+    p->delta_p_ = v3(rec + 4);
+    p->delta_q_ = Eigen::Quaterniond(rec[7], rec[8], rec[9], rec[10]);
+    p->delta_v_ = v3(rec + 11);
+    p->linearized_ba_ = v3(rec + 14);
+    p->linearized_bg_ = v3(rec + 17);
+    for (int i = 0; i < 15; i++) for (int j = 0; j < 15; j++) { p->jacobian_(i, j) = rec[20 + i * 15 + j]; p->covariance_(i, j) = rec[245 + i * 15 + j]; }
+    ImuFactor f(p.get());
+    const double* blocks[6] = {params, params + 3, params + 7, params + 16, params + 19, params + 23};
+    double* jb[6] = {jac, jac + 45, jac + 105, jac + 240, jac + 285, jac + 345};
+    return f.Evaluate(blocks, residual, jb) ? 0 : 1;
+}
+
 }  // extern "C"
