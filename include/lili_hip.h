@@ -121,8 +121,9 @@ int lili_set_debug(lili_ctx* ctx, int keep_neighbors);
  *                 a scan with more features than guessed is matched again the plain way; results identical either way; not taken with persistent_iterate; default 1), "frame_extract_stream" (1 = a frame whose
  *                 local map is still to be built runs its extraction on a stream of its own, next to the ring merge instead of in front of it: 15-30 us per frame faster in a
  *                 process with one context, ~100 us SLOWER in a process that holds many streams (they share the runtime's few hardware queues); default 0), "imu_time" (1 = lili_imu_preintegrate brackets its kernel with
- *                 two events for lili_imu_kernel_ms; default 0).
- *   extraction    "rot_fold" (1 = the ring stage of lili_extract_rot writes the scan's feature lists itself, four launches; 0 = per-ring lists and a concatenation
+ *                 two events for lili_imu_kernel_ms; default 0), "local_graph_time" (1 = the lili_local_graph* calls bracket their kernel with two events for
+ *                 lili_local_graph_kernel_ms; default 0).
+ *   extraction   "rot_fold" (1 = the ring stage of lili_extract_rot writes the scan's feature lists itself, four launches; 0 = per-ring lists and a concatenation
  *                 launch, also the fallback of a look-back that gave up; default 1), "rot_segment_wait" (1 = a segment whose pick may lie under marks of the
  *                 segment before it waits for them inside the segment stage; 0 = the ring stage repeats such a segment; default 1).
  *   archive / map "archive_max_mb" (bound on the keyframe archive's slab pool in MiB; 0 = unlimited, the default; a push beyond it fails), "archive_slab_mb" (size of
@@ -788,6 +789,65 @@ typedef struct lili_imu_kf_state { int64_t idx; double t_cur; double acc0[3], gy
 void lili_imu_kf_reset(lili_imu_kf_state* st);
 int lili_imu_keyframe_samples(lili_imu_kf_state* st, const double* stamps, const double* acc, const double* gyr, size_t n, double t_kf,
                               double* dt_out, double* acc_out, double* gyr_out, size_t cap, size_t* n_out);
+
+/* ---- Per-frame trajectory: IMU chain and local pose graph on the device (lili_local_graph.hip) --------------------------
+ * What buildLocalPoseGraph and optimizeLocalGraph (L/src/BackendFusion.cpp:1892-2175, 1309-1384, L/include/factors/LidarPoseFactor.h) do after a window
+ * solve: a pose for each of the n scans between two keyframes.  A pose is 7 doubles, p (3) then q (w, x, y, z); a measurement is 7 doubles, delta p then
+ * delta q.  Everything is host memory; every call is blocking: one packed upload from page-locked staging, ONE launch of one workgroup (f64, no
+ * contraction), one synchronisation.
+ *
+ * LILI_LOCAL_MAX_FRAMES: L/src/LidarOdometry.cpp:575 makes a scan a keyframe at the latest when two non-keyframes precede it, so the reference itself
+ * never produces n > 2; 16 leaves room for other keyframe rules and keeps every matrix of the solve (6 n = 96 columns, block tridiagonal) in LDS.
+ *
+ * lili_local_graph_propagate — the IMU walk of L:1897-2108 and the measurements of L:2110-2170.  walk: the raw sample buffer (stamps / acc / gyr, n_imu
+ *   entries), ii0 = imu_idx_in_kf of the left keyframe, scan_stamps = the n + 2 stamps t_0 (left keyframe), t_1 .. t_n (the scans), t_{n+1} (right keyframe),
+ *   the start state (P0, R0 row-major and multiplied on as it is, V0: INTEGRATION.md says which Ps / Rs / Vs the reference passes), g (subtracted from the
+ *   rotated accelerations) and the left anchor's pose, which the first measurement is relative to.  Kept from the text: biases are zero; deltaQ is the
+ *   un-normalised small-angle quaternion, turned into a matrix and multiplied on, R is never re-normalised; accelerations are clamped to +-15 / +-15 / +-18
+ *   wherever the text clamps (not at the opening interpolation of a non-keyframe interval, but at the one of the closing interval); the sample loop compares
+ *   with a strict <; the index steps back by one after every frame but the last; the closing partial step takes dt1 from the sample in front of the index
+ *   even when the loop consumed nothing; the quaternion of a matrix follows Eigen's branches.  f32_positions != 0: a frame's position goes through the float
+ *   members of pcl::PointXYZI as pose_each_frame stores it (the quaternions are PointPoseInfo's doubles); 0: f64 throughout.
+ *   Out: poses (n x 7), end_state (15: P, R row-major, V at t_{n+1}), meas ((n + 1) x 7).
+ * lili_local_graph_evaluate — cost, gradient (6 n) and J^T J (6 n x 6 n, row-major, exactly zero outside the block tridiagonal) of the n + 1 factors at
+ *   `poses`, in the local coordinates of ceres::QuaternionParameterization (translation block, then rotation block per frame); anchors = p_L q_L p_R q_R (14).
+ *   Residual k = 2 vec(dq^-1 q_a^-1 q_b), then q_a^-1 (p_b - p_a) - dp on nodes k, k + 1 of [L, x_1 .. x_n, R], unit weight, no loss, inverse() = conjugate /
+ *   squared norm; the Jacobians are analytic.
+ * lili_local_graph_solve — Ceres 2.0's TrustRegionMinimizer with DoglegStrategy (TRADITIONAL_DOGLEG, Jacobi scaling) on that problem from `poses`
+ *   (in: the initial frame poses, out: the solved ones) as one persistent single-workgroup launch; options NULL = lili_lm_default_options (max_iterations
+ *   15, as optimizeLocalGraph sets it).  The regularised normal equations are solved by a banded Cholesky factorisation where Ceres uses QR on the augmented
+ *   Jacobian.  A candidate that triggers the parameter or the function tolerance is not taken.
+ * lili_local_graph — propagate, then solve from the propagated poses between the left anchor and `right` (the right keyframe's solved pose), in the same
+ *   single launch: poses, meas and summary are byte-identical to the two calls in a row.
+ * n = 0 (two keyframes in a row) is valid everywhere: no poses, one measurement, zero iterations, termination LILI_LM_GRADIENT_TOLERANCE (nothing to move),
+ *   initial_cost = final_cost = the cost of the one factor between the anchors.
+ * LILI_E_ARG — a null pointer, n outside 0 .. LILI_LOCAL_MAX_FRAMES, a non-finite input, scan stamps that are not strictly increasing, ii0 < 0, any sample
+ *   index the walk would read at or beyond n_imu (the text reads imu_buf[ii + 1] past the last scan stamp; checked on the host before the launch), an
+ *   interpolation with dt1 + dt2 == 0, more than LILI_IMU_MAX_SAMPLES samples between the first and the last index read, options as lili_s2m_solve_lm
+ *   refuses them — leaves every output untouched. */
+#define LILI_LOCAL_MAX_FRAMES 16
+typedef struct lili_local_walk {
+    const double* stamps; const double* acc; const double* gyr;    /* n_imu, n_imu x 3, n_imu x 3 */
+    int64_t n_imu, ii0;
+    const double* scan_stamps;                                      /* n + 2 */
+    double P0[3], R0[9], V0[3], g[3];
+    double left[7];                                                 /* the left anchor's pose */
+    int32_t f32_positions, reserved_;
+} lili_local_walk;
+typedef struct lili_local_graph_summary {
+    lili_lm_summary lm;                          /* termination: LILI_LM_*; n_surf / n_edge are 0 */
+    double final_mu;                             /* DoglegStrategy's mu after the last linearisation */
+    int32_t dogleg_case[LILI_LM_MAX_LOG];        /* per logged candidate: 1 = Gauss-Newton step, 2 = scaled gradient, 3 = interpolated between the two */
+    int32_t reused[LILI_LM_MAX_LOG];             /* ... and whether it came from the previous candidate's subproblem (after a rejected step) */
+} lili_local_graph_summary;
+int lili_local_graph_propagate(lili_ctx* ctx, const lili_local_walk* walk, int n, double* poses, double* end_state, double* meas);
+int lili_local_graph_evaluate(lili_ctx* ctx, int n, const double* anchors, const double* meas, const double* poses, double* cost, double* gradient, double* jtj);
+int lili_local_graph_solve(lili_ctx* ctx, int n, const double* anchors, const double* meas, double* poses, const lili_lm_options* options,
+                           lili_local_graph_summary* summary);
+int lili_local_graph(lili_ctx* ctx, const lili_local_walk* walk, int n, const double* right, const lili_lm_options* options, double* poses, double* meas,
+                     lili_local_graph_summary* summary);
+/* Device time of the last lili_local_graph* call's kernel in milliseconds (option "local_graph_time", tools/local_graph_time.py); LILI_E_STATE when there is none. */
+int lili_local_graph_kernel_ms(lili_ctx* ctx, float* ms);
 
 /* ---- callers / data formats either side of the path ------------------------- */
 

@@ -106,6 +106,26 @@ class ImuKfState(C.Structure):
     _fields_ = [("idx", C.c_int64), ("t_cur", C.c_double), ("acc0", C.c_double * 3), ("gyr0", C.c_double * 3), ("first", C.c_int32), ("reserved", C.c_int32)]
 
 
+LOCAL_MAX_FRAMES = 16
+
+
+class LocalWalk(C.Structure):
+    _fields_ = [("stamps", C.POINTER(C.c_double)), ("acc", C.POINTER(C.c_double)), ("gyr", C.POINTER(C.c_double)), ("n_imu", C.c_int64), ("ii0", C.c_int64),
+                ("scan_stamps", C.POINTER(C.c_double)), ("P0", C.c_double * 3), ("R0", C.c_double * 9), ("V0", C.c_double * 3), ("g", C.c_double * 3),
+                ("left", C.c_double * 7), ("f32_positions", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class LocalGraphSummary(C.Structure):
+    _fields_ = [("lm", LmSummary), ("final_mu", C.c_double), ("dogleg_case", C.c_int32 * LM_MAX_LOG), ("reused", C.c_int32 * LM_MAX_LOG)]
+
+    def as_dict(self):
+        d = self.lm.as_dict()
+        for e, case, reused in zip(d["log"], self.dogleg_case, self.reused):
+            e["case"], e["reused"] = int(case), bool(reused)
+        d["final_mu"] = self.final_mu
+        return d
+
+
 class WindowPrior(C.Structure):
     _fields_ = [("n_rows", C.c_int32), ("n_cols", C.c_int32), ("n_blocks", C.c_int32), ("reserved_", C.c_int32), ("block_kind", C.POINTER(C.c_int32)),
                 ("block_keyframe", C.POINTER(C.c_int32)), ("x0", C.POINTER(C.c_double)), ("J0", C.POINTER(C.c_double)), ("r0", C.POINTER(C.c_double))]
@@ -289,6 +309,11 @@ _SIGS = {
     "lili_imu_kf_reset": (None, [C.c_void_p]),
     "lili_imu_keyframe_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                             C.POINTER(C.c_size_t)]),
+    "lili_local_graph_propagate": (C.c_int, [C.c_void_p, C.POINTER(LocalWalk), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lili_local_graph_evaluate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "lili_local_graph_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LmOptions), C.POINTER(LocalGraphSummary)]),
+    "lili_local_graph": (C.c_int, [C.c_void_p, C.POINTER(LocalWalk), C.c_int, C.c_void_p, C.POINTER(LmOptions), C.c_void_p, C.c_void_p, C.POINTER(LocalGraphSummary)]),
+    "lili_local_graph_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "lili_marg_add_lidar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
     "lili_gn_step_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_gram_to_factor": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),

@@ -192,6 +192,7 @@ void lili_ctx_destroy(lili_ctx* ctx) {
     if (ctx->ext_loop && ctx->ext_loop_free) ctx->ext_loop_free(ctx->ext_loop);
     if (ctx->ext_archive && ctx->ext_archive_free) ctx->ext_archive_free(ctx->ext_archive);
     if (ctx->ext_imu && ctx->ext_imu_free) ctx->ext_imu_free(ctx->ext_imu);
+    if (ctx->ext_local && ctx->ext_local_free) ctx->ext_local_free(ctx->ext_local);
     for (auto& st : ctx->side) if (st) (void)hipStreamDestroy(st);
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
     if (ctx->extract_fork_ev) (void)hipEventDestroy(ctx->extract_fork_ev);
@@ -253,6 +254,7 @@ int lili_set_option(lili_ctx* ctx, const char* name, int value) {
     if (std::strcmp(name, "overlap_gn") == 0) { ctx->overlap_gn = value != 0; return LILI_OK; }
 #endif      // lili_s2m_iterate*: the association behind a reduction + GN kernel starts without waiting for it (0: three barriers per iteration)
     if (std::strcmp(name, "imu_time") == 0) { ctx->imu_time = value != 0; return LILI_OK; }
+    if (std::strcmp(name, "local_graph_time") == 0) { ctx->local_graph_time = value != 0; return LILI_OK; }
     if (std::strcmp(name, "archive_max_mb") == 0) { if (value < 0) return ctx->fail(LILI_E_ARG, "archive_max_mb must be >= 0 (0: unlimited)"); ctx->archive_max_mb = value; return LILI_OK; }
     if (std::strcmp(name, "archive_slab_mb") == 0) { if (value < 1 || value > 65536) return ctx->fail(LILI_E_ARG, "archive_slab_mb must be in 1..65536"); ctx->archive_slab_mb = value; return LILI_OK; }      // slabs handed out stay as they are
     if (std::strcmp(name, "global_map_batch_points") == 0) {

@@ -240,6 +240,9 @@ struct lili_ctx {
         int n_rows = 0, n_cols = 0, n_blocks = 0, rank = 0, sweeps[2] = {0, 0};
         int32_t kind[3 * LILI_WINDOW_MAX_KF] = {}, kf[3 * LILI_WINDOW_MAX_KF] = {};
     } win_res_tab;
+    void* ext_local = nullptr;               // local pose graph: page-locked staging, device buffers, timing events (lili_local_graph.hip)
+    void (*ext_local_free)(void*) = nullptr;
+    bool local_graph_time = false;           // option "local_graph_time": events around k_local_graph (lili_local_graph_kernel_ms)
 };
 
 #define HIPCHK(expr)                                                                                         \

@@ -185,6 +185,34 @@ struct ImuSegDev {
     double ba[3], bg[3], g[3];
     double P0[3], R0[9], V0[3];
 };
+// Local pose graph (k_local_graph in lili_local_graph.hip): ONE workgroup of one wave.  The packed upload is LocalGraphIn followed by the n_rows sample rows the
+// walk reads, 7 doubles each (stamp, acc[3], gyr[3]), rebased so that row 0 is sample ii0.  mode: what the launch does.
+constexpr int kLocalThreads = 64;
+constexpr int kLocalMaxFrames = LILI_LOCAL_MAX_FRAMES, kLocalMaxFactors = kLocalMaxFrames + 1, kLocalMaxN = 6 * kLocalMaxFrames;
+constexpr int kLocalBand = 12;       // H = J^T J is block tridiagonal with 6 x 6 blocks: row i holds columns i - 11 .. i of the lower triangle, [i * kLocalBand + (i - j)]
+constexpr int kLocalStageRows = 256; // sample rows kept in LDS for the walk; a longer subrange is read from global memory
+constexpr int kLocalRow = 7;
+enum { kLocalWalk = 1, kLocalEvaluate = 2, kLocalSolve = 4 };
+struct LocalOptDev {                 // the members lm_trust_init reads
+    int max_iter, pad_;
+    double function_tolerance, gradient_tolerance, parameter_tolerance;
+    double initial_radius, max_radius, min_radius, min_relative_decrease, min_lm_diagonal, max_lm_diagonal;
+};
+struct LocalGraphIn {
+    int n, mode, n_rows, f32_positions;
+    LocalOptDev opt;
+    double T[kLocalMaxFrames + 2];
+    double P0[3], R0[9], V0[3], g[3];
+    double left[7], right[7];
+    double meas[kLocalMaxFactors * 7];      // read unless mode has kLocalWalk
+    double poses[kLocalMaxFrames * 7];      // the state to evaluate / the initial state, unless mode has kLocalWalk
+};
+struct LocalGraphOut {
+    double poses[kLocalMaxFrames * 7], end_state[15], meas[kLocalMaxFactors * 7];
+    double cost, gradient[kLocalMaxN];
+    lili_local_graph_summary summary;
+    double jtj[kLocalMaxN * kLocalMaxN];    // kLocalEvaluate only: the leading (6 n)^2 doubles, row-major with stride 6 n
+};
 struct ImuOutDev {                   // lili_window_imu's numbers, then the prediction
     double sum_dt, g[3], delta_p[3], delta_q[4], delta_v[3], lin_ba[3], lin_bg[3], jacobian[225], covariance[225];
     double P1[3], R1[9], V1[3];

@@ -45,6 +45,8 @@ template <int L> __global__ void k_associate_coop_window(WinAssocArgs, MatchPara
 template <int L> __global__ void k_iterate_coop(AssocArgs, AssocArgs, MatchParams, IterArgs);
 // lili_imu.hip: IMU pre-integration, one workgroup per segment
 __global__ void k_imu_preintegrate(const ImuSegDev*, const double*, ImuOutDev*);
+// lili_local_graph.hip: IMU walk and local pose graph, one workgroup of one wave
+__global__ void k_local_graph(const LocalGraphIn*, LocalGraphOut*);
 }  // namespace lili
 
 // lili_map.hip: the three-kernel exclusive scan (k_scan_block_sums, k_scan_sums, k_scan_apply) of n words into out[0 .. n]; in == out is allowed

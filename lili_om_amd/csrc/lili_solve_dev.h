@@ -1,6 +1,7 @@
 // The pieces that end an evaluation in every device solver — "turn a Gram partial into a step on a pose" — in ONE definition each:
 //   gn_update_block (lili_s2m.hip: launch-by-launch Gauss-Newton), solve_lm_body (lili_s2m_lm.hip: per-slot Levenberg-Marquardt),
-//   k_iterate_coop (lili_s2m_coop.hip: persistent Gauss-Newton), k_window_solve (lili_window.hip: the joint keyframe window).
+//   k_iterate_coop (lili_s2m_coop.hip: persistent Gauss-Newton), k_window_solve (lili_window.hip: the joint keyframe window); the trust-region bookkeeping is
+//   also k_local_graph's (lili_local_graph.hip: the per-frame chain, dogleg).
 // Every workgroup of a persistent launch runs these on the same bits and must arrive at the same bits, and the trust-region decisions follow
 // Ceres' order of checks: a change here changes all four solvers at once, which is the point.  Everything is __device__ __forceinline__ or a type;
 // the library is built with -ffp-contract=off, so the value of every result is fixed by the expression trees below.
@@ -112,7 +113,8 @@ struct LmTrust {
     double function_tolerance, gradient_tolerance, parameter_tolerance;
     double max_radius, min_radius, min_relative_decrease, min_lm_diagonal, max_lm_diagonal;
 };
-__device__ __forceinline__ void lm_trust_init(LmTrust& t, const LmArgs& o) {      // ONE lane
+template <class Options>      // LmArgs, or any struct with its option members (LocalOptDev)
+__device__ __forceinline__ void lm_trust_init(LmTrust& t, const Options& o) {      // ONE lane
     t.max_iter = o.max_iter;
     t.function_tolerance = o.function_tolerance; t.gradient_tolerance = o.gradient_tolerance; t.parameter_tolerance = o.parameter_tolerance;
     t.max_radius = o.max_radius; t.min_radius = o.min_radius; t.min_relative_decrease = o.min_relative_decrease;
@@ -141,8 +143,12 @@ __device__ __forceinline__ bool lm_trust_invalid(LmTrust& t, const double radius
     return true;          // (the loop head checks max iterations, then the radius)
 }
 // The candidate's cost is known: accept or reject, by ONE lane.  xnorm = |x| at the accepted point.  `boss` writes row n_log of summary->it.  Sets cost, radius,
-// decrease, n_ok, it, term, go, take and returns `accepted`; what "taking" the candidate means is the caller's.
-__device__ __forceinline__ int lm_trust_judge(LmTrust& t, const double new_cost, const double xnorm, lili_lm_summary* summary, int& n_log, const bool boss) {
+// decrease, n_ok, it, term, go, take and returns `accepted`; what "taking" the candidate means is the caller's.  The log row, the order of the checks and the
+// minimum-radius exit are TrustRegionMinimizer's and the same for every strategy; how the radius moves is the strategy's: accepted_radius(t, rho) and
+// rejected_radius(t) (lambdas or functors, inlined).
+template <class Accepted, class Rejected>
+__device__ __forceinline__ int lm_trust_judge_with(LmTrust& t, const double new_cost, const double xnorm, lili_lm_summary* summary, int& n_log, const bool boss,
+                                                   Accepted accepted_radius, Rejected rejected_radius) {
     int accepted = 0, stop = 0;
     const double rho = (t.cost - new_cost) / t.model_change;
     if (boss && summary && n_log < LILI_LM_MAX_LOG) {
@@ -156,13 +162,10 @@ __device__ __forceinline__ int lm_trust_judge(LmTrust& t, const double new_cost,
     else if (fabs(t.cost - new_cost) <= t.function_tolerance * t.cost) { t.term = LILI_LM_FUNCTION_TOLERANCE; stop = 1; }
     else if (rho > t.min_relative_decrease) {
         accepted = 1;
-        const double f = 2.0 * rho - 1.0;
-        t.radius = fmin(t.max_radius, t.radius / fmax(1.0 / 3.0, 1.0 - f * f * f));
-        t.decrease = 2.0;
+        accepted_radius(t, rho);
     } else {
-        // LevenbergMarquardtStrategy::StepRejected: no clamp; MinTrustRegionRadiusReached ends the solve (CONVERGENCE) once the radius is
-        // at or below min_trust_region_radius
-        t.radius = t.radius / t.decrease; t.decrease *= 2.0;
+        // StepRejected; MinTrustRegionRadiusReached ends the solve (CONVERGENCE) once the radius is at or below min_trust_region_radius
+        rejected_radius(t);
         if (!(t.radius > t.min_radius)) { t.term = t.it + 1 >= t.max_iter ? LILI_LM_MAX_ITERATIONS : LILI_LM_MIN_RADIUS; stop = 1; }      // (max iterations is checked first)
     }
     if (accepted) { t.cost = new_cost; t.n_ok++; }
@@ -172,6 +175,16 @@ __device__ __forceinline__ int lm_trust_judge(LmTrust& t, const double new_cost,
     t.go = stop ? 0 : 1;
     t.take = accepted;
     return accepted;
+}
+// LevenbergMarquardtStrategy: StepAccepted's cubic, clamped to max_radius; StepRejected divides by a divisor that doubles with every rejection in a row, no clamp
+__device__ __forceinline__ int lm_trust_judge(LmTrust& t, const double new_cost, const double xnorm, lili_lm_summary* summary, int& n_log, const bool boss) {
+    return lm_trust_judge_with(t, new_cost, xnorm, summary, n_log, boss,
+        [](LmTrust& s, const double rho) {
+            const double f = 2.0 * rho - 1.0;
+            s.radius = fmin(s.max_radius, s.radius / fmax(1.0 / 3.0, 1.0 - f * f * f));
+            s.decrease = 2.0;
+        },
+        [](LmTrust& s) { s.radius = s.radius / s.decrease; s.decrease *= 2.0; });
 }
 __device__ __forceinline__ void lm_write_summary(lili_lm_summary* summary, const LmTrust& t, const double cost0, const int n_log, const int* counts) {
     summary->iterations = t.it; summary->successful_steps = t.n_ok; summary->termination = t.term;
