@@ -105,7 +105,8 @@ int lili_set_debug(lili_ctx* ctx, int keep_neighbors);
  *                 MI355X), "merge_kinds" (1 = surf and edge of a keyframe share ONE association and ONE linearisation launch; default 1), "fuse_lin"
  *                 (1 = flavours without count scaling run two launches per iteration below ~100 k queries, the association linearises on the fly;
  *                 default 1; "fuse_lin_block" its workgroup size), "assoc_lpq" (lanes per query in the association of small scans: 0 = by size,
- *                 1 / 2 / 4 / 8 / 16 forces a value), "count_barrier" (default 0, measured no gain), "persistent_iterate" (1 = scans of <= 128
+ *                 1 / 2 / 4 / 8 / 16 forces a value), "assoc_prio" (1 = the waves of the association kernels run at issue priority 1 while they search and at
+ *                 0 from the fit on; default 1, same bits, 0 for A/B), "count_barrier" (default 0, measured no gain), "persistent_iterate" (1 = scans of <= 128
  *                 cooperative workgroups run a whole registration as ONE persistent launch; default 0, measured slower; poses then differ by the
  *                 partition of the Gram sum, <= 1e-10), "p2p_fusion" (0 = lili_s2m_iterate_sharded runs lili_p2p_allreduce as its own launches;
  *                 default 1);

@@ -230,6 +230,7 @@ int lili_set_option(lili_ctx* ctx, const char* name, int value) {
         if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return ctx->fail(LILI_E_ARG, "assoc_lpq must be 0 (auto), 1, 2, 4, 8 or 16");
         ctx->assoc_lpq = value; return LILI_OK;
     }
+    if (std::strcmp(name, "assoc_prio") == 0) { ctx->assoc_prio = value != 0; return LILI_OK; }      // association: wave priority 1 while searching, 0 from the fit on (0: no priority changes, A/B)
     if (std::strcmp(name, "fuse_lin_block") == 0) { if (value != 0 && value != kAssocBlock && value != kBlock) return ctx->fail(LILI_E_ARG, "fuse_lin_block must be 0 (auto), 64 or 256"); ctx->fuse_lin_block = value; return LILI_OK; }
     if (std::strcmp(name, "fine_grid") == 0) { ctx->fine_grid = value != 0; return LILI_OK; }
     if (std::strcmp(name, "sort_ride_hist") == 0) { ctx->sort_ride_hist = value != 0; return LILI_OK; }

@@ -170,6 +170,11 @@ struct lili_ctx {
     double focus[3] = {0, 0, 0}, focus_radius = 0;   // lili_map_focus: where the super-row copy is built (radius 0: everywhere)
     int fuse_lin_block = 0;      // 0 = by scan size, else 64 / 256 (A/B, tests)
     int assoc_lpq = 0;           // lanes per query of the association: 0 = by launch size (coop_lanes), 1 = one lane per query always, 2 / 4 / 8 / 16 forced (A/B, tests)
+    bool assoc_prio = true;      // the association waves run at issue priority 1 (s_setprio) from kernel entry until their five winners are resolved and at 0 from the fit on
+                                 // (phase_prio): the one-lane kernels and k_associate_coop<L, false>.  Same bits.  Measured, six alternating 200-step regions each (it/s, median,
+                                 // min-max): 0: 32 361 (32 320-32 431), 1: 32 978 (32 919-33 090), the commit before: 32 246 (32 043-32 396) — 30.90 -> 30.32 us per step;
+                                 // trace: k_associate_surf 16.48 -> 16.01 us, k_associate_coop<2> (first launch after a restart) 29.95 -> 28.74 us (medians of four traces);
+                                 // profiles/r07_assoc_prio_ab.jsonl.  The waves of a SIMD still end staggered (profiles/r07_assoc_phases_prio1.txt): DESIGN.md §4
     bool count_barrier = false;  // (measured: 19.4 vs 19.8 us per iteration at 2 k queries — the wait for the slowest workgroup costs what the launch saved; off by default)
 
     bool persistent_off_now = false;  // set by lili_s2m_iterate_window for more than four slots

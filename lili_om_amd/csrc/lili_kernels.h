@@ -89,6 +89,8 @@ struct MatchParams {     // device copy of lili_s2m_params (+ derived values)
     int debug;   // LILI_DEBUG env, tests and profiling builds only: 256 / 512 = clock stamps of the linearisation / reduction / association prologue into SlotState::tprof,
                  // 2048 = never fall back to the pivoted QR, 16384 = always the pivoted QR, 32768 = exact (d2, index) selector only (the tier tests force both tiers and
                  // compare bit for bit), 4096 = per-workgroup timestamps (only in a -DLILI_PHASE_PROBE build: tools/assoc_blocks.py, tools/assoc_phases.sh)
+    int assoc_prio;   // option "assoc_prio" (lili_ctx.h), set by the launchers of the one-lane association kernels and of k_associate_coop<L, false> alone (with_prio, lili_match.hip): the
+                      // waves run at issue priority 1 while they search and at 0 from the fit on (phase_prio, lili_s2m_dev.h)
 };
 
 // Arguments of one kind (surf or edge) of the combined linearisation launch k_linearize.

@@ -58,6 +58,13 @@ static int check_slot_list(lili_ctx* ctx, const int* slots, int n_slots, const c
     return LILI_OK;
 }
 
+// the kernel's copy of the parameters for a launch of the one-lane association kernels and of k_associate_coop<L, false>: these carry the context's "assoc_prio"
+// (phase_prio, lili_s2m_dev.h); every other kernel sees 0
+static MatchParams with_prio(const lili_ctx* ctx, const MatchParams& P) {
+    MatchParams k = P;
+    k.assoc_prio = ctx->assoc_prio ? 1 : 0;
+    return k;
+}
 // a pose the host provides ...
 static PoseArg pose_at(const double t[3], const double q[4]) {
     PoseArg pa{};
@@ -267,9 +274,9 @@ static int launch_associate(lili_ctx* ctx, int slot, int kind, const PoseArg& pa
     } else if (kind == LILI_KIND_SURF) {
         if (!livox_aux_ok(m, ks, kind, P))
             return ctx->fail(LILI_E_STATE, !m.has_aux ? "associate: Livox variant needs reflectivity (aux_offset) on the surf map" : "associate: Livox variant needs reflectivity (aux_offset) on the surf queries");
-        launch_k(ctx->stream, any_order, k_associate_surf<kAssocBlock>, grid, block, 0, a.queries, n, a.g, pa, P, a.rec0, static_cast<double*>(a.rec1), a.valid, a.dbg_idx, a.dbg_d2, a.block_counts);
+        launch_k(ctx->stream, any_order, k_associate_surf<kAssocBlock>, grid, block, 0, a.queries, n, a.g, pa, with_prio(ctx, P), a.rec0, static_cast<double*>(a.rec1), a.valid, a.dbg_idx, a.dbg_d2, a.block_counts);
     } else {
-        launch_k(ctx->stream, any_order, k_associate_edge<kAssocBlock>, grid, block, 0, a.queries, n, a.g, pa, P, a.rec0, static_cast<float4*>(a.rec1), a.valid, a.dbg_idx, a.dbg_d2, a.block_counts);
+        launch_k(ctx->stream, any_order, k_associate_edge<kAssocBlock>, grid, block, 0, a.queries, n, a.g, pa, with_prio(ctx, P), a.rec0, static_cast<float4*>(a.rec1), a.valid, a.dbg_idx, a.dbg_d2, a.block_counts);
     }
     HIPCHK(hipGetLastError());
     return LILI_OK;
@@ -293,7 +300,7 @@ static int launch_associate_both(lili_ctx* ctx, int slot, const PoseArg& pa, con
     if (!coop_eligible(ctx, slot, LILI_MASK_SURF | LILI_MASK_EDGE, P, &n_all)) return 1;
     AssocArgs A[2];
     for (int kind = 0; kind < 2; kind++) TRY(assoc_args_of(ctx, slot, kind, ctx->map[kind].view, ctx->slots[slot].k[kind].n_blocks, 1, A[kind]));
-    launch_k(ctx->stream, pa.wait_key != 0ull, k_associate_both, dim3(A[0].nb + A[1].nb), dim3(kAssocBlock), 0, A[0], A[1], pa, P);
+    launch_k(ctx->stream, pa.wait_key != 0ull, k_associate_both, dim3(A[0].nb + A[1].nb), dim3(kAssocBlock), 0, A[0], A[1], pa, with_prio(ctx, P));
     HIPCHK(hipGetLastError());
     return LILI_OK;
 }
@@ -336,10 +343,11 @@ static int launch_associate_coop(lili_ctx* ctx, int slot, int kind_mask, const P
     if (lin) for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) HIPCHK(sl.k[kind].partials_wave.ensure((size_t)A[kind].nb * kPartialStride * sizeof(double)));
     const dim3 grid(A[0].nb + A[1].nb), block(256);
     double* ps = sl.k[0].partials_wave.as<double>(); double* pe = sl.k[1].partials_wave.as<double>();
+    const MatchParams Pk = with_prio(ctx, P);      // the association-only launch carries the option (measured on the first launch after a restart, L = 2: lili_ctx.h); the linearising one does not
     if (!with_lanes(L, [&](auto lanes) {
             constexpr int LL = decltype(lanes)::value;
             if (lin) hipLaunchKernelGGL((k_associate_coop<LL, true>), grid, block, 0, ctx->stream, A[0], A[1], pa, P, ps, pe, ctx->state(slot), cb_blocks);
-            else launch_k(ctx->stream, pa.wait_key != 0ull, (k_associate_coop<LL, false>), grid, block, 0, A[0], A[1], pa, P, ps, pe, ctx->state(slot), 0);
+            else launch_k(ctx->stream, pa.wait_key != 0ull, (k_associate_coop<LL, false>), grid, block, 0, A[0], A[1], pa, Pk, ps, pe, ctx->state(slot), 0);
         })) return 1;
     if (lin) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, (const double*)ps, A[0].nb, (const double*)pe, A[1].nb, d_out, ctx->state(slot),
                                 1 | (P.debug & 256), P2PView{}, 0ull, (double*)nullptr, ctx->take_state_mirror(slot), pa.state);
@@ -475,9 +483,9 @@ static int launch_associate_lin_reduce(lili_ctx* ctx, int slot, int kind_mask, c
         HIPCHK(ks.partials_wave.ensure((size_t)ks.n_blocks * kPartialStride * sizeof(double)));      // (n_blocks >= nb: bs is kAssocBlock or larger)
     }
     // k_associate_lin: blocks [0, E.nb) edge, the rest surf
-    if (bs == kAssocBlock) hipLaunchKernelGGL(k_associate_lin<kAssocBlock>, dim3(A[0].nb + A[1].nb), dim3(kAssocBlock), 0, ctx->stream, A[0], A[1], pa, P,
+    if (bs == kAssocBlock) hipLaunchKernelGGL(k_associate_lin<kAssocBlock>, dim3(A[0].nb + A[1].nb), dim3(kAssocBlock), 0, ctx->stream, A[0], A[1], pa, with_prio(ctx, P),
                                               sl.k[0].partials_wave.as<double>(), sl.k[1].partials_wave.as<double>());
-    else hipLaunchKernelGGL(k_associate_lin<kBlock>, dim3(A[0].nb + A[1].nb), dim3(kBlock), 0, ctx->stream, A[0], A[1], pa, P,
+    else hipLaunchKernelGGL(k_associate_lin<kBlock>, dim3(A[0].nb + A[1].nb), dim3(kBlock), 0, ctx->stream, A[0], A[1], pa, with_prio(ctx, P),
                             sl.k[0].partials_wave.as<double>(), sl.k[1].partials_wave.as<double>());
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, (const double*)sl.k[0].partials_wave.as<double>(), A[0].nb,
                        (const double*)sl.k[1].partials_wave.as<double>(), A[1].nb, d_out, ctx->state(slot), 1 | (P.debug & 256), P2PView{}, 0ull, (double*)nullptr, ctx->take_state_mirror(slot), pa.state);

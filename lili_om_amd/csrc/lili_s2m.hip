@@ -672,6 +672,7 @@ __device__ __forceinline__ void assoc_surf_body(
 #ifdef LILI_PHASE_PROBE
     const long long t_begin = (P.debug & 4096) ? (long long)__builtin_amdgcn_s_memrealtime() : 0ll;   // profiling build only (tools/assoc_blocks.py)
 #endif
+    phase_prio(P, true);                                                    // body level: every lane of the wave passes here
     const int i0 = bid * BS;
     const bool live = i0 + (int)threadIdx.x < n_q;
     const int i = live ? i0 + (int)threadIdx.x : 0;
@@ -691,6 +692,7 @@ __device__ __forceinline__ void assoc_surf_body(
 #endif
     PHASE_STAMP(pp, 1, px);                                                 // query loaded and moved into the map frame
     if (live) knn5_grid(g, tab, px, py, pz, gate_bound(P.kd_max_radius), nn, P.debug, pp);
+    phase_prio(P, false);                                                   // between the two `if (live)`: winners resolved, the fit begins
     bool ok = false;
     if (live) {
         store_debug_nn(g, nn, i, dbg_idx, dbg_d2);
@@ -733,6 +735,7 @@ __device__ __forceinline__ void assoc_edge_body(
         const float4* __restrict__ queries, int n_q, const GridView& g, const PoseArg& pa, const MatchParams& P,
         float4* __restrict__ rec_a, float4* __restrict__ rec_b, unsigned char* __restrict__ valid,
         int* __restrict__ dbg_idx, float* __restrict__ dbg_d2, int* __restrict__ block_counts, int bid, TAB& tab, LaneRec* rec_out = nullptr) {
+    phase_prio(P, true);                                                    // body level: every lane of the wave passes here
     const int i0 = bid * BS;
     const bool live = i0 + (int)threadIdx.x < n_q;
     const int i = live ? i0 + (int)threadIdx.x : 0;
@@ -743,6 +746,7 @@ __device__ __forceinline__ void assoc_edge_body(
     float px = (float)pmd.x, py = (float)pmd.y, pz = (float)pmd.z;
     Top5 nn; nn.have = false;
     if (live) knn5_grid(g, tab, px, py, pz, gate_bound(P.edge_gate), nn);
+    phase_prio(P, false);                                                   // between the two `if (live)`: winners resolved, the fit begins
     bool ok = false;
     if (live) {
         store_debug_nn(g, nn, i, dbg_idx, dbg_d2);

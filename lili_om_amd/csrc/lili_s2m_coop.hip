@@ -186,6 +186,7 @@ __device__ __forceinline__ void assoc_coop_block(const AssocArgs& A /*the argume
                                                  double* __restrict__ part_surf, double* __restrict__ part_edge, SlotState* cb_state, int cb_blocks) {
     // (the caller selects A: a select between two by-value kernel arguments stays an address select in the kernel-argument segment only when it is
     // written in the kernel itself — through this function's parameters it put both structs into scratch, 408 bytes per lane)
+    phase_prio(P, true);                       // (every lane of the workgroup passes here and at the second call: knn5_coop takes `live` as an argument)
     constexpr int QPB = kCoopBlock / L;
     const int sub = (int)threadIdx.x & (L - 1);
     const int i = vb * QPB + ((int)threadIdx.x / L);
@@ -197,6 +198,7 @@ __device__ __forceinline__ void assoc_coop_block(const AssocArgs& A /*the argume
     const float px = (float)pmd.x, py = (float)pmd.y, pz = (float)pmd.z;
     Top5 nn;
     knn5_coop<L>(A.g, live, sub, px, py, pz, gate_bound(edge ? P.edge_gate : P.kd_max_radius), nn);
+    phase_prio(P, false);                      // winners resolved, the fit begins
     const bool mine = live && sub == 0;        // the lane that owns the group's record
     LaneRec rec{};
     bool ok = false;

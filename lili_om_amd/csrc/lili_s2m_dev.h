@@ -533,6 +533,16 @@ __device__ __forceinline__ bool knn5_grid_sel(const GridView& g, TAB& tab, float
     if constexpr (std::is_same<SEL, Sel5K>::value) return sel.finish(g, qx, qy, qz, best);
     else { sel.to_top5(best); return sel.final_tie(); }
 }
+// Issue priority of the wave by the phase it is in (option "assoc_prio"): 1 from kernel entry until the five winners are resolved, 0 from the fit on, so
+// that on a SIMD a wave that still searches (a chain of loads) issues before one that has reached its fit (f64 arithmetic).  s_setprio is a scalar instruction and
+// ignores EXEC: a call stands only where EVERY lane of the wave passes — in the association bodies, never inside knn5_grid_sel, whose lanes leave one by one (no query,
+// non-finite, outside the grid, tie-redo).  The switch is a kernel argument (one scalar branch around the instruction).
+__device__ __forceinline__ void phase_prio(const MatchParams& P, bool searching) {
+    if (P.assoc_prio) {
+        if (searching) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+    }
+}
 // Fast selection first; the rare queries with an exact distance tie that could matter are repeated with the exact
 // (distance, original index) selector, so the result is always the oracle's.
 template <class TAB>

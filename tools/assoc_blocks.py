@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Profiling aid: per-workgroup begin / end timestamps of one k_associate_surf launch of the bench workload
 (LILI_DEBUG bit 4096 writes them into the neighbour debug rows).  Prints the distribution of wave lifetimes, the start
-skew and how well the SIMDs are packed.  usage: python tools/assoc_blocks.py [after_iters] [extra LILI_DEBUG bits]"""
+skew and how well the SIMDs are packed.  usage: python tools/assoc_blocks.py [after_iters] [extra LILI_DEBUG bits]
+LILI_OPTS="name=value ..." in the environment sets context options first (e.g. LILI_OPTS=assoc_prio=0 for an A/B of the wave priorities)."""
 import os
 import sys
 
@@ -23,6 +24,8 @@ t0, q0 = synth.perturbed_pose(t_body, q_body, np.random.default_rng(synth.SEED_P
 scan = bench.ring_major(w["scan_xyz"], w["scan_ring"])
 ctx = L.Context(0)
 ctx.set_debug(True)
+for kv in os.environ.get("LILI_OPTS", "").split():
+    ctx.set_option(kv.split("=")[0], int(kv.split("=")[1]))
 m = L.ScanToMapMatcher(ctx, P)
 m.set_input_cloud(L.KIND_SURF, w["map_xyz"])
 m.set_queries(0, L.KIND_SURF, scan)
