@@ -1,6 +1,8 @@
 """IMU pre-integration, the parts that need no GPU:
   * tests/golden/ref_preint.npz is what the reference's own header gives now (oracle/_ref/libref_imu.so, where it is built) and what the oracle's
-    restatement gives within the tolerances tests/test_window_cpu.py applies between the two (state 1e-13, Jacobian / covariance 1e-11 of the largest entry);
+    restatement gives within the tolerances tests/test_window_cpu.py applies between the two (state 1e-13, Jacobian / covariance 1e-11 of the largest entry:
+    numpy's `@` sums in another order; per 3 x 3 block and at 5e-14 on the hard streams in tests/test_preint_hard_cases_cpu.py).  That tolerance is the
+    ORACLE's: the device is held to equality entry by entry (tests/preint_hard_cases.py::compare, tests/test_imu_preint_gpu.py);
   * lili_imu_keyframe_samples against the plain-float restatement of L/src/BackendFusion.cpp:1700-1771 (tests/preint_model.py): bit for bit — the
     arithmetic is a handful of IEEE operations in a fixed order;
   * the new structs' sizes and offsets against the header compiled as plain C."""
