@@ -33,20 +33,15 @@ __global__ __launch_bounds__(256) void k_readback_gather(GatherTable t, unsigned
 int lili_readback_add(lili_ctx* ctx, void* dst, const void* d_src, size_t bytes, hipStream_t stream) {
     if (bytes == 0) return LILI_OK;
     hipStream_t s = stream ? stream : ctx->stream;
-    if (!ctx->h_pin) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pin), kPinBytes, hipHostMallocDefault));
-        void* d = nullptr;
-        if (hipHostGetDevicePointer(&d, ctx->h_pin, 0) != hipSuccess) { (void)hipGetLastError(); d = nullptr; }
-        ctx->h_pin_dev = static_cast<unsigned char*>(d);
-    }
+    HIPCHK(ctx->h_pin.ensure(kPinBytes));
     const size_t off = (ctx->h_pin_used + 15) & ~(size_t)15;
     if (off + bytes > kPinBytes) {        // (does not happen with the library's own reads; a large one goes the plain way)
         HIPCHK(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, s));
         return LILI_OK;
     }
-    const bool lazy = ctx->h_pin_dev && s == ctx->stream && bytes <= 16384 && ctx->readback_gather && (int)ctx->h_pin_lazy.size() < lili::kGatherMax;
+    const bool lazy = ctx->h_pin.dev() && s == ctx->stream && bytes <= 16384 && ctx->readback_gather && (int)ctx->h_pin_lazy.size() < lili::kGatherMax;
     if (lazy) ctx->h_pin_lazy.push_back({d_src, off, bytes});
-    else HIPCHK(hipMemcpyAsync(ctx->h_pin + off, d_src, bytes, hipMemcpyDeviceToHost, s));
+    else HIPCHK(hipMemcpyAsync(ctx->h_pin.as<unsigned char>() + off, d_src, bytes, hipMemcpyDeviceToHost, s));
     ctx->h_pin_items.push_back({dst, off, bytes});
     ctx->h_pin_used = off + bytes;
     return LILI_OK;
@@ -70,13 +65,13 @@ int lili_readback_finish(lili_ctx* ctx, hipStream_t stream) {
         lili::GatherTable t{};
         t.n = (int)ctx->h_pin_lazy.size();
         for (int k = 0; k < t.n; k++) { t.src[k] = static_cast<const unsigned char*>(ctx->h_pin_lazy[k].src); t.off[k] = (unsigned)ctx->h_pin_lazy[k].off; t.bytes[k] = (unsigned)ctx->h_pin_lazy[k].bytes; }
-        hipLaunchKernelGGL(lili::k_readback_gather, dim3(1), dim3(256), 0, ctx->stream, t, ctx->h_pin_dev);
+        hipLaunchKernelGGL(lili::k_readback_gather, dim3(1), dim3(256), 0, ctx->stream, t, ctx->h_pin.dev_as<unsigned char>());
         e = hipGetLastError();
         ctx->h_pin_lazy.clear();
         if (e == hipSuccess && s != ctx->stream) e = hipStreamSynchronize(ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) for (const auto& it : ctx->h_pin_items) std::memcpy(it.dst, ctx->h_pin + it.off, it.bytes);
+    if (e == hipSuccess) for (const auto& it : ctx->h_pin_items) std::memcpy(it.dst, ctx->h_pin.as<unsigned char>() + it.off, it.bytes);
     ctx->h_pin_items.clear();
     ctx->h_pin_used = 0;
     ctx->readback_gen++;
@@ -176,29 +171,13 @@ int lili_ctx_create(lili_ctx** out, int device, void* stream) {
 void lili_ctx_destroy(lili_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
+    // nothing is freed before every stream of the context has drained: its members free themselves, in no particular order, and the owned main stream goes last
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->build_stream) { (void)hipStreamSynchronize(ctx->build_stream); (void)hipStreamDestroy(ctx->build_stream); }
-    for (int k = 0; k < 2; k++) { if (ctx->build_done[k]) (void)hipEventDestroy(ctx->build_done[k]); if (ctx->main_mark[k]) (void)hipEventDestroy(ctx->main_mark[k]); }
-    if (ctx->cloud_ready) (void)hipEventDestroy(ctx->cloud_ready);
-    for (auto& m : ctx->map) { m.sorted_f.release(); m.aux_sorted_f.release(); m.cell_start_f.release(); m.cell_start9.release(); m.cell_start9_f.release(); m.row9.release(); m.sorted.release(); m.aux_sorted.release(); m.cell_start.release(); m.cell_tmp.release(); m.pt_cell.release(); m.block_sums.release(); }
-    for (auto& s : ctx->slots) for (auto& k : s.k) { k.q.release(); k.rec0.release(); k.rec1.release(); k.valid.release(); k.dbg_idx.release(); k.dbg_d2.release(); k.partials.release(); k.partials_wave.release(); k.block_counts.release(); }
-    if (ctx->h_records) { (void)hipHostFree(ctx->h_records); ctx->h_records = nullptr; }
-    if (ctx->h_pin) { (void)hipHostFree(ctx->h_pin); ctx->h_pin = nullptr; }
-    if (ctx->h_state_mirror) { (void)hipHostFree(ctx->h_state_mirror); ctx->h_state_mirror = nullptr; ctx->h_state_mirror_dev = nullptr; }
-    ctx->states.release(); ctx->staging.release(); ctx->gram.release(); ctx->win_rec.release(); ctx->win_counts.release(); ctx->misc.release();
-    if (ctx->ext_rot && ctx->ext_rot_free) ctx->ext_rot_free(ctx->ext_rot);
-    if (ctx->ext_livox && ctx->ext_livox_free) ctx->ext_livox_free(ctx->ext_livox);
-    if (ctx->ext_voxel && ctx->ext_voxel_free) ctx->ext_voxel_free(ctx->ext_voxel);
-    if (ctx->ext_loop && ctx->ext_loop_free) ctx->ext_loop_free(ctx->ext_loop);
-    if (ctx->ext_archive && ctx->ext_archive_free) ctx->ext_archive_free(ctx->ext_archive);
-    if (ctx->ext_imu && ctx->ext_imu_free) ctx->ext_imu_free(ctx->ext_imu);
-    if (ctx->ext_local && ctx->ext_local_free) ctx->ext_local_free(ctx->ext_local);
-    for (auto& st : ctx->side) if (st) (void)hipStreamDestroy(st);
-    if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
-    if (ctx->extract_fork_ev) (void)hipEventDestroy(ctx->extract_fork_ev);
-    for (auto& e : ctx->join_ev) if (e) (void)hipEventDestroy(e);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
+    if (ctx->build_stream) (void)hipStreamSynchronize(ctx->build_stream);
+    for (auto& st : ctx->side) if (st) (void)hipStreamSynchronize(st);
+    hipStream_t own = ctx->own_stream ? ctx->stream : nullptr;
     delete ctx;
+    if (own) (void)hipStreamDestroy(own);
 }
 
 const char* lili_last_error(const lili_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }

@@ -157,7 +157,7 @@ struct ArcKeyframe { ArcCloud c[kKinds]; double time = 0, t_po[3] = {0, 0, 0}, q
 
 struct Folded { int id; double t[3], q[4]; };      // a keyframe the table holds and the map pose it was folded at
 struct GlobalMap {
-    void* sort = nullptr;                            // the batch sort's own buffers (lili_voxel.hip)
+    std::unique_ptr<ExtState> sort;                  // the batch sort's own buffers (lili_voxel.hip)
     DevBuf key[2], sum[2], cnt[2];
     int cur = 0;
     long long n_tab = 0;
@@ -174,21 +174,15 @@ struct GlobalMap {
     std::vector<lili::GmSeg> seg_host;
     bool has_map = false;                            // `out` holds the centroids of a successful build
     void clear_table() { n_tab = 0; folded.clear(); box_any = false; n_raw = 0; valid = false; has_map = false; }
-    void release() {
-        lili_vox_sort_free(sort); sort = nullptr;
-        for (DevBuf* b : {&key[0], &key[1], &sum[0], &sum[1], &cnt[0], &cnt[1], &raw, &spts, &flags, &slot, &head_pos, &bkey, &pos, &is_new, &new_rank, &bsum, &bcnt, &long_list, &sums,
-                          &segs, &res, &out}) b->release();
-        clear_table();
-    }
     size_t table_bytes() const { size_t b = out.cap; for (int k = 0; k < 2; k++) b += key[k].cap + sum[k].cap + cnt[k].cap; return b; }
     size_t work_bytes() const {
-        size_t b = lili_vox_sort_bytes(sort);
+        size_t b = lili_vox_sort_bytes(sort.get());
         for (const DevBuf* d : {&raw, &spts, &flags, &slot, &head_pos, &bkey, &pos, &is_new, &new_rank, &bsum, &bcnt, &long_list, &sums, &segs, &res}) b += d->cap;
         return b;
     }
 };
 
-struct ArchiveState {
+struct ArchiveState : ExtState {
     std::vector<Slab> slabs;
     std::vector<ArcKeyframe> kf;
     double t_bl[3] = {0, 0, 0}, q_bl[4] = {1, 0, 0, 0};
@@ -198,13 +192,10 @@ struct ArchiveState {
     std::vector<double> pose_tmp;
     GlobalMap gm;
     void free_slabs() { for (auto& s : slabs) if (s.p) (void)hipFree(s.p); slabs.clear(); bytes = 0; }
-    void release() { free_slabs(); kf.clear(); gm.release(); }
+    ~ArchiveState() override { free_slabs(); }
 };
 
-ArchiveState* archive_of(lili_ctx* ctx) {
-    if (!ctx->ext_archive) { ctx->ext_archive = new ArchiveState(); ctx->ext_archive_free = [](void* p) { auto* s = static_cast<ArchiveState*>(p); s->release(); delete s; }; }
-    return static_cast<ArchiveState*>(ctx->ext_archive);
-}
+ArchiveState* archive_of(lili_ctx* ctx) { return ext_of<ArchiveState>(ctx, lili_ctx::kExtArchive); }
 
 // keyframe_map_pose: (q_po * q_bl, q_po * t_bl + t_po) in f64, Eigen's operation order (L:2659-2660, 2489-2490; lili_om_amd/api.py keyframe_map_pose)
 void map_pose(const double t_po[3], const double a[4], const double t_bl[3], const double b[4], double t[3], double q[4]) {
@@ -344,7 +335,7 @@ int fold_batch(lili_ctx* ctx, GlobalMap& G, int total) {
     unsigned sentinel = 0;
     const unsigned* d_keys = nullptr;
     const int* d_order = nullptr;
-    int rc = lili_voxel_sort_dev(ctx, &G.sort, G.raw.as<float4>(), n, G.leaf, &status, box, &sentinel, &d_keys, &d_order);
+    int rc = lili_voxel_sort_dev(ctx, G.sort, G.raw.as<float4>(), n, G.leaf, &status, box, &sentinel, &d_keys, &d_order);
     if (rc != LILI_OK) return rc;
     if (status == 2) return LILI_OK;      // no finite point: nothing to fold
     if (status == 3) return ctx->fail(LILI_E_ARG, kVoxelOverflowMsg);

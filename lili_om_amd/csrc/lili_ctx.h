@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/lili_hip.h"
 #include "lili_kernels.h"
+#include "lili_own.h"
 
 #include <algorithm>
 #include <cmath>
@@ -9,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -16,26 +18,6 @@
 using namespace lili;
 
 namespace lili_detail {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes + 256 <= cap) return hipSuccess;      // (every buffer keeps >= 256 bytes of slack behind what was asked for: kernels may read whole 16-byte vectors at the end)
-        if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
-    void swap(DevBuf& o) { void* tp = p; p = o.p; o.p = tp; size_t tc = cap; cap = o.cap; o.cap = tc; }
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }   // lili_ctx_destroy deletes the context with its device current
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 struct MapIndex {
     bool valid = false;
@@ -112,17 +94,17 @@ struct lili_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    hipStream_t side[LILI_MAX_SLOTS] = {};   // lili_s2m_iterate_window: one extra stream per concurrently iterated slot (lazy)
-    hipEvent_t fork_ev = nullptr, join_ev[LILI_MAX_SLOTS] = {};
+    Stream side[LILI_MAX_SLOTS];   // lili_s2m_iterate_window: one extra stream per concurrently iterated slot (lazy)
+    Event fork_ev, join_ev[LILI_MAX_SLOTS];
     bool keep_nn = false;
     std::string err;
     MapIndex map[2];
     // lili_map_set_begin / _end: the NEXT index of a kind is built on its own stream (own scratch: staging, bbox / density words) while work
     // already enqueued keeps using the current one
     MapIndex map_next[2];
-    hipStream_t build_stream = nullptr;
-    hipEvent_t build_done[2] = {}, main_mark[2] = {};
-    hipEvent_t cloud_ready = nullptr;      // lili_map_set_begin with a device cloud: the build stream waits for what the context's stream has enqueued so far
+    Stream build_stream;
+    Event build_done[2], main_mark[2];
+    Event cloud_ready;      // lili_map_set_begin with a device cloud: the build stream waits for what the context's stream has enqueued so far
     unsigned long long lm_launches = 0;    // lili_s2m_solve_lm launches of this context: part of the granule keys, so no launch ever sees an older one's partials as its own
     SpecBox spec_box[2];
     bool map_guess_box = true;             // lili_map_set without a box from its caller starts from the previous build's box (+ margin) and checks it at its final read-back (0: measure first, A/B)
@@ -146,17 +128,16 @@ struct lili_ctx {
     DevBuf misc;         // bbox words etc.
     // Small device-to-host reads (counts, boxes, states) land in a page-locked scratch and are copied out after the synchronisation: a D2H into
     // pageable memory is staged by the runtime and blocks, which costs ~10 us more per read (64 KB; lili_readback_* in lili_api.hip).
-    unsigned char* h_pin = nullptr;
+    PinBuf h_pin;
     size_t h_pin_used = 0;
     unsigned long long readback_gen = 0;      // number of lili_readback_finish calls so far: a deferred reader knows whether its items have been delivered
     struct PinItem { void* dst; size_t off, bytes; };
     std::vector<PinItem> h_pin_items;
     struct LazyItem { const void* src; size_t off, bytes; };
     std::vector<LazyItem> h_pin_lazy;          // items whose device-side read happens in lili_readback_finish's gather launch (k_readback_gather)
-    unsigned char* h_pin_dev = nullptr;        // the scratch as the device sees it
     bool readback_gather = true;
-    double* h_records = nullptr;   // page-locked landing area for LILI_MAX_SLOTS Gram records (+ 2 x LILI_MAX_SLOTS counts behind them)
-    double* h_records_dev = nullptr;   // the same memory as the device sees it: the blocking calls' reduction kernels write their records THERE (round 4: no copy launch between the kernel and the host)
+    PinBuf h_records;   // page-locked landing area for LILI_MAX_SLOTS Gram records (+ 2 x LILI_MAX_SLOTS counts behind them)
+                         // (h_records.dev() is the same memory as the device sees it: the blocking calls' reduction kernels write their records THERE — round 4: no copy launch between the kernel and the host)
     int max_cells = 1 << 27;
     int grid_reach = 2;          // 2: cells smaller than the gate radius, inner 3x3x3 block first, shell on demand (knn5_grid)
     bool fuse_tail = false;      // reduce (+ GN) inside the linearisation launch (its last block sweeps the other blocks' granule-tagged partials):
@@ -201,7 +182,7 @@ struct lili_ctx {
     // previous frame left pending — they share nothing — instead of in front of it.  `extract_side_next`: the next deferred extraction may take side[kExtractSide] (one shot,
     // set by the frame); `extract_join_pending`: the context's stream has not yet waited for that extraction — lili_readback_finish does, before it gathers.
     static constexpr int kExtractSide = 2;
-    hipEvent_t extract_fork_ev = nullptr;
+    Event extract_fork_ev;
     bool frame_extract_stream = false, extract_side_next = false, extract_join_pending = false;      // (default OFF: measured -15..30 us per frame in a process with one context, +100 us in one that holds a dozen streams — the whole bench —)
     bool rot_fold = true, rot_segment_wait = true;      // lili_extract_rot: k_rot_ring writes the scan's lists itself (0: k_rot_compact behind it) / a segment whose pick may lie under its predecessor's marks waits for them in k_rot_segments (0: k_rot_ring redoes it) — A/B and fallback paths
     int frame_guess_misses = 0;         // frames whose guessed feature counts were too small (matched again the plain way)
@@ -210,18 +191,9 @@ struct lili_ctx {
     int sort_digit_bits = 8;     // radix sort of the voxel filter: 8-bit digits (4 = the round-2 passes, A/B)
     int rot_atan = 2;            // ROT extractor: 2 = glibc fdlibm float atan / atan2 (the reference build's bits), 1 = f64 functions rounded to f32
     int n_simd = 0;              // SIMDs of the device (CUs x 4)
-    void* ext_rot = nullptr;                 // extractor state (lili_extract_rot.hip), freed through ext_rot_free
-    void (*ext_rot_free)(void*) = nullptr;
-    void* ext_livox = nullptr;
-    void (*ext_livox_free)(void*) = nullptr;
-    void* ext_voxel = nullptr;               // voxel filter / local-map ring buffer (lili_voxel.hip)
-    void (*ext_voxel_free)(void*) = nullptr;
-    void* ext_loop = nullptr;                // loop-closure registration: its source, target, index and work buffers (lili_loop.hip)
-    void (*ext_loop_free)(void*) = nullptr;
-    void* ext_archive = nullptr;             // keyframe archive and global map (lili_archive.hip)
-    void (*ext_archive_free)(void*) = nullptr;
-    void* ext_imu = nullptr;                 // IMU pre-integration: page-locked staging, device buffers, timing events (lili_imu.hip)
-    void (*ext_imu_free)(void*) = nullptr;
+    // What a module keeps per context, created by its first call (ext_of) and deleted with the context
+    enum { kExtRot, kExtLivox, kExtVoxel /* voxel filter / local-map ring */, kExtLoop, kExtArchive /* keyframe archive and global map */, kExtImu, kExtLocal /* local pose graph */, kExtCount };
+    std::unique_ptr<ExtState> ext[kExtCount];
     bool imu_time = false;                   // option "imu_time": events around k_imu_preintegrate (lili_imu_kernel_ms)
     int archive_max_mb = 0;                  // bound on the archive's slab pool (0: none)
     int archive_slab_mb = 64;
@@ -232,11 +204,11 @@ struct lili_ctx {
     double* gram_of(int slot) { return gram.as<double>() + (size_t)slot * LILI_GRAM_DOUBLES; }
     // Page-locked copy of the slots' states for "iterate, then read the pose" without a copy launch (lili_pipeline.hip): `state_mirror_want` asks the next lili_s2m_iterate to
     // hand the mirror to the reduction + GN kernel of its LAST iteration (take_state_mirror: one shot); a path without such a kernel leaves the host's sentinel in place.
-    lili::SlotState* h_state_mirror = nullptr; lili::SlotState* h_state_mirror_dev = nullptr;
+    PinBuf h_state_mirror;
     bool state_mirror_want = false, state_mirror_armed = false;
-    lili::SlotState* take_state_mirror(int slot) { if (!state_mirror_armed || !h_state_mirror_dev) return nullptr; state_mirror_armed = false; return h_state_mirror_dev + slot; }
+    lili::SlotState* take_state_mirror(int slot) { lili::SlotState* d = h_state_mirror.dev_as<lili::SlotState>(); if (!state_mirror_armed || !d) return nullptr; state_mirror_armed = false; return d + slot; }
     double* pub_of(int slot) { return pose_pub.as<double>() + (size_t)slot * kPubReplicas * kPubStride; }      // option overlap_gn: the slot's published-pose copies
-    // lili_window_cycle (behind every older member, whose offsets stay what they were): the RESIDENT prior (x0, r0, J0, A0 as WinDev lays them out; set by
+    // lili_window_cycle: the RESIDENT prior (x0, r0, J0, A0 as WinDev lays them out; set by
     // lili_window_prior_set or by a successful cycle, which has k_window_marg_cycle write win_res_nxt and then swaps the two — no other call touches either), the cycle's
     // device result, the slots' states as they were before the solve (put back when the cycle fails behind it)
     DevBuf win_res, win_res_nxt, win_cyc, win_state_bak;
@@ -245,8 +217,6 @@ struct lili_ctx {
         int n_rows = 0, n_cols = 0, n_blocks = 0, rank = 0, sweeps[2] = {0, 0};
         int32_t kind[3 * LILI_WINDOW_MAX_KF] = {}, kf[3 * LILI_WINDOW_MAX_KF] = {};
     } win_res_tab;
-    void* ext_local = nullptr;               // local pose graph: page-locked staging, device buffers, timing events (lili_local_graph.hip)
-    void (*ext_local_free)(void*) = nullptr;
     bool local_graph_time = false;           // option "local_graph_time": events around k_local_graph (lili_local_graph_kernel_ms)
 };
 
@@ -257,6 +227,64 @@ struct lili_ctx {
     } while (0)
 #define ARGCHK(cond, msg) do { if (!(cond)) return ctx->fail(LILI_E_ARG, msg); } while (0)
 #define TRY(expr) do { const int _rc = (expr); if (_rc != LILI_OK) return _rc; } while (0)      // a library call's status, handed on
+
+// the module state `which` of a context as T, created on first use
+template <class T> T* ext_of(lili_ctx* ctx, int which) {
+    if (!ctx->ext[which]) ctx->ext[which].reset(new T());
+    return static_cast<T*>(ctx->ext[which].get());
+}
+
+inline bool finite_n(const double* p, size_t n) {
+    for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false;
+    return true;
+}
+
+// the caller's trust-region options or the defaults; _checked: with the range checks every solver that takes them shares (`who` starts the message)
+inline lili_lm_options lm_options_or_default(const lili_lm_options* options) {
+    lili_lm_options opt;
+    if (options) opt = *options; else lili_lm_default_options(&opt);
+    return opt;
+}
+inline int lm_options_checked(lili_ctx* ctx, const char* who, const lili_lm_options* options, lili_lm_options* opt) {
+    *opt = lm_options_or_default(options);
+    ARGCHK(opt->max_iterations >= 1 && opt->max_iterations <= 1000, std::string(who) + ": max_iterations must be in 1..1000");
+    ARGCHK(opt->initial_radius > 0 && opt->max_radius >= opt->initial_radius && opt->min_radius > 0 && opt->min_lm_diagonal > 0 && opt->max_lm_diagonal >= opt->min_lm_diagonal,
+           std::string(who) + ": inconsistent trust-region options");
+    return LILI_OK;
+}
+
+// A staged one-shot job (IMU pre-integration, the local pose graph): the host packs its input into page-locked memory, one launch turns it into a result block, and the
+// call waits for the part of the result it wants.  Page-locked staging, the device copies, and the two events of a timed run.
+struct StagedJob : ExtState {
+    PinBuf in, out;
+    DevBuf d_in, d_out;
+    Event ev0, ev1;
+    float last_ms = -1.f;      // kernel time of the last run, < 0: it was not timed
+    // room for `in_bytes` of input (the page-locked side grows to twice what is asked) and `out_cap` of result
+    int size(lili_ctx* ctx, size_t in_bytes, size_t out_cap) {
+        if (in.cap < in_bytes) HIPCHK(in.ensure(in_bytes * 2));
+        HIPCHK(out.ensure(out_cap));
+        HIPCHK(d_in.ensure(in_bytes));
+        HIPCHK(d_out.ensure(out_cap));
+        return LILI_OK;
+    }
+    // upload, `launch()` on the context's stream (between the events if timed), read `out_bytes` of the result back, synchronise
+    template <class Launch> int run(lili_ctx* ctx, bool timed, size_t in_bytes, size_t out_bytes, Launch launch) {
+        HIPCHK(hipMemcpyAsync(d_in.p, in.p, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (timed) {
+            HIPCHK(ev0.get(hipEventDefault)); HIPCHK(ev1.get(hipEventDefault));
+            HIPCHK(hipEventRecord(ev0, ctx->stream));
+        }
+        launch();
+        HIPCHK(hipGetLastError());
+        if (timed) HIPCHK(hipEventRecord(ev1, ctx->stream));
+        HIPCHK(hipMemcpyAsync(out.p, d_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        last_ms = -1.f;
+        if (timed) HIPCHK(hipEventElapsedTime(&last_ms, ev0, ev1));
+        return LILI_OK;
+    }
+};
 
 // PCL's "leaf size is too small for the input dataset": the refusal of lili_voxel_filter, and of lili_global_map for everything it has folded
 constexpr const char* kVoxelOverflowMsg = "voxel_filter: leaf size too small for the cloud extent (voxel index would overflow int32, as in PCL)";
@@ -287,13 +315,12 @@ int lili_voxel_filter_dev_enqueue(lili_ctx* ctx, const float4* d_pts, int n, flo
 int lili_voxel_filter_dev_complete(lili_ctx* ctx, const float4** d_out, int* n_out);
 int lili_localmap_push_dev(lili_ctx* ctx, int kind, const float4* d_pts, int n, const lili::SlotState* d_state, int width);
 int lili_localmap_ring_size(lili_ctx* ctx, int kind);
-// lili_voxel.hip -> lili_archive.hip: the stable order of a device cloud by pcl::VoxelGrid's box-relative voxel index, on sort buffers of the caller's own (`*priv`, created
-// here, freed by lili_vox_sort_free): the filter's state, its ring and its key-bit guesses stay as they are.  *status: 0 = sorted (keys / order valid until the next sort
-// on `*priv`; keys equal to `*sentinel` are the non-finite rows, last), 2 = no finite point, 3 = PCL's int32 voxel-index overflow; box = min xyz, max xyz of the finite
+// lili_voxel.hip -> lili_archive.hip: the stable order of a device cloud by pcl::VoxelGrid's box-relative voxel index, on sort buffers of the caller's own (`priv`, created
+// here): the filter's state, its ring and its key-bit guesses stay as they are.  *status: 0 = sorted (keys / order valid until the next sort
+// on `priv`; keys equal to `*sentinel` are the non-finite rows, last), 2 = no finite point, 3 = PCL's int32 voxel-index overflow; box = min xyz, max xyz of the finite
 // rows.  Blocking (the box is read back).
-int lili_voxel_sort_dev(lili_ctx* ctx, void** priv, const float4* d_pts, int n, float leaf, int* status, float box[6], unsigned* sentinel, const unsigned** d_keys, const int** d_order);
-void lili_vox_sort_free(void* priv);
-size_t lili_vox_sort_bytes(const void* priv);
+int lili_voxel_sort_dev(lili_ctx* ctx, std::unique_ptr<ExtState>& priv, const float4* d_pts, int n, float leaf, int* status, float box[6], unsigned* sentinel, const unsigned** d_keys, const int** d_order);
+size_t lili_vox_sort_bytes(const ExtState* priv);
 // lili_extract_livox.hip -> lili_pipeline.hip: the extraction enqueued without its synchronisation, and the counts taken afterwards
 int lili_extract_livox_enqueue(lili_ctx* ctx, const lili_cloud* scan, int curvature_offset, const double q_imu[4], const lili_livox_params* params);
 int lili_extract_livox_complete(lili_ctx* ctx);

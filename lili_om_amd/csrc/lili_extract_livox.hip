@@ -308,29 +308,20 @@ __global__ void k_livox_xyzc(const float4* __restrict__ a, const float4* __restr
 }  // namespace lili
 
 namespace lili_detail {
-struct LivoxBuffers {
+struct LivoxBuffers : ExtState {
     DevBuf und, curv, keep, owner, state, cut_a, cut_b, cut_src, cell_pt, cell_curv, cell_src, blk_keep;
     DevBuf blk_nedge, blk_edge_cell, blk_edge_dir, blk_nsurf, blk_surf_cell, blk_surf_nrm;
     DevBuf edge_a, edge_b, edge_cell, surf_a, surf_b, surf_cell, pack, pack_e, pack_s, xyzc_edge, xyzc_surf;
     lili::LivoxState host{};
-    int* h_counts = nullptr;          // page-locked {n_cut, n_edge, n_surf}, written by k_livox_pack3; h_counts_dev: the same memory as the device sees it
-    int* h_counts_dev = nullptr;
+    PinBuf h_counts;         // page-locked {n_cut, n_edge, n_surf}, written by k_livox_pack3
     bool have = false;
     unsigned long long pending_gen = 0;      // ctx->readback_gen when the counts' read-back joined the pending list
     bool pending = false;    // lili_extract_livox_enqueue: the counts' read-back is on the stream, lili_extract_livox_complete has not taken it yet
     bool armed = false;      // the ownership table holds "no owner" everywhere (k_livox_init once, k_livox_grid after every scan)
-    void release() {
-        for (DevBuf* b : {&und, &curv, &keep, &owner, &state, &cut_a, &cut_b, &cut_src, &cell_pt, &cell_curv, &cell_src, &blk_nedge, &blk_edge_cell,
-                          &blk_edge_dir, &blk_nsurf, &blk_surf_cell, &blk_surf_nrm, &edge_a, &edge_b, &edge_cell, &surf_a, &surf_b, &surf_cell, &pack, &pack_e, &pack_s, &blk_keep, &xyzc_edge, &xyzc_surf}) b->release();
-        if (h_counts) { (void)hipHostFree(h_counts); h_counts = nullptr; h_counts_dev = nullptr; }
-    }
 };
 }  // namespace lili_detail
 
-static lili_detail::LivoxBuffers* livox_of(lili_ctx* ctx) {
-    if (!ctx->ext_livox) { ctx->ext_livox = new lili_detail::LivoxBuffers(); ctx->ext_livox_free = [](void* p) { auto* r = static_cast<lili_detail::LivoxBuffers*>(p); r->release(); delete r; }; }
-    return static_cast<lili_detail::LivoxBuffers*>(ctx->ext_livox);
-}
+static lili_detail::LivoxBuffers* livox_of(lili_ctx* ctx) { return ext_of<lili_detail::LivoxBuffers>(ctx, lili_ctx::kExtLivox); }
 
 // the edge and the surf list in ONE launch (workgroups [0, nb0): the first list)
 __device__ __forceinline__ void livox_pack_one(int i, const float4* __restrict__ a, const float4* __restrict__ b, int n, int pcl_layout, float* __restrict__ out) {
@@ -461,9 +452,9 @@ static int extract_livox_impl(lili_ctx* ctx, const lili_cloud* scan, int curvatu
     ctx->extract_side_next = false;
     if (on_side) {
         constexpr int kS = lili_ctx::kExtractSide;
-        if (!ctx->side[kS]) HIPCHK(hipStreamCreateWithFlags(&ctx->side[kS], hipStreamNonBlocking));
-        if (!ctx->join_ev[kS]) HIPCHK(hipEventCreateWithFlags(&ctx->join_ev[kS], hipEventDisableTiming));
-        if (!ctx->extract_fork_ev) HIPCHK(hipEventCreateWithFlags(&ctx->extract_fork_ev, hipEventDisableTiming));
+        HIPCHK(ctx->side[kS].get());
+        HIPCHK(ctx->join_ev[kS].get());
+        HIPCHK(ctx->extract_fork_ev.get());
         xs = ctx->side[kS];
         HIPCHK(hipEventRecord(ctx->extract_fork_ev, ctx->stream));      // (behind whatever the previous frame left on the context's stream: its ring push)
         HIPCHK(hipStreamWaitEvent(xs, ctx->extract_fork_ev, 0));
@@ -490,12 +481,7 @@ static int extract_livox_impl(lili_ctx* ctx, const lili_cloud* scan, int curvatu
     // All three outputs in page-locked host memory (what a node that publishes them would use): ONE packing launch writes them across PCIe after the compaction — no
     // staging copies, no side stream, no count round trip (k_livox_pack3).
     const auto out_ok = [](const lili_feature_out* o) { return o && o->data && o->capacity > 0 && o->mem == LILI_MEM_HOST && (o->stride == 0 || o->stride == 32 || o->stride == 48); };
-    if (!B->h_counts) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&B->h_counts), 4 * sizeof(int), hipHostMallocDefault));
-        void* d = nullptr;
-        if (hipHostGetDevicePointer(&d, B->h_counts, 0) != hipSuccess) { (void)hipGetLastError(); d = nullptr; }
-        B->h_counts_dev = static_cast<int*>(d);
-    }
+    HIPCHK(B->h_counts.ensure(4 * sizeof(int)));
     void *dc = nullptr, *de3 = nullptr, *ds3 = nullptr;
     bool all3 = n > 0 && out_ok(cutted) && out_ok(edge) && out_ok(surf);
     if (all3) { dc = lili_pinned_dev_ptr(cutted->data, 16); de3 = lili_pinned_dev_ptr(edge->data, 16); ds3 = lili_pinned_dev_ptr(surf->data, 16); all3 = dc && de3 && ds3; }
@@ -506,9 +492,9 @@ static int extract_livox_impl(lili_ctx* ctx, const lili_cloud* scan, int curvatu
     if (!all3 && n > 0 && cutted && cutted->data && cutted->mem == LILI_MEM_HOST && cutted->capacity > 0) {
         rc = livox_pack(ctx, B->pack, cutted, B->cut_a.as<float4>(), B->cut_b.as<float4>(), &st->n_cut, (size_t)n);
         if (rc != LILI_OK) return rc;
-        if (!ctx->fork_ev) HIPCHK(hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
-        if (!ctx->side[1]) HIPCHK(hipStreamCreateWithFlags(&ctx->side[1], hipStreamNonBlocking));
-        if (!ctx->join_ev[1]) HIPCHK(hipEventCreateWithFlags(&ctx->join_ev[1], hipEventDisableTiming));
+        HIPCHK(ctx->fork_ev.get());
+        HIPCHK(ctx->side[1].get());
+        HIPCHK(ctx->join_ev[1].get());
         HIPCHK(hipEventRecord(ctx->fork_ev, ctx->stream));
         cut_early = true;
     }
@@ -535,7 +521,7 @@ static int extract_livox_impl(lili_ctx* ctx, const lili_cloud* scan, int curvatu
         hipLaunchKernelGGL(k_livox_pack3, dim3(nbc + nb0 + nb1), dim3(256), 0, ctx->stream,
                            nbc, B->cut_a.as<float4>(), B->cut_b.as<float4>(), &st->n_cut, (int)kc, cutted->stride == 48 ? 1 : 0, static_cast<float*>(dc),
                            nb0, B->edge_a.as<float4>(), B->edge_b.as<float4>(), &st->n_edge, (int)k0, edge->stride == 48 ? 1 : 0, static_cast<float*>(de3),
-                           B->surf_a.as<float4>(), B->surf_b.as<float4>(), &st->n_surf, (int)k1, surf->stride == 48 ? 1 : 0, static_cast<float*>(ds3), B->h_counts_dev);
+                           B->surf_a.as<float4>(), B->surf_b.as<float4>(), &st->n_surf, (int)k1, surf->stride == 48 ? 1 : 0, static_cast<float*>(ds3), B->h_counts.dev_as<int>());
         if (hipGetLastError() != hipSuccess) rc = ctx->fail(LILI_E_HIP, "extract_livox: pack launch failed");
         direct = true;
     }
@@ -563,7 +549,7 @@ static int extract_livox_impl(lili_ctx* ctx, const lili_cloud* scan, int curvatu
         if (rc == LILI_OK) rc = livox_pack(ctx, B->pack_s, surf, B->surf_a.as<float4>(), B->surf_b.as<float4>(), &st->n_surf, (size_t)kLvCells);
     }
     if (rc != LILI_OK) return rc;
-    const bool counts_direct = all3 && B->h_counts_dev != nullptr;      // the counts arrive with the packing kernel
+    const bool counts_direct = all3 && B->h_counts.dev() != nullptr;      // the counts arrive with the packing kernel
     if (!counts_direct) { rc = lili_readback_add(ctx, &B->host, st, sizeof(LivoxState)); if (rc) return rc; }
     if (defer && !counts_direct && !cut_early) { B->pending = true; B->pending_gen = ctx->readback_gen; return LILI_OK; }      // (no caller buffers in this mode: nothing else to do once the counts are there)
     if (cut_early) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->join_ev[1], 0));
@@ -576,7 +562,7 @@ static int extract_livox_impl(lili_ctx* ctx, const lili_cloud* scan, int curvatu
         return LILI_OK;
     };
     if (direct) { sent_e = std::min((size_t)kLvCells, edge->capacity); sent_s = std::min((size_t)kLvCells, surf->capacity); }
-    if (counts_direct) { HIPCHK(hipStreamSynchronize(ctx->stream)); B->host.n_cut = B->h_counts[0]; B->host.n_edge = B->h_counts[1]; B->host.n_surf = B->h_counts[2]; }
+    if (counts_direct) { HIPCHK(hipStreamSynchronize(ctx->stream)); const int* h = B->h_counts.as<int>(); B->host.n_cut = h[0]; B->host.n_edge = h[1]; B->host.n_surf = h[2]; }
     else { const int rb = lili_readback_finish(ctx); if (rc) return rc; if (rb) return rb; }      // (the pending read is always finished)  — the call's synchronisation
     drain_side.s = nullptr;      // joined: the synchronisation above covered the side stream's copy (hipStreamWaitEvent on its join event)
     B->have = true;

@@ -1605,7 +1605,7 @@ __global__ __launch_bounds__(256) void k_rot_send(const RotState* __restrict__ s
 // C ABI
 // ================================================================================================
 namespace lili_detail {
-struct RotBuffers {
+struct RotBuffers : ExtState {
     DevBuf in, scan_id, ori_raw, block_hist, block_half, state, full, full_src, curv, label, sort_ind;
     DevBuf vkey, seg_out, ring_ncand, sorted_k, sorted_vox, sorted_len;      // k_rot_scatter -> k_rot_segments -> k_rot_ring
     DevBuf ring_edge, ring_sharp, ring_flat, lessflat_tmp, surf_tmp, surf_cnt_tmp;
@@ -1616,26 +1616,16 @@ struct RotBuffers {
     int prev_edge = 0, prev_surf = 0;
     DevBuf big_mark, big_vidx, big_ord_a, big_ord_b, big_rcnt;   // working set of rings beyond the LDS budget (k_rot_select_big)
     lili::RotState host{};
-    lili::RotState* h_state = nullptr;       // page-locked mirror of the device state, written by k_rot_compact; h_state_dev: the same memory as the device sees it
-    lili::RotState* h_state_dev = nullptr;
+    PinBuf h_state;       // page-locked mirror of the device state (a RotState and the give-up word), written by k_rot_compact
     int n_in = 0;
     bool have = false;
     // an extraction that has been enqueued but not completed (lili_extract_rot_enqueue / _complete: the front-end frame pipeline overlaps its kernels with the local map's)
     struct Pending { bool on = false; lili_rot_params params{}; double q_imu[4] = {1, 0, 0, 0}, q_lb[4] = {1, 0, 0, 0}; lili::RotRingScratch X{}; bool full_early = false, sent_edge = false, sent_surf = false;
                      unsigned long long gen = 0; } pend;
-    void release() {
-        for (DevBuf* b : {&in, &scan_id, &ori_raw, &block_hist, &block_half, &state, &full, &full_src, &curv, &label, &sort_ind, &vkey, &seg_out, &ring_ncand, &sorted_k, &sorted_vox,
-                          &sorted_len, &big_mark, &big_vidx, &big_ord_a, &big_ord_b, &big_rcnt, &ring_edge, &ring_sharp, &ring_flat,
-                          &lessflat_tmp, &surf_tmp, &surf_cnt_tmp, &edge_idx, &edge_pts, &sharp_idx, &flat_idx, &lessflat_idx, &surf, &surf_cnt, &fold_words}) b->release();
-        if (h_state) { (void)hipHostFree(h_state); h_state = nullptr; h_state_dev = nullptr; }
-    }
 };
 }  // namespace lili_detail
 
-static lili_detail::RotBuffers* rot_of(lili_ctx* ctx) {
-    if (!ctx->ext_rot) { ctx->ext_rot = new lili_detail::RotBuffers(); ctx->ext_rot_free = [](void* p) { auto* r = static_cast<lili_detail::RotBuffers*>(p); r->release(); delete r; }; }
-    return static_cast<lili_detail::RotBuffers*>(ctx->ext_rot);
-}
+static lili_detail::RotBuffers* rot_of(lili_ctx* ctx) { return ext_of<lili_detail::RotBuffers>(ctx, lili_ctx::kExtRot); }
 
 static int copy_out_f4(lili_ctx* ctx, const lili_feature_out* o, const float4* d_src, size_t count) {
     if (!o || !o->data || count == 0) return LILI_OK;
@@ -1701,12 +1691,7 @@ static int rot_enqueue(lili_ctx* ctx, const lili_cloud* scan, const double q_imu
     R->n_in = n;
     HIPCHK(R->state.ensure(sizeof(RotState)));
     RotState* st = R->state.as<RotState>();
-    if (!R->h_state) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&R->h_state), sizeof(RotState) + 64, hipHostMallocDefault));      // (+ the word k_rot_ring raises when a look-back gave up)
-        void* d = nullptr;
-        if (hipHostGetDevicePointer(&d, R->h_state, 0) != hipSuccess) { (void)hipGetLastError(); d = nullptr; }
-        R->h_state_dev = static_cast<RotState*>(d);
-    }
+    HIPCHK(R->h_state.ensure(sizeof(RotState) + 64));      // (+ the word k_rot_ring raises when a look-back gave up)
     if (n == 0) HIPCHK(hipMemsetAsync(st, 0, sizeof(RotState), ctx->stream));      // (the kernels below write every field they later read; an empty scan launches none)
     RotRingScratch X{};
     if (n > 0) {
@@ -1740,9 +1725,9 @@ static int rot_enqueue(lili_ctx* ctx, const lili_cloud* scan, const double q_imu
         // blocks the host right here, before k_rot_segments is even launched — then the plain copy at the end is the better one.
         const bool full_pinned = full && full->data && full->mem == LILI_MEM_HOST && lili_pinned_dev_ptr(full->data, 16) != nullptr;
         if (full_pinned && (full->stride == 0 || full->stride == sizeof(float4)) && full->capacity > 0) {
-            if (!ctx->fork_ev) HIPCHK(hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
-            if (!ctx->side[1]) HIPCHK(hipStreamCreateWithFlags(&ctx->side[1], hipStreamNonBlocking));
-            if (!ctx->join_ev[1]) HIPCHK(hipEventCreateWithFlags(&ctx->join_ev[1], hipEventDisableTiming));
+            HIPCHK(ctx->fork_ev.get());
+            HIPCHK(ctx->side[1].get());
+            HIPCHK(ctx->join_ev[1].get());
             HIPCHK(hipEventRecord(ctx->fork_ev, ctx->stream));
             HIPCHK(hipStreamWaitEvent(ctx->side[1], ctx->fork_ev, 0));
             // (the runtime's copy: a thin copy kernel of the library's own was measured 21 us per call slower)
@@ -1753,20 +1738,20 @@ static int rot_enqueue(lili_ctx* ctx, const lili_cloud* scan, const double q_imu
         }
         hipLaunchKernelGGL(k_rot_segments, dim3(kStage3Blocks), dim3(kRotBlock), std::max(sizeof(SegLds), sizeof(OrderLds)), ctx->stream, R->full.as<float4>(), R->vkey.as<unsigned>(), P, st, R->curv.as<float>(),
                            R->sort_ind.as<int>(), R->label.as<int>(), X);
-        if (R->h_state) *reinterpret_cast<volatile int*>(R->h_state + 1) = 0;      // the word a ring raises when its look-back gives up
+        if (R->h_state.p) *reinterpret_cast<volatile int*>(R->h_state.as<RotState>() + 1) = 0;      // the word a ring raises when its look-back gives up
         if (ctx->rot_fold) {   // the ring stage writes the scan's lists itself (RotFold): four launches
             RotFold F{};
             F.words = R->fold_words.as<unsigned long long>();
             F.tag = R->fold_tag;
             F.edge_idx = R->edge_idx.as<int>(); F.edge_pts = R->edge_pts.as<float4>(); F.sharp_idx = R->sharp_idx.as<int>(); F.flat_idx = R->flat_idx.as<int>();
             F.lessflat_idx = R->lessflat_idx.as<int>(); F.surf = R->surf.as<float4>(); F.surf_cnt = R->surf_cnt.as<int>();
-            F.mirror = R->h_state_dev;
-            F.give_up = R->h_state_dev ? reinterpret_cast<int*>(R->h_state_dev + 1) : nullptr;
+            F.mirror = R->h_state.dev_as<RotState>();
+            F.give_up = R->h_state.dev_as<RotState>() ? reinterpret_cast<int*>(R->h_state.dev_as<RotState>() + 1) : nullptr;
             if (sink) { F.q_surf = sink->q_surf; F.cap_surf = sink->cap_surf; F.q_edge = sink->q_edge; F.cap_edge = sink->cap_edge; F.q_state = sink->state; for (int i = 0; i < 7; i++) F.q_pose[i] = sink->pose[i]; }
             launch_rot_ring(ctx, R, P, st, X, F);
         } else {               // option "rot_fold" = 0 (A/B, and the path a ring's given-up look-back falls back to): per-ring lists, then the concatenation launch of rounds 3-5
             launch_rot_ring(ctx, R, P, st, X, RotFold{});
-            launch_rot_compact(ctx, R, st, R->h_state_dev);
+            launch_rot_compact(ctx, R, st, R->h_state.dev_as<RotState>());
         }
         HIPCHK(hipGetLastError());
         // page-locked feature buffers are written right behind the concatenation, `count` records each, before the host has seen the counts: the state's read-back below
@@ -1805,10 +1790,10 @@ static int rot_complete(lili_ctx* ctx, lili_feature_out* full, lili_feature_out*
     RotState* st = R->state.as<RotState>();
     int rc = LILI_OK;
     static const bool phases = getenv("LILI_ROT_PHASES") != nullptr;      // (the mirror's diagnostics of the last launch may be stale: the profiling tool reads the state itself)
-    if (n > 0 && R->h_state_dev && !phases) {          // the state came with the ring kernel's last workgroup: wait, read it where it landed
+    if (n > 0 && R->h_state.dev_as<RotState>() && !phases) {          // the state came with the ring kernel's last workgroup: wait, read it where it landed
         if (!synced) HIPCHK(hipStreamSynchronize(ctx->stream));
-        std::memcpy(&R->host, R->h_state, sizeof(RotState));
-        if (*reinterpret_cast<volatile int*>(R->h_state + 1)) R->host.fold_failed = 1;
+        std::memcpy(&R->host, R->h_state.p, sizeof(RotState));
+        if (*reinterpret_cast<volatile int*>(R->h_state.as<RotState>() + 1)) R->host.fold_failed = 1;
     } else { TRY(lili_readback_now(ctx, &R->host, st, sizeof(RotState))); }
     if (n == 0) { R->host.first_valid = R->host.half_idx = 0x7fffffff; R->host.last_valid = -1; }
     if (n > 0 && (R->host.vox_overflow || R->host.fallback_rings > 0 || R->host.fold_failed)) sent_edge = sent_surf = false;      // the lists are about to change: copied again below

@@ -314,29 +314,6 @@ __global__ __launch_bounds__(kImuThreads) void k_imu_preintegrate(const ImuSegDe
 
 }  // namespace lili
 
-namespace {
-// page-locked staging for the packed upload and the results, the device copies, and the two timing events
-struct ImuBuffers {
-    unsigned char* h_in = nullptr; size_t h_in_cap = 0;
-    unsigned char* h_out = nullptr; size_t h_out_cap = 0;
-    DevBuf d_in, d_out;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float last_ms = -1.f;
-};
-void imu_free(void* p) {
-    ImuBuffers* B = static_cast<ImuBuffers*>(p);
-    if (B->h_in) (void)hipHostFree(B->h_in);
-    if (B->h_out) (void)hipHostFree(B->h_out);
-    if (B->ev0) (void)hipEventDestroy(B->ev0);
-    if (B->ev1) (void)hipEventDestroy(B->ev1);
-    delete B;
-}
-bool finite_n(const double* p, size_t n) {
-    for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false;
-    return true;
-}
-}  // namespace
-
 extern "C" {
 
 int lili_imu_preintegrate(lili_ctx* ctx, const lili_imu_segment* seg, int n_seg, lili_window_imu* out, lili_imu_prediction* pred) {
@@ -356,24 +333,12 @@ int lili_imu_preintegrate(lili_ctx* ctx, const lili_imu_segment* seg, int n_seg,
         n_rows += (size_t)g.n + 1;
     }
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ctx->ext_imu) { ctx->ext_imu = new ImuBuffers(); ctx->ext_imu_free = imu_free; }
-    ImuBuffers* B = static_cast<ImuBuffers*>(ctx->ext_imu);
+    StagedJob* B = ext_of<StagedJob>(ctx, lili_ctx::kExtImu);
     const size_t hdr_bytes = sizeof(ImuSegDev) * LILI_IMU_MAX_SEGMENTS, in_bytes = hdr_bytes + n_rows * kImuRow * sizeof(double), out_bytes = sizeof(ImuOutDev) * n_seg;
-    if (B->h_in_cap < in_bytes) {
-        if (B->h_in) { HIPCHK(hipHostFree(B->h_in)); B->h_in = nullptr; B->h_in_cap = 0; }
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&B->h_in), in_bytes * 2, hipHostMallocDefault));
-        B->h_in_cap = in_bytes * 2;
-    }
-    if (B->h_out_cap < out_bytes) {
-        if (B->h_out) { HIPCHK(hipHostFree(B->h_out)); B->h_out = nullptr; B->h_out_cap = 0; }
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&B->h_out), sizeof(ImuOutDev) * LILI_IMU_MAX_SEGMENTS, hipHostMallocDefault));
-        B->h_out_cap = sizeof(ImuOutDev) * LILI_IMU_MAX_SEGMENTS;
-    }
-    HIPCHK(B->d_in.ensure(in_bytes));
-    HIPCHK(B->d_out.ensure(sizeof(ImuOutDev) * LILI_IMU_MAX_SEGMENTS));
+    TRY(B->size(ctx, in_bytes, sizeof(ImuOutDev) * LILI_IMU_MAX_SEGMENTS));
     // ---- pack: headers, then n + 1 rows per segment
-    ImuSegDev* H = reinterpret_cast<ImuSegDev*>(B->h_in);
-    double* R = reinterpret_cast<double*>(B->h_in + hdr_bytes);
+    ImuSegDev* H = B->in.as<ImuSegDev>();
+    double* R = reinterpret_cast<double*>(B->in.as<unsigned char>() + hdr_bytes);
     size_t row = 0;
     for (int s = 0; s < n_seg; s++) {
         const lili_imu_segment& g = seg[s];
@@ -392,20 +357,11 @@ int lili_imu_preintegrate(lili_ctx* ctx, const lili_imu_segment* seg, int n_seg,
         }
         row += (size_t)g.n + 1;
     }
-    HIPCHK(hipMemcpyAsync(B->d_in.p, B->h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->imu_time) {
-        if (!B->ev0) { HIPCHK(hipEventCreate(&B->ev0)); HIPCHK(hipEventCreate(&B->ev1)); }
-        HIPCHK(hipEventRecord(B->ev0, ctx->stream));
-    }
-    hipLaunchKernelGGL(k_imu_preintegrate, dim3(n_seg), dim3(kImuThreads), 0, ctx->stream, B->d_in.as<ImuSegDev>(),
-                       reinterpret_cast<const double*>(B->d_in.as<unsigned char>() + hdr_bytes), B->d_out.as<ImuOutDev>());
-    HIPCHK(hipGetLastError());
-    if (ctx->imu_time) HIPCHK(hipEventRecord(B->ev1, ctx->stream));
-    HIPCHK(hipMemcpyAsync(B->h_out, B->d_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    B->last_ms = -1.f;
-    if (ctx->imu_time) HIPCHK(hipEventElapsedTime(&B->last_ms, B->ev0, B->ev1));
-    const ImuOutDev* o = reinterpret_cast<const ImuOutDev*>(B->h_out);
+    TRY(B->run(ctx, ctx->imu_time, in_bytes, out_bytes, [&] {
+        hipLaunchKernelGGL(k_imu_preintegrate, dim3(n_seg), dim3(kImuThreads), 0, ctx->stream, B->d_in.as<ImuSegDev>(),
+                           reinterpret_cast<const double*>(B->d_in.as<unsigned char>() + hdr_bytes), B->d_out.as<ImuOutDev>());
+    }));
+    const ImuOutDev* o = B->out.as<ImuOutDev>();
     for (int s = 0; s < n_seg; s++) {
         std::memcpy(&out[s], &o[s], sizeof(lili_window_imu));
         if (seg[s].predict) std::memcpy(&pred[s], o[s].P1, sizeof(lili_imu_prediction));
@@ -416,7 +372,7 @@ int lili_imu_preintegrate(lili_ctx* ctx, const lili_imu_segment* seg, int n_seg,
 int lili_imu_kernel_ms(lili_ctx* ctx, float* ms) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(ms, "imu_kernel_ms: null argument");
-    const ImuBuffers* B = static_cast<const ImuBuffers*>(ctx->ext_imu);
+    const StagedJob* B = static_cast<const StagedJob*>(ctx->ext[lili_ctx::kExtImu].get());
     if (!B || B->last_ms < 0.f) return ctx->fail(LILI_E_STATE, "imu_kernel_ms: no timed lili_imu_preintegrate yet (option imu_time)");
     *ms = B->last_ms;
     return LILI_OK;

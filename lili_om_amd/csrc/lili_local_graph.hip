@@ -565,26 +565,6 @@ __global__ __launch_bounds__(kLocalThreads) void k_local_graph(const LocalGraphI
 }  // namespace lili
 
 namespace {
-// page-locked staging for the packed upload and the results, the device copies, and the two timing events
-struct LocalBuffers {
-    unsigned char* h_in = nullptr; size_t h_in_cap = 0;
-    LocalGraphOut* h_out = nullptr;
-    DevBuf d_in, d_out;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float last_ms = -1.f;
-};
-void local_free(void* p) {
-    LocalBuffers* B = static_cast<LocalBuffers*>(p);
-    if (B->h_in) (void)hipHostFree(B->h_in);
-    if (B->h_out) (void)hipHostFree(B->h_out);
-    if (B->ev0) (void)hipEventDestroy(B->ev0);
-    if (B->ev1) (void)hipEventDestroy(B->ev1);
-    delete B;
-}
-bool finite_n(const double* p, size_t n) {
-    for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false;
-    return true;
-}
 // The sample indices the walk reads, from the stamps alone (the device walks them the same way): false where the text would read at or beyond n_imu or divide by
 // dt1 + dt2 == 0; *hi = the highest index read.
 bool walk_indices(const double* st, int64_t n_imu, int64_t ii0, const double* T, int n, int64_t* hi) {
@@ -606,10 +586,7 @@ bool walk_indices(const double* st, int64_t n_imu, int64_t ii0, const double* T,
     return true;
 }
 int check_options(lili_ctx* ctx, const lili_lm_options* options, lili_lm_options* opt) {
-    if (options) *opt = *options; else lili_lm_default_options(opt);
-    ARGCHK(opt->max_iterations >= 1 && opt->max_iterations <= 1000, "local_graph: max_iterations must be in 1..1000");
-    ARGCHK(opt->initial_radius > 0 && opt->max_radius >= opt->initial_radius && opt->min_radius > 0 && opt->min_lm_diagonal > 0 && opt->max_lm_diagonal >= opt->min_lm_diagonal,
-           "local_graph: inconsistent trust-region options");
+    TRY(lm_options_checked(ctx, "local_graph", options, opt));
     ARGCHK(std::isfinite(opt->function_tolerance) && std::isfinite(opt->gradient_tolerance) && std::isfinite(opt->parameter_tolerance) && std::isfinite(opt->initial_radius) &&
            std::isfinite(opt->max_radius) && std::isfinite(opt->min_relative_decrease) && std::isfinite(opt->max_lm_diagonal), "local_graph: an option is not finite");
     return LILI_OK;
@@ -642,20 +619,11 @@ void pack_walk(const lili_local_walk* w, int n, int64_t hi, LocalGraphIn* H, dou
     }
 }
 // staging sized for n_rows sample rows; the header zeroed, n / mode / options set
-int local_begin(lili_ctx* ctx, int n, int mode, int n_rows, const lili_lm_options* opt, LocalBuffers** Bp, LocalGraphIn** Hp) {
+int local_begin(lili_ctx* ctx, int n, int mode, int n_rows, const lili_lm_options* opt, StagedJob** Bp, LocalGraphIn** Hp) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ctx->ext_local) { ctx->ext_local = new LocalBuffers(); ctx->ext_local_free = local_free; }
-    LocalBuffers* B = static_cast<LocalBuffers*>(ctx->ext_local);
-    const size_t in_bytes = sizeof(LocalGraphIn) + (size_t)n_rows * kLocalRow * sizeof(double);
-    if (B->h_in_cap < in_bytes) {
-        if (B->h_in) { HIPCHK(hipHostFree(B->h_in)); B->h_in = nullptr; B->h_in_cap = 0; }
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&B->h_in), in_bytes * 2, hipHostMallocDefault));
-        B->h_in_cap = in_bytes * 2;
-    }
-    if (!B->h_out) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&B->h_out), sizeof(LocalGraphOut), hipHostMallocDefault));
-    HIPCHK(B->d_in.ensure(in_bytes));
-    HIPCHK(B->d_out.ensure(sizeof(LocalGraphOut)));
-    LocalGraphIn* H = reinterpret_cast<LocalGraphIn*>(B->h_in);
+    StagedJob* B = ext_of<StagedJob>(ctx, lili_ctx::kExtLocal);
+    TRY(B->size(ctx, sizeof(LocalGraphIn) + (size_t)n_rows * kLocalRow * sizeof(double), sizeof(LocalGraphOut)));
+    LocalGraphIn* H = B->in.as<LocalGraphIn>();
     std::memset(H, 0, sizeof *H);
     H->n = n; H->mode = mode; H->n_rows = 0;
     if (opt) {
@@ -669,23 +637,13 @@ int local_begin(lili_ctx* ctx, int n, int mode, int n_rows, const lili_lm_option
     return LILI_OK;
 }
 // upload, launch, read `out_bytes` of the result back, synchronise
-int local_run(lili_ctx* ctx, LocalBuffers* B, size_t out_bytes) {
-    const LocalGraphIn* H = reinterpret_cast<const LocalGraphIn*>(B->h_in);
-    const size_t in_bytes = sizeof(LocalGraphIn) + (size_t)H->n_rows * kLocalRow * sizeof(double);
-    HIPCHK(hipMemcpyAsync(B->d_in.p, B->h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->local_graph_time) {
-        if (!B->ev0) { HIPCHK(hipEventCreate(&B->ev0)); HIPCHK(hipEventCreate(&B->ev1)); }
-        HIPCHK(hipEventRecord(B->ev0, ctx->stream));
-    }
-    hipLaunchKernelGGL(k_local_graph, dim3(1), dim3(kLocalThreads), 0, ctx->stream, B->d_in.as<LocalGraphIn>(), B->d_out.as<LocalGraphOut>());
-    HIPCHK(hipGetLastError());
-    if (ctx->local_graph_time) HIPCHK(hipEventRecord(B->ev1, ctx->stream));
-    HIPCHK(hipMemcpyAsync(B->h_out, B->d_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    B->last_ms = -1.f;
-    if (ctx->local_graph_time) HIPCHK(hipEventElapsedTime(&B->last_ms, B->ev0, B->ev1));
-    return LILI_OK;
+int local_run(lili_ctx* ctx, StagedJob* B, size_t out_bytes) {
+    const size_t in_bytes = sizeof(LocalGraphIn) + (size_t)B->in.as<LocalGraphIn>()->n_rows * kLocalRow * sizeof(double);
+    return B->run(ctx, ctx->local_graph_time, in_bytes, out_bytes, [&] {
+        hipLaunchKernelGGL(k_local_graph, dim3(1), dim3(kLocalThreads), 0, ctx->stream, B->d_in.as<LocalGraphIn>(), B->d_out.as<LocalGraphOut>());
+    });
 }
+const LocalGraphOut* local_out(const StagedJob* B) { return B->out.as<LocalGraphOut>(); }
 constexpr size_t kOutSmall = offsetof(LocalGraphOut, jtj);
 int check_chain(lili_ctx* ctx, int n, const double* anchors, const double* meas, const double* poses) {
     ARGCHK(n >= 0 && n <= LILI_LOCAL_MAX_FRAMES, "local_graph: n must be in 0 .. 16");
@@ -702,13 +660,13 @@ int lili_local_graph_propagate(lili_ctx* ctx, const lili_local_walk* walk, int n
     int64_t hi = 0;
     TRY(check_walk(ctx, walk, n, &hi));
     ARGCHK((n == 0 || poses) && end_state && meas, "local_graph_propagate: null argument");
-    LocalBuffers* B; LocalGraphIn* H;
+    StagedJob* B; LocalGraphIn* H;
     TRY(local_begin(ctx, n, kLocalWalk, (int)(hi - walk->ii0) + 1, nullptr, &B, &H));
     pack_walk(walk, n, hi, H, reinterpret_cast<double*>(H + 1));
     TRY(local_run(ctx, B, kOutSmall));
-    if (n) std::memcpy(poses, B->h_out->poses, sizeof(double) * 7 * n);
-    std::memcpy(end_state, B->h_out->end_state, sizeof B->h_out->end_state);
-    std::memcpy(meas, B->h_out->meas, sizeof(double) * 7 * (n + 1));
+    if (n) std::memcpy(poses, local_out(B)->poses, sizeof(double) * 7 * n);
+    std::memcpy(end_state, local_out(B)->end_state, sizeof local_out(B)->end_state);
+    std::memcpy(meas, local_out(B)->meas, sizeof(double) * 7 * (n + 1));
     return LILI_OK;
 }
 
@@ -716,15 +674,15 @@ int lili_local_graph_evaluate(lili_ctx* ctx, int n, const double* anchors, const
     if (!ctx) return LILI_E_ARG;
     TRY(check_chain(ctx, n, anchors, meas, poses));
     ARGCHK(cost && (n == 0 || (gradient && jtj)), "local_graph_evaluate: null argument");
-    LocalBuffers* B; LocalGraphIn* H;
+    StagedJob* B; LocalGraphIn* H;
     TRY(local_begin(ctx, n, kLocalEvaluate, 0, nullptr, &B, &H));
     std::memcpy(H->left, anchors, sizeof H->left); std::memcpy(H->right, anchors + 7, sizeof H->right);
     std::memcpy(H->meas, meas, sizeof(double) * 7 * (n + 1));
     if (n) std::memcpy(H->poses, poses, sizeof(double) * 7 * n);
     const size_t N = 6 * (size_t)n;
     TRY(local_run(ctx, B, kOutSmall + N * N * sizeof(double)));
-    *cost = B->h_out->cost;
-    if (n) { std::memcpy(gradient, B->h_out->gradient, sizeof(double) * N); std::memcpy(jtj, B->h_out->jtj, sizeof(double) * N * N); }
+    *cost = local_out(B)->cost;
+    if (n) { std::memcpy(gradient, local_out(B)->gradient, sizeof(double) * N); std::memcpy(jtj, local_out(B)->jtj, sizeof(double) * N * N); }
     return LILI_OK;
 }
 
@@ -735,14 +693,14 @@ int lili_local_graph_solve(lili_ctx* ctx, int n, const double* anchors, const do
     ARGCHK(summary, "local_graph_solve: null summary");
     lili_lm_options opt;
     TRY(check_options(ctx, options, &opt));
-    LocalBuffers* B; LocalGraphIn* H;
+    StagedJob* B; LocalGraphIn* H;
     TRY(local_begin(ctx, n, kLocalSolve, 0, &opt, &B, &H));
     std::memcpy(H->left, anchors, sizeof H->left); std::memcpy(H->right, anchors + 7, sizeof H->right);
     std::memcpy(H->meas, meas, sizeof(double) * 7 * (n + 1));
     if (n) std::memcpy(H->poses, poses, sizeof(double) * 7 * n);
     TRY(local_run(ctx, B, kOutSmall));
-    if (n) std::memcpy(poses, B->h_out->poses, sizeof(double) * 7 * n);
-    *summary = B->h_out->summary;
+    if (n) std::memcpy(poses, local_out(B)->poses, sizeof(double) * 7 * n);
+    *summary = local_out(B)->summary;
     return LILI_OK;
 }
 
@@ -755,21 +713,21 @@ int lili_local_graph(lili_ctx* ctx, const lili_local_walk* walk, int n, const do
     ARGCHK(finite_n(right, 7), "local_graph: an input is not finite");
     lili_lm_options opt;
     TRY(check_options(ctx, options, &opt));
-    LocalBuffers* B; LocalGraphIn* H;
+    StagedJob* B; LocalGraphIn* H;
     TRY(local_begin(ctx, n, kLocalWalk | kLocalSolve, (int)(hi - walk->ii0) + 1, &opt, &B, &H));
     pack_walk(walk, n, hi, H, reinterpret_cast<double*>(H + 1));
     std::memcpy(H->right, right, sizeof H->right);
     TRY(local_run(ctx, B, kOutSmall));
-    if (n) std::memcpy(poses, B->h_out->poses, sizeof(double) * 7 * n);
-    std::memcpy(meas, B->h_out->meas, sizeof(double) * 7 * (n + 1));
-    *summary = B->h_out->summary;
+    if (n) std::memcpy(poses, local_out(B)->poses, sizeof(double) * 7 * n);
+    std::memcpy(meas, local_out(B)->meas, sizeof(double) * 7 * (n + 1));
+    *summary = local_out(B)->summary;
     return LILI_OK;
 }
 
 int lili_local_graph_kernel_ms(lili_ctx* ctx, float* ms) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(ms, "local_graph_kernel_ms: null argument");
-    const LocalBuffers* B = static_cast<const LocalBuffers*>(ctx->ext_local);
+    const StagedJob* B = static_cast<const StagedJob*>(ctx->ext[lili_ctx::kExtLocal].get());
     if (!B || B->last_ms < 0.f) return ctx->fail(LILI_E_STATE, "local_graph_kernel_ms: no timed lili_local_graph* call yet (option local_graph_time)");
     *ms = B->last_ms;
     return LILI_OK;

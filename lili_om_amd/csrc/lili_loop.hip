@@ -13,8 +13,7 @@
 #include <climits>
 #include <memory>
 
-int lili_loop_assemble(lili_ctx* ctx, void** priv, const lili_cloud* clouds, int n_clouds, const double* t, const double* q, float leaf, lili_detail::DevBuf& out, int64_t* n_raw, int64_t* n_ds);
-void lili_loop_vox_free(void* p);
+int lili_loop_assemble(lili_ctx* ctx, std::unique_ptr<ExtState>& priv, const lili_cloud* clouds, int n_clouds, const double* t, const double* q, float leaf, lili_detail::DevBuf& out, int64_t* n_raw, int64_t* n_ds);
 int lili_grid_build_plain(lili_ctx* ctx, lili_detail::MapIndex& m, const float4* d_pts, int n, const double mn[3], const double mx[3], double cell, lili::GridView& out);
 
 namespace lili {
@@ -378,8 +377,8 @@ __global__ __launch_bounds__(kIcpBlock) void k_icp_box(const float4* __restrict_
 
 namespace {
 
-struct LoopState {
-    void* vox = nullptr;                 // the assembly's own VoxelGrid buffers (lili_voxel.hip)
+struct LoopState : ExtState {
+    std::unique_ptr<ExtState> vox;               // the assembly's own VoxelGrid buffers (lili_voxel.hip)
     DevBuf cloud[2];
     int64_t n[2] = {0, 0};
     bool has[2] = {false, false};
@@ -388,17 +387,9 @@ struct LoopState {
     DevBuf hint, out_idx, out_d2, part, fpart, dev, box_mm, box_sums;
     bool has_corr = false;
     std::unique_ptr<lili::IcpDev> h_dev{new lili::IcpDev()}, h_init{new lili::IcpDev()};
-    void release() {
-        lili_loop_vox_free(vox); vox = nullptr;
-        for (DevBuf* b : {&cloud[0], &cloud[1], &hint, &out_idx, &out_d2, &part, &fpart, &dev, &box_mm, &box_sums, &idx.sorted, &idx.aux_sorted, &idx.cell_start, &idx.cell_tmp,
-                          &idx.pt_cell, &idx.block_sums, &idx.cell_start9, &idx.row9}) b->release();
-    }
 };
 
-LoopState* loop_of(lili_ctx* ctx) {
-    if (!ctx->ext_loop) { ctx->ext_loop = new LoopState(); ctx->ext_loop_free = [](void* p) { auto* s = static_cast<LoopState*>(p); s->release(); delete s; }; }
-    return static_cast<LoopState*>(ctx->ext_loop);
-}
+LoopState* loop_of(lili_ctx* ctx) { return ext_of<LoopState>(ctx, lili_ctx::kExtLoop); }
 
 // the target's index: cells sized from the density (about one point per cell of the box), the centroid as the origin of the partials.  Blocking.
 int index_target(lili_ctx* ctx, LoopState* L) {
@@ -484,7 +475,7 @@ int lili_loop_cloud(lili_ctx* ctx, int which, const lili_cloud* clouds, int n_cl
     LoopState* L = loop_of(ctx);
     L->has[which] = false; L->has_corr = false;
     int64_t nd = 0;
-    int rc = lili_loop_assemble(ctx, &L->vox, clouds, n_clouds, t, q, leaf, L->cloud[which], n_raw, &nd);
+    int rc = lili_loop_assemble(ctx, L->vox, clouds, n_clouds, t, q, leaf, L->cloud[which], n_raw, &nd);
     if (rc != LILI_OK) return rc;
     L->n[which] = nd;
     if (n_ds) *n_ds = nd;

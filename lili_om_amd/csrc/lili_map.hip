@@ -362,10 +362,10 @@ int lili_map_set_begin(lili_ctx* ctx, int kind, const lili_cloud* cloud, double 
     if (!ctx->build_stream) {          // lowest priority: the latency-bound iteration kernels on the context's stream go first
         int lo = 0, hi = 0;
         if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { (void)hipGetLastError(); lo = 0; }
-        HIPCHK(hipStreamCreateWithPriority(&ctx->build_stream, hipStreamNonBlocking, lo));
+        HIPCHK(ctx->build_stream.get(lo));
     }
-    if (!ctx->build_done[kind]) HIPCHK(hipEventCreateWithFlags(&ctx->build_done[kind], hipEventDisableTiming));
-    if (!ctx->main_mark[kind]) HIPCHK(hipEventCreateWithFlags(&ctx->main_mark[kind], hipEventDisableTiming));
+    HIPCHK(ctx->build_done[kind].get());
+    HIPCHK(ctx->main_mark[kind].get());
     if (ctx->misc_build.ensure(kMiscAlloc) != hipSuccess) return ctx->fail(LILI_E_NOMEM, "map_set_begin: scratch allocation failed");
     // the buffers being rebuilt are the ones the index before the current one lived in: everything enqueued up to the swap that retired
     // them (main_mark, recorded by lili_map_set_end) has to be through before they are overwritten — NOT what was enqueued since, which
@@ -375,7 +375,7 @@ int lili_map_set_begin(lili_ctx* ctx, int kind, const lili_cloud* cloud, double 
     // commit, an extractor): the build reads it from ANOTHER stream, so it has to wait for everything enqueued there so far — lili_map_set
     // got this ordering from the stream itself.  (Work on a third stream of the caller's is the caller's to order: synchronise it before _begin.)
     if (cloud && cloud->mem == LILI_MEM_DEVICE) {
-        if (!ctx->cloud_ready) HIPCHK(hipEventCreateWithFlags(&ctx->cloud_ready, hipEventDisableTiming));
+        HIPCHK(ctx->cloud_ready.get());
         HIPCHK(hipEventRecord(ctx->cloud_ready, ctx->stream));
         HIPCHK(hipStreamWaitEvent(ctx->build_stream, ctx->cloud_ready, 0));
     }

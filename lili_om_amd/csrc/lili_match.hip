@@ -148,23 +148,19 @@ template <typename F> static bool with_lanes(int L, F&& f) {
 constexpr size_t kHRecordDoubles = (size_t)LILI_MAX_SLOTS * LILI_GRAM_DOUBLES + 2 * LILI_MAX_SLOTS;      // records | 2 x MAX_SLOTS window counts | 2 x MAX_SLOTS per-slot counts (ints)
 constexpr size_t kHWindowCountsOff = (size_t)LILI_MAX_SLOTS * LILI_GRAM_DOUBLES * sizeof(double), kHSlotCountsOff = kHWindowCountsOff + 2 * LILI_MAX_SLOTS * sizeof(int);
 static int ensure_h_records(lili_ctx* ctx) {
-    if (ctx->h_records) return LILI_OK;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_records), kHRecordDoubles * sizeof(double), hipHostMallocDefault));
-    void* d = nullptr;
-    if (hipHostGetDevicePointer(&d, ctx->h_records, 0) != hipSuccess) { (void)hipGetLastError(); d = nullptr; }
-    ctx->h_records_dev = static_cast<double*>(d);
+    HIPCHK(ctx->h_records.ensure(kHRecordDoubles * sizeof(double)));
     return LILI_OK;
 }
 // Where a blocking call's last kernel leaves its result (after ensure_h_records): `off` bytes into the landing area, or — where the device cannot see that
 // memory — the device buffer `fallback`, which then comes back through the read-back queue.
 struct Landing {
     lili_ctx* ctx; size_t off; void* fallback;
-    bool direct() const { return ctx->h_records_dev != nullptr; }
-    template <class T> T* dev() const { return direct() ? reinterpret_cast<T*>(reinterpret_cast<char*>(ctx->h_records_dev) + off) : static_cast<T*>(fallback); }
+    bool direct() const { return ctx->h_records.dev() != nullptr; }
+    template <class T> T* dev() const { return direct() ? reinterpret_cast<T*>(ctx->h_records.dev_as<char>() + off) : static_cast<T*>(fallback); }
     int fetch(void* host_dst, size_t bytes) const {      // the call's one synchronisation
         if (!direct()) return lili_readback_now(ctx, host_dst, fallback, bytes);
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        std::memcpy(host_dst, reinterpret_cast<const char*>(ctx->h_records) + off, bytes);
+        std::memcpy(host_dst, ctx->h_records.as<char>() + off, bytes);
         return LILI_OK;
     }
 };
@@ -577,13 +573,13 @@ int lili_s2m_associate_window(lili_ctx* ctx, const int* slots, int n_slots, int 
     if (rc != LILI_OK && rc != 1) return rc;
     rc = LILI_OK;
     if (!one_launch) {
-        if (!ctx->fork_ev) HIPCHK(hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
+        HIPCHK(ctx->fork_ev.get());
         HIPCHK(hipEventRecord(ctx->fork_ev, ctx->stream));
     }
     for (int i = 0; i < n_slots && rc == LILI_OK && !one_launch; i++) {
         if (i > 0) {
-            if (!ctx->side[i]) HIPCHK(hipStreamCreateWithFlags(&ctx->side[i], hipStreamNonBlocking));
-            if (!ctx->join_ev[i]) HIPCHK(hipEventCreateWithFlags(&ctx->join_ev[i], hipEventDisableTiming));
+            HIPCHK(ctx->side[i].get());
+            HIPCHK(ctx->join_ev[i].get());
             HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->fork_ev, 0));
             ctx->stream = ctx->side[i];
         }
@@ -611,7 +607,7 @@ int lili_s2m_associate_window(lili_ctx* ctx, const int* slots, int n_slots, int 
         WindowArgs w;
         TRY(window_args(ctx, slots, n_slots, kind_mask, w, "associate_window"));
         TRY(ensure_h_records(ctx));
-        if (!ctx->h_records_dev) HIPCHK(ctx->win_counts.ensure(sizeof(int) * 2 * LILI_MAX_SLOTS));
+        if (!ctx->h_records.dev()) HIPCHK(ctx->win_counts.ensure(sizeof(int) * 2 * LILI_MAX_SLOTS));
         const Landing land{ctx, kHWindowCountsOff, ctx->win_counts.p};
         hipLaunchKernelGGL(k_window_counts, dim3(1), dim3(kBlock), 0, ctx->stream, w, land.dev<int>(), P2PView{});
         HIPCHK(hipGetLastError());
@@ -641,7 +637,7 @@ int lili_s2m_linearize_window(lili_ctx* ctx, const int* slots, int n_slots, int 
     ARGCHK(t && q && params && gram, "linearize_window: null argument");
     HIPCHK(hipSetDevice(ctx->device));
     TRY(ensure_h_records(ctx));
-    if (!ctx->h_records_dev) HIPCHK(ctx->win_rec.ensure(sizeof(double) * LILI_GRAM_DOUBLES * LILI_MAX_SLOTS));
+    if (!ctx->h_records.dev()) HIPCHK(ctx->win_rec.ensure(sizeof(double) * LILI_GRAM_DOUBLES * LILI_MAX_SLOTS));
     const Landing land{ctx, 0, ctx->win_rec.p};      // k_window_reduce writes the n records
     TRY(linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, nullptr, nullptr, land.dev<double>(), 0));
     double host[LILI_GRAM_DOUBLES * LILI_MAX_SLOTS];
@@ -910,10 +906,7 @@ static int launch_solve_lm(lili_ctx* ctx, int slot, int kind_mask, const lili_s2
     TRY(check_kind_mask(ctx, kind_mask, "solve_lm"));
     ARGCHK(params, "solve_lm: null params");
     lili_lm_options opt;
-    if (options) opt = *options; else lili_lm_default_options(&opt);
-    ARGCHK(opt.max_iterations >= 1 && opt.max_iterations <= 1000, "solve_lm: max_iterations must be in 1..1000");
-    ARGCHK(opt.initial_radius > 0 && opt.max_radius >= opt.initial_radius && opt.min_radius > 0 && opt.min_lm_diagonal > 0 && opt.max_lm_diagonal >= opt.min_lm_diagonal,
-           "solve_lm: inconsistent trust-region options");
+    TRY(lm_options_checked(ctx, "solve_lm", options, &opt));
     Slot& sl = ctx->slots[slot];
     LmArgs a{};
     int64_t n_all = 0;
@@ -1276,10 +1269,10 @@ int lili_s2m_linearize_window_sharded(lili_ctx* ctx, const int* slots, int n_slo
     int rc = linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, allreduce, comm, d_gram, 0);
     if (rc != LILI_OK) return rc;
     { const int rc_h = ensure_h_records(ctx); if (rc_h != LILI_OK) return rc_h; }
-    HIPCHK(hipMemcpyAsync(ctx->h_records, d_gram, (size_t)n_slots * LILI_GRAM_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->h_records.p, d_gram, (size_t)n_slots * LILI_GRAM_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < n_slots; i++) {
-        const double* h = ctx->h_records + (size_t)i * LILI_GRAM_DOUBLES;
+        const double* h = ctx->h_records.as<double>() + (size_t)i * LILI_GRAM_DOUBLES;
         std::memcpy(gram + (size_t)64 * i, h, 64 * sizeof(double));
         if (cost) cost[i] = h[64];
         if (counts) { counts[2 * i] = (int)h[65]; counts[2 * i + 1] = (int)h[66]; }
@@ -1372,10 +1365,10 @@ int lili_s2m_linearize_window_gather_at(lili_ctx* ctx, const int* slots, int n_s
     int rc = window_gather_impl(ctx, slots, n_slots, kind_mask, params, owner, rank, allreduce, comm, d_gram, 0, t, q);
     if (rc != LILI_OK) return rc;
     { const int rc_h = ensure_h_records(ctx); if (rc_h != LILI_OK) return rc_h; }
-    HIPCHK(hipMemcpyAsync(ctx->h_records, d_gram, (size_t)n_slots * LILI_GRAM_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->h_records.p, d_gram, (size_t)n_slots * LILI_GRAM_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < n_slots; i++) {
-        const double* h = ctx->h_records + (size_t)i * LILI_GRAM_DOUBLES;
+        const double* h = ctx->h_records.as<double>() + (size_t)i * LILI_GRAM_DOUBLES;
         std::memcpy(gram + (size_t)64 * i, h, 64 * sizeof(double));
         if (cost) cost[i] = h[64];
         if (counts) { counts[2 * i] = (int)h[65]; counts[2 * i + 1] = (int)h[66]; }
@@ -1408,15 +1401,15 @@ int lili_s2m_iterate_window(lili_ctx* ctx, const int* slots, int n_slots, int ki
     if (!ctx) return LILI_E_ARG;
     TRY(check_slot_list(ctx, slots, n_slots, "iterate_window"));
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ctx->fork_ev) HIPCHK(hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
+    HIPCHK(ctx->fork_ev.get());
     HIPCHK(hipEventRecord(ctx->fork_ev, ctx->stream));
     hipStream_t main_stream = ctx->stream;
     int rc = LILI_OK;
     ctx->persistent_off_now = n_slots > 4;       // more than four persistent launches side by side could not all be resident
     for (int i = 0; i < n_slots && rc == LILI_OK; i++) {
         if (i > 0) {
-            if (!ctx->side[i]) HIPCHK(hipStreamCreateWithFlags(&ctx->side[i], hipStreamNonBlocking));
-            if (!ctx->join_ev[i]) HIPCHK(hipEventCreateWithFlags(&ctx->join_ev[i], hipEventDisableTiming));
+            HIPCHK(ctx->side[i].get());
+            HIPCHK(ctx->join_ev[i].get());
             HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->fork_ev, 0));
             ctx->stream = ctx->side[i];          // the launch helpers enqueue on ctx->stream (one thread per context)
         }

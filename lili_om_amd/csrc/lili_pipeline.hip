@@ -71,22 +71,18 @@ int lili_frontend_flush(lili_ctx* ctx, const lili_s2m_params* match, const lili_
 // of the slot's state as well (gn_update_block).  arm_pose_mirror before lili_s2m_iterate; read_pose_after_iterate synchronises and takes the mirror — or, if the
 // iteration ran a path without that kernel (the sentinel is still there), reads the state back the plain way.
 static int arm_pose_mirror(lili_ctx* ctx, int slot) {
-    if (!ctx->h_state_mirror) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_state_mirror), sizeof(SlotState) * LILI_MAX_SLOTS, hipHostMallocDefault));
-        void* d = nullptr;
-        if (hipHostGetDevicePointer(&d, ctx->h_state_mirror, 0) != hipSuccess) { (void)hipGetLastError(); d = nullptr; }
-        ctx->h_state_mirror_dev = static_cast<SlotState*>(d);
-    }
-    *reinterpret_cast<volatile int*>(&ctx->h_state_mirror[slot].gn_status) = -1;
-    ctx->state_mirror_want = ctx->h_state_mirror_dev != nullptr;
+    HIPCHK(ctx->h_state_mirror.ensure(sizeof(SlotState) * LILI_MAX_SLOTS));
+    *reinterpret_cast<volatile int*>(&ctx->h_state_mirror.as<SlotState>()[slot].gn_status) = -1;
+    ctx->state_mirror_want = ctx->h_state_mirror.dev() != nullptr;
     return LILI_OK;
 }
 static int read_pose_after_iterate(lili_ctx* ctx, int slot, SlotState* st) {
     ctx->state_mirror_want = false;
     int rc = lili_readback_finish(ctx);
     if (rc != LILI_OK) return rc;
-    const int status = ctx->h_state_mirror ? *reinterpret_cast<volatile int*>(&ctx->h_state_mirror[slot].gn_status) : -1;
-    if (status != -1) { for (int i = 0; i < 7; i++) st->pose[i] = ctx->h_state_mirror[slot].pose[i]; st->gn_status = status; return LILI_OK; }
+    const SlotState* mirror = ctx->h_state_mirror.as<SlotState>();
+    const int status = mirror ? *reinterpret_cast<const volatile int*>(&mirror[slot].gn_status) : -1;
+    if (status != -1) { for (int i = 0; i < 7; i++) st->pose[i] = mirror[slot].pose[i]; st->gn_status = status; return LILI_OK; }
     rc = lili_readback_add(ctx, st, ctx->state(slot), sizeof(*st));
     if (rc != LILI_OK) return rc;
     return lili_readback_finish(ctx);

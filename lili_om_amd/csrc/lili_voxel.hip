@@ -733,7 +733,7 @@ namespace lili_detail {
 // `src`: the rows as pushed (LiDAR frame) — lili_localmap_repose re-runs transformCloud from them —, in the same allocation as the map-frame rows, behind them (one
 // allocation per keyframe, as before it kept them: a hipMalloc / hipFree is a device-wide synchronisation); `t` / `q`: the pose `pts` was placed at, unknown
 // (pose_known false) for a push at a pose read on the device (lili_localmap_push_dev)
-struct Keyframe { DevBuf pts; float4* src = nullptr; int n = 0; unsigned seq = 0; double t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0}; bool pose_known = false; void release() { pts.release(); src = nullptr; } };
+struct Keyframe { DevBuf pts; float4* src = nullptr; int n = 0; unsigned seq = 0; double t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0}; bool pose_known = false; };
 // the ring of one kind, sorted by absolute voxel key (older keyframes first inside a voxel): see k_merge_old / k_merge_new
 struct SortedRing {
     DevBuf key[2], pt[2], seq[2];
@@ -742,20 +742,19 @@ struct SortedRing {
     float leaf = 0.f;
     bool valid = false;
     std::vector<std::pair<unsigned, int>> members;      // (sequence number, points) of the keyframes it holds, oldest first
-    void release() { for (int b = 0; b < 2; b++) { key[b].release(); pt[b].release(); seq[b].release(); } valid = false; n = 0; members.clear(); }
 };
-struct VoxelBuffers {
+struct VoxelBuffers : ExtState {
     DevBuf keys_a, keys_b, vals_a, vals_b, hist, hist_scan, sums, flags, slots, out, out_cnt, in, concat, concat_tab;
-    std::vector<Keyframe*> ring[2];    // per kind, oldest first
+    std::vector<std::unique_ptr<Keyframe>> ring[2];    // per kind, oldest first
     SortedRing sorted[2];
-    std::vector<Keyframe*> pool;       // popped keyframes: their device buffers are reused by the next push (no hipMalloc / hipFree per keyframe: each is a device-wide synchronisation of ~100 us)
+    std::vector<std::unique_ptr<Keyframe>> pool;       // popped keyframes: their device buffers are reused by the next push (no hipMalloc / hipFree per keyframe: each is a device-wide synchronisation of ~100 us)
     unsigned next_seq = 1;
     DevBuf head_pos;
     DevBuf kf_key, kf_pt, seg_seq;     // the new keyframe sorted by key; sequence numbers of the concatenation's segments
     DevBuf kf_seq;                     // the commit after a repose: the sequence number of every new entry (several keyframes merged in at once)
     // lili_localmap_repose's segment table: page-locked staging owned by the context (never an async copy from a host vector that goes out of scope), reused
     // once the copy recorded by `repose_ev` has run; the device copy in repose_tab
-    void* repose_pin = nullptr; size_t repose_pin_cap = 0; hipEvent_t repose_ev = nullptr; bool repose_ev_armed = false;
+    PinBuf repose_pin; Event repose_ev; bool repose_ev_armed = false;
     DevBuf repose_tab;
     std::vector<unsigned> seg_seq_host;
     int incremental_commits = 0, full_commits = 0;
@@ -771,16 +770,7 @@ struct VoxelBuffers {
     int bits_guess[2] = {0, 0}; float guess_leaf[2] = {0, 0}; int guess_low[2] = {0, 0};
     int key_guesses = 0, key_guess_misses = 0;
     unsigned out_box[6] = {0, 0, 0, 0, 0, 0};   // bounding box of `out` (ordered-uint words, k_bbox_dev) after an incremental commit
-    void release() {
-        for (DevBuf* b : {&keys_a, &keys_b, &vals_a, &vals_b, &hist, &hist_scan, &sums, &flags, &slots, &out, &out_cnt, &in, &concat, &concat_tab}) b->release();
-        for (auto& r : ring) { for (auto* k : r) { k->release(); delete k; } r.clear(); }
-        for (auto* k : pool) { k->release(); delete k; }
-        pool.clear();
-        for (auto& sr : sorted) sr.release();
-        kf_key.release(); kf_pt.release(); seg_seq.release(); kf_seq.release(); head_pos.release(); spts.release(); qout.release(); qout_cnt.release(); repose_tab.release();
-        if (repose_ev) { (void)hipEventSynchronize(repose_ev); (void)hipEventDestroy(repose_ev); repose_ev = nullptr; }
-        if (repose_pin) { (void)hipHostFree(repose_pin); repose_pin = nullptr; repose_pin_cap = 0; }
-    }
+    ~VoxelBuffers() override { if (repose_ev) (void)hipEventSynchronize(repose_ev); }      // the copy out of repose_pin has run before that memory goes
 };
 }  // namespace lili_detail
 
@@ -792,10 +782,7 @@ __global__ void k_concat(const lili_detail::ConcatSeg* __restrict__ segs, int n_
     out[i] = segs[lo].src[i - segs[lo].first];
 }
 
-static lili_detail::VoxelBuffers* vox_of(lili_ctx* ctx) {
-    if (!ctx->ext_voxel) { ctx->ext_voxel = new lili_detail::VoxelBuffers(); ctx->ext_voxel_free = [](void* p) { auto* r = static_cast<lili_detail::VoxelBuffers*>(p); r->release(); delete r; }; }
-    return static_cast<lili_detail::VoxelBuffers*>(ctx->ext_voxel);
-}
+static lili_detail::VoxelBuffers* vox_of(lili_ctx* ctx) { return ext_of<lili_detail::VoxelBuffers>(ctx, lili_ctx::kExtVoxel); }
 
 // Exclusive scan of a SHORT array (<= 64 k words: the head / keep flags of a frame's voxel filter and ring merge, the digit histograms of a radix pass) in ONE launch
 // with NO communication between workgroups (round 5, second version): tile t (2048 words, 256 threads) sums the words in FRONT of it itself — at most 30 tiles of
@@ -1236,7 +1223,6 @@ int lili_localmap_reset(lili_ctx* ctx, int kind) {
     ARGCHK(kind == 0 || kind == 1, "localmap_reset: bad kind");
     auto* V = vox_of(ctx);
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (auto* k : V->ring[kind]) { k->release(); delete k; }
     V->ring[kind].clear();
     V->sorted[kind].valid = false; V->sorted[kind].n = 0; V->sorted[kind].members.clear();
     return LILI_OK;
@@ -1246,30 +1232,30 @@ int lili_localmap_reset(lili_ctx* ctx, int kind) {
 static int localmap_push_f4(lili_ctx* ctx, int kind, const float4* d_in, int n, const double* t, const double* q, const SlotState* d_state, int width) {
     auto* V = vox_of(ctx);
     // a buffer from the pool of popped keyframes if one is large enough (the steady state: keyframes of similar size), else a new one
-    lili_detail::Keyframe* kf = nullptr;
-    for (size_t i = 0; i < V->pool.size(); i++) if (V->pool[i]->pts.cap >= (size_t)n * 32) { kf = V->pool[i]; V->pool.erase(V->pool.begin() + (long)i); break; }
-    if (!kf) kf = new lili_detail::Keyframe();
+    std::unique_ptr<lili_detail::Keyframe> kf;
+    for (size_t i = 0; i < V->pool.size(); i++) if (V->pool[i]->pts.cap >= (size_t)n * 32) { kf = std::move(V->pool[i]); V->pool.erase(V->pool.begin() + (long)i); break; }
+    if (!kf) kf.reset(new lili_detail::Keyframe());
     kf->n = n;
     kf->seq = V->next_seq++;
     kf->pose_known = !d_state;
     if (!d_state) { std::memcpy(kf->t, t, sizeof(kf->t)); std::memcpy(kf->q, q, sizeof(kf->q)); }
     if (kf->n > 0) {
         hipError_t e = kf->pts.ensure((size_t)kf->n * 32);      // map-frame rows, then the rows as pushed
-        if (e != hipSuccess) { delete kf; return ctx->fail(LILI_E_HIP, "localmap_push: allocation failed"); }
+        if (e != hipSuccess) return ctx->fail(LILI_E_HIP, "localmap_push: allocation failed");
         kf->src = kf->pts.as<float4>() + kf->n;
         if (d_state) hipLaunchKernelGGL(k_transform_cloud_state, dim3(nblocks(kf->n, 256)), dim3(256), 0, ctx->stream, d_in, kf->n, d_state, kf->pts.as<float4>(), kf->src);
         else hipLaunchKernelGGL(k_transform_cloud, dim3(nblocks(kf->n, 256)), dim3(256), 0, ctx->stream, d_in, kf->n,
                                 dq{q[0], q[1], q[2], q[3]}, d3{t[0], t[1], t[2]}, kf->pts.as<float4>(), kf->src);
         hipError_t le = hipGetLastError();
-        if (le != hipSuccess) { delete kf; return ctx->fail(LILI_E_HIP, std::string("localmap_push: ") + hipGetErrorString(le)); }
+        if (le != hipSuccess) return ctx->fail(LILI_E_HIP, std::string("localmap_push: ") + hipGetErrorString(le));
     }
-    V->ring[kind].push_back(kf);
+    V->ring[kind].push_back(std::move(kf));
     while ((int)V->ring[kind].size() > width) {   // recent_*_keyframes.pop_front() (L:1449-1450)
         // the popped keyframe's buffer goes to the pool: everything that reads it was enqueued on this stream before whatever will overwrite it
-        auto* old = V->ring[kind].front();
+        auto old = std::move(V->ring[kind].front());
         V->ring[kind].erase(V->ring[kind].begin());
-        if (V->pool.size() < 4) V->pool.push_back(old);
-        else { HIPCHK(hipStreamSynchronize(ctx->stream)); old->release(); delete old; }
+        if (V->pool.size() < 4) V->pool.push_back(std::move(old));
+        else HIPCHK(hipStreamSynchronize(ctx->stream));      // (then `old` frees its buffer)
     }
     return LILI_OK;
 }
@@ -1304,7 +1290,7 @@ int lili_localmap_repose(lili_ctx* ctx, int kind_mask, int n, const double* t, c
         const auto& ring = V->ring[kind];
         changed[kind].assign((size_t)n, 0);
         for (int j = 0; j < n; j++) {
-            const lili_detail::Keyframe* k = ring[(size_t)j];
+            const lili_detail::Keyframe* k = ring[(size_t)j].get();
             const bool c = !k->pose_known || std::memcmp(k->t, t + 3 * j, sizeof(k->t)) != 0 || std::memcmp(k->q, q + 4 * j, sizeof(k->q)) != 0;
             changed[kind][(size_t)j] = c;
             if (c && first[kind] == (size_t)n) first[kind] = (size_t)j;
@@ -1318,15 +1304,11 @@ int lili_localmap_repose(lili_ctx* ctx, int kind_mask, int n, const double* t, c
     if (total > 0) {
         const size_t bytes = segs.size() * sizeof(ReposeSeg);
         if (V->repose_ev_armed) { HIPCHK(hipEventSynchronize(V->repose_ev)); V->repose_ev_armed = false; }      // (the previous table's copy has run long ago: no wait in practice)
-        if (!V->repose_ev) HIPCHK(hipEventCreateWithFlags(&V->repose_ev, hipEventDisableTiming));
-        if (V->repose_pin_cap < bytes) {
-            if (V->repose_pin) { HIPCHK(hipHostFree(V->repose_pin)); V->repose_pin = nullptr; V->repose_pin_cap = 0; }
-            HIPCHK(hipHostMalloc(&V->repose_pin, bytes * 2));
-            V->repose_pin_cap = bytes * 2;
-        }
-        std::memcpy(V->repose_pin, segs.data(), bytes);
+        HIPCHK(V->repose_ev.get());
+        if (V->repose_pin.cap < bytes) HIPCHK(V->repose_pin.ensure(bytes * 2));
+        std::memcpy(V->repose_pin.p, segs.data(), bytes);
         HIPCHK(V->repose_tab.ensure(bytes));
-        HIPCHK(hipMemcpyAsync(V->repose_tab.p, V->repose_pin, bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(V->repose_tab.p, V->repose_pin.p, bytes, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipEventRecord(V->repose_ev, ctx->stream));
         V->repose_ev_armed = true;
         hipLaunchKernelGGL(k_ring_repose, dim3(nblocks(total, 256)), dim3(256), 0, ctx->stream, V->repose_tab.as<ReposeSeg>(), (int)segs.size(), total);
@@ -1336,7 +1318,7 @@ int lili_localmap_repose(lili_ctx* ctx, int kind_mask, int n, const double* t, c
         if (!(kind_mask & (1 << kind))) continue;
         auto& ring = V->ring[kind];
         for (size_t j = first[kind]; j < (size_t)n; j++) {
-            lili_detail::Keyframe* k = ring[j];
+            lili_detail::Keyframe* k = ring[j].get();
             k->seq = V->next_seq++;      // fresh numbers in ring order: above every entry the sorted ring keeps
             if (changed[kind][j]) { std::memcpy(k->t, t + 3 * j, sizeof(k->t)); std::memcpy(k->q, q + 4 * j, sizeof(k->q)); k->pose_known = true; }
         }
@@ -1464,7 +1446,7 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
     auto& ring = V->ring[kind];
     lili_detail::SortedRing& S = V->sorted[kind];
     size_t total = 0;
-    for (auto* k : ring) total += (size_t)k->n;
+    for (const auto& k : ring) total += (size_t)k->n;
     if (n_raw) *n_raw = (int64_t)total;
     unsigned* d_bad = reinterpret_cast<unsigned*>(ctx->misc.as<char>() + 256);      // (the bounding-box words of voxel_sort live in the first 24 bytes)
     // ---- what changed since the sorted ring was built: keyframes popped at the front, keyframes pushed at the back
@@ -1483,7 +1465,7 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
                 resuffix = true;
                 keep_lo = S.members[f].first; keep_hi = S.members[f + m - 1].first;
                 for (size_t i = 0; i < S.members.size(); i++) if (i < f || i >= f + m) n_drop += S.members[i].second;
-                for (size_t i = m; i < ring.size(); i++) add.push_back(ring[i]);
+                for (size_t i = m; i < ring.size(); i++) add.push_back(ring[i].get());
                 long long n_add = 0;
                 for (auto* k : add) n_add += k->n;
                 if (S.n - n_drop + n_add != (long long)total) inc = false;      // (the merge writes exactly the ring's points; anything else is not this case)
@@ -1496,7 +1478,7 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
             size_t m = 0;
             while (f + m < S.members.size() && m < ring.size() && S.members[f + m].first == ring[m]->seq) m++;
             if (f + m != S.members.size()) inc = false;                    // the ring is not "old members, then new keyframes"
-            for (size_t i = m; i < ring.size(); i++) add.push_back(ring[i]);
+            for (size_t i = m; i < ring.size(); i++) add.push_back(ring[i].get());
             if (add.size() > 2) inc = false;                               // several pending keyframes: the rebuild is cheaper than as many merge passes
         }
     }
@@ -1514,7 +1496,7 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
         }
         if (rc != LILI_OK) { S.valid = false; return rc; }
         S.members.clear();
-        for (auto* k : ring) S.members.push_back({k->seq, k->n});
+        for (const auto& k : ring) S.members.push_back({k->seq, k->n});
         const long long n = S.n;
         V->n_out = 0;
         unsigned bad = 0;
@@ -1575,7 +1557,7 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
         std::vector<unsigned>& sseq = V->seg_seq_host;
         segs.clear(); sseq.clear();
         size_t off = 0;
-        for (auto* k : ring) { if (k->n) { segs.push_back({k->pts.as<float4>(), (long long)off}); sseq.push_back(k->seq); } off += (size_t)k->n; }
+        for (const auto& k : ring) { if (k->n) { segs.push_back({k->pts.as<float4>(), (long long)off}); sseq.push_back(k->seq); } off += (size_t)k->n; }
         if (!segs.empty()) {
             HIPCHK(V->concat_tab.ensure(segs.size() * sizeof(lili_detail::ConcatSeg)));
             HIPCHK(hipMemcpyAsync(V->concat_tab.p, segs.data(), segs.size() * sizeof(lili_detail::ConcatSeg), hipMemcpyHostToDevice, ctx->stream));
@@ -1601,7 +1583,7 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
             TRY(lili_readback_now(ctx, &bad, d_bad, 4));
             S.cur = 0; S.n = (long long)total; S.leaf = leaf; S.valid = bad == 0;
             S.members.clear();
-            for (auto* k : ring) S.members.push_back({k->seq, k->n});
+            for (const auto& k : ring) S.members.push_back({k->seq, k->n});
         }
     }
     if (n_map) *n_map = V->n_out;
@@ -1691,13 +1673,12 @@ int lili_localmap_ring_size(lili_ctx* ctx, int kind) { return (int)vox_of(ctx)->
 
 
 // lili_loop.hip: detectLoopClosure's submap — transformCloud of every cloud, concatenated, then VoxelGrid(leaf) (leaf <= 0: none) — into `out` (float4 rows).  The filter
-// runs on a VoxelBuffers of the loop's own (`*priv`, created here, freed by lili_loop_vox_free) and always the measured way: the local map's buffers, its ring and the key-bit
+// runs on a VoxelBuffers of the loop's own (`priv`, created here) and always the measured way: the local map's buffers, its ring and the key-bit
 // guesses of lili_voxel_filter_stats stay as they are.  Blocking.
-struct LoopVox { lili_detail::VoxelBuffers V; DevBuf segs, staging, raw; std::vector<LoopSeg> seg_host; };
-void lili_loop_vox_free(void* p) { if (p) { auto* L = static_cast<LoopVox*>(p); L->V.release(); delete L; } }
-int lili_loop_assemble(lili_ctx* ctx, void** priv, const lili_cloud* clouds, int n_clouds, const double* t, const double* q, float leaf, DevBuf& out, int64_t* n_raw, int64_t* n_ds) {
-    if (!*priv) *priv = new LoopVox();
-    auto* L = static_cast<LoopVox*>(*priv);
+struct LoopVox : ExtState { lili_detail::VoxelBuffers V; DevBuf segs, staging, raw; std::vector<LoopSeg> seg_host; };
+int lili_loop_assemble(lili_ctx* ctx, std::unique_ptr<ExtState>& priv, const lili_cloud* clouds, int n_clouds, const double* t, const double* q, float leaf, DevBuf& out, int64_t* n_raw, int64_t* n_ds) {
+    if (!priv) priv.reset(new LoopVox());
+    auto* L = static_cast<LoopVox*>(priv.get());
     L->seg_host.assign(n_clouds, LoopSeg{});
     long long total = 0, host_bytes = 0;
     for (int k = 0; k < n_clouds; k++) {
@@ -1755,16 +1736,15 @@ int lili_loop_assemble(lili_ctx* ctx, void** priv, const lili_cloud* clouds, int
 }
 
 // lili_archive.hip: the sort of one batch of the global map (declared in lili_ctx.h), the measured way on buffers of its own
-struct SortVox { lili_detail::VoxelBuffers V; };
-void lili_vox_sort_free(void* p) { if (p) { auto* S = static_cast<SortVox*>(p); S->V.release(); delete S; } }
-size_t lili_vox_sort_bytes(const void* p) {
+struct SortVox : ExtState { lili_detail::VoxelBuffers V; };
+size_t lili_vox_sort_bytes(const ExtState* p) {
     if (!p) return 0;
     const auto& V = static_cast<const SortVox*>(p)->V;
     return V.keys_a.cap + V.keys_b.cap + V.vals_a.cap + V.vals_b.cap + V.hist.cap + V.hist_scan.cap + V.sums.cap;
 }
-int lili_voxel_sort_dev(lili_ctx* ctx, void** priv, const float4* d_pts, int n, float leaf, int* status, float box[6], unsigned* sentinel, const unsigned** d_keys, const int** d_order) {
-    if (!*priv) *priv = new SortVox();
-    auto* S = static_cast<SortVox*>(*priv);
+int lili_voxel_sort_dev(lili_ctx* ctx, std::unique_ptr<ExtState>& priv, const float4* d_pts, int n, float leaf, int* status, float box[6], unsigned* sentinel, const unsigned** d_keys, const int** d_order) {
+    if (!priv) priv.reset(new SortVox());
+    auto* S = static_cast<SortVox*>(priv.get());
     { const int rl = lili_lazy_sources_clear_of(ctx, ctx->misc.p, 64); if (rl != LILI_OK) return rl; }      // the box words (ctx->misc)
     VoxDev P;
     const int rc = voxel_sort(ctx, &S->V, d_pts, n, leaf, P, false, status, box);

@@ -1279,8 +1279,7 @@ static int window_cycle_body(lili_ctx* ctx, const lili_window_problem* problem, 
     const int n_kf = problem->n_kf;
     WinCycleMargArgs c{};
     if ((rc = window_marg_table(ctx, problem, "window_cycle", c)) != LILI_OK) return rc;
-    lili_lm_options opt;
-    if (options) opt = *options; else lili_lm_default_options(&opt);
+    const lili_lm_options opt = lm_options_or_default(options);
     HIPCHK(hipSetDevice(ctx->device));
     for (DevBuf* b : {&ctx->win_res, &ctx->win_res_nxt})
         if (!b->p) { HIPCHK(b->ensure(sizeof(WinPriorDev))); HIPCHK(hipMemsetAsync(b->p, 0, sizeof(WinPriorDev), ctx->stream)); }
