@@ -165,10 +165,30 @@ struct Landing {
     }
 };
 
-extern "C" {
 // --------------------------------------------------------------------------------------------
 // queries / associate / linearize
 // --------------------------------------------------------------------------------------------
+// The slot's partitions for n queries: association workgroups of one wave (kAssocBlock), linearisation blocks of kLinBlock (1024) threads, at most kMaxLinBlocks
+// partials.  The linearisation block size is FIXED (it was chosen per scan size in round 1): the block partition of the Gram sum — hence its rounding — must not
+// depend on options that may change between set_queries and iterate (the fused tail needs all 1024 threads for its reduction).
+static void size_queries(KindSlot& ks, int64_t n) {
+    ks.n_q = n;
+    ks.n_blocks = nblocks(ks.n_q, kAssocBlock);
+    ks.n_lin_blocks = std::min(nblocks(ks.n_q, kLinBlock), kMaxLinBlocks);
+}
+// the record buffers of the slot's queries and one partial / one count per block of those partitions
+static int ensure_query_buffers(lili_ctx* ctx, KindSlot& ks) {
+    const size_t n = (size_t)ks.n_q;
+    if (!n) return LILI_OK;
+    HIPCHK(ks.rec0.ensure(n * sizeof(float4)));
+    HIPCHK(ks.rec1.ensure(n * sizeof(float4)));   // surf: doubles (8 B) fit in the float4 budget
+    HIPCHK(ks.valid.ensure(n));
+    HIPCHK(ks.partials.ensure((size_t)ks.n_lin_blocks * kPartialStride * sizeof(double)));
+    HIPCHK(ks.block_counts.ensure((size_t)ks.n_blocks * sizeof(int)));
+    return LILI_OK;
+}
+
+extern "C" {
 int lili_s2m_set_queries(lili_ctx* ctx, int slot, int kind, const lili_cloud* cloud) {
     if (!ctx) return LILI_E_ARG;
     TRY(check_slot(ctx, slot, "set_queries"));
@@ -177,23 +197,10 @@ int lili_s2m_set_queries(lili_ctx* ctx, int slot, int kind, const lili_cloud* cl
     HIPCHK(hipSetDevice(ctx->device));
     KindSlot& ks = ctx->slots[slot].k[kind];
     ks.has_queries = false; ks.has_records = false; ks.launches = 0;
-    int rc = lili_ingest_cloud(ctx, cloud, ks.q);
-    if (rc != LILI_OK) return rc;
-    ks.n_q = (int64_t)cloud->n;
+    TRY(lili_ingest_cloud(ctx, cloud, ks.q));
     ks.has_aux = cloud->aux_offset >= 0;
-    ks.n_blocks = nblocks(ks.n_q, kAssocBlock);
-    // linearisation: kLinBlock (1024) threads per block, at most kMaxLinBlocks partials.  The block size is FIXED (it was chosen
-    // per scan size in round 1): the block partition of the Gram sum — hence its rounding — must not depend on options that may
-    // change between set_queries and iterate (the fused tail needs all 1024 threads for its reduction).
-    ks.n_lin_blocks = std::min(nblocks(ks.n_q, kLinBlock), kMaxLinBlocks);
-    size_t n = (size_t)ks.n_q;
-    if (n) {
-        HIPCHK(ks.rec0.ensure(n * sizeof(float4)));
-        HIPCHK(ks.rec1.ensure(n * sizeof(float4)));   // surf: doubles (8 B) fit in the float4 budget
-        HIPCHK(ks.valid.ensure(n));
-        HIPCHK(ks.partials.ensure((size_t)ks.n_lin_blocks * kPartialStride * sizeof(double)));
-        HIPCHK(ks.block_counts.ensure((size_t)ks.n_blocks * sizeof(int)));
-    }
+    size_queries(ks, (int64_t)cloud->n);
+    TRY(ensure_query_buffers(ctx, ks));
     ks.has_queries = true;
     return LILI_OK;
 }
@@ -212,17 +219,10 @@ int lili_s2m_set_queries_counted(lili_ctx* ctx, int slot, int kind, int n_guess)
     ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS && (kind == 0 || kind == 1) && n_guess > 0, "set_queries_counted: bad argument");
     KindSlot& ks = ctx->slots[slot].k[kind];
     ks.has_queries = false; ks.has_records = false; ks.launches = 0;
-    const size_t n = (size_t)n_guess;
-    HIPCHK(ks.q.ensure(n * sizeof(float4)));
-    ks.n_q = n_guess;
+    HIPCHK(ks.q.ensure((size_t)n_guess * sizeof(float4)));
     ks.has_aux = true;
-    ks.n_blocks = nblocks(ks.n_q, kAssocBlock);
-    ks.n_lin_blocks = std::min(nblocks(ks.n_q, kLinBlock), kMaxLinBlocks);
-    HIPCHK(ks.rec0.ensure(n * sizeof(float4)));
-    HIPCHK(ks.rec1.ensure(n * sizeof(float4)));
-    HIPCHK(ks.valid.ensure(n));
-    HIPCHK(ks.partials.ensure((size_t)ks.n_lin_blocks * kPartialStride * sizeof(double)));
-    HIPCHK(ks.block_counts.ensure((size_t)ks.n_blocks * sizeof(int)));
+    size_queries(ks, n_guess);
+    TRY(ensure_query_buffers(ctx, ks));
     ks.has_queries = true;
     return LILI_OK;
 }
@@ -231,9 +231,7 @@ int lili_s2m_trim_queries(lili_ctx* ctx, int slot, int kind, int n) {
     if (!ctx) return LILI_E_ARG;
     KindSlot& ks = ctx->slots[slot].k[kind];
     ARGCHK(ks.has_queries && n >= 0 && n <= ks.n_q, "trim_queries: bad argument");
-    ks.n_q = n;
-    ks.n_blocks = nblocks(ks.n_q, kAssocBlock);
-    ks.n_lin_blocks = std::min(nblocks(ks.n_q, kLinBlock), kMaxLinBlocks);
+    size_queries(ks, n);      // (n_assoc_blocks stays: see above)
     return LILI_OK;
 }
 extern "C" {
@@ -285,6 +283,18 @@ static int launch_sum_counts(lili_ctx* ctx, int slot, int kind_mask, int* d_out 
     if ((kind_mask & LILI_MASK_SURF) && s.k[0].has_records && s.k[0].n_q > 0) { bs = s.k[0].block_counts.as<int>(); nbs = s.k[0].n_assoc_blocks; }
     if ((kind_mask & LILI_MASK_EDGE) && s.k[1].has_records && s.k[1].n_q > 0) { be = s.k[1].block_counts.as<int>(); nbe = s.k[1].n_assoc_blocks; }
     hipLaunchKernelGGL(k_sum_counts, dim3(1), dim3(kBlock), 0, ctx->stream, bs, nbs, be, nbe, ctx->state(slot), d_out, xv ? *xv : P2PView{});
+    HIPCHK(hipGetLastError());
+    return LILI_OK;
+}
+
+// k_reduce_partials, one workgroup: the block partials of the two kinds (nb = 0: none of that kind) -> the slot's 72-double record in d_out and, with bit 0 of
+// `flags`, its Gauss-Newton update from the pose `pa` was linearised at.  What differs between the launchers stands at their calls: `xv` the exchange across ranks
+// folded into the kernel, `pub_key` / `pub` the key and the buffer the new pose is published under (option "overlap_gn"), `mirror` whether this launch takes the
+// page-locked state mirror if one is armed (one shot: the LAST update of a registration).
+static int launch_reduce_partials(lili_ctx* ctx, int slot, const double* part_surf, int nb_surf, const double* part_edge, int nb_edge, double* d_out, int flags,
+                                  const PoseArg& pa, bool mirror, const P2PView& xv = P2PView{}, unsigned long long pub_key = 0ull, double* pub = nullptr) {
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, part_surf, nb_surf, part_edge, nb_edge, d_out, ctx->state(slot), flags, xv, pub_key, pub,
+                       mirror ? ctx->take_state_mirror(slot) : nullptr, pa.state);
     HIPCHK(hipGetLastError());
     return LILI_OK;
 }
@@ -345,9 +355,8 @@ static int launch_associate_coop(lili_ctx* ctx, int slot, int kind_mask, const P
             if (lin) hipLaunchKernelGGL((k_associate_coop<LL, true>), grid, block, 0, ctx->stream, A[0], A[1], pa, P, ps, pe, ctx->state(slot), cb_blocks);
             else launch_k(ctx->stream, pa.wait_key != 0ull, (k_associate_coop<LL, false>), grid, block, 0, A[0], A[1], pa, Pk, ps, pe, ctx->state(slot), 0);
         })) return 1;
-    if (lin) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, (const double*)ps, A[0].nb, (const double*)pe, A[1].nb, d_out, ctx->state(slot),
-                                1 | (P.debug & 256), P2PView{}, 0ull, (double*)nullptr, ctx->take_state_mirror(slot), pa.state);
     HIPCHK(hipGetLastError());
+    if (lin) TRY(launch_reduce_partials(ctx, slot, ps, A[0].nb, pe, A[1].nb, d_out, 1 | (P.debug & 256), pa, true));
     sl.use_global_counts = false;
     return LILI_OK;
 }
@@ -433,23 +442,40 @@ static int launch_iterate_persistent(lili_ctx* ctx, int slot, int kind_mask, con
     return LILI_OK;
 }
 
-static LinArgs lin_args_of(lili_ctx* ctx, int slot, int kind) {
-    KindSlot& ks = ctx->slots[slot].k[kind];
-    LinArgs A{};
-    A.queries = ks.q.as<float4>(); A.n_q = (int)ks.n_q; A.rec0 = ks.rec0.as<float4>(); A.rec1 = ks.rec1.p; A.valid = ks.valid.as<unsigned char>();
-    A.block_counts = ctx->slots[slot].use_global_counts ? nullptr : ks.block_counts.as<int>(); A.n_bc = ks.n_assoc_blocks;
-    A.partials = ks.partials.as<double>(); A.nb = ks.n_lin_blocks;
-    return A;
+// The kinds of kind_mask that have queries on the slot, as linearisation arguments (A[kind] of any other kind stays empty: no blocks); *n_kinds: how many.
+// Every kind in the mask must have been associated, queries or not: the refusal is `who`'s, in the words `first`.
+static int lin_kinds(lili_ctx* ctx, int slot, int kind_mask, const char* who, LinArgs A[2], int* n_kinds, const char* first = ": associate first") {
+    *n_kinds = 0;
+    for (int kind = 0; kind < 2; kind++) {
+        LinArgs& a = A[kind] = LinArgs{};
+        if (!(kind_mask & (1 << kind))) continue;
+        const KindSlot& ks = ctx->slots[slot].k[kind];
+        if (!ks.has_records) return ctx->fail(LILI_E_STATE, std::string(who) + first);
+        if (ks.n_q == 0) continue;
+        a.queries = ks.q.as<float4>(); a.n_q = (int)ks.n_q; a.rec0 = ks.rec0.as<float4>(); a.rec1 = ks.rec1.p; a.valid = ks.valid.as<unsigned char>();
+        a.block_counts = ctx->slots[slot].use_global_counts ? nullptr : ks.block_counts.as<int>(); a.n_bc = ks.n_assoc_blocks;
+        a.partials = ks.partials.as<double>(); a.nb = ks.n_lin_blocks;
+        ++*n_kinds;
+    }
+    return LILI_OK;
+}
+// k_linearize of one slot at `pa`, both kinds of A in ONE launch (no kind: no launch); `tail`: what its last block to finish does with the block partials
+static int launch_linearize_merged(lili_ctx* ctx, int slot, const LinArgs A[2], int n_kinds, const PoseArg& pa, const MatchParams& P, const FuseTail& tail) {
+    if (n_kinds == 0) return LILI_OK;
+    const Slot& s = ctx->slots[slot];
+    hipLaunchKernelGGL(k_linearize, dim3(A[0].nb + A[1].nb), dim3(kLinBlock), lds_linearize(kLinBlock), ctx->stream, A[0], A[1], pa, P, ctx->state(slot),
+                       s.use_global_counts ? s.global_counts : nullptr, tail);
+    HIPCHK(hipGetLastError());
+    return LILI_OK;
+}
+// the same with the block partials left in the slot's buffers (no reduction): the first half of launch_linearize_reduce's plain case
+static int launch_linearize_only(lili_ctx* ctx, int slot, int kind_mask, const PoseArg& pa, const MatchParams& P) {
+    LinArgs A[2];
+    int n_kinds;
+    TRY(lin_kinds(ctx, slot, kind_mask, "linearize", A, &n_kinds));
+    return launch_linearize_merged(ctx, slot, A, n_kinds, pa, P, FuseTail{});
 }
 
-// Linearisation of the kinds in kind_mask and the reduction of their block partials to the 72-double record (and the GN update
-// if do_gn).  Default: ONE launch — k_linearize covers both kinds and its last block to finish reduces (+ solves), see fused_tail.
-// Options for A/B: merge_kinds = 0 (one launch per kind), fuse_tail = 0 (k_reduce_partials as its own launch).  These variants
-// add the same numbers in the same order: the record is bit-identical.  NOT so the paths that linearise inside the association launch
-// (fuse_lin / k_associate_lin, k_associate_coop<L, true>): there the PARTITION of the Gram sum follows the association's workgroups
-// (64 or 256 queries per partial, 256 / L with L lanes per query), so lili_s2m_iterate, lili_s2m_iterate_restart with assoc_ms (which
-// takes the three-launch path to bracket the association) and fuse_lin = 0 agree to ~1e-16 relative per entry, not bit for bit, and the
-// low-order bits can change across the size thresholds of launch_associate_lin_reduce / coop_lanes (tests: <= 1e-10 on the pose).
 // One outer iteration in TWO launches for the flavours without count scaling (k_associate_lin: association + linearisation, then the
 // reduction + GN update).  Returns 1 if the configuration is not eligible (the caller then takes the three-launch path).
 static int launch_associate_lin_reduce(lili_ctx* ctx, int slot, int kind_mask, const PoseArg& pa, const MatchParams& P, double* d_out) {
@@ -483,49 +509,77 @@ static int launch_associate_lin_reduce(lili_ctx* ctx, int slot, int kind_mask, c
                                               sl.k[0].partials_wave.as<double>(), sl.k[1].partials_wave.as<double>());
     else hipLaunchKernelGGL(k_associate_lin<kBlock>, dim3(A[0].nb + A[1].nb), dim3(kBlock), 0, ctx->stream, A[0], A[1], pa, with_prio(ctx, P),
                             sl.k[0].partials_wave.as<double>(), sl.k[1].partials_wave.as<double>());
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, (const double*)sl.k[0].partials_wave.as<double>(), A[0].nb,
-                       (const double*)sl.k[1].partials_wave.as<double>(), A[1].nb, d_out, ctx->state(slot), 1 | (P.debug & 256), P2PView{}, 0ull, (double*)nullptr, ctx->take_state_mirror(slot), pa.state);
     HIPCHK(hipGetLastError());
+    TRY(launch_reduce_partials(ctx, slot, sl.k[0].partials_wave.as<double>(), A[0].nb, sl.k[1].partials_wave.as<double>(), A[1].nb, d_out, 1 | (P.debug & 256), pa, true));
     sl.use_global_counts = false;
     return LILI_OK;
 }
 
+// Linearisation of the kinds in kind_mask and the reduction of their block partials to the 72-double record (and the GN update
+// if do_gn).  Default: ONE launch — k_linearize covers both kinds and its last block to finish reduces (+ solves), see fused_tail.
+// Options for A/B: merge_kinds = 0 (one launch per kind), fuse_tail = 0 (k_reduce_partials as its own launch).  These variants
+// add the same numbers in the same order: the record is bit-identical.  NOT so the paths that linearise inside the association launch
+// (fuse_lin / k_associate_lin, k_associate_coop<L, true>): there the PARTITION of the Gram sum follows the association's workgroups
+// (64 or 256 queries per partial, 256 / L with L lanes per query), so lili_s2m_iterate, lili_s2m_iterate_restart with assoc_ms (which
+// takes the three-launch path to bracket the association) and fuse_lin = 0 agree to ~1e-16 relative per entry, not bit for bit, and the
+// low-order bits can change across the size thresholds of launch_associate_lin_reduce / coop_lanes (tests: <= 1e-10 on the pose).
+// With no kind present nothing is linearised, and k_reduce_partials still runs: it writes the zero record.
 // pub_key (in / out, optional): != 0 asks the reduction + GN kernel to publish the new pose for an association launch that starts without waiting for it (option
 // "overlap_gn", iterate_impl); set to 0 here when this call's structure has no such kernel (fused tail) — the caller then launches the association the plain way.
 static int launch_linearize_reduce(lili_ctx* ctx, int slot, int kind_mask, const PoseArg& pa, const MatchParams& P, double* d_out, int do_gn,
                                    const P2PView* xv = nullptr, unsigned long long* pub_key = nullptr) {
     Slot& s = ctx->slots[slot];
-    LinArgs A[2] = {LinArgs{}, LinArgs{}};
-    int n_kinds = 0;
-    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-        KindSlot& ks = s.k[kind];
-        if (!ks.has_records) return ctx->fail(LILI_E_STATE, "linearize: associate first");
-        if (ks.n_q == 0) continue;
-        A[kind] = lin_args_of(ctx, slot, kind);
-        n_kinds++;
-    }
-    const int* ng = s.use_global_counts ? s.global_counts : nullptr;
+    LinArgs A[2];
+    int n_kinds;
+    TRY(lin_kinds(ctx, slot, kind_mask, "linearize", A, &n_kinds));
     FuseTail fz{};
     fz.mode = (ctx->fuse_tail && n_kinds > 0 && !xv) ? (do_gn ? 2 : 1) : 0;     // the exchange across ranks lives in k_reduce_partials
     fz.out = d_out; fz.state = ctx->state(slot); fz.debug = P.debug; fz.pose_src = pa.state;
     fz.part_surf = A[0].partials; fz.nb_surf = A[0].nb; fz.part_edge = A[1].partials; fz.nb_edge = A[1].nb;
-    const FuseTail off{};
-    const size_t lds = lds_linearize(kLinBlock);
     if (n_kinds == 2 && !ctx->merge_kinds) {       // A/B: one launch per kind, the tail on the second
-        FuseTail pub = off;
+        FuseTail pub{};
         if (fz.mode) { pub = fz; pub.mode = 3; }     // publish granules under the same key; the edge launch reduces both kinds
+        const int* ng = s.use_global_counts ? s.global_counts : nullptr;
+        const size_t lds = lds_linearize(kLinBlock);
         hipLaunchKernelGGL(k_linearize, dim3(A[0].nb), dim3(kLinBlock), lds, ctx->stream, A[0], LinArgs{}, pa, P, ctx->state(slot), ng, pub);
         hipLaunchKernelGGL(k_linearize, dim3(A[1].nb), dim3(kLinBlock), lds, ctx->stream, LinArgs{}, A[1], pa, P, ctx->state(slot), ng, fz);
-    } else if (n_kinds > 0) {
-        hipLaunchKernelGGL(k_linearize, dim3(A[0].nb + A[1].nb), dim3(kLinBlock), lds, ctx->stream, A[0], A[1], pa, P, ctx->state(slot), ng, fz);
-    }
-    HIPCHK(hipGetLastError());
-    if (!fz.mode) {
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, fz.part_surf, fz.nb_surf, fz.part_edge, fz.nb_edge, d_out, ctx->state(slot), (do_gn ? 1 : 0) | (P.debug & 256),
-                           xv ? *xv : P2PView{}, (pub_key && do_gn) ? *pub_key : 0ull, ctx->pub_of(slot), do_gn ? ctx->take_state_mirror(slot) : nullptr, pa.state);
         HIPCHK(hipGetLastError());
+    } else {
+        TRY(launch_linearize_merged(ctx, slot, A, n_kinds, pa, P, fz));      // (fz.mode 0: launch_linearize_only's launch)
+    }
+    if (!fz.mode) {     // the plain site: the slot's publish buffer, the mirror only where the launch updates the pose
+        TRY(launch_reduce_partials(ctx, slot, fz.part_surf, fz.nb_surf, fz.part_edge, fz.nb_edge, d_out, (do_gn ? 1 : 0) | (P.debug & 256), pa, do_gn != 0,
+                                   xv ? *xv : P2PView{}, (pub_key && do_gn) ? *pub_key : 0ull, ctx->pub_of(slot)));
     } else if (pub_key) *pub_key = 0ull;
     if (pub_key && !do_gn) *pub_key = 0ull;
+    return LILI_OK;
+}
+
+// One slot's entry of a WindowArgs, what k_window_reduce / k_window_counts / k_window_gn read of it: its state and, for the kinds in the mask that have queries,
+// where the block partials of its linearisation land and the per-block counts of its last association.  `gather` (the slot-per-rank window): no count pointers and
+// the slot's global-count flags cleared — the owner's count IS the global one; a slot this rank does not own (`owned` false) contributes its state alone: a zero
+// record from this rank (k_window_reduce sums nothing).
+static int window_slot(lili_ctx* ctx, int slot, int kind_mask, bool owned, bool gather, const char* who, WindowSlot& ws) {
+    ws.state = ctx->state(slot);
+    if (!owned) return LILI_OK;
+    Slot& sl = ctx->slots[slot];
+    if (gather) { sl.use_global_counts = false; sl.sticky_global_counts = false; }
+    LinArgs A[2];      // (what k_linearize gets for the slot: the partials land where it writes them)
+    int n_kinds;
+    TRY(lin_kinds(ctx, slot, kind_mask, who, A, &n_kinds, gather ? ": associate the owned keyframes first" : ": associate first"));
+    ws.part_surf = A[0].partials; ws.nb_surf = A[0].nb; ws.part_edge = A[1].partials; ws.nb_edge = A[1].nb;
+    if (gather) return LILI_OK;
+    if (A[0].n_q > 0) { ws.bc_surf = sl.k[0].block_counts.as<int>(); ws.nbc_surf = A[0].n_bc; }      // the slot's own counts, global counts in use or not
+    if (A[1].n_q > 0) { ws.bc_edge = sl.k[1].block_counts.as<int>(); ws.nbc_edge = A[1].n_bc; }
+    return LILI_OK;
+}
+// the checked slot list of a window call as kernel arguments; `who`: the entry point's name
+static int window_args(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, WindowArgs& w, const char* who) {
+    TRY(check_kind_mask(ctx, kind_mask, who));
+    TRY(check_slot_list(ctx, slots, n_slots, who));
+    w = WindowArgs{};
+    w.n = n_slots;
+    for (int i = 0; i < n_slots; i++) TRY(window_slot(ctx, slots[i], kind_mask, true, false, who, w.s[i]));
     return LILI_OK;
 }
 
@@ -554,7 +608,6 @@ int lili_s2m_associate(lili_ctx* ctx, int slot, int kind, const double t_assoc[3
     return LILI_OK;
 }
 
-static int window_args(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, WindowArgs& w, const char* who);
 // Association of SEVERAL slots in one call (the keyframes of the sliding window, L/src/BackendFusion.cpp:919-936: findCorrespondingSurfFeatures +
 // findCorrespondingCornerFeatures per keyframe): both kinds of a slot share a launch where possible, the slots run on forked streams, the
 // correspondence counts come back in ONE synchronisation.  Results are those of lili_s2m_associate per slot and kind.
@@ -566,23 +619,15 @@ int lili_s2m_associate_window(lili_ctx* ctx, const int* slots, int n_slots, int 
     ARGCHK(t_assoc && q_assoc && params, "associate_window: null argument");
     TRY(check_slot_list(ctx, slots, n_slots, "associate_window"));      // (the launches below index the slots: not left to window_args)
     HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t main_stream = ctx->stream;
     const MatchParams P = to_device_params(params);
     int rc = launch_associate_coop_window(ctx, slots, n_slots, kind_mask, t_assoc, q_assoc, P);      // every keyframe in ONE launch where the cooperative kernel applies
     const bool one_launch = rc == LILI_OK;
     if (rc != LILI_OK && rc != 1) return rc;
     rc = LILI_OK;
-    if (!one_launch) {
-        HIPCHK(ctx->fork_ev.get());
-        HIPCHK(hipEventRecord(ctx->fork_ev, ctx->stream));
-    }
+    ForkJoin fj(ctx->stream, ctx->fork_ev, ctx->side, ctx->join_ev);      // (ctx->stream is a side stream only between fork(i) and join(i))
+    if (!one_launch) HIPCHK(fj.begin());
     for (int i = 0; i < n_slots && rc == LILI_OK && !one_launch; i++) {
-        if (i > 0) {
-            HIPCHK(ctx->side[i].get());
-            HIPCHK(ctx->join_ev[i].get());
-            HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->fork_ev, 0));
-            ctx->stream = ctx->side[i];
-        }
+        HIPCHK(fj.fork(i));
         const PoseArg pa = pose_at(t_assoc + 3 * i, q_assoc + 4 * i);
         ctx->slots[slots[i]].use_global_counts = false; ctx->slots[slots[i]].sticky_global_counts = false;
         rc = launch_associate_coop(ctx, slots[i], kind_mask, pa, P, false, nullptr);
@@ -591,15 +636,8 @@ int lili_s2m_associate_window(lili_ctx* ctx, const int* slots, int n_slots, int 
             rc = LILI_OK;
             for (int kind = 0; kind < 2 && rc == LILI_OK; kind++) if (kind_mask & (1 << kind)) rc = launch_associate(ctx, slots[i], kind, pa, P);
         }
-        hipError_t e = hipSuccess;
-        if (i > 0) {
-            e = hipEventRecord(ctx->join_ev[i], ctx->side[i]);
-            ctx->stream = main_stream;
-            if (e == hipSuccess) e = hipStreamWaitEvent(main_stream, ctx->join_ev[i], 0);
-        }
-        if (e != hipSuccess) { ctx->stream = main_stream; return ctx->fail(LILI_E_HIP, std::string("associate_window: ") + hipGetErrorString(e)); }
+        HIPCHK(fj.join(i));      // (whatever rc: the branch's launches are joined before the call synchronises and reports)
     }
-    ctx->stream = main_stream;
     if (rc != LILI_OK) { HIPCHK(hipStreamSynchronize(ctx->stream)); return rc; }      // nothing of this call stays in flight
     if (n_res) {
         // the counts of every slot in ONE launch (k_window_counts: [surf, edge] per slot, also left in the slots' states) and ONE read-back
@@ -621,33 +659,20 @@ int lili_s2m_associate_window(lili_ctx* ctx, const int* slots, int n_slots, int 
     return LILI_OK;
 }
 
-// Linearisation of SEVERAL slots in one call (one evaluation of the joint sliding window: a Gram per keyframe, L/src/BackendFusion.cpp:919-980 under
-// ceres::Solve's up to 15 evaluations; the body of lili::LidarWindowFactor::Evaluate in include/lili_ceres_adapter.h).  Round 4: TWO launches and
-// ONE read-back whatever the number of keyframes — k_linearize_window (every slot's records, the slot in the block index), k_window_reduce (every
-// slot's block partials -> n x 72 doubles), one copy through the page-locked scratch, one synchronisation.  It was three forked streams, three
-// event pairs, 2 n launches and n copies (80 us per 3-keyframe evaluation against 29 us for one keyframe alone).  Results are those of
-// lili_s2m_linearize per slot, bit for bit (same bodies, same block geometry, the additions of reduce_partials_block in the same order).
-static int linearize_window_impl(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const double* t, const double* q,
-                                 lili_allreduce_fn allreduce, void* comm, double* d_gram, int do_gn);
-int lili_s2m_linearize_window(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const double* t /*3 per slot*/, const double* q /*4 per slot*/,
-                              const lili_s2m_params* params, double* gram /*64 per slot*/, double* cost /*1 per slot, optional*/, int* counts /*2 per slot, optional*/) {
-    if (!ctx) return LILI_E_ARG;
-    ARGCHK(slots && n_slots >= 1 && n_slots <= LILI_MAX_SLOTS, "linearize_window: 1..LILI_MAX_SLOTS slots");
-    TRY(check_kind_mask(ctx, kind_mask, "linearize_window"));
-    ARGCHK(t && q && params && gram, "linearize_window: null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    TRY(ensure_h_records(ctx));
-    if (!ctx->h_records.dev()) HIPCHK(ctx->win_rec.ensure(sizeof(double) * LILI_GRAM_DOUBLES * LILI_MAX_SLOTS));
-    const Landing land{ctx, 0, ctx->win_rec.p};      // k_window_reduce writes the n records
-    TRY(linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, nullptr, nullptr, land.dev<double>(), 0));
-    double host[LILI_GRAM_DOUBLES * LILI_MAX_SLOTS];
-    TRY(land.fetch(host, sizeof(double) * LILI_GRAM_DOUBLES * n_slots));
-    for (int i = 0; i < n_slots; i++) {
-        const double* h = host + (size_t)i * LILI_GRAM_DOUBLES;
+// n records as the kernels leave them on the host (LILI_GRAM_DOUBLES each: the 8 x 8 Gram, the cost, the surf and the edge count) -> the caller's arrays
+static void records_out(const double* h, int n, double* gram, double* cost, int* counts) {
+    for (int i = 0; i < n; i++, h += LILI_GRAM_DOUBLES) {
         std::memcpy(gram + (size_t)64 * i, h, 64 * sizeof(double));
         if (cost) cost[i] = h[64];
         if (counts) { counts[2 * i] = (int)h[65]; counts[2 * i + 1] = (int)h[66]; }
     }
+}
+// the same for n records in the caller's device buffer: one copy through the page-locked landing area, one synchronisation
+static int records_from_device(lili_ctx* ctx, const double* d_gram, int n, double* gram, double* cost, int* counts) {
+    TRY(ensure_h_records(ctx));
+    HIPCHK(hipMemcpyAsync(ctx->h_records.p, d_gram, (size_t)n * LILI_GRAM_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    records_out(ctx->h_records.as<double>(), n, gram, cost, counts);
     return LILI_OK;
 }
 
@@ -664,9 +689,7 @@ int lili_s2m_linearize(lili_ctx* ctx, int slot, int kind_mask, const double t[3]
     TRY(launch_linearize_reduce(ctx, slot, kind_mask, pose_at(t, q), P, land.dev<double>(), 0));
     double host[LILI_GRAM_DOUBLES];
     TRY(land.fetch(host, sizeof(host)));
-    std::memcpy(gram, host, 64 * sizeof(double));
-    if (cost) *cost = host[64];
-    if (counts) { counts[0] = (int)host[65]; counts[1] = (int)host[66]; }
+    records_out(host, 1, gram, cost, counts);
     return LILI_OK;
 }
 
@@ -810,11 +833,9 @@ int lili_s2m_debug_times(lili_ctx* ctx, int slot, long long out[16]) {
     return LILI_OK;
 }
 
-static int associate_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, unsigned long long wait_key, int pose_slot = -1);
-int lili_s2m_associate_dev(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params) { return associate_dev_impl(ctx, slot, kind_mask, params, 0ull); }
 // wait_key != 0 (iterate_impl, option "overlap_gn"): the launch carries no barrier against the reduction + GN kernel enqueued right before it and takes the pose from
 // the granules that kernel publishes (load_assoc_pose / wait_published_pose)
-static int associate_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, unsigned long long wait_key, int pose_slot) {
+static int associate_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, unsigned long long wait_key, int pose_slot = -1) {
     if (!ctx) return LILI_E_ARG;
     TRY(check_slot(ctx, slot, "associate_dev"));
     TRY(check_kind_mask(ctx, kind_mask, "associate_dev"));
@@ -834,12 +855,10 @@ static int associate_dev_impl(lili_ctx* ctx, int slot, int kind_mask, const lili
         int rc = launch_associate_both(ctx, slot, pa, P);
         if (rc != 1) return rc;     // 1 = not eligible: one launch per kind below
     }
-    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-        int rc = launch_associate(ctx, slot, kind, pa, P);
-        if (rc != LILI_OK) return rc;
-    }
+    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) TRY(launch_associate(ctx, slot, kind, pa, P));
     return LILI_OK;
 }
+int lili_s2m_associate_dev(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params) { return associate_dev_impl(ctx, slot, kind_mask, params, 0ull); }
 
 int lili_s2m_counts_export(lili_ctx* ctx, int slot, int32_t* d_counts) {
     if (!ctx) return LILI_E_ARG;
@@ -882,10 +901,7 @@ int lili_s2m_iterate_inner(lili_ctx* ctx, int slot, int kind_mask, const lili_s2
     if (!ctx) return LILI_E_ARG;
     ARGCHK(n_iters >= 0, "iterate_inner: negative n_iters");
     TRY(check_slot(ctx, slot, "iterate_inner"));
-    for (int it = 0; it < n_iters; it++) {
-        int rc = linearize_dev_impl(ctx, slot, kind_mask, params, ctx->gram_of(slot), 1, want_cost);
-        if (rc != LILI_OK) return rc;
-    }
+    for (int it = 0; it < n_iters; it++) TRY(linearize_dev_impl(ctx, slot, kind_mask, params, ctx->gram_of(slot), 1, want_cost));
     return LILI_OK;
 }
 
@@ -909,17 +925,14 @@ static int launch_solve_lm(lili_ctx* ctx, int slot, int kind_mask, const lili_s2
     TRY(lm_options_checked(ctx, "solve_lm", options, &opt));
     Slot& sl = ctx->slots[slot];
     LmArgs a{};
-    int64_t n_all = 0;
-    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-        KindSlot& ks = sl.k[kind];
-        if (!ks.has_records) return ctx->fail(LILI_E_STATE, "solve_lm: associate first");
-        if (ks.n_q == 0) continue;
-        LinArgs A = lin_args_of(ctx, slot, kind);
-        A.block_counts = ks.block_counts.as<int>(); A.partials = nullptr;
-        (kind == 0 ? a.S : a.E) = A;
-        n_all += ks.n_q;
+    LinArgs A[2];
+    int n_kinds;
+    TRY(lin_kinds(ctx, slot, kind_mask, "solve_lm", A, &n_kinds));
+    if (n_kinds == 0) return ctx->fail(LILI_E_STATE, "solve_lm: no records");
+    for (int kind = 0; kind < 2; kind++) if (A[kind].n_q > 0) {      // always the slot's own counts; the launch keeps its partials in lm_part
+        A[kind].block_counts = sl.k[kind].block_counts.as<int>(); A[kind].partials = nullptr;
     }
-    if (n_all == 0) return ctx->fail(LILI_E_STATE, "solve_lm: no records");
+    a.S = A[0]; a.E = A[1];
     // workgroups: 512 records each, split between the kinds in proportion, at most max_blocks in total (a kind that is present gets at least one)
     const int want_s = a.S.n_q > 0 ? nblocks(a.S.n_q, kLmThreads) : 0, want_e = a.E.n_q > 0 ? nblocks(a.E.n_q, kLmThreads) : 0;
     int nb_s = want_s, nb_e = want_e;
@@ -958,8 +971,7 @@ int lili_s2m_solve_lm(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_par
     if (!ctx) return LILI_E_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     const int max_blocks = std::max(1, std::min(ctx->n_simd / 4 - 16, 240));     // one workgroup per CU, a few CUs left to whatever else runs
-    int rc = launch_solve_lm(ctx, slot, kind_mask, params, options, max_blocks);
-    if (rc != LILI_OK) return rc;
+    TRY(launch_solve_lm(ctx, slot, kind_mask, params, options, max_blocks));
     if (summary) TRY(lili_readback_now(ctx, summary, ctx->slots[slot].lm_summary.p, sizeof(lili_lm_summary)));
     return LILI_OK;
 }
@@ -975,8 +987,7 @@ int lili_s2m_solve_lm_window(lili_ctx* ctx, const int* slots, int n_slots, int k
     W.n = n_slots;
     int nb = 0;
     for (int i = 0; i < n_slots; i++) {
-        const int rc = launch_solve_lm(ctx, slots[i], kind_mask, params, options, max_blocks, &W.a[i]);
-        if (rc != LILI_OK) return rc;
+        TRY(launch_solve_lm(ctx, slots[i], kind_mask, params, options, max_blocks, &W.a[i]));
         W.first_block[i] = nb;
         nb += W.a[i].nb;
     }
@@ -992,8 +1003,7 @@ int lili_s2m_solve_lm_window(lili_ctx* ctx, const int* slots, int n_slots, int k
 }
 
 int lili_s2m_accumulate(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, double* d_gram) {
-    int rc = lili_s2m_associate_dev(ctx, slot, kind_mask, params);
-    if (rc != LILI_OK) return rc;
+    TRY(lili_s2m_associate_dev(ctx, slot, kind_mask, params));
     return lili_s2m_linearize_dev(ctx, slot, kind_mask, params, d_gram);
 }
 
@@ -1017,12 +1027,12 @@ int lili_s2m_pose_copy(lili_ctx* ctx, int dst_slot, int src_slot) {
     return LILI_OK;
 }
 
-// n_iters outer iterations; if restart_every > 0 the pose of `slot` is re-initialised from `restart_slot` before
-// iterations 0, restart_every, 2*restart_every, ... — "one registration = restart_every GN iterations".  No copy launch: the
-// kernels of such an iteration read the pose from the restart slot's state, and its reduction + GN kernel writes the updated
-// pose (the restart pose itself if the step is rejected) into the slot's own state (only the persistent launch of small scans,
-// which reads its own slot, is still preceded by k_pose_copy).  If assoc_ms is non-NULL the association launches are bracketed by HIP events on the context's
-// stream and their total duration is returned (this variant synchronises at the end).
+// the library's own exchange if `allreduce` / `comm` name one that can be folded into the kernels (*out, else null); false: that communicator has failed
+static bool p2p_comm(lili_ctx* ctx, lili_allreduce_fn allreduce, void* comm, lili_p2p** out) {
+    *out = (allreduce == &lili_p2p_allreduce && lili_p2p_usable(reinterpret_cast<lili_p2p*>(comm), ctx) && !ctx->no_p2p_fusion) ? reinterpret_cast<lili_p2p*>(comm) : nullptr;
+    return !(allreduce == &lili_p2p_allreduce && comm && lili_p2p_status(reinterpret_cast<lili_p2p*>(comm)) != 0);
+}
+
 // one outer iteration through k_associate_lin (see launch_associate_lin_reduce); 1 = not eligible
 static int iterate_fused_lin(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, int pose_slot) {
     if (!ctx->fuse_lin) return 1;
@@ -1030,6 +1040,12 @@ static int iterate_fused_lin(lili_ctx* ctx, int slot, int kind_mask, const lili_
     P.no_cost = 1;             // the record stays inside the library, only the GN step is used
     return launch_associate_lin_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot, params, pose_slot), P, ctx->gram_of(slot));
 }
+// n_iters outer iterations; if restart_every > 0 the pose of `slot` is re-initialised from `restart_slot` before
+// iterations 0, restart_every, 2*restart_every, ... — "one registration = restart_every GN iterations".  No copy launch: the
+// kernels of such an iteration read the pose from the restart slot's state, and its reduction + GN kernel writes the updated
+// pose (the restart pose itself if the step is rejected) into the slot's own state (only the persistent launch of small scans,
+// which reads its own slot, is still preceded by k_pose_copy).  If assoc_ms is non-NULL the association launches are bracketed by HIP events on the context's
+// stream and their total duration is returned (this variant synchronises at the end).
 static int iterate_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, int n_iters, int restart_every, int restart_slot, float* assoc_ms) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(n_iters >= 0, "iterate: negative n_iters");
@@ -1063,16 +1079,14 @@ static int iterate_impl(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_p
             if (rc2 != 1) return rc2;
         }
         if (assoc_ms) HIPCHK(hipEventRecord(ev[2 * it], ctx->stream));
-        int rc = associate_dev_impl(ctx, slot, kind_mask, params, wait_key, pose_slot);
-        if (rc != LILI_OK) return rc;
+        TRY(associate_dev_impl(ctx, slot, kind_mask, params, wait_key, pose_slot));
         if (assoc_ms) HIPCHK(hipEventRecord(ev[2 * it + 1], ctx->stream));
         // Round 5, "overlap_gn": when the NEXT thing on the stream is this slot's next association, the reduction + GN kernel publishes the new pose as keyed granules and
         // that association is launched WITHOUT a barrier against it: its 3 125 waves are dispatched, load their queries and poll for the pose while the one-workgroup
         // reduction still runs — two barriers and one flag hop per iteration instead of three barriers.  Keys never repeat within a context.
         unsigned long long pub_key = 0ull;
         if (ctx->overlap_gn && !assoc_ms && it + 1 < n_iters && !(restart_every > 0 && (it + 1) % restart_every == 0)) pub_key = (++ctx->gn_seq) * 0x9E3779B97F4A7C15ull;
-        rc = linearize_dev_impl(ctx, slot, kind_mask, params, ctx->gram_of(slot), 1, 0, &pub_key, pose_slot);
-        if (rc != LILI_OK) return rc;
+        TRY(linearize_dev_impl(ctx, slot, kind_mask, params, ctx->gram_of(slot), 1, 0, &pub_key, pose_slot));
         wait_key = pub_key;
     }
     ctx->state_mirror_armed = false;      // (a path without a reduction + GN kernel has not taken it)
@@ -1093,39 +1107,37 @@ int lili_s2m_iterate_sharded(lili_ctx* ctx, int slot, int kind_mask, const lili_
     const bool count_scaled = params->scale_surf_num > 0 || params->scale_edge_num > 0;   // ROT: residual scale = num / GLOBAL count
     // The library's own peer-to-peer exchange (lili_p2p_allreduce) is folded INTO the count kernel and INTO the partial-reduction /
     // Gauss-Newton kernel: 4 launches per iteration (associate, counts + exchange, linearise, reduce + exchange + GN) instead of 7.
-    lili_p2p* p2p = (allreduce == &lili_p2p_allreduce && lili_p2p_usable(reinterpret_cast<lili_p2p*>(comm), ctx) && !ctx->no_p2p_fusion) ? reinterpret_cast<lili_p2p*>(comm) : nullptr;
-    // a communicator on which an exchange has given up is dead for good (its ranks no longer hold the same pose): refuse, loudly
-    if (allreduce == &lili_p2p_allreduce && comm && lili_p2p_status(reinterpret_cast<lili_p2p*>(comm)) != 0)
+    // A communicator on which an exchange has given up is dead for good (its ranks no longer hold the same pose): refuse, loudly
+    lili_p2p* p2p = nullptr;
+    if (!p2p_comm(ctx, allreduce, comm, &p2p))
         return ctx->fail(LILI_E_STATE, "iterate_sharded: the lili_p2p communicator has failed (a peer's record did not arrive within its timeout); SlotState gn_status is 2 on the ranks that noticed");
     for (int it = 0; it < n_iters; it++) {
-        int rc;
         const bool restart = restart_every > 0 && it % restart_every == 0;
         const int pose_slot = restart ? restart_slot : slot;      // (as in iterate_impl: no copy launch)
         if (restart) { TRY(check_slot(ctx, slot, "iterate_sharded")); ctx->slots[slot].assoc_since_pose = 0; }
-        if ((rc = associate_dev_impl(ctx, slot, kind_mask, params, 0ull, pose_slot)) != LILI_OK) return rc;
+        TRY(associate_dev_impl(ctx, slot, kind_mask, params, 0ull, pose_slot));
         if (p2p) {
-            ARGCHK(slot >= 0 && slot < LILI_MAX_SLOTS && (kind_mask & ~3) == 0 && kind_mask != 0, "iterate_sharded: bad slot / kind mask");
             if (count_scaled) {
                 const P2PView v = lili_p2p_next_view(p2p);
-                if ((rc = launch_sum_counts(ctx, slot, LILI_MASK_SURF | LILI_MASK_EDGE, d_counts, &v)) != LILI_OK) return rc;
-                if ((rc = lili_s2m_counts_import(ctx, slot, d_counts)) != LILI_OK) return rc;
+                TRY(launch_sum_counts(ctx, slot, LILI_MASK_SURF | LILI_MASK_EDGE, d_counts, &v));
+                TRY(lili_s2m_counts_import(ctx, slot, d_counts));
             }
             const MatchParams P = to_device_params(params);
             const P2PView v = lili_p2p_next_view(p2p);
-            if ((rc = launch_linearize_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot, nullptr, pose_slot), P, d_gram, 1, &v)) != LILI_OK) return rc;
+            TRY(launch_linearize_reduce(ctx, slot, kind_mask, pose_of_slot(ctx, slot, nullptr, pose_slot), P, d_gram, 1, &v));
             ctx->slots[slot].use_global_counts = false;
             continue;
         }
         if (count_scaled) {
-            if ((rc = lili_s2m_counts_export(ctx, slot, d_counts)) != LILI_OK) return rc;
+            TRY(lili_s2m_counts_export(ctx, slot, d_counts));
             if (allreduce && allreduce(d_counts, d_counts, 2, /*ncclInt32*/ 2, /*ncclSum*/ 0, comm, (void*)ctx->stream) != 0)
                 return ctx->fail(LILI_E_HIP, "iterate_sharded: all-reduce of the correspondence counts failed");
-            if ((rc = lili_s2m_counts_import(ctx, slot, d_counts)) != LILI_OK) return rc;
+            TRY(lili_s2m_counts_import(ctx, slot, d_counts));
         }
-        if ((rc = linearize_dev_impl(ctx, slot, kind_mask, params, d_gram, 0, 0, nullptr, pose_slot)) != LILI_OK) return rc;
+        TRY(linearize_dev_impl(ctx, slot, kind_mask, params, d_gram, 0, 0, nullptr, pose_slot));
         if (allreduce && allreduce(d_gram, d_gram, LILI_GRAM_DOUBLES, /*ncclFloat64*/ 8, /*ncclSum*/ 0, comm, (void*)ctx->stream) != 0)
             return ctx->fail(LILI_E_HIP, "iterate_sharded: all-reduce of the Gram record failed");
-        if ((rc = gn_update_impl(ctx, slot, d_gram, pose_slot)) != LILI_OK) return rc;
+        TRY(gn_update_impl(ctx, slot, d_gram, pose_slot));
     }
     return LILI_OK;
 }
@@ -1133,44 +1145,6 @@ int lili_s2m_iterate_sharded(lili_ctx* ctx, int slot, int kind_mask, const lili_
 // --------------------------------------------------------------------------------------------
 // the sliding window across ranks (BASELINE configs[4])
 // --------------------------------------------------------------------------------------------
-static int window_args(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, WindowArgs& w, const char* who) {
-    ARGCHK(slots && n_slots >= 1 && n_slots <= LILI_MAX_SLOTS, std::string(who) + ": 1..LILI_MAX_SLOTS slots");
-    TRY(check_kind_mask(ctx, kind_mask, who));
-    TRY(check_slot_list(ctx, slots, n_slots, who));
-    w = WindowArgs{};
-    w.n = n_slots;
-    for (int i = 0; i < n_slots; i++) {
-        Slot& sl = ctx->slots[slots[i]];
-        WindowSlot& ws = w.s[i];
-        ws.state = ctx->state(slots[i]);
-        for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-            KindSlot& ks = sl.k[kind];
-            if (!ks.has_records) return ctx->fail(LILI_E_STATE, std::string(who) + ": associate first");
-            if (ks.n_q == 0) continue;
-            if (kind == 0) { ws.part_surf = ks.partials.as<double>(); ws.nb_surf = ks.n_lin_blocks; ws.bc_surf = ks.block_counts.as<int>(); ws.nbc_surf = ks.n_assoc_blocks; }
-            else { ws.part_edge = ks.partials.as<double>(); ws.nb_edge = ks.n_lin_blocks; ws.bc_edge = ks.block_counts.as<int>(); ws.nbc_edge = ks.n_assoc_blocks; }
-        }
-    }
-    return LILI_OK;
-}
-// k_linearize of one slot at `pa`, block partials left in the slot's buffers (no reduction): the first half of launch_linearize_reduce
-static int launch_linearize_only(lili_ctx* ctx, int slot, int kind_mask, const PoseArg& pa, const MatchParams& P) {
-    Slot& s = ctx->slots[slot];
-    LinArgs A[2] = {LinArgs{}, LinArgs{}};
-    int n_kinds = 0;
-    for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-        KindSlot& ks = s.k[kind];
-        if (!ks.has_records) return ctx->fail(LILI_E_STATE, "linearize: associate first");
-        if (ks.n_q == 0) continue;
-        A[kind] = lin_args_of(ctx, slot, kind);
-        n_kinds++;
-    }
-    if (n_kinds == 0) return LILI_OK;
-    const int* ng = s.use_global_counts ? s.global_counts : nullptr;
-    hipLaunchKernelGGL(k_linearize, dim3(A[0].nb + A[1].nb), dim3(kLinBlock), lds_linearize(kLinBlock), ctx->stream, A[0], A[1], pa, P, ctx->state(slot), ng, FuseTail{});
-    HIPCHK(hipGetLastError());
-    return LILI_OK;
-}
 // k_linearize of EVERY slot of a window in ONE launch (k_linearize_window), block partials left in the slots' buffers.  t / q: 3 / 4 doubles per
 // slot (host poses), or both null for the slots' device poses.  Bit-identical to launch_linearize_only slot by slot (same bodies, same block geometry).
 static int launch_linearize_window(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const double* t, const double* q, const MatchParams& P) {
@@ -1183,15 +1157,11 @@ static int launch_linearize_window(lili_ctx* ctx, const int* slots, int n_slots,
         Slot& s = ctx->slots[slots[i]];
         WinLinSlot& ws = W.s[W.n];
         ws = WinLinSlot{};
-        int n_kinds = 0;
-        for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-            KindSlot& ks = s.k[kind];
-            if (!ks.has_records) return ctx->fail(LILI_E_STATE, "linearize: associate first");
-            if (ks.n_q == 0) continue;
-            (kind == 0 ? ws.S : ws.E) = lin_args_of(ctx, slots[i], kind);
-            n_kinds++;
-        }
-        if (n_kinds == 0) continue;             // nothing to linearise for this slot: k_window_reduce sees nb = 0 and writes a zero record
+        LinArgs A[2];
+        int n_kinds;
+        TRY(lin_kinds(ctx, slots[i], kind_mask, "linearize", A, &n_kinds));
+        ws.S = A[0]; ws.E = A[1];
+        if (n_kinds == 0) continue;            // nothing to linearise for this slot: k_window_reduce sees nb = 0 and writes a zero record
         ws.pa = t && q ? pose_at(t + 3 * i, q + 4 * i) : pose_of_slot(ctx, slots[i]);
         ws.state = ctx->state(slots[i]);
         ws.n_global = s.use_global_counts ? s.global_counts : nullptr;
@@ -1204,9 +1174,17 @@ static int launch_linearize_window(lili_ctx* ctx, const int* slots, int n_slots,
     HIPCHK(hipGetLastError());
     return LILI_OK;
 }
-static bool p2p_comm(lili_ctx* ctx, lili_allreduce_fn allreduce, void* comm, lili_p2p** out) {
-    *out = (allreduce == &lili_p2p_allreduce && lili_p2p_usable(reinterpret_cast<lili_p2p*>(comm), ctx) && !ctx->no_p2p_fusion) ? reinterpret_cast<lili_p2p*>(comm) : nullptr;
-    return !(allreduce == &lili_p2p_allreduce && comm && lili_p2p_status(reinterpret_cast<lili_p2p*>(comm)) != 0);      // false: the communicator has failed
+// The tail of a window evaluation: k_window_reduce — every slot's block partials -> n x LILI_GRAM_DOUBLES in d_gram, with the exchange across ranks (p2p, or none: one
+// rank) and the Gauss-Newton update of every slot inside the launch — or, where the exchange is the caller's all-reduce, that call and k_window_gn behind it.
+static int launch_window_tail(lili_ctx* ctx, const WindowArgs& w, lili_p2p* p2p, lili_allreduce_fn allreduce, void* comm, double* d_gram, int do_gn, const char* who) {
+    const bool in_kernel = p2p != nullptr || allreduce == nullptr;
+    hipLaunchKernelGGL(k_window_reduce, dim3(1), dim3(1024), 0, ctx->stream, w, d_gram, (do_gn && in_kernel) ? 1 : 0, p2p ? lili_p2p_next_view(p2p) : P2PView{});
+    HIPCHK(hipGetLastError());
+    if (in_kernel) return LILI_OK;
+    if (allreduce(d_gram, d_gram, (size_t)LILI_GRAM_DOUBLES * w.n, /*ncclFloat64*/ 8, /*ncclSum*/ 0, comm, (void*)ctx->stream) != 0)
+        return ctx->fail(LILI_E_HIP, std::string(who) + ": all-reduce of the Gram records failed");
+    if (do_gn) { hipLaunchKernelGGL(k_window_gn, dim3(1), dim3(64), 0, ctx->stream, w, (const double*)d_gram); HIPCHK(hipGetLastError()); }
+    return LILI_OK;
 }
 
 // The correspondence counts of every slot, summed over the ranks in ONE exchange of 2 n int32, into d_counts ([surf, edge] per slot, DEVICE,
@@ -1217,8 +1195,7 @@ int lili_s2m_counts_window_sharded(lili_ctx* ctx, const int* slots, int n_slots,
     ARGCHK(d_counts, "counts_window_sharded: null d_counts");
     HIPCHK(hipSetDevice(ctx->device));
     WindowArgs w;
-    int rc = window_args(ctx, slots, n_slots, kind_mask, w, "counts_window_sharded");
-    if (rc != LILI_OK) return rc;
+    TRY(window_args(ctx, slots, n_slots, kind_mask, w, "counts_window_sharded"));
     lili_p2p* p2p = nullptr;
     if (!p2p_comm(ctx, allreduce, comm, &p2p)) return ctx->fail(LILI_E_STATE, "counts_window_sharded: the lili_p2p communicator has failed");
     hipLaunchKernelGGL(k_window_counts, dim3(1), dim3(kBlock), 0, ctx->stream, w, d_counts, p2p ? lili_p2p_next_view(p2p) : P2PView{});
@@ -1231,24 +1208,17 @@ int lili_s2m_counts_window_sharded(lili_ctx* ctx, const int* slots, int n_slots,
 
 // ONE evaluation of the joint window on the device: every slot linearised at its device pose (this rank's shard of its records), the
 // n x LILI_GRAM_DOUBLES records reduced in one launch and summed over the ranks in ONE exchange into d_gram (DEVICE, caller-owned).  Async.
+// `who`: the entry point's name, the head of its messages.
 static int linearize_window_impl(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const double* t, const double* q,
-                                 lili_allreduce_fn allreduce, void* comm, double* d_gram, int do_gn) {
+                                 lili_allreduce_fn allreduce, void* comm, double* d_gram, int do_gn, const char* who) {
     WindowArgs w;
-    int rc = window_args(ctx, slots, n_slots, kind_mask, w, "linearize_window_sharded");
-    if (rc != LILI_OK) return rc;
+    TRY(window_args(ctx, slots, n_slots, kind_mask, w, who));
     lili_p2p* p2p = nullptr;
-    if (!p2p_comm(ctx, allreduce, comm, &p2p)) return ctx->fail(LILI_E_STATE, "linearize_window_sharded: the lili_p2p communicator has failed");
+    if (!p2p_comm(ctx, allreduce, comm, &p2p)) return ctx->fail(LILI_E_STATE, std::string(who) + ": the lili_p2p communicator has failed");
     MatchParams P = to_device_params(params);
     if (do_gn) P.no_cost = 1;
-    if ((rc = launch_linearize_window(ctx, slots, n_slots, kind_mask, t, q, P)) != LILI_OK) return rc;
-    const bool in_kernel = p2p != nullptr || allreduce == nullptr;        // exchange (or none: one rank) and GN inside the reduction launch
-    hipLaunchKernelGGL(k_window_reduce, dim3(1), dim3(1024), 0, ctx->stream, w, d_gram, (do_gn && in_kernel) ? 1 : 0, p2p ? lili_p2p_next_view(p2p) : P2PView{});
-    HIPCHK(hipGetLastError());
-    if (!in_kernel) {
-        if (allreduce(d_gram, d_gram, (size_t)LILI_GRAM_DOUBLES * n_slots, /*ncclFloat64*/ 8, /*ncclSum*/ 0, comm, (void*)ctx->stream) != 0)
-            return ctx->fail(LILI_E_HIP, "linearize_window_sharded: all-reduce of the Gram records failed");
-        if (do_gn) { hipLaunchKernelGGL(k_window_gn, dim3(1), dim3(64), 0, ctx->stream, w, (const double*)d_gram); HIPCHK(hipGetLastError()); }
-    }
+    TRY(launch_linearize_window(ctx, slots, n_slots, kind_mask, t, q, P));
+    TRY(launch_window_tail(ctx, w, p2p, allreduce, comm, d_gram, do_gn, who));
     for (int i = 0; i < n_slots; i++) if (!ctx->slots[slots[i]].sticky_global_counts) ctx->slots[slots[i]].use_global_counts = false;
     return LILI_OK;
 }
@@ -1257,7 +1227,27 @@ int lili_s2m_linearize_window_dev(lili_ctx* ctx, const int* slots, int n_slots, 
     if (!ctx) return LILI_E_ARG;
     ARGCHK(params && d_gram, "linearize_window_dev: null argument");
     HIPCHK(hipSetDevice(ctx->device));
-    return linearize_window_impl(ctx, slots, n_slots, kind_mask, params, nullptr, nullptr, allreduce, comm, d_gram, 0);
+    return linearize_window_impl(ctx, slots, n_slots, kind_mask, params, nullptr, nullptr, allreduce, comm, d_gram, 0, "linearize_window_dev");
+}
+// Linearisation of SEVERAL slots in one call (one evaluation of the joint sliding window: a Gram per keyframe, L/src/BackendFusion.cpp:919-980 under
+// ceres::Solve's up to 15 evaluations; the body of lili::LidarWindowFactor::Evaluate in include/lili_ceres_adapter.h).  Round 4: TWO launches and
+// ONE read-back whatever the number of keyframes — k_linearize_window (every slot's records, the slot in the block index), k_window_reduce (every
+// slot's block partials -> n x 72 doubles), one copy through the page-locked scratch, one synchronisation.  It was three forked streams, three
+// event pairs, 2 n launches and n copies (80 us per 3-keyframe evaluation against 29 us for one keyframe alone).  Results are those of
+// lili_s2m_linearize per slot, bit for bit (same bodies, same block geometry, the additions of reduce_partials_block in the same order).
+int lili_s2m_linearize_window(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const double* t /*3 per slot*/, const double* q /*4 per slot*/,
+                              const lili_s2m_params* params, double* gram /*64 per slot*/, double* cost /*1 per slot, optional*/, int* counts /*2 per slot, optional*/) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(t && q && params && gram, "linearize_window: null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    TRY(ensure_h_records(ctx));
+    if (!ctx->h_records.dev()) HIPCHK(ctx->win_rec.ensure(sizeof(double) * LILI_GRAM_DOUBLES * LILI_MAX_SLOTS));
+    const Landing land{ctx, 0, ctx->win_rec.p};      // k_window_reduce writes the n records
+    TRY(linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, nullptr, nullptr, land.dev<double>(), 0, "linearize_window"));      // (checks the slot list)
+    double host[LILI_GRAM_DOUBLES * LILI_MAX_SLOTS];
+    TRY(land.fetch(host, sizeof(double) * LILI_GRAM_DOUBLES * n_slots));
+    records_out(host, n_slots, gram, cost, counts);
+    return LILI_OK;
 }
 // The same at host-provided poses, blocking, records copied out: what one evaluation of the caller's solver costs on the lidar side when the
 // window is sharded over ranks (every rank calls it with the same poses and gets the same bits).
@@ -1266,18 +1256,8 @@ int lili_s2m_linearize_window_sharded(lili_ctx* ctx, const int* slots, int n_slo
     if (!ctx) return LILI_E_ARG;
     ARGCHK(t && q && params && d_gram && gram, "linearize_window_sharded: null argument");
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, allreduce, comm, d_gram, 0);
-    if (rc != LILI_OK) return rc;
-    { const int rc_h = ensure_h_records(ctx); if (rc_h != LILI_OK) return rc_h; }
-    HIPCHK(hipMemcpyAsync(ctx->h_records.p, d_gram, (size_t)n_slots * LILI_GRAM_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < n_slots; i++) {
-        const double* h = ctx->h_records.as<double>() + (size_t)i * LILI_GRAM_DOUBLES;
-        std::memcpy(gram + (size_t)64 * i, h, 64 * sizeof(double));
-        if (cost) cost[i] = h[64];
-        if (counts) { counts[2 * i] = (int)h[65]; counts[2 * i + 1] = (int)h[66]; }
-    }
-    return LILI_OK;
+    TRY(linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, allreduce, comm, d_gram, 0, "linearize_window_sharded"));
+    return records_from_device(ctx, d_gram, n_slots, gram, cost, counts);
 }
 // n_iters outer iterations of every slot of the window, queries sharded over the ranks: per iteration the slots' associations, ONE exchange
 // of the 2 n counts (count-scaled flavours only), the slots' linearisations, ONE reduction launch ending with ONE exchange of the n x 72
@@ -1287,17 +1267,17 @@ int lili_s2m_iterate_window_sharded(lili_ctx* ctx, const int* slots, int n_slots
                                     lili_allreduce_fn allreduce, void* comm, int32_t* d_counts, double* d_gram) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(n_iters >= 0 && params && d_counts && d_gram, "iterate_window_sharded: bad argument");
+    TRY(check_kind_mask(ctx, kind_mask, "iterate_window_sharded"));
+    TRY(check_slot_list(ctx, slots, n_slots, "iterate_window_sharded"));      // (in front of the first launch)
     HIPCHK(hipSetDevice(ctx->device));
     const bool count_scaled = params->scale_surf_num > 0 || params->scale_edge_num > 0;
     for (int it = 0; it < n_iters; it++) {
-        int rc;
         for (int i = 0; i < n_slots; i++) {
-            ARGCHK(slots && slots[i] >= 0 && slots[i] < LILI_MAX_SLOTS, "iterate_window_sharded: bad slot");
             ctx->slots[slots[i]].sticky_global_counts = false;
-            if ((rc = lili_s2m_associate_dev(ctx, slots[i], kind_mask, params)) != LILI_OK) return rc;
+            TRY(lili_s2m_associate_dev(ctx, slots[i], kind_mask, params));
         }
-        if (count_scaled && (rc = lili_s2m_counts_window_sharded(ctx, slots, n_slots, kind_mask, allreduce, comm, d_counts)) != LILI_OK) return rc;
-        if ((rc = linearize_window_impl(ctx, slots, n_slots, kind_mask, params, nullptr, nullptr, allreduce, comm, d_gram, 1)) != LILI_OK) return rc;
+        if (count_scaled) TRY(lili_s2m_counts_window_sharded(ctx, slots, n_slots, kind_mask, allreduce, comm, d_counts));
+        TRY(linearize_window_impl(ctx, slots, n_slots, kind_mask, params, nullptr, nullptr, allreduce, comm, d_gram, 1, "iterate_window_sharded"));
     }
     return LILI_OK;
 }
@@ -1308,45 +1288,34 @@ int lili_s2m_iterate_window_sharded(lili_ctx* ctx, const int* slots, int n_slots
 // that do not own a keyframe need neither its queries nor its records, only its pose slot (every rank applies the same Gauss-Newton update to the same record).
 // Counts need no exchange: the owner's count IS the global one (ROT residual scale, R/src/BackendFusion.cpp:843,861).  The latency floor of an iteration is the one of a
 // single full-size keyframe (the query-sharded modes shrink the association's throughput part but keep its latency chain — DESIGN §5), and K keyframes advance on K ranks.
+static int check_gather_args(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const int* owner, int rank, const char* who) {
+    TRY(check_slot_list(ctx, slots, n_slots, who));
+    TRY(check_kind_mask(ctx, kind_mask, who));
+    ARGCHK(owner && rank >= 0, std::string(who) + ": bad argument");
+    for (int i = 0; i < n_slots; i++) ARGCHK(owner[i] >= 0, std::string(who) + ": bad owner");
+    return LILI_OK;
+}
 static int window_gather_impl(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const int* owner, int rank,
                               lili_allreduce_fn allreduce, void* comm, double* d_gram, int do_gn, const double* t = nullptr, const double* q = nullptr /* body poses of ALL slots (else the device poses) */) {
-    ARGCHK(slots && n_slots >= 1 && n_slots <= LILI_MAX_SLOTS, "window_gather: 1..LILI_MAX_SLOTS slots");
-    ARGCHK((kind_mask & ~3) == 0 && kind_mask != 0 && owner && rank >= 0, "window_gather: bad argument");
+    TRY(check_gather_args(ctx, slots, n_slots, kind_mask, owner, rank, "window_gather"));
     int mine[LILI_MAX_SLOTS], n_mine = 0;
     double t_mine[3 * LILI_MAX_SLOTS], q_mine[4 * LILI_MAX_SLOTS];
     WindowArgs w{};
     w.n = n_slots;
     for (int i = 0; i < n_slots; i++) {
-        ARGCHK(slots[i] >= 0 && slots[i] < LILI_MAX_SLOTS && owner[i] >= 0, "window_gather: bad slot / owner");
-        for (int k = 0; k < i; k++) ARGCHK(slots[k] != slots[i], "window_gather: duplicate slot");
-        w.s[i].state = ctx->state(slots[i]);
-        if (owner[i] != rank) continue;             // a zero record from this rank: no partials (k_window_reduce sums nothing)
-        if (t && q) { for (int k = 0; k < 3; k++) t_mine[3 * n_mine + k] = t[3 * i + k]; for (int k = 0; k < 4; k++) q_mine[4 * n_mine + k] = q[4 * i + k]; }
-        mine[n_mine++] = slots[i];
-        Slot& sl = ctx->slots[slots[i]];
-        sl.use_global_counts = false; sl.sticky_global_counts = false;
-        for (int kind = 0; kind < 2; kind++) if (kind_mask & (1 << kind)) {
-            KindSlot& ks = sl.k[kind];
-            if (!ks.has_records) return ctx->fail(LILI_E_STATE, "window_gather: associate the owned keyframes first");
-            if (ks.n_q == 0) continue;
-            if (kind == 0) { w.s[i].part_surf = ks.partials.as<double>(); w.s[i].nb_surf = ks.n_lin_blocks; }
-            else { w.s[i].part_edge = ks.partials.as<double>(); w.s[i].nb_edge = ks.n_lin_blocks; }
+        const bool owned = owner[i] == rank;
+        if (owned) {
+            if (t && q) { for (int k = 0; k < 3; k++) t_mine[3 * n_mine + k] = t[3 * i + k]; for (int k = 0; k < 4; k++) q_mine[4 * n_mine + k] = q[4 * i + k]; }
+            mine[n_mine++] = slots[i];
         }
+        TRY(window_slot(ctx, slots[i], kind_mask, owned, true, "window_gather", w.s[i]));
     }
     lili_p2p* p2p = nullptr;
     if (!p2p_comm(ctx, allreduce, comm, &p2p)) return ctx->fail(LILI_E_STATE, "window_gather: the lili_p2p communicator has failed");
     MatchParams P = to_device_params(params);
     if (do_gn) P.no_cost = 1;
-    if (n_mine > 0) { const int rc = launch_linearize_window(ctx, mine, n_mine, kind_mask, t && q ? t_mine : nullptr, t && q ? q_mine : nullptr, P); if (rc != LILI_OK) return rc; }
-    const bool in_kernel = p2p != nullptr || allreduce == nullptr;
-    hipLaunchKernelGGL(k_window_reduce, dim3(1), dim3(1024), 0, ctx->stream, w, d_gram, (do_gn && in_kernel) ? 1 : 0, p2p ? lili_p2p_next_view(p2p) : P2PView{});
-    HIPCHK(hipGetLastError());
-    if (!in_kernel) {
-        if (allreduce(d_gram, d_gram, (size_t)LILI_GRAM_DOUBLES * n_slots, /*ncclFloat64*/ 8, /*ncclSum*/ 0, comm, (void*)ctx->stream) != 0)
-            return ctx->fail(LILI_E_HIP, "window_gather: exchange of the Gram records failed");
-        if (do_gn) { hipLaunchKernelGGL(k_window_gn, dim3(1), dim3(64), 0, ctx->stream, w, (const double*)d_gram); HIPCHK(hipGetLastError()); }
-    }
-    return LILI_OK;
+    if (n_mine > 0) TRY(launch_linearize_window(ctx, mine, n_mine, kind_mask, t && q ? t_mine : nullptr, t && q ? q_mine : nullptr, P));
+    return launch_window_tail(ctx, w, p2p, allreduce, comm, d_gram, do_gn, "window_gather");
 }
 int lili_s2m_linearize_window_gather(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const int* owner, int rank,
                                      lili_allreduce_fn allreduce, void* comm, double* d_gram) {
@@ -1362,32 +1331,18 @@ int lili_s2m_linearize_window_gather_at(lili_ctx* ctx, const int* slots, int n_s
     if (!ctx) return LILI_E_ARG;
     ARGCHK(t && q && params && d_gram && gram, "linearize_window_gather_at: null argument");
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = window_gather_impl(ctx, slots, n_slots, kind_mask, params, owner, rank, allreduce, comm, d_gram, 0, t, q);
-    if (rc != LILI_OK) return rc;
-    { const int rc_h = ensure_h_records(ctx); if (rc_h != LILI_OK) return rc_h; }
-    HIPCHK(hipMemcpyAsync(ctx->h_records.p, d_gram, (size_t)n_slots * LILI_GRAM_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < n_slots; i++) {
-        const double* h = ctx->h_records.as<double>() + (size_t)i * LILI_GRAM_DOUBLES;
-        std::memcpy(gram + (size_t)64 * i, h, 64 * sizeof(double));
-        if (cost) cost[i] = h[64];
-        if (counts) { counts[2 * i] = (int)h[65]; counts[2 * i + 1] = (int)h[66]; }
-    }
-    return LILI_OK;
+    TRY(window_gather_impl(ctx, slots, n_slots, kind_mask, params, owner, rank, allreduce, comm, d_gram, 0, t, q));
+    return records_from_device(ctx, d_gram, n_slots, gram, cost, counts);
 }
 int lili_s2m_iterate_window_gather(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, int n_iters, const int* owner, int rank,
                                    lili_allreduce_fn allreduce, void* comm, double* d_gram) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(n_iters >= 0 && params && d_gram && owner && slots, "iterate_window_gather: bad argument");
+    TRY(check_gather_args(ctx, slots, n_slots, kind_mask, owner, rank, "iterate_window_gather"));      // (in front of the first launch)
     HIPCHK(hipSetDevice(ctx->device));
     for (int it = 0; it < n_iters; it++) {
-        for (int i = 0; i < n_slots; i++) if (owner[i] == rank) {
-            ARGCHK(slots[i] >= 0 && slots[i] < LILI_MAX_SLOTS, "iterate_window_gather: bad slot");
-            const int rc = lili_s2m_associate_dev(ctx, slots[i], kind_mask, params);
-            if (rc != LILI_OK) return rc;
-        }
-        const int rc = window_gather_impl(ctx, slots, n_slots, kind_mask, params, owner, rank, allreduce, comm, d_gram, 1);
-        if (rc != LILI_OK) return rc;
+        for (int i = 0; i < n_slots; i++) if (owner[i] == rank) TRY(lili_s2m_associate_dev(ctx, slots[i], kind_mask, params));
+        TRY(window_gather_impl(ctx, slots, n_slots, kind_mask, params, owner, rank, allreduce, comm, d_gram, 1));
     }
     return LILI_OK;
 }
@@ -1401,28 +1356,16 @@ int lili_s2m_iterate_window(lili_ctx* ctx, const int* slots, int n_slots, int ki
     if (!ctx) return LILI_E_ARG;
     TRY(check_slot_list(ctx, slots, n_slots, "iterate_window"));
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(ctx->fork_ev.get());
-    HIPCHK(hipEventRecord(ctx->fork_ev, ctx->stream));
-    hipStream_t main_stream = ctx->stream;
+    ForkJoin fj(ctx->stream, ctx->fork_ev, ctx->side, ctx->join_ev);      // the launch helpers enqueue on ctx->stream (one thread per context)
+    HIPCHK(fj.begin());
     int rc = LILI_OK;
     ctx->persistent_off_now = n_slots > 4;       // more than four persistent launches side by side could not all be resident
     for (int i = 0; i < n_slots && rc == LILI_OK; i++) {
-        if (i > 0) {
-            HIPCHK(ctx->side[i].get());
-            HIPCHK(ctx->join_ev[i].get());
-            HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->fork_ev, 0));
-            ctx->stream = ctx->side[i];          // the launch helpers enqueue on ctx->stream (one thread per context)
-        }
+        HIPCHK(fj.fork(i));
         rc = iterate_impl(ctx, slots[i], kind_mask, params, n_iters, 0, 0, nullptr);
         if (i + 1 == n_slots || rc != LILI_OK) ctx->persistent_off_now = false;
-        if (i > 0) {
-            hipError_t e = hipEventRecord(ctx->join_ev[i], ctx->side[i]);
-            ctx->stream = main_stream;
-            if (e != hipSuccess) return ctx->fail(LILI_E_HIP, "iterate_window: hipEventRecord failed");
-            HIPCHK(hipStreamWaitEvent(main_stream, ctx->join_ev[i], 0));
-        }
+        HIPCHK(fj.join(i));
     }
-    ctx->stream = main_stream;
     return rc;
 }
 
@@ -1525,7 +1468,7 @@ int lili_gram_to_factor(const double gram[64], double cost, double residuals[9],
 // the slots' DEVICE poses as lili_s2m_iterate reads them (lili_window_cycle: same kernel bodies, same fixed-order reduction, so the same bytes at the same doubles) —
 // (lili_s2m_linearize_window's launches, records left in d_gram), the arguments of a slot's share of a persistent LM launch, the device parameters.
 int lili_match_window_records(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const double* t, const double* q, double* d_gram) {
-    return linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, nullptr, nullptr, d_gram, 0);
+    return linearize_window_impl(ctx, slots, n_slots, kind_mask, params, t, q, nullptr, nullptr, d_gram, 0, "linearize_window");
 }
 int lili_match_lm_args(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, const lili_lm_options* options, int max_blocks, lili::LmArgs* out) {
     return launch_solve_lm(ctx, slot, kind_mask, params, options, max_blocks, out);

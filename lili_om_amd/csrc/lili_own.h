@@ -86,6 +86,41 @@ struct Stream {
     ~Stream() { release(); }
 };
 
+// A call whose branches run side by side: branch i > 0 on side[i], behind the event begin() records on the main stream, and joined back into the main stream by
+// join[i]; branch 0 on the main stream itself — no event, no other stream.  `current` is the owner's "stream the launch helpers enqueue on": it is a side stream
+// only between fork(i) and join(i), and the destructor puts the main stream back on whatever path the call leaves.
+struct ForkJoin {
+    ForkJoin(hipStream_t& current, Event& fork_ev, Stream* side, Event* join_ev) : current(current), home(current), fork_ev(fork_ev), side(side), join_ev(join_ev) {}
+    ForkJoin(const ForkJoin&) = delete;
+    ForkJoin& operator=(const ForkJoin&) = delete;
+    ~ForkJoin() { current = home; }
+    hipError_t begin() {
+        const hipError_t e = fork_ev.get();
+        return e != hipSuccess ? e : hipEventRecord(fork_ev, home);
+    }
+    hipError_t fork(int i) {
+        if (i == 0) return hipSuccess;
+        hipError_t e = side[i].get();
+        if (e == hipSuccess) e = join_ev[i].get();
+        if (e == hipSuccess) e = hipStreamWaitEvent(side[i], fork_ev, 0);
+        if (e == hipSuccess) current = side[i];
+        return e;
+    }
+    hipError_t join(int i) {
+        if (i == 0) return hipSuccess;
+        const hipError_t e = hipEventRecord(join_ev[i], side[i]);
+        current = home;
+        return e != hipSuccess ? e : hipStreamWaitEvent(home, join_ev[i], 0);
+    }
+
+private:
+    hipStream_t& current;
+    const hipStream_t home;      // the main stream: what `current` was when the call began
+    Event& fork_ev;
+    Stream* side;
+    Event* join_ev;
+};
+
 // What a module keeps per context (lili_ctx::ext): created by the module's first call, deleted with the context.
 struct ExtState { virtual ~ExtState() = default; };
 

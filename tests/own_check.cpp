@@ -1,6 +1,6 @@
 // Stand-alone check of the owner types in lili_om_amd/csrc/lili_own.h, built and run by tests/test_own_cpu.py under the address and undefined-behaviour
 // sanitizers.  The runtime calls the header uses are counting stand-ins on malloc / free: every resource is tracked while it lives, a free of something that
-// is not live is recorded as an error, and two switches make the next allocation / the device-pointer query fail.  Exits non-zero at the first failed check.
+// is not live is recorded as an error, and two switches make the next allocation / the device-pointer query fail.  Event records and stream waits (ForkJoin) are logged in order; a third switch fails them.  Exits non-zero at the first failed check.
 #include "../lili_om_amd/csrc/lili_own.h"
 
 #include <cstdint>
@@ -16,7 +16,10 @@ Kind g_dev, g_pin, g_event, g_stream;
 std::map<void*, void*> g_dev_of_pin;      // what the device-pointer query answers for a live page-locked block (a fresh value per allocation)
 uintptr_t g_next_dev = 0x1000;
 int g_bad_frees = 0, g_last_error_reads = 0;
-bool g_fail_alloc = false, g_fail_devptr = false;
+bool g_fail_alloc = false, g_fail_devptr = false, g_fail_enqueue = false;
+struct Op { char what; void* event; void* stream; };
+std::vector<Op> g_ops;
+bool same(const Op& o, char what, void* event, void* stream) { return o.what == what && o.event == event && o.stream == stream; }
 
 hipError_t make(Kind& k, void** out, size_t bytes) {
     if (g_fail_alloc) return hipErrorOutOfMemory;
@@ -58,6 +61,9 @@ hipError_t hipEventDestroy(hipEvent_t e) { return drop(g_event, e); }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned int) { return make(g_stream, reinterpret_cast<void**>(s), 8); }
 hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned int, int) { return make(g_stream, reinterpret_cast<void**>(s), 8); }
 hipError_t hipStreamDestroy(hipStream_t s) { return drop(g_stream, s); }
+// what ForkJoin enqueues: logged in order ('R'ecord / 'W'ait, the event, the stream); `g_fail_enqueue` makes every such call fail
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { g_ops.push_back({'R', e, s}); return g_fail_enqueue ? hipErrorInvalidValue : hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned int) { g_ops.push_back({'W', e, s}); return g_fail_enqueue ? hipErrorInvalidValue : hipSuccess; }
 }
 
 using namespace lili_detail;
@@ -181,11 +187,87 @@ static void check_ext_states() {
     (void)half;
 }
 
+// a context-like owner of the streams and events ForkJoin works on; `work` stands for a launch helper: it enqueues on `stream`, whatever that is at the time
+struct Forker {
+    hipStream_t stream;
+    Stream side[4];
+    Event fork_ev, join_ev[4];
+    void work() { g_ops.push_back({'K', nullptr, stream}); }
+    // three branches, leaving early — between fork and join — in branch `leave_in` (-1: never)
+    hipError_t run(int leave_in) {
+        ForkJoin fj(stream, fork_ev, side, join_ev);
+        hipError_t e = fj.begin();
+        for (int i = 0; i < 3 && e == hipSuccess; i++) {
+            if ((e = fj.fork(i)) != hipSuccess) return e;
+            work();
+            if (i == leave_in) return hipErrorUnknown;
+            e = fj.join(i);
+        }
+        return e;
+    }
+};
+
+static void check_fork_join() {
+    int main_tag = 0;
+    hipStream_t const main_stream = reinterpret_cast<hipStream_t>(&main_tag);
+    const int events0 = g_event.made, streams0 = g_stream.made;
+    {
+        Forker f;
+        f.stream = main_stream;
+        {   // branch 0 alone: no event, no stream, nothing enqueued but the work — on the main stream
+            ForkJoin fj(f.stream, f.fork_ev, f.side, f.join_ev);
+            g_ops.clear();
+            CHECK(fj.fork(0) == hipSuccess && f.stream == main_stream);
+            f.work();
+            CHECK(fj.join(0) == hipSuccess && f.stream == main_stream);
+            CHECK(g_ops.size() == 1 && same(g_ops[0], 'K', nullptr, main_stream));
+            CHECK(g_event.made == events0 && g_stream.made == streams0 && !f.fork_ev && !f.side[0] && !f.join_ev[0]);
+        }
+        // a whole call: fork -> work -> join per branch, in this order on these streams; the main stream is current again at the end
+        g_ops.clear();
+        CHECK(f.run(-1) == hipSuccess && f.stream == main_stream);
+        CHECK(g_event.made == events0 + 3 && g_stream.made == streams0 + 2 && !f.side[0] && !f.join_ev[0]);      // fork_ev, join_ev[1..2]; side[1..2]
+        hipStream_t s1 = f.side[1], s2 = f.side[2];
+        hipEvent_t fe = f.fork_ev, j1 = f.join_ev[1], j2 = f.join_ev[2];
+        const Op want[] = {{'R', fe, main_stream}, {'K', nullptr, main_stream},
+                           {'W', fe, s1}, {'K', nullptr, s1}, {'R', j1, s1}, {'W', j1, main_stream},
+                           {'W', fe, s2}, {'K', nullptr, s2}, {'R', j2, s2}, {'W', j2, main_stream}};
+        CHECK(g_ops.size() == sizeof(want) / sizeof(want[0]));
+        for (size_t i = 0; i < g_ops.size(); i++) CHECK(same(g_ops[i], want[i].what, want[i].event, want[i].stream));
+        // a second call creates nothing more
+        CHECK(f.run(-1) == hipSuccess && g_event.made == events0 + 3 && g_stream.made == streams0 + 2);
+        // an early return with a branch still open: the work went to the side stream, the main stream is current afterwards, nothing was joined
+        g_ops.clear();
+        CHECK(f.run(2) == hipErrorUnknown && f.stream == main_stream);
+        CHECK(g_ops.size() == 8 && same(g_ops[7], 'K', nullptr, s2));
+        CHECK(f.run(0) == hipErrorUnknown && f.stream == main_stream);
+        // a failing enqueue: fork leaves the main stream current; join puts it back before it reports
+        {
+            ForkJoin fj(f.stream, f.fork_ev, f.side, f.join_ev);
+            g_fail_enqueue = true;
+            CHECK(fj.begin() != hipSuccess && fj.fork(1) != hipSuccess && f.stream == main_stream);
+            g_fail_enqueue = false;
+            CHECK(fj.fork(1) == hipSuccess && f.stream == s1);
+            g_fail_enqueue = true;
+            CHECK(fj.join(1) != hipSuccess && f.stream == main_stream);
+            g_fail_enqueue = false;
+        }
+        // a stream or an event that cannot be created: the same
+        Forker g;
+        g.stream = main_stream;
+        g_fail_alloc = true;
+        CHECK(g.run(-1) != hipSuccess && g.stream == main_stream && !g.fork_ev);
+        g_fail_alloc = false;
+    }
+    CHECK(g_event.live.empty() && g_stream.live.empty() && g_bad_frees == 0);
+}
+
 int main() {
     check_devbuf();
     check_pinbuf();
     check_event_and_stream();
     check_ext_states();
+    check_fork_join();
     CHECK(live_total() == 0 && g_bad_frees == 0);
     std::puts("own_check: ok");
     return 0;
