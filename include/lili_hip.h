@@ -850,6 +850,83 @@ int lili_local_graph(lili_ctx* ctx, const lili_local_walk* walk, int n, const do
 /* Device time of the last lili_local_graph* call's kernel in milliseconds (option "local_graph_time", tools/local_graph_time.py); LILI_E_STATE when there is none. */
 int lili_local_graph_kernel_ms(lili_ctx* ctx, float* ms);
 
+/* ---- Global pose graph over every frame: loop-closure correction on the device (lili_pose_graph.hip) ------------------
+ * What saveKeyFramesAndFactors (L/src/BackendFusion.cpp:1820-1889), performLoopClosure (L:2587-2633) and correctPoses (L:2177-2311) do with GTSAM: one node per
+ * scan, a prior on node 0, a chain factor between consecutive scans, a few loop factors; solved as a batch by Gauss-Newton with full relinearisation.
+ *
+ * Conventions.  A pose is 7 doubles, p (3) then q (w, x, y, z).  The tangent is xi = (omega, v), ROTATION FIRST (gtsam::Pose3's order: the reference's variance
+ * vectors apply index for index).  X (+) xi = (p + R v, normalise(q * Exp(omega)));  between(A, B) = (R_A^T (p_B - p_A), q_A^-1 * q_B).
+ * Between-factor on nodes (a, b), measurement Z = (t_Z, q_Z), variances s^2 (6):  e = (Log(R_Z^T R_A^T R_B), R_Z^T (R_A^T (p_B - p_A) - t_Z)),  r = e / s.
+ * Prior on node 0: e = (Log(R_Z^T R_0), R_Z^T (p_0 - t_Z)).  Cost = 1/2 sum |r|^2, no loss function.  The right Jacobian inverse of SO(3) inside the factor
+ * Jacobians uses its series below LILI_PG_SMALL_ANGLE (rad) and the closed form above it.
+ * Node 0's prior sits at its own pose as given; the chain measurement of node i is between(pose[i - 1], pose[i]) of the poses AS GIVEN AT APPEND TIME and is
+ * frozen from then on; the initial estimate of a new node is its given pose.  Quaternions are normalised on entry.
+ *
+ * lili_pose_graph_reset    — empties the graph (device memory is kept).
+ * lili_pose_graph_append   — n >= 1 new nodes.  prev: NULL for the first call on an empty graph (node 0 gets the prior), otherwise the pose of the graph's LAST
+ *                            node in the frame of `poses` (the caller's current value for it; the first new node's measurement is between(prev, poses[0])).
+ *                            *first_id (optional) = the id of poses[0].
+ * lili_pose_graph_add_loop — BetweenFactor(from, to, meas, var): meas = between(corrected pose of `from`, pose of `to`) (lili_loop_measurement), var = 6 variances.
+ * lili_pose_graph_info / _get / _set — sizes; estimates of nodes first .. first + n - 1; overwrite those estimates (measurements stay as they are).
+ * lili_pose_graph_evaluate — at the current estimates: cost, gradient (6 N), the diagonal blocks of H = J^T J (N x 36, row-major 6 x 6, loop factors included),
+ *                            sub (N - 1 blocks): sub[i] = H block (i + 1, i) of the CHAIN factor alone, loop_blocks[l] = H block (from, to) of loop l alone.
+ *                            sub may be NULL for N == 1, loop_blocks for no loops.  options NULL = the defaults (only the variances are read).
+ * lili_pose_graph_solve    — Gauss-Newton: H delta = -g, X <- X (+) delta.  Per iteration, in this order: |g|inf <= gradient_tolerance ends it before a step
+ *                            (LILI_LM_GRADIENT_TOLERANCE); a non-positive pivot ends it with the previous estimate (LILI_LM_NUMERICAL_FAILURE); a step that raises
+ *                            the cost is NOT taken (LILI_PG_COST_INCREASED, the previous estimate); otherwise the step is taken and |delta|inf <=
+ *                            parameter_tolerance (LILI_LM_PARAMETER_TOLERANCE), |cost - new cost| <= function_tolerance * cost (LILI_LM_FUNCTION_TOLERANCE), then
+ *                            max_iterations (LILI_LM_MAX_ITERATIONS) end it.  summary: iterations = steps computed; cost[k], step_inf[k] = the candidate's cost and
+ *                            |delta|inf of iteration k, grad_inf[k] = |g|inf at its linearisation (the first 16).  The elimination is a one-level nested
+ *                            dissection: separators = every loop endpoint and every node id that is a multiple of LILI_PG_SEGMENT; the stretches between them are
+ *                            eliminated side by side, the reduced system (<= 768 unknowns) by one workgroup.  Every launch of the solve is enqueued up front; one
+ *                            synchronisation, one read-back; blocking.  The same graph gives the same bits on every run.
+ *                            The reference's isam->update(graph); isam->update() is nearest to max_iterations = 2.
+ * lili_pose_graph_kernel_ms — device time of the last lili_pose_graph_solve's launches in milliseconds; LILI_E_STATE when there is none.
+ *
+ * LILI_E_ARG, with every output and the graph untouched: a null pointer (ctx, poses, meas, var, summary, cost, gradient, diag; sub / loop_blocks where they have
+ * entries), a non-finite input, a quaternion more than 1e-6 from unit norm, a non-positive variance, from == to, an id or a range outside the graph, n < 1,
+ * more than LILI_PG_MAX_NODES nodes or LILI_PG_MAX_LOOPS loops, append with prev != NULL on an empty graph or prev == NULL on a non-empty one, max_iterations
+ * outside 1 .. 1000, a tolerance that is negative or not finite.  LILI_E_STATE: evaluate / solve on an empty graph. */
+#define LILI_PG_MAX_NODES 32768
+#define LILI_PG_MAX_LOOPS 32
+#define LILI_PG_SEGMENT 512                /* fixed separators sit at multiples of it: 64 + 2 x 32 separators = 768 reduced unknowns at the caps */
+#define LILI_PG_MAX_LOG 16
+#define LILI_PG_SMALL_ANGLE 0.1
+#define LILI_PG_COST_INCREASED 7           /* termination, next to the LILI_LM_* codes */
+typedef struct lili_pg_options {
+    int32_t max_iterations, reserved_;
+    double function_tolerance, gradient_tolerance, parameter_tolerance;
+    double prior_var[6], odom_var[6];      /* variances in tangent order (omega, v) */
+} lili_pg_options;
+typedef struct lili_pg_summary {
+    int32_t iterations, termination, n_nodes, n_loops;
+    double initial_cost, final_cost;
+    double cost[LILI_PG_MAX_LOG], step_inf[LILI_PG_MAX_LOG], grad_inf[LILI_PG_MAX_LOG];
+} lili_pg_summary;
+/* max_iterations 10, tolerances 1e-6 / 1e-10 / 1e-8 (lili_lm_default_options), prior 1e-6 x 3, 1e-8 x 3, odometry 1e-6 x 3, 1e-4 x 3 (L:552-557) */
+void lili_pg_default_options(lili_pg_options* opt);
+int lili_pose_graph_reset(lili_ctx* ctx);
+int lili_pose_graph_append(lili_ctx* ctx, const double* prev, const double* poses, int n, int* first_id);
+int lili_pose_graph_add_loop(lili_ctx* ctx, int from, int to, const double meas[7], const double var[6]);
+int lili_pose_graph_info(lili_ctx* ctx, int* n_nodes, int* n_loops);
+int lili_pose_graph_get(lili_ctx* ctx, int first, int n, double* poses);
+int lili_pose_graph_set(lili_ctx* ctx, int first, int n, const double* poses);
+int lili_pose_graph_evaluate(lili_ctx* ctx, const lili_pg_options* options, double* cost, double* gradient, double* diag, double* sub, double* loop_blocks);
+int lili_pose_graph_solve(lili_ctx* ctx, const lili_pg_options* options, lili_pg_summary* summary);
+int lili_pose_graph_kernel_ms(lili_ctx* ctx, float* ms);
+/* The loop factor's measurement (L:2587-2615), host side, no context: T_icp (row-major 4 x 4) corrects the latest keyframe's pose, meas = between(T_icp o
+ * pose_latest, pose_closest) with both quaternions normalised.  LILI_E_ARG: a null pointer, a non-finite input, a zero quaternion. */
+int lili_loop_measurement(const double T_icp[16], const double pose_latest[7], const double pose_closest[7], double meas[7]);
+/* correctPoses (L:2177-2311) statement by statement on host arrays, no context.  In: solution (n_frames x 7, p then q: the solved nodes),
+ * keyframe_id_in_frame (n_keyframes), slide_window_width (>= 2), f32_positions (as lili_local_walk: positions go through pcl's floats).  In / out: abs_poses
+ * (n_abs x 7 in the reference's layout q (w, x, y, z) then p; the window's tail is re-chained from its own relative transforms), keyframe_poses (n_keyframes x 7,
+ * p then q: pose_cloud_frame / pose_info_cloud_frame).  Out: frame_poses (n_frames x 7, p then q: pose_each_frame / pose_info_each_frame), last_pose (7, the
+ * abs_poses layout), select_pose (3).  Rs / Ps of the window follow from abs_poses and are the caller's.  The text's index arithmetic is kept; LILI_E_ARG (nothing
+ * written) where it would leave an array: a null pointer, slide_window_width < 2 or > n_abs or > n_keyframes, n_abs > n_keyframes + 1,
+ * n_keyframes - slide_window_width + 2 > n_abs, a keyframe id outside 0 .. n_frames - 1, a non-finite input. */
+int lili_correct_poses(const double* solution, int n_frames, const int32_t* keyframe_id_in_frame, int n_keyframes, int slide_window_width, int f32_positions,
+                       double* abs_poses, int n_abs, double* frame_poses, double* keyframe_poses, double last_pose[7], double select_pose[3]);
+
 /* ---- callers / data formats either side of the path ------------------------- */
 
 /* Livox CustomMsg points -> the PointXYZINormal cloud the Livox extractor consumes; replaces livoxLidarHandler

@@ -7,9 +7,10 @@ from . import api  # noqa: F401
 from .loop import LoopClosure  # noqa: F401
 from .archive import KeyframeArchive, GlobalMap, ARCHIVE_EDGE, ARCHIVE_SURF, ARCHIVE_FULL  # noqa: F401
 from .local_graph import LocalGraph, FrameTrajectory  # noqa: F401
+from .pose_graph import PoseGraph, correct_poses, loop_measurement  # noqa: F401
 from .api import (Context, ScanToMapMatcher, RotExtractor, LivoxExtractor, LocalMap, FrontendOdometry, RotFrontendOdometry, BackendKeyframes, WindowSolver, WindowCycleOptions, WindowCycleResult, ImuPreintegrator, LiliError, make_params,  # noqa: F401
                   load_library, KIND_SURF, KIND_EDGE, MASK_SURF, MASK_EDGE)
 
 __all__ = ["api", "Context", "ScanToMapMatcher", "RotExtractor", "LivoxExtractor", "LocalMap", "FrontendOdometry", "RotFrontendOdometry", "BackendKeyframes", "WindowSolver", "WindowCycleOptions", "WindowCycleResult", "ImuPreintegrator", "LiliError", "make_params", "load_library",
-           "KIND_SURF", "KIND_EDGE", "MASK_SURF", "MASK_EDGE", "LoopClosure", "KeyframeArchive", "GlobalMap", "LocalGraph", "FrameTrajectory",
+           "KIND_SURF", "KIND_EDGE", "MASK_SURF", "MASK_EDGE", "LoopClosure", "KeyframeArchive", "GlobalMap", "LocalGraph", "FrameTrajectory", "PoseGraph", "correct_poses", "loop_measurement",
            "ARCHIVE_EDGE", "ARCHIVE_SURF", "ARCHIVE_FULL"]

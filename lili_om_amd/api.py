@@ -126,6 +126,25 @@ class LocalGraphSummary(C.Structure):
         return d
 
 
+PG_MAX_NODES, PG_MAX_LOOPS, PG_SEGMENT, PG_MAX_LOG, PG_COST_INCREASED = 32768, 32, 512, 16, 7
+
+
+class PgOptions(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("reserved_", C.c_int32), ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
+                ("parameter_tolerance", C.c_double), ("prior_var", C.c_double * 6), ("odom_var", C.c_double * 6)]
+
+
+class PgSummary(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("termination", C.c_int32), ("n_nodes", C.c_int32), ("n_loops", C.c_int32), ("initial_cost", C.c_double),
+                ("final_cost", C.c_double), ("cost", C.c_double * PG_MAX_LOG), ("step_inf", C.c_double * PG_MAX_LOG), ("grad_inf", C.c_double * PG_MAX_LOG)]
+
+    def as_dict(self):
+        k = min(self.iterations, PG_MAX_LOG)
+        kg = min(self.iterations + (1 if self.termination in (1, 5) else 0), PG_MAX_LOG)      # a solve that ends at a linearisation (gradient, pivot) has one more of them than steps
+        return dict(iterations=self.iterations, termination=self.termination, n_nodes=self.n_nodes, n_loops=self.n_loops, initial_cost=self.initial_cost,
+                    final_cost=self.final_cost, cost=list(self.cost[:k]), step_inf=list(self.step_inf[:k]), grad_inf=list(self.grad_inf[:kg]))
+
+
 class WindowPrior(C.Structure):
     _fields_ = [("n_rows", C.c_int32), ("n_cols", C.c_int32), ("n_blocks", C.c_int32), ("reserved_", C.c_int32), ("block_kind", C.POINTER(C.c_int32)),
                 ("block_keyframe", C.POINTER(C.c_int32)), ("x0", C.POINTER(C.c_double)), ("J0", C.POINTER(C.c_double)), ("r0", C.POINTER(C.c_double))]
@@ -314,6 +333,18 @@ _SIGS = {
     "lili_local_graph_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LmOptions), C.POINTER(LocalGraphSummary)]),
     "lili_local_graph": (C.c_int, [C.c_void_p, C.POINTER(LocalWalk), C.c_int, C.c_void_p, C.POINTER(LmOptions), C.c_void_p, C.c_void_p, C.POINTER(LocalGraphSummary)]),
     "lili_local_graph_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "lili_pg_default_options": (None, [C.POINTER(PgOptions)]),
+    "lili_pose_graph_reset": (C.c_int, [C.c_void_p]),
+    "lili_pose_graph_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "lili_pose_graph_add_loop": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "lili_pose_graph_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lili_pose_graph_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "lili_pose_graph_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "lili_pose_graph_evaluate": (C.c_int, [C.c_void_p, C.POINTER(PgOptions), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lili_pose_graph_solve": (C.c_int, [C.c_void_p, C.POINTER(PgOptions), C.POINTER(PgSummary)]),
+    "lili_pose_graph_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "lili_loop_measurement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lili_correct_poses": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_marg_add_lidar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
     "lili_gn_step_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_gram_to_factor": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),

@@ -215,6 +215,40 @@ struct LocalGraphOut {
     lili_local_graph_summary summary;
     double jtj[kLocalMaxN * kLocalMaxN];    // kLocalEvaluate only: the leading (6 n)^2 doubles, row-major with stride 6 n
 };
+// Global pose graph (lili_pose_graph.hip).  Factor f of N nodes and L loops: 0 = the prior on node 0, 1 .. N - 1 = the chain factor (f - 1, f),
+// N + l = loop l.  Separator k is node sep[k]; segment k = the nodes between separator k and separator k + 1 (or the end of the chain).
+constexpr int kPgMaxNodes = LILI_PG_MAX_NODES, kPgMaxLoops = LILI_PG_MAX_LOOPS, kPgSegment = LILI_PG_SEGMENT;
+constexpr int kPgMaxSep = kPgMaxNodes / kPgSegment + 2 * kPgMaxLoops, kPgMaxReduced = 6 * kPgMaxSep;
+constexpr int kPgWide = 1024;        // threads of the single-workgroup stages (gate, reduced system, retract and cost)
+constexpr int kPgCols = 13;          // columns a segment carries through its elimination: the right-hand side, 6 of its left separator, 6 of its right one
+constexpr int kPgGram = kPgCols * kPgCols;
+static_assert(kPgMaxReduced <= 768 && kPgMaxReduced <= kPgWide, "the reduced system is factored by one workgroup, one row per thread");
+struct PgLoop { int from, to, sep_from, sep_to; double meas[7], w[6]; };      // w = 1 / sqrt(variance)
+struct PgSeg { int left, first, last, right; };      // separator node ids (right = -1: the chain ends first), interior nodes first .. last (first > last: none)
+struct PgTables {
+    int n, n_loops, n_sep, max_iter;
+    double function_tolerance, gradient_tolerance, parameter_tolerance;
+    double w_prior[6], w_odom[6];
+    int sep[kPgMaxSep];
+    PgSeg seg[kPgMaxSep];
+    PgLoop loop[kPgMaxLoops];
+};
+struct PgState {
+    int done, fail;                  // done: the termination word — every later launch returns at its first instruction; fail: a segment met a non-positive pivot
+    double cost, gmax;
+    lili_pg_summary s;
+};
+struct PgDev {
+    const PgTables* tab;
+    PgState* st;
+    double *X, *Xn;                  // estimates, candidate (7 per node)
+    const double* meas;              // meas[i] = the measurement of factor i (7 per node; 0: the prior's)
+    double *fr, *fJ;                 // per factor: weighted residual (6), Jacobian blocks of its first and second node (2 x 36, row-major)
+    double *g, *D, *S, *LB;          // gradient (6 N), diagonal blocks (36 N), sub[i] = chain block (i + 1, i) (36 N), loop blocks (from, to) (36 L)
+    double *Ld, *Ls, *Y;             // per eliminated node: Cholesky factor of its pivot block (36), L block (i + 1, i) (36), the carried columns (6 x 13, column by column)
+    double *gram;                    // per segment: sum of Y^T Y (13 x 13)
+    double *red, *delta;             // the reduced system's lower triangle, column by column ([col * n + row]); the step (6 N)
+};
 struct ImuOutDev {                   // lili_window_imu's numbers, then the prediction
     double sum_dt, g[3], delta_p[3], delta_q[4], delta_v[3], lin_ba[3], lin_bg[3], jacobian[225], covariance[225];
     double P1[3], R1[9], V1[3];

@@ -47,6 +47,16 @@ template <int L> __global__ void k_iterate_coop(AssocArgs, AssocArgs, MatchParam
 __global__ void k_imu_preintegrate(const ImuSegDev*, const double*, ImuOutDev*);
 // lili_local_graph.hip: IMU walk and local pose graph, one workgroup of one wave
 __global__ void k_local_graph(const LocalGraphIn*, LocalGraphOut*);
+// lili_pose_graph.hip: the global pose graph, one launch per stage of a Gauss-Newton iteration
+__global__ void k_pg_append(const double*, int, int, double*, double*);
+__global__ void k_pg_linearize(PgDev);
+__global__ void k_pg_assemble(PgDev);
+__global__ void k_pg_gate(PgDev, int);
+__global__ void k_pg_eliminate(PgDev);
+__global__ void k_pg_reduced_assemble(PgDev);
+__global__ void k_pg_reduced_solve(PgDev);
+__global__ void k_pg_backsub(PgDev);
+__global__ void k_pg_retract_cost(PgDev);
 }  // namespace lili
 
 // lili_map.hip: the three-kernel exclusive scan (k_scan_block_sums, k_scan_sums, k_scan_apply) of n words into out[0 .. n]; in == out is allowed

@@ -1,0 +1,950 @@
+// Global pose graph over every frame (include/lili_hip.h: lili_pose_graph*): what saveKeyFramesAndFactors, performLoopClosure and correctPoses
+// (L/src/BackendFusion.cpp:1820-1889, 2587-2633, 2177-2311) hand to GTSAM, as a batch Gauss-Newton solve on the device, f64, no contraction.
+//
+// One iteration is eight launches, every one enqueued up front; none waits for another workgroup, every loop is bounded by the graph's size:
+//   k_pg_linearize         two lanes per factor: the even one the weighted residual and the Jacobian block of the factor's first node, the odd one the second node's;
+//   k_pg_assemble          one lane per entry of H and g, by gather: a node sums its <= 2 chain contributions, then its loop contributions in loop order;
+//   k_pg_gate              one workgroup: |g|inf (and, before the first step, the cost) in a fixed order; sets the termination word at the gradient tolerance;
+//   k_pg_eliminate         one wave per segment: 6 x 6-block Cholesky along the chain between two separators, lane c carrying column c of
+//                          [L block^T | g | columns of the left separator | columns of the right separator] through the forward substitution, and the 13 x 13
+//                          Gram of the carried columns — the segment's Schur contribution;
+//   k_pg_reduced_assemble  one workgroup per block of the reduced system over the separators: diagonal, Schur terms, loop blocks in loop order;
+//   k_pg_reduced_solve     one workgroup: dense left-looking Cholesky (one row per thread, fixed-order sums) and the two substitutions;
+//   k_pg_backsub           one wave per segment, every lane the same arithmetic: the interior nodes' step from the separators';
+//   k_pg_retract_cost      one workgroup: the candidate, its cost in a fixed order, the accept / stop decision, the termination word.
+// No atomics anywhere: H, g, the cost and the step are pure functions of the graph.
+#include "lili_launch.h"
+#include "lili_device_math.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <string>
+
+namespace lili {
+
+__device__ __forceinline__ dq pg_conj(const dq q) { return dq{q.w, -q.x, -q.y, -q.z}; }
+__device__ __forceinline__ dq pg_quat(const double* p) { return dq{p[3], p[4], p[5], p[6]}; }
+__device__ __forceinline__ void pg_mat(const dq q, double R[9]) { const double a[4] = {q.w, q.x, q.y, q.z}; quat_to_mat(a, R); }
+__device__ __forceinline__ void pg_mm3(const double* A, const double* B, double* O) {
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) O[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+// Log of a unit quaternion as a rotation vector, the angle in [0, pi]
+__device__ __forceinline__ void pg_log(dq q, double phi[3]) {
+    if (q.w < 0.0) q = dq{-q.w, -q.x, -q.y, -q.z};
+    const double n2 = (q.x * q.x + q.y * q.y) + q.z * q.z;
+    double k = 2.0;
+    if (n2 > 0.0) { const double n = sqrt(n2); k = 2.0 * atan2(n, q.w) / n; }
+    phi[0] = k * q.x; phi[1] = k * q.y; phi[2] = k * q.z;
+}
+// the inverse of SO(3)'s right Jacobian: I + [phi]x / 2 + c [phi]x^2, c by its series below LILI_PG_SMALL_ANGLE
+__device__ __forceinline__ void pg_jr_inv(const double phi[3], double M[9]) {
+    const double t2 = (phi[0] * phi[0] + phi[1] * phi[1]) + phi[2] * phi[2];
+    double c;
+    if (t2 < LILI_PG_SMALL_ANGLE * LILI_PG_SMALL_ANGLE) c = 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0)));
+    else { const double t = sqrt(t2); c = 1.0 / t2 - (1.0 + cos(t)) / (2.0 * t * sin(t)); }
+    const double S[9] = {0.0, -phi[2], phi[1], phi[2], 0.0, -phi[0], -phi[1], phi[0], 0.0};
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) M[3 * i + j] = ((i == j ? 1.0 : 0.0) + 0.5 * S[3 * i + j]) + c * (phi[i] * phi[j] - (i == j ? t2 : 0.0));
+}
+// e = (Log(R_Z^T R_A^T R_B), R_Z^T (R_A^T (p_B - p_A) - t_Z)); also qab = q_A^-1 q_B, d = R_A^T (p_B - p_A), qe = q_Z^-1 qab
+__device__ __forceinline__ void pg_error(const d3 pa, const dq qa, const d3 pb, const dq qb, const double* Z, double e[6], dq& qab, d3& d, dq& qe) {
+    const dq ia = pg_conj(qa), iz = pg_conj(pg_quat(Z));
+    d = qrot(ia, pb - pa);
+    const d3 ev = qrot(iz, d - d3{Z[0], Z[1], Z[2]});
+    qab = qmul(ia, qb);
+    qe = qmul(iz, qab);
+    pg_log(qe, e);
+    e[3] = ev.x; e[4] = ev.y; e[5] = ev.z;
+}
+__device__ __forceinline__ double pg_sq6(const double* r) { return ((((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]) + r[3] * r[3]) + r[4] * r[4]) + r[5] * r[5]; }
+// the two poses, the measurement and the weights of factor f at the estimates x
+struct PgFactorIn { d3 pa, pb; dq qa, qb; const double* Z; const double* w; };
+__device__ __forceinline__ PgFactorIn pg_factor(const PgTables& T, const double* x, const double* meas, const int f) {
+    PgFactorIn F;
+    int a = -1, b = 0;
+    if (f == 0) { F.Z = meas; F.w = T.w_prior; }
+    else if (f < T.n) { a = f - 1; b = f; F.Z = meas + 7 * (size_t)f; F.w = T.w_odom; }
+    else { const PgLoop& l = T.loop[f - T.n]; a = l.from; b = l.to; F.Z = l.meas; F.w = l.w; }
+    if (a < 0) { F.pa = d3{0.0, 0.0, 0.0}; F.qa = dq{1.0, 0.0, 0.0, 0.0}; }
+    else { const double* A = x + 7 * (size_t)a; F.pa = d3{A[0], A[1], A[2]}; F.qa = pg_quat(A); }
+    const double* B = x + 7 * (size_t)b;
+    F.pb = d3{B[0], B[1], B[2]}; F.qb = pg_quat(B);
+    return F;
+}
+__device__ __forceinline__ double pg_factor_cost(const PgTables& T, const double* x, const double* meas, const int f) {
+    const PgFactorIn F = pg_factor(T, x, meas, f);
+    double e[6], r[6];
+    dq qab, qe; d3 d;
+    pg_error(F.pa, F.qa, F.pb, F.qb, F.Z, e, qab, d, qe);
+#pragma unroll
+    for (int k = 0; k < 6; k++) r[k] = e[k] * F.w[k];
+    return pg_sq6(r);
+}
+// sum / maximum over the kPgWide threads of the single-workgroup stages, in a fixed order; every thread gets the result
+__device__ __forceinline__ double pg_block_sum(double v, double* sh) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int s = kPgWide / 2; s > 0; s >>= 1) { if (t < s) sh[t] = sh[t] + sh[t + s]; __syncthreads(); }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ double pg_block_max(double v, double* sh) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int s = kPgWide / 2; s > 0; s >>= 1) { if (t < s) sh[t] = fmax(sh[t], sh[t + s]); __syncthreads(); }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+// new nodes first .. first + n - 1 from the staged rows (row 0 = prev, rows 1 .. n = the poses): estimates and frozen measurements
+__global__ void k_pg_append(const double* __restrict__ rows, const int first, const int n, double* __restrict__ X, double* __restrict__ meas) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int id = first + i;
+    const double* B = rows + 7 * (size_t)(i + 1);
+    const double* A = rows + 7 * (size_t)i;
+    double* x = X + 7 * (size_t)id;
+    double* m = meas + 7 * (size_t)id;
+#pragma unroll
+    for (int k = 0; k < 7; k++) x[k] = B[k];
+    if (id == 0) {
+#pragma unroll
+        for (int k = 0; k < 7; k++) m[k] = B[k];
+        return;
+    }
+    const dq ia = pg_conj(pg_quat(A));
+    const d3 t = qrot(ia, d3{B[0] - A[0], B[1] - A[1], B[2] - A[2]});
+    const dq q = qmul(ia, pg_quat(B));
+    m[0] = t.x; m[1] = t.y; m[2] = t.z; m[3] = q.w; m[4] = q.x; m[5] = q.y; m[6] = q.z;
+}
+
+__global__ __launch_bounds__(256) void k_pg_linearize(const PgDev G) {
+    if (G.st->done) return;
+    const PgTables& T = *G.tab;
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const int f = tid >> 1, side = tid & 1;
+    if (f >= T.n + T.n_loops) return;
+    const PgFactorIn F = pg_factor(T, G.X, G.meas, f);
+    double e[6], Jri[9];
+    dq qab, qe; d3 d;
+    pg_error(F.pa, F.qa, F.pb, F.qb, F.Z, e, qab, d, qe);
+    pg_jr_inv(e, Jri);
+    double* J = G.fJ + (size_t)f * 72 + 36 * side;
+    if (side == 0) {
+        double* r = G.fr + (size_t)f * 6;
+#pragma unroll
+        for (int k = 0; k < 6; k++) r[k] = e[k] * F.w[k];
+        // first node: [-Jr^-1 Rab^T, 0; R_Z^T [d]x, -R_Z^T]
+        double Rab[9], RabT[9], Rz[9], A[9], Bm[9];
+        pg_mat(qab, Rab);
+        pg_mat(pg_conj(pg_quat(F.Z)), Rz);
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) RabT[3 * i + j] = Rab[3 * j + i];
+        pg_mm3(Jri, RabT, A);
+        const double Sd[9] = {0.0, -d.z, d.y, d.z, 0.0, -d.x, -d.y, d.x, 0.0};
+        pg_mm3(Rz, Sd, Bm);
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                J[6 * i + j] = -A[3 * i + j] * F.w[i]; J[6 * i + 3 + j] = 0.0;
+                J[6 * (3 + i) + j] = Bm[3 * i + j] * F.w[3 + i]; J[6 * (3 + i) + 3 + j] = -Rz[3 * i + j] * F.w[3 + i];
+            }
+    } else {
+        // second node: [Jr^-1, 0; 0, R_Z^T R_A^T R_B]
+        double Re[9];
+        pg_mat(qe, Re);
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                J[6 * i + j] = Jri[3 * i + j] * F.w[i]; J[6 * i + 3 + j] = 0.0;
+                J[6 * (3 + i) + j] = 0.0; J[6 * (3 + i) + 3 + j] = Re[3 * i + j] * F.w[3 + i];
+            }
+    }
+}
+
+// (A^T B)[r][c] of two row-major 6 x 6 blocks, and (A^T v)[c]
+__device__ __forceinline__ double pg_atb(const double* A, const double* B, const int r, const int c) {
+    double s = A[r] * B[c];
+#pragma unroll
+    for (int k = 1; k < 6; k++) s += A[6 * k + r] * B[6 * k + c];
+    return s;
+}
+__device__ __forceinline__ double pg_atv(const double* A, const double* v, const int c) {
+    double s = A[c] * v[0];
+#pragma unroll
+    for (int k = 1; k < 6; k++) s += A[6 * k + c] * v[k];
+    return s;
+}
+__global__ __launch_bounds__(256) void k_pg_assemble(const PgDev G) {
+    if (G.st->done) return;
+    const PgTables& T = *G.tab;
+    const int n = T.n, L = T.n_loops;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= (long long)n * 78) {
+        const int t = (int)(tid - (long long)n * 78);
+        if (t >= 36 * L) return;
+        const int l = t / 36, e = t - 36 * l;
+        const double* J = G.fJ + (size_t)(n + l) * 72;
+        G.LB[t] = pg_atb(J, J + 36, e / 6, e % 6);
+        return;
+    }
+    const int i = (int)(tid / 78), e = (int)(tid - (long long)i * 78);
+    const double* Jb = G.fJ + (size_t)i * 72 + 36;                  // factor i: node i is its second node
+    const double* Ja = G.fJ + (size_t)(i + 1) * 72;                 // factor i + 1: node i is its first node
+    const bool next = i + 1 < n;
+    if (e < 36) {
+        const int r = e / 6, c = e - 6 * r;
+        double v = pg_atb(Jb, Jb, r, c);
+        if (next) v += pg_atb(Ja, Ja, r, c);
+        for (int l = 0; l < L; l++) {
+            const double* Jl = G.fJ + (size_t)(n + l) * 72;
+            if (T.loop[l].from == i) v += pg_atb(Jl, Jl, r, c);
+            if (T.loop[l].to == i) v += pg_atb(Jl + 36, Jl + 36, r, c);
+        }
+        G.D[(size_t)i * 36 + e] = v;
+    } else if (e < 72) {
+        const int r = (e - 36) / 6, c = (e - 36) - 6 * r;
+        G.S[(size_t)i * 36 + (e - 36)] = next ? pg_atb(Ja + 36, Ja, r, c) : 0.0;      // block (i + 1, i): second node's rows, first node's columns
+    } else {
+        const int c = e - 72;
+        double v = pg_atv(Jb, G.fr + (size_t)i * 6, c);
+        if (next) v += pg_atv(Ja, G.fr + (size_t)(i + 1) * 6, c);
+        for (int l = 0; l < L; l++) {
+            const double* Jl = G.fJ + (size_t)(n + l) * 72;
+            const double* rl = G.fr + (size_t)(n + l) * 6;
+            if (T.loop[l].from == i) v += pg_atv(Jl, rl, c);
+            if (T.loop[l].to == i) v += pg_atv(Jl + 36, rl, c);
+        }
+        G.g[(size_t)i * 6 + c] = v;
+    }
+}
+
+// evaluate == 0: the head of an iteration; != 0: lili_pose_graph_evaluate (cost and |g|inf into the state, nothing decided)
+__global__ __launch_bounds__(kPgWide) void k_pg_gate(const PgDev G, const int evaluate) {
+    if (G.st->done) return;
+    __shared__ double sh[kPgWide];
+    const PgTables& T = *G.tab;
+    const int t = threadIdx.x, it = G.st->s.iterations;
+    double m = 0.0;
+    for (int i = t; i < 6 * T.n; i += kPgWide) m = fmax(m, fabs(G.g[i]));
+    m = pg_block_max(m, sh);
+    double cost = G.st->cost;
+    if (it == 0 || evaluate) {
+        double c = 0.0;
+        for (int f = t; f < T.n + T.n_loops; f += kPgWide) c += pg_sq6(G.fr + (size_t)f * 6);
+        cost = 0.5 * pg_block_sum(c, sh);
+    }
+    if (t == 0) {
+        PgState& st = *G.st;
+        st.gmax = m; st.fail = 0;
+        if (it == 0 || evaluate) { st.cost = cost; st.s.initial_cost = cost; st.s.final_cost = cost; }
+        if (!evaluate) {
+            if (it < LILI_PG_MAX_LOG) st.s.grad_inf[it] = m;
+            if (m <= T.gradient_tolerance) { st.s.termination = LILI_LM_GRADIENT_TOLERANCE; st.done = 1; }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_pg_eliminate(const PgDev G) {
+    if (G.st->done) return;
+    __shared__ double sLs[36];      // L block (i, i - 1), row by row
+    __shared__ double sY[6 * kPgCols];      // the carried columns of node i, column by column
+    const PgTables& T = *G.tab;
+    const PgSeg sg = T.seg[blockIdx.x];
+    const int c = threadIdx.x, n = T.n;
+    double yprev[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, acc[3] = {0.0, 0.0, 0.0};
+    bool ok = true;
+    for (int i = sg.first; i <= sg.last; i++) {
+        const bool first = i == sg.first;
+        // the pivot block D_i - Ls Ls^T and its Cholesky factor, by every lane on the same bits
+        double A[36];
+        const double* Di = G.D + (size_t)i * 36;
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int q = 0; q <= r; q++) {
+                double v = Di[6 * r + q];
+                if (!first) {
+                    double s = sLs[6 * r] * sLs[6 * q];
+#pragma unroll
+                    for (int k = 1; k < 6; k++) s += sLs[6 * r + k] * sLs[6 * q + k];
+                    v -= s;
+                }
+                A[6 * r + q] = v;
+            }
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            double s = A[6 * j + j];
+#pragma unroll
+            for (int k = 0; k < j; k++) s -= A[6 * j + k] * A[6 * j + k];
+            ok = ok && (s > 0.0);
+            const double l = sqrt(s);
+            A[6 * j + j] = l;
+#pragma unroll
+            for (int r = j + 1; r < 6; r++) {
+                double v = A[6 * r + j];
+#pragma unroll
+                for (int k = 0; k < j; k++) v -= A[6 * r + k] * A[6 * j + k];
+                A[6 * r + j] = v / l;
+            }
+        }
+        // this lane's column of [S_i^T | g_i | E_left | E_right] - Ls [0 | Y_(i-1)], then the forward substitution
+        double z[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (c < 6) {
+            if (i + 1 < n) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) z[k] = G.S[(size_t)i * 36 + 6 * c + k];
+            }
+        } else if (c == 6) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) z[k] = G.g[(size_t)i * 6 + k];
+        } else if (c < 13) {
+            if (first) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) z[k] = G.S[(size_t)sg.left * 36 + 6 * k + (c - 7)];      // block (left + 1, left), its column c - 7
+            }
+        } else if (c < 19) {
+            if (i == sg.last && sg.right >= 0) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) z[k] = G.S[(size_t)i * 36 + 6 * (c - 13) + k];           // block (last, right) = block (right, last)^T, its column c - 13
+            }
+        }
+        if (!first && c >= 6) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                double s = sLs[6 * k] * yprev[0];
+#pragma unroll
+                for (int m = 1; m < 6; m++) s += sLs[6 * k + m] * yprev[m];
+                z[k] -= s;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            double v = z[k];
+#pragma unroll
+            for (int m = 0; m < k; m++) v -= A[6 * k + m] * z[m];
+            z[k] = v / A[6 * k + k];
+        }
+        __syncthreads();      // every lane has read sLs and sY of the previous node
+        if (c < 6) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) { sLs[6 * c + k] = z[k]; G.Ls[(size_t)i * 36 + 6 * c + k] = z[k]; }
+        } else if (c < 6 + kPgCols) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) { sY[6 * (c - 6) + k] = z[k]; G.Y[(size_t)i * (6 * kPgCols) + 6 * (c - 6) + k] = z[k]; yprev[k] = z[k]; }
+        }
+        if (c == 63) {
+#pragma unroll
+            for (int r = 0; r < 6; r++)
+#pragma unroll
+                for (int q = 0; q < 6; q++) G.Ld[(size_t)i * 36 + 6 * r + q] = q <= r ? A[6 * r + q] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 3; u++) {
+            const int e = c + 64 * u;
+            if (e < kPgGram) {
+                const int a = e / kPgCols, b = e - kPgCols * a;
+                double s = sY[6 * a] * sY[6 * b];
+#pragma unroll
+                for (int k = 1; k < 6; k++) s += sY[6 * a + k] * sY[6 * b + k];
+                acc[u] += s;
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 3; u++) { const int e = c + 64 * u; if (e < kPgGram) G.gram[(size_t)blockIdx.x * kPgGram + e] = acc[u]; }
+    if (!ok && c == 0) G.st->fail = 1;
+}
+
+// block (p, q), p >= q, of the reduced system over the separators, and (block (p, p)) its right-hand side g_p minus the Schur terms, kept in delta's rows of the separators
+__global__ __launch_bounds__(64) void k_pg_reduced_assemble(const PgDev G) {
+    if (G.st->done) return;
+    const PgTables& T = *G.tab;
+    const int K = T.n_sep, nr = 6 * K;
+    const int p = blockIdx.x / K, q = blockIdx.x - K * p;
+    if (p < q) return;
+    const int t = threadIdx.x;
+    const int sp = T.sep[p], sq = T.sep[q];
+    const bool seg_p = T.seg[p].first <= T.seg[p].last;                       // the segment to the right of separator p has nodes
+    const bool seg_l = p > 0 && T.seg[p - 1].first <= T.seg[p - 1].last;      // ... to its left
+    if (t < 36) {
+        const int r = t / 6, c = t - 6 * r;
+        double v = 0.0;
+        if (p == q) {
+            v = G.D[(size_t)sp * 36 + t];
+            if (seg_p) v -= G.gram[(size_t)p * kPgGram + (1 + r) * kPgCols + (1 + c)];
+            if (seg_l) v -= G.gram[(size_t)(p - 1) * kPgGram + (7 + r) * kPgCols + (7 + c)];
+        } else if (p == q + 1) {
+            if (T.seg[q].first <= T.seg[q].last) v = -G.gram[(size_t)q * kPgGram + (7 + r) * kPgCols + (1 + c)];
+            else v = G.S[(size_t)sq * 36 + t];
+        }
+        for (int l = 0; l < T.n_loops; l++) {
+            if (T.loop[l].sep_from == p && T.loop[l].sep_to == q) v += G.LB[36 * l + 6 * r + c];
+            if (T.loop[l].sep_to == p && T.loop[l].sep_from == q) v += G.LB[36 * l + 6 * c + r];
+        }
+        G.red[(size_t)(6 * q + c) * nr + (6 * p + r)] = v;
+    } else if (t < 42 && p == q) {
+        const int r = t - 36;
+        double v = G.g[(size_t)sp * 6 + r];
+        if (seg_p) v -= G.gram[(size_t)p * kPgGram + (1 + r) * kPgCols];
+        if (seg_l) v -= G.gram[(size_t)(p - 1) * kPgGram + (7 + r) * kPgCols];
+        G.delta[(size_t)sp * 6 + r] = v;
+    }
+}
+
+__global__ __launch_bounds__(kPgWide) void k_pg_reduced_solve(const PgDev G) {
+    if (G.st->done) return;
+    __shared__ double sy[kPgMaxReduced], srow[kPgMaxReduced];
+    __shared__ double spiv;
+    const PgTables& T = *G.tab;
+    const int nr = 6 * T.n_sep, i = threadIdx.x;
+    double* R = G.red;
+    bool ok = G.st->fail == 0;
+    if (i < nr) sy[i] = G.delta[(size_t)T.sep[i / 6] * 6 + i % 6];
+    for (int j = 0; j < nr; j++) {
+        if (i < j) srow[i] = R[(size_t)i * nr + j];      // row j of L
+        __syncthreads();
+        double s = 0.0;
+        if (i >= j && i < nr) {
+            s = R[(size_t)j * nr + i];
+            for (int k = 0; k < j; k++) s -= R[(size_t)k * nr + i] * srow[k];
+            if (i == j) spiv = s;
+        }
+        __syncthreads();
+        const double piv = spiv;
+        ok = ok && (piv > 0.0);
+        const double l = sqrt(piv);
+        if (i >= j && i < nr) R[(size_t)j * nr + i] = i == j ? l : s / l;
+        __syncthreads();      // column j is in front of the next column's reads of it
+    }
+    __syncthreads();
+    if (!ok) {
+        if (i == 0) { G.st->s.termination = LILI_LM_NUMERICAL_FAILURE; G.st->done = 1; }
+        return;
+    }
+    for (int j = 0; j < nr; j++) {      // L y = b
+        const double yj = sy[j] / R[(size_t)j * nr + j];
+        __syncthreads();
+        if (i == j) sy[j] = yj;
+        else if (i > j && i < nr) sy[i] -= R[(size_t)j * nr + i] * yj;
+        __syncthreads();
+    }
+    for (int j = nr - 1; j >= 0; j--) {      // L^T x = y
+        const double xj = sy[j] / R[(size_t)j * nr + j];
+        __syncthreads();
+        if (i == j) sy[j] = xj;
+        else if (i < j) sy[i] -= R[(size_t)i * nr + j] * xj;
+        __syncthreads();
+    }
+    if (i < nr) G.delta[(size_t)T.sep[i / 6] * 6 + i % 6] = -sy[i];
+}
+
+__global__ __launch_bounds__(64) void k_pg_backsub(const PgDev G) {
+    if (G.st->done) return;
+    const PgTables& T = *G.tab;
+    const PgSeg sg = T.seg[blockIdx.x];
+    double xl[6], xr[6], xn[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 6; k++) { xl[k] = G.delta[(size_t)sg.left * 6 + k]; xr[k] = sg.right >= 0 ? G.delta[(size_t)sg.right * 6 + k] : 0.0; }
+    for (int i = sg.last; i >= sg.first; i--) {
+        const double* Y = G.Y + (size_t)i * (6 * kPgCols);
+        const double* Ls = G.Ls + (size_t)i * 36;
+        const double* Ld = G.Ld + (size_t)i * 36;
+        double x[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            double s = Y[k];
+#pragma unroll
+            for (int m = 0; m < 6; m++) s += Y[6 * (1 + m) + k] * xl[m];
+#pragma unroll
+            for (int m = 0; m < 6; m++) s += Y[6 * (7 + m) + k] * xr[m];
+            s = -s;
+            if (i < sg.last) {
+#pragma unroll
+                for (int m = 0; m < 6; m++) s -= Ls[6 * m + k] * xn[m];
+            }
+            x[k] = s;
+        }
+#pragma unroll
+        for (int k = 5; k >= 0; k--) {
+            double v = x[k];
+#pragma unroll
+            for (int m = k + 1; m < 6; m++) v -= Ld[6 * m + k] * x[m];
+            x[k] = v / Ld[6 * k + k];
+        }
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) G.delta[(size_t)i * 6 + k] = x[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) xn[k] = x[k];
+    }
+}
+
+__global__ __launch_bounds__(kPgWide) void k_pg_retract_cost(const PgDev G) {
+    if (G.st->done) return;
+    __shared__ double sh[kPgWide];
+    __shared__ int s_accept;
+    const PgTables& T = *G.tab;
+    const int t = threadIdx.x, n = T.n;
+    double smax = 0.0;
+    for (int i = t; i < n; i += kPgWide) {
+        const double* x = G.X + 7 * (size_t)i;
+        const double* dl = G.delta + 6 * (size_t)i;
+        double* o = G.Xn + 7 * (size_t)i;
+        const dq q = pg_quat(x);
+        const d3 p = d3{x[0], x[1], x[2]} + qrot(q, d3{dl[3], dl[4], dl[5]});
+        const double t2 = (dl[0] * dl[0] + dl[1] * dl[1]) + dl[2] * dl[2];
+        double sc = 0.5, cw = 1.0;
+        if (t2 > 0.0) { const double th = sqrt(t2); sc = sin(0.5 * th) / th; cw = cos(0.5 * th); }
+        const dq qn = qmul(q, dq{cw, sc * dl[0], sc * dl[1], sc * dl[2]});
+        const double nq = sqrt(((qn.w * qn.w + qn.x * qn.x) + qn.y * qn.y) + qn.z * qn.z);
+        o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = qn.w / nq; o[4] = qn.x / nq; o[5] = qn.y / nq; o[6] = qn.z / nq;
+#pragma unroll
+        for (int k = 0; k < 6; k++) smax = fmax(smax, fabs(dl[k]));
+    }
+    smax = pg_block_max(smax, sh);      // (its barriers also put the candidate in front of the reads below)
+    double c = 0.0;
+    for (int f = t; f < n + T.n_loops; f += kPgWide) c += pg_factor_cost(T, G.Xn, G.meas, f);
+    const double new_cost = 0.5 * pg_block_sum(c, sh);
+    if (t == 0) {
+        PgState& st = *G.st;
+        const int it = st.s.iterations;
+        const double cost = st.cost;
+        if (it < LILI_PG_MAX_LOG) { st.s.cost[it] = new_cost; st.s.step_inf[it] = smax; }
+        st.s.iterations = it + 1;
+        int accept = 0;
+        if (!(new_cost <= cost)) { st.s.termination = LILI_PG_COST_INCREASED; st.done = 1; }
+        else {
+            accept = 1;
+            st.cost = new_cost; st.s.final_cost = new_cost;
+            if (smax <= T.parameter_tolerance) { st.s.termination = LILI_LM_PARAMETER_TOLERANCE; st.done = 1; }
+            else if (fabs(cost - new_cost) <= T.function_tolerance * cost) { st.s.termination = LILI_LM_FUNCTION_TOLERANCE; st.done = 1; }
+            else if (it + 1 >= T.max_iter) { st.s.termination = LILI_LM_MAX_ITERATIONS; st.done = 1; }
+        }
+        s_accept = accept;
+    }
+    __syncthreads();
+    if (s_accept) for (int e = t; e < 7 * n; e += kPgWide) G.X[e] = G.Xn[e];
+}
+
+}  // namespace lili
+
+namespace {
+
+struct PoseGraphState : ExtState {
+    int n = 0, n_loops = 0;
+    PgLoop loops[kPgMaxLoops];
+    DevBuf X, Xn, meas, tab, st, stage, fr, fJ, g, D, S, LB, Ld, Ls, Y, gram, red, delta;
+    PinBuf h_tab, h_io;
+    Event ev0, ev1;
+    float last_ms = -1.f;
+    // the graph itself is allocated once at the caps (3.7 MB): it has to outlive every call
+    int persist(lili_ctx* ctx) {
+        HIPCHK(X.ensure(sizeof(double) * 7 * kPgMaxNodes));
+        HIPCHK(meas.ensure(sizeof(double) * 7 * kPgMaxNodes));
+        HIPCHK(tab.ensure(sizeof(PgTables)));
+        HIPCHK(st.ensure(sizeof(PgState)));
+        HIPCHK(h_tab.ensure(sizeof(PgTables) + sizeof(PgState)));
+        return LILI_OK;
+    }
+    // the work arrays of an evaluation (solve: and of the elimination) for the current sizes
+    int work(lili_ctx* ctx, int n_sep, bool solve) {
+        const size_t N = (size_t)n, F = (size_t)n + kPgMaxLoops, d = sizeof(double);
+        HIPCHK(fr.ensure(F * 6 * d)); HIPCHK(fJ.ensure(F * 72 * d));
+        HIPCHK(g.ensure(N * 6 * d)); HIPCHK(D.ensure(N * 36 * d)); HIPCHK(S.ensure(N * 36 * d)); HIPCHK(LB.ensure((size_t)kPgMaxLoops * 36 * d));
+        if (solve) {
+            HIPCHK(Xn.ensure(N * 7 * d));
+            HIPCHK(Ld.ensure(N * 36 * d)); HIPCHK(Ls.ensure(N * 36 * d)); HIPCHK(Y.ensure(N * 6 * kPgCols * d));
+            HIPCHK(gram.ensure((size_t)kPgMaxSep * kPgGram * d));
+            HIPCHK(red.ensure((size_t)36 * n_sep * n_sep * d));
+            HIPCHK(delta.ensure(N * 6 * d));
+        }
+        return LILI_OK;
+    }
+    PgDev dev() const {
+        PgDev G{};
+        G.tab = tab.as<PgTables>(); G.st = st.as<PgState>();
+        G.X = X.as<double>(); G.Xn = Xn.as<double>(); G.meas = meas.as<double>();
+        G.fr = fr.as<double>(); G.fJ = fJ.as<double>(); G.g = g.as<double>(); G.D = D.as<double>(); G.S = S.as<double>(); G.LB = LB.as<double>();
+        G.Ld = Ld.as<double>(); G.Ls = Ls.as<double>(); G.Y = Y.as<double>(); G.gram = gram.as<double>(); G.red = red.as<double>(); G.delta = delta.as<double>();
+        return G;
+    }
+};
+PoseGraphState* pg_of(lili_ctx* ctx) { return ext_of<PoseGraphState>(ctx, lili_ctx::kExtPoseGraph); }
+
+// n poses: finite, quaternions within 1e-6 of unit norm; out = the poses with the quaternions normalised
+int check_poses(lili_ctx* ctx, const char* who, const double* poses, size_t n, double* out) {
+    ARGCHK(finite_n(poses, 7 * n), std::string(who) + ": an input is not finite");
+    for (size_t i = 0; i < n; i++) {
+        const double* q = poses + 7 * i + 3;
+        const double nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+        ARGCHK(std::fabs(nq - 1.0) <= 1e-6, std::string(who) + ": a quaternion is more than 1e-6 from unit norm");
+    }
+    for (size_t i = 0; i < n; i++) {
+        const double* p = poses + 7 * i;
+        const double nq = std::sqrt(((p[3] * p[3] + p[4] * p[4]) + p[5] * p[5]) + p[6] * p[6]);
+        for (int k = 0; k < 3; k++) out[7 * i + k] = p[k];
+        for (int k = 3; k < 7; k++) out[7 * i + k] = p[k] / nq;
+    }
+    return LILI_OK;
+}
+int check_options(lili_ctx* ctx, const lili_pg_options* options, lili_pg_options* opt) {
+    if (options) *opt = *options; else lili_pg_default_options(opt);
+    ARGCHK(opt->max_iterations >= 1 && opt->max_iterations <= 1000, "pose_graph: max_iterations must be in 1..1000");
+    ARGCHK(std::isfinite(opt->function_tolerance) && std::isfinite(opt->gradient_tolerance) && std::isfinite(opt->parameter_tolerance) && opt->function_tolerance >= 0 &&
+           opt->gradient_tolerance >= 0 && opt->parameter_tolerance >= 0, "pose_graph: a tolerance is negative or not finite");
+    for (int k = 0; k < 6; k++)
+        ARGCHK(std::isfinite(opt->prior_var[k]) && std::isfinite(opt->odom_var[k]) && opt->prior_var[k] > 0 && opt->odom_var[k] > 0, "pose_graph: a variance is not positive and finite");
+    return LILI_OK;
+}
+// the tables of a solve / an evaluation in the page-locked block, the state behind them; returns the number of separators
+int fill_tables(PoseGraphState* P, const lili_pg_options& opt) {
+    PgTables* T = P->h_tab.as<PgTables>();
+    std::memset(T, 0, sizeof *T);
+    T->n = P->n; T->n_loops = P->n_loops; T->max_iter = opt.max_iterations;
+    T->function_tolerance = opt.function_tolerance; T->gradient_tolerance = opt.gradient_tolerance; T->parameter_tolerance = opt.parameter_tolerance;
+    for (int k = 0; k < 6; k++) { T->w_prior[k] = 1.0 / std::sqrt(opt.prior_var[k]); T->w_odom[k] = 1.0 / std::sqrt(opt.odom_var[k]); }
+    int K = 0;
+    for (int s = 0; s < P->n; s += kPgSegment) T->sep[K++] = s;
+    for (int l = 0; l < P->n_loops; l++) { T->sep[K++] = P->loops[l].from; T->sep[K++] = P->loops[l].to; }
+    std::sort(T->sep, T->sep + K);
+    K = (int)(std::unique(T->sep, T->sep + K) - T->sep);
+    for (int k = 0; k < K; k++) {
+        const bool more = k + 1 < K;
+        T->seg[k] = PgSeg{T->sep[k], T->sep[k] + 1, more ? T->sep[k + 1] - 1 : P->n - 1, more ? T->sep[k + 1] : -1};
+    }
+    for (int l = 0; l < P->n_loops; l++) {
+        T->loop[l] = P->loops[l];
+        T->loop[l].sep_from = (int)(std::lower_bound(T->sep, T->sep + K, P->loops[l].from) - T->sep);
+        T->loop[l].sep_to = (int)(std::lower_bound(T->sep, T->sep + K, P->loops[l].to) - T->sep);
+    }
+    T->n_sep = K;
+    PgState* S = reinterpret_cast<PgState*>(T + 1);
+    std::memset(S, 0, sizeof *S);
+    S->s.n_nodes = P->n; S->s.n_loops = P->n_loops;
+    return K;
+}
+int upload_tables(lili_ctx* ctx, PoseGraphState* P) {
+    HIPCHK(hipMemcpyAsync(P->tab.p, P->h_tab.p, sizeof(PgTables), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(P->st.p, P->h_tab.as<PgTables>() + 1, sizeof(PgState), hipMemcpyHostToDevice, ctx->stream));
+    return LILI_OK;
+}
+void launch_linearize(lili_ctx* ctx, const PoseGraphState* P, const PgDev& G) {
+    const int F = P->n + P->n_loops;
+    hipLaunchKernelGGL(k_pg_linearize, dim3(nblocks(2 * (int64_t)F, 256)), dim3(256), 0, ctx->stream, G);
+    hipLaunchKernelGGL(k_pg_assemble, dim3(nblocks((int64_t)P->n * 78 + 36 * P->n_loops, 256)), dim3(256), 0, ctx->stream, G);
+}
+
+// ---- host-side quaternion algebra as Eigen 3.3 evaluates it (q = w, x, y, z)
+struct hq { double w, x, y, z; };
+struct hv { double x, y, z; };
+hq h_mul(const hq a, const hq b) {
+    return hq{a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z,
+              a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x};
+}
+hq h_inv(const hq q) {
+    const double n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
+    return hq{q.w / n2, -q.x / n2, -q.y / n2, -q.z / n2};
+}
+hv h_cross(const hv a, const hv b) { return hv{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+hv h_rot(const hq q, const hv v) {
+    const hv u{q.x, q.y, q.z};
+    hv uv = h_cross(u, v);
+    uv = hv{uv.x + uv.x, uv.y + uv.y, uv.z + uv.z};
+    const hv c = h_cross(u, uv);
+    return hv{(v.x + q.w * uv.x) + c.x, (v.y + q.w * uv.y) + c.y, (v.z + q.w * uv.z) + c.z};
+}
+hq h_normalized(const hq q) {
+    const double n = std::sqrt(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+    return hq{q.w / n, q.x / n, q.y / n, q.z / n};
+}
+// Eigen::Quaterniond(const Matrix3d&), m row-major
+hq h_from_matrix(const double* m) {
+    double t = m[0] + m[4] + m[8];
+    double q[4];
+    if (t > 0.0) {
+        t = std::sqrt(t + 1.0);
+        q[0] = 0.5 * t;
+        t = 0.5 / t;
+        q[1] = (m[7] - m[5]) * t; q[2] = (m[2] - m[6]) * t; q[3] = (m[3] - m[1]) * t;
+    } else {
+        int i = 0;
+        if (m[4] > m[0]) i = 1;
+        if (m[8] > m[4 * i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+        q[1 + i] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[3 * k + j] - m[3 * j + k]) * t;
+        q[1 + j] = (m[3 * j + i] + m[3 * i + j]) * t;
+        q[1 + k] = (m[3 * k + i] + m[3 * i + k]) * t;
+    }
+    return hq{q[0], q[1], q[2], q[3]};
+}
+bool h_finite(const double* p, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false; return true; }
+
+}  // namespace
+
+extern "C" {
+
+void lili_pg_default_options(lili_pg_options* o) {
+    if (!o) return;
+    o->max_iterations = 10; o->reserved_ = 0;
+    o->function_tolerance = 1e-6; o->gradient_tolerance = 1e-10; o->parameter_tolerance = 1e-8;
+    for (int k = 0; k < 3; k++) { o->prior_var[k] = 1e-6; o->prior_var[3 + k] = 1e-8; o->odom_var[k] = 1e-6; o->odom_var[3 + k] = 1e-4; }
+}
+
+int lili_pose_graph_reset(lili_ctx* ctx) {
+    if (!ctx) return LILI_E_ARG;
+    PoseGraphState* P = pg_of(ctx);
+    P->n = 0; P->n_loops = 0;
+    return LILI_OK;
+}
+
+int lili_pose_graph_info(lili_ctx* ctx, int* n_nodes, int* n_loops) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(n_nodes && n_loops, "pose_graph_info: null argument");
+    const PoseGraphState* P = pg_of(ctx);
+    *n_nodes = P->n; *n_loops = P->n_loops;
+    return LILI_OK;
+}
+
+int lili_pose_graph_append(lili_ctx* ctx, const double* prev, const double* poses, int n, int* first_id) {
+    if (!ctx) return LILI_E_ARG;
+    PoseGraphState* P = pg_of(ctx);
+    ARGCHK(poses, "pose_graph_append: null poses");
+    ARGCHK(n >= 1 && n <= kPgMaxNodes - P->n, "pose_graph_append: n < 1, or more than LILI_PG_MAX_NODES nodes");
+    ARGCHK((prev != nullptr) == (P->n > 0), "pose_graph_append: prev must be NULL on an empty graph and the last node's pose on any other");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t bytes = sizeof(double) * 7 * ((size_t)n + 1);
+    HIPCHK(P->h_io.ensure(bytes));
+    double* rows = P->h_io.as<double>();
+    if (prev) TRY(check_poses(ctx, "pose_graph_append", prev, 1, rows));
+    else std::memset(rows, 0, sizeof(double) * 7);
+    TRY(check_poses(ctx, "pose_graph_append", poses, (size_t)n, rows + 7));
+    TRY(P->persist(ctx));
+    HIPCHK(P->stage.ensure(bytes));
+    HIPCHK(hipMemcpyAsync(P->stage.p, rows, bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_pg_append, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, P->stage.as<double>(), P->n, n, P->X.as<double>(), P->meas.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (first_id) *first_id = P->n;
+    P->n += n;
+    return LILI_OK;
+}
+
+int lili_pose_graph_add_loop(lili_ctx* ctx, int from, int to, const double meas[7], const double var[6]) {
+    if (!ctx) return LILI_E_ARG;
+    PoseGraphState* P = pg_of(ctx);
+    ARGCHK(meas && var, "pose_graph_add_loop: null argument");
+    ARGCHK(from >= 0 && from < P->n && to >= 0 && to < P->n && from != to, "pose_graph_add_loop: from / to must be two different nodes of the graph");
+    ARGCHK(P->n_loops < kPgMaxLoops, "pose_graph_add_loop: more than LILI_PG_MAX_LOOPS loops");
+    ARGCHK(finite_n(var, 6), "pose_graph_add_loop: an input is not finite");
+    for (int k = 0; k < 6; k++) ARGCHK(var[k] > 0, "pose_graph_add_loop: a variance is not positive");
+    PgLoop l{};
+    TRY(check_poses(ctx, "pose_graph_add_loop", meas, 1, l.meas));
+    l.from = from; l.to = to;
+    for (int k = 0; k < 6; k++) l.w[k] = 1.0 / std::sqrt(var[k]);
+    P->loops[P->n_loops++] = l;
+    return LILI_OK;
+}
+
+int lili_pose_graph_get(lili_ctx* ctx, int first, int n, double* poses) {
+    if (!ctx) return LILI_E_ARG;
+    PoseGraphState* P = pg_of(ctx);
+    ARGCHK(poses, "pose_graph_get: null poses");
+    ARGCHK(first >= 0 && n >= 1 && first <= P->n && n <= P->n - first, "pose_graph_get: range outside the graph");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t bytes = sizeof(double) * 7 * (size_t)n;
+    HIPCHK(P->h_io.ensure(bytes));
+    HIPCHK(hipMemcpyAsync(P->h_io.p, P->X.as<double>() + 7 * (size_t)first, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(poses, P->h_io.p, bytes);
+    return LILI_OK;
+}
+
+int lili_pose_graph_set(lili_ctx* ctx, int first, int n, const double* poses) {
+    if (!ctx) return LILI_E_ARG;
+    PoseGraphState* P = pg_of(ctx);
+    ARGCHK(poses, "pose_graph_set: null poses");
+    ARGCHK(first >= 0 && n >= 1 && first <= P->n && n <= P->n - first, "pose_graph_set: range outside the graph");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t bytes = sizeof(double) * 7 * (size_t)n;
+    HIPCHK(P->h_io.ensure(bytes));
+    TRY(check_poses(ctx, "pose_graph_set", poses, (size_t)n, P->h_io.as<double>()));
+    HIPCHK(hipMemcpyAsync(P->X.as<double>() + 7 * (size_t)first, P->h_io.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return LILI_OK;
+}
+
+int lili_pose_graph_evaluate(lili_ctx* ctx, const lili_pg_options* options, double* cost, double* gradient, double* diag, double* sub, double* loop_blocks) {
+    if (!ctx) return LILI_E_ARG;
+    PoseGraphState* P = pg_of(ctx);
+    ARGCHK(cost && gradient && diag && (sub || P->n <= 1) && (loop_blocks || P->n_loops == 0), "pose_graph_evaluate: null argument");
+    lili_pg_options opt;
+    TRY(check_options(ctx, options, &opt));
+    if (P->n == 0) return ctx->fail(LILI_E_STATE, "pose_graph_evaluate: the graph is empty");
+    HIPCHK(hipSetDevice(ctx->device));
+    TRY(P->persist(ctx));
+    TRY(P->work(ctx, 0, false));
+    const size_t N = (size_t)P->n, L = (size_t)P->n_loops, d = sizeof(double);
+    const size_t o_g = 0, o_D = o_g + 6 * N, o_S = o_D + 36 * N, o_L = o_S + 36 * N, total = o_L + 36 * L;
+    HIPCHK(P->h_io.ensure(total * d));
+    fill_tables(P, opt);
+    TRY(upload_tables(ctx, P));
+    const PgDev G = P->dev();
+    launch_linearize(ctx, P, G);
+    hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 1);
+    HIPCHK(hipGetLastError());
+    double* h = P->h_io.as<double>();
+    PgState* hs = reinterpret_cast<PgState*>(P->h_tab.as<PgTables>() + 1);
+    HIPCHK(hipMemcpyAsync(hs, P->st.p, sizeof(PgState), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h + o_g, P->g.p, 6 * N * d, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h + o_D, P->D.p, 36 * N * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (N > 1) HIPCHK(hipMemcpyAsync(h + o_S, P->S.p, 36 * (N - 1) * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (L) HIPCHK(hipMemcpyAsync(h + o_L, P->LB.p, 36 * L * d, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *cost = hs->cost;
+    std::memcpy(gradient, h + o_g, 6 * N * d);
+    std::memcpy(diag, h + o_D, 36 * N * d);
+    if (N > 1) std::memcpy(sub, h + o_S, 36 * (N - 1) * d);
+    if (L) std::memcpy(loop_blocks, h + o_L, 36 * L * d);
+    return LILI_OK;
+}
+
+int lili_pose_graph_solve(lili_ctx* ctx, const lili_pg_options* options, lili_pg_summary* summary) {
+    if (!ctx) return LILI_E_ARG;
+    PoseGraphState* P = pg_of(ctx);
+    ARGCHK(summary, "pose_graph_solve: null summary");
+    lili_pg_options opt;
+    TRY(check_options(ctx, options, &opt));
+    if (P->n == 0) return ctx->fail(LILI_E_STATE, "pose_graph_solve: the graph is empty");
+    HIPCHK(hipSetDevice(ctx->device));
+    TRY(P->persist(ctx));
+    const int K = fill_tables(P, opt);
+    TRY(P->work(ctx, K, true));
+    TRY(upload_tables(ctx, P));
+    const PgDev G = P->dev();
+    HIPCHK(P->ev0.get(hipEventDefault)); HIPCHK(P->ev1.get(hipEventDefault));
+    HIPCHK(hipEventRecord(P->ev0, ctx->stream));
+    for (int it = 0; it < opt.max_iterations; it++) {
+        launch_linearize(ctx, P, G);
+        hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 0);
+        hipLaunchKernelGGL(k_pg_eliminate, dim3(K), dim3(64), 0, ctx->stream, G);
+        hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(K * K), dim3(64), 0, ctx->stream, G);
+        hipLaunchKernelGGL(k_pg_reduced_solve, dim3(1), dim3(kPgWide), 0, ctx->stream, G);
+        hipLaunchKernelGGL(k_pg_backsub, dim3(K), dim3(64), 0, ctx->stream, G);
+        hipLaunchKernelGGL(k_pg_retract_cost, dim3(1), dim3(kPgWide), 0, ctx->stream, G);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(P->ev1, ctx->stream));
+    PgState* hs = reinterpret_cast<PgState*>(P->h_tab.as<PgTables>() + 1);
+    HIPCHK(hipMemcpyAsync(hs, P->st.p, sizeof(PgState), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipEventElapsedTime(&P->last_ms, P->ev0, P->ev1));
+    *summary = hs->s;
+    return LILI_OK;
+}
+
+int lili_pose_graph_kernel_ms(lili_ctx* ctx, float* ms) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(ms, "pose_graph_kernel_ms: null argument");
+    const PoseGraphState* P = static_cast<const PoseGraphState*>(ctx->ext[lili_ctx::kExtPoseGraph].get());
+    if (!P || P->last_ms < 0.f) return ctx->fail(LILI_E_STATE, "pose_graph_kernel_ms: no lili_pose_graph_solve yet");
+    *ms = P->last_ms;
+    return LILI_OK;
+}
+
+int lili_loop_measurement(const double T_icp[16], const double pose_latest[7], const double pose_closest[7], double meas[7]) {
+    if (!T_icp || !pose_latest || !pose_closest || !meas) return LILI_E_ARG;
+    if (!h_finite(T_icp, 16) || !h_finite(pose_latest, 7) || !h_finite(pose_closest, 7)) return LILI_E_ARG;
+    // L:2587-2600: quaternionIncre(R), transitionIncre; corrected = incre * toCorrect
+    const double R[9] = {T_icp[0], T_icp[1], T_icp[2], T_icp[4], T_icp[5], T_icp[6], T_icp[8], T_icp[9], T_icp[10]};
+    const hq q_inc = h_from_matrix(R);
+    const hq q_lat{pose_latest[3], pose_latest[4], pose_latest[5], pose_latest[6]}, q_clo{pose_closest[3], pose_closest[4], pose_closest[5], pose_closest[6]};
+    const hq q_cor = h_mul(q_inc, q_lat);
+    const hv r = h_rot(q_inc, hv{pose_latest[0], pose_latest[1], pose_latest[2]});
+    const hv t_cor{r.x + T_icp[3], r.y + T_icp[7], r.z + T_icp[11]};
+    const double n_from = q_cor.x * q_cor.x + q_cor.y * q_cor.y + q_cor.z * q_cor.z + q_cor.w * q_cor.w;
+    const double n_to = q_clo.x * q_clo.x + q_clo.y * q_clo.y + q_clo.z * q_clo.z + q_clo.w * q_clo.w;
+    if (!(n_from > 0.0) || !(n_to > 0.0) || !std::isfinite(n_from) || !std::isfinite(n_to)) return LILI_E_ARG;
+    // L:2602-2622: Rot3::Quaternion of both (unit quaternions), poseFrom.between(poseTo)
+    const hq qf = h_normalized(q_cor), qt = h_normalized(q_clo);
+    const hq fi{qf.w, -qf.x, -qf.y, -qf.z};
+    const hv t = h_rot(fi, hv{pose_closest[0] - t_cor.x, pose_closest[1] - t_cor.y, pose_closest[2] - t_cor.z});
+    const hq q = h_normalized(h_mul(fi, qt));
+    if (!std::isfinite(t.x) || !std::isfinite(t.y) || !std::isfinite(t.z) || !std::isfinite(q.w)) return LILI_E_ARG;
+    meas[0] = t.x; meas[1] = t.y; meas[2] = t.z; meas[3] = q.w; meas[4] = q.x; meas[5] = q.y; meas[6] = q.z;
+    return LILI_OK;
+}
+
+int lili_correct_poses(const double* solution, int n_frames, const int32_t* keyframe_id_in_frame, int n_keyframes, int slide_window_width, int f32_positions,
+                       double* abs_poses, int n_abs, double* frame_poses, double* keyframe_poses, double last_pose[7], double select_pose[3]) {
+    if (!solution || !keyframe_id_in_frame || !abs_poses || !frame_poses || !keyframe_poses || !last_pose || !select_pose) return LILI_E_ARG;
+    const int w = slide_window_width;
+    if (n_frames < 1 || n_keyframes < 1 || n_abs < 1 || w < 2 || w > n_abs || w > n_keyframes || n_abs > n_keyframes + 1 || n_keyframes - w + 2 > n_abs) return LILI_E_ARG;
+    for (int i = 0; i <= n_keyframes - w; i++) if (keyframe_id_in_frame[i] < 0 || keyframe_id_in_frame[i] >= n_frames) return LILI_E_ARG;
+    if (!h_finite(solution, 7 * (size_t)n_frames) || !h_finite(abs_poses, 7 * (size_t)n_abs)) return LILI_E_ARG;
+    auto A = [&](int i) { return abs_poses + 7 * (size_t)i; };
+    auto pos = [&](double v) { return f32_positions ? (double)(float)v : v; };
+    // L:2186-2209: the relative transforms of the window's tail
+    hq qrel[64]; hv trel[64];
+    if (w - 1 > 64) return LILI_E_ARG;
+    for (int i = n_abs - w; i < n_abs - 1; i++) {
+        const hq qf{A(i)[0], A(i)[1], A(i)[2], A(i)[3]}, qt{A(i + 1)[0], A(i + 1)[1], A(i + 1)[2], A(i + 1)[3]};
+        const hv tf{A(i)[4], A(i)[5], A(i)[6]}, tt{A(i + 1)[4], A(i + 1)[5], A(i + 1)[6]};
+        qrel[i - (n_abs - w)] = h_mul(h_inv(qf), qt);
+        trel[i - (n_abs - w)] = h_rot(h_inv(qf), hv{tt.x - tf.x, tt.y - tf.y, tt.z - tf.z});
+    }
+    // L:2211-2225: every frame from the solution
+    for (int i = 0; i < n_frames; i++) {
+        const double* s = solution + 7 * (size_t)i;
+        double* f = frame_poses + 7 * (size_t)i;
+        f[0] = pos(s[0]); f[1] = pos(s[1]); f[2] = pos(s[2]);
+        f[3] = s[3]; f[4] = s[4]; f[5] = s[5]; f[6] = s[6];
+    }
+    // L:2227-2258: the keyframes outside the window's tail, and abs_poses[i + 1]
+    for (int i = 0; i <= n_keyframes - w; i++) {
+        const double* f = frame_poses + 7 * (size_t)keyframe_id_in_frame[i];
+        double* k = keyframe_poses + 7 * (size_t)i;
+        for (int c = 0; c < 7; c++) k[c] = f[c];
+        A(i + 1)[0] = k[3]; A(i + 1)[1] = k[4]; A(i + 1)[2] = k[5]; A(i + 1)[3] = k[6];
+        A(i + 1)[4] = k[0]; A(i + 1)[5] = k[1]; A(i + 1)[6] = k[2];
+    }
+    // L:2260-2298: the tail re-chained
+    for (int i = n_abs - w; i < n_abs - 1; i++) {
+        hq iq{A(i)[0], A(i)[1], A(i)[2], A(i)[3]};
+        hv it{A(i)[4], A(i)[5], A(i)[6]};
+        const hv r = h_rot(iq, trel[i - n_abs + w]);
+        it = hv{it.x + r.x, it.y + r.y, it.z + r.z};
+        iq = h_mul(iq, qrel[i - n_abs + w]);
+        A(i + 1)[0] = iq.w; A(i + 1)[1] = iq.x; A(i + 1)[2] = iq.y; A(i + 1)[3] = iq.z;
+        A(i + 1)[4] = it.x; A(i + 1)[5] = it.y; A(i + 1)[6] = it.z;
+        double* k = keyframe_poses + 7 * (size_t)i;
+        k[0] = pos(A(i + 1)[4]); k[1] = pos(A(i + 1)[5]); k[2] = pos(A(i + 1)[6]);
+        k[3] = A(i + 1)[0]; k[4] = A(i + 1)[1]; k[5] = A(i + 1)[2]; k[6] = A(i + 1)[3];
+    }
+    // L:2300-2308
+    for (int i = 0; i < 7; i++) last_pose[i] = A(n_abs - w)[i];
+    select_pose[0] = pos(last_pose[4]); select_pose[1] = pos(last_pose[5]); select_pose[2] = pos(last_pose[6]);
+    return LILI_OK;
+}
+
+}  // extern "C"

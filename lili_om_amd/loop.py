@@ -1,5 +1,5 @@
 """Loop closure on the device: performLoopClosure / detectLoopClosure (L/src/BackendFusion.cpp:2423-2642, R/src/BackendFusion.cpp ~2233-2405) up to the
-BetweenFactor the reference hands to iSAM2.  The pose graph (iSAM2, correctPoses) stays with the caller.  Nothing here imports oracle/."""
+BetweenFactor the reference hands to iSAM2.  The pose graph behind it is lili_om_amd.pose_graph (PoseGraph.add_loop_from_icp, solve, correct_poses).  Nothing here imports oracle/."""
 import ctypes as C
 
 import numpy as np

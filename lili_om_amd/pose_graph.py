@@ -1,0 +1,137 @@
+"""Global pose graph over every frame (include/lili_hip.h: lili_pose_graph*): the reference's saveKeyFramesAndFactors / performLoopClosure /
+correctPoses without GTSAM.  A pose is 7 doubles, p (3) then q (w, x, y, z); the tangent is (omega, v), rotation first.  PoseGraph needs a context (the solve
+runs on the GPU, there is no other path); correct_poses and loop_measurement are host functions of the library.
+
+A full loop closure, with a KeyframeArchive `archive`, a FrameTrajectory `traj` whose frames are the graph's nodes and the window's abs_poses:
+
+    found = loop.perform(None, None, select_pose, t_now)                    # LoopClosure(ctx, archive=archive): detect, submaps, ICP
+    if found is not None:
+        latest, his = found[0], found[1]
+        ts, qs, _ = archive.poses()
+        graph.add_loop_from_icp(traj.keyframe_id_in_frame[latest], traj.keyframe_id_in_frame[his], loop.last["transform"],
+                                np.concatenate([ts[latest], qs[latest]]), np.concatenate([ts[his], qs[his]]), loop.last["fitness"])
+        graph.solve(max_iterations=2)                                        # isam->update(graph); isam->update()
+        out = correct_poses(graph.poses(), traj.keyframe_id_in_frame, width, abs_poses, np.hstack([ts, qs]))
+        traj.rewrite(out["frame_poses"])
+        archive.set_poses(0, out["keyframe_poses"][:, 0:3], out["keyframe_poses"][:, 3:7])      # then lili_localmap_repose of the rings
+"""
+import ctypes as C
+
+import numpy as np
+
+from .api import LiliError, PgOptions, PgSummary, _ptr, load_library
+
+
+def _f64(a, shape):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.size != int(np.prod(shape)):
+        raise LiliError(f"expected {int(np.prod(shape))} doubles, got {a.size}")
+    return a.reshape(shape)
+
+
+def loop_measurement(T_icp, pose_latest, pose_closest):
+    """The loop factor's measurement (L/src/BackendFusion.cpp:2587-2622): between(T_icp o pose_latest, pose_closest)"""
+    T, a, b, m = _f64(T_icp, (16,)), _f64(pose_latest, (7,)), _f64(pose_closest, (7,)), np.zeros(7)
+    if load_library().lili_loop_measurement(_ptr(T), _ptr(a), _ptr(b), _ptr(m)) != 0:
+        raise LiliError("lili_loop_measurement: bad argument")
+    return m
+
+
+def correct_poses(solution, keyframe_id_in_frame, slide_window_width, abs_poses, keyframe_poses, f32_positions=False):
+    """correctPoses (L:2177-2311) on copies of the caller's arrays -> dict(abs_poses (n_abs, 7: q wxyz then p), frame_poses (n_frames, 7), keyframe_poses
+    (n_keyframes, 7), last_pose (7, the abs_poses layout), select_pose (3)).  solution: the solved nodes (PoseGraph.poses())."""
+    sol = np.ascontiguousarray(solution, np.float64).reshape(-1, 7)
+    ids = np.ascontiguousarray(keyframe_id_in_frame, np.int32).reshape(-1)
+    ab = np.array(abs_poses, np.float64, order="C").reshape(-1, 7)
+    kf = np.array(keyframe_poses, np.float64, order="C").reshape(-1, 7)
+    if kf.shape[0] != ids.shape[0]:
+        raise LiliError("correct_poses: one keyframe pose per keyframe id")
+    frames, last, sel = np.zeros_like(sol), np.zeros(7), np.zeros(3)
+    rc = load_library().lili_correct_poses(_ptr(sol), sol.shape[0], _ptr(ids), ids.shape[0], int(slide_window_width), 1 if f32_positions else 0, _ptr(ab), ab.shape[0],
+                                           _ptr(frames), _ptr(kf), _ptr(last), _ptr(sel))
+    if rc != 0:
+        raise LiliError("lili_correct_poses: bad argument")
+    return dict(abs_poses=ab, frame_poses=frames, keyframe_poses=kf, last_pose=last, select_pose=sel)
+
+
+class PoseGraph:
+    """The graph of one context: one node per scan, a prior on node 0, chain factors frozen at append time, loop factors."""
+
+    def __init__(self, ctx):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.last_summary = None
+
+    def options(self, **kw):
+        o = PgOptions()
+        self.lib.lili_pg_default_options(C.byref(o))
+        for k, v in kw.items():
+            if k in ("prior_var", "odom_var"):
+                getattr(o, k)[:] = _f64(v, (6,)).tolist()
+            else:
+                setattr(o, k, v)
+        return o
+
+    def reset(self):
+        self.ctx._chk(self.lib.lili_pose_graph_reset(self.ctx.h))
+
+    def info(self):
+        """(nodes, loops)"""
+        n, l = C.c_int(0), C.c_int(0)
+        self.ctx._chk(self.lib.lili_pose_graph_info(self.ctx.h, C.byref(n), C.byref(l)))
+        return n.value, l.value
+
+    def append(self, poses, prev=None):
+        """new nodes at `poses` (n, 7); prev: None on an empty graph, otherwise the last node's pose in the frame of `poses`.  -> the first new id"""
+        p = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        pv = None if prev is None else _f64(prev, (7,))
+        first = C.c_int(-1)
+        self.ctx._chk(self.lib.lili_pose_graph_append(self.ctx.h, _ptr(pv), _ptr(p), p.shape[0], C.byref(first)))
+        return first.value
+
+    def add_loop(self, node_from, node_to, meas, var):
+        m = _f64(meas, (7,))
+        v = np.full(6, float(var)) if np.ndim(var) == 0 else _f64(var, (6,))
+        self.ctx._chk(self.lib.lili_pose_graph_add_loop(self.ctx.h, int(node_from), int(node_to), _ptr(m), _ptr(v)))
+
+    def add_loop_from_icp(self, node_from, node_to, T_icp, pose_latest, pose_closest, fitness):
+        """performLoopClosure's factor (L:2587-2625): the measurement from the ICP transform and the two keyframe poses, all six variances = the fitness"""
+        m = loop_measurement(T_icp, pose_latest, pose_closest)
+        self.add_loop(node_from, node_to, m, float(fitness))
+        return m
+
+    def poses(self, first=0, n=None):
+        n = self.info()[0] - first if n is None else int(n)
+        out = np.zeros((max(n, 0), 7))
+        if n > 0:
+            self.ctx._chk(self.lib.lili_pose_graph_get(self.ctx.h, int(first), n, _ptr(out)))
+        return out
+
+    def set_poses(self, poses, first=0):
+        """overwrite estimates; the measurements stay"""
+        p = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        self.ctx._chk(self.lib.lili_pose_graph_set(self.ctx.h, int(first), p.shape[0], _ptr(p)))
+
+    def evaluate(self, options=None):
+        """-> cost, gradient (N, 6), diagonal blocks (N, 6, 6), sub (N - 1, 6, 6): chain block (i + 1, i), loop blocks (L, 6, 6): block (from, to)"""
+        n, l = self.info()
+        cost, g, D, S, LB = C.c_double(0.0), np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((max(n - 1, 0), 6, 6)), np.zeros((l, 6, 6))
+        self.ctx._chk(self.lib.lili_pose_graph_evaluate(self.ctx.h, C.byref(options) if options is not None else None, C.byref(cost), _ptr(g), _ptr(D),
+                                                        _ptr(S) if n > 1 else None, _ptr(LB) if l else None))
+        return float(cost.value), g, D, S, LB
+
+    def solve(self, options=None, **kw):
+        """Gauss-Newton on the device -> summary dict (iterations, termination, costs, step and gradient norms); the estimates are read with poses()"""
+        if options is None and kw:
+            options = self.options(**kw)
+        s = PgSummary()
+        self.ctx._chk(self.lib.lili_pose_graph_solve(self.ctx.h, C.byref(options) if options is not None else None, C.byref(s)))
+        self.last_summary = s
+        return s.as_dict()
+
+    def kernel_ms(self):
+        ms = C.c_float(0)
+        self.ctx._chk(self.lib.lili_pose_graph_kernel_ms(self.ctx.h, C.byref(ms)))
+        return float(ms.value)
+
+
+__all__ = ["PoseGraph", "correct_poses", "loop_measurement"]
