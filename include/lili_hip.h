@@ -348,6 +348,55 @@ int lili_frontend_reset(lili_ctx* ctx);
  * lili_map_info) or ends a sequence.  Blocking; n_map_raw / n_map optional. */
 int lili_frontend_flush(lili_ctx* ctx, const lili_s2m_params* match, const lili_frontend_options* opt, int32_t* n_map_raw, int32_t* n_map);
 
+/* ---- keyframe hand-over: what LidarOdometry::run does once it has a pose (L/src/LidarOdometry.cpp:565-586, 624-650, 675-680; the same text in R/) ---------------- */
+
+/* The keyframe decision of the odometry node (L:565-585 with the counters of L:325-331, 675-676), host code without a context.  One lili_kf_rule_step per frame, in order, with the
+ * pose the frame ended at (t, q = abs_pose) and whether it was matched (lili_frontend_result.matched; a frame that was not — the early return of L:485-488 — keeps the flag of
+ * the frame before it).  Returns LILI_KF_NO (0), LILI_KF_YES (1: publish /odom and the three clouds, deskewed when if_to_deskew is set) or, for the FIRST call after a reset,
+ * LILI_KF_FIRST (2: checkInitialization, L:201-219 — the clouds go out as they are, never deskewed, and no /odom; `matched` and the pose are not looked at, the flag stays
+ * set as `bool kf = true` leaves it).  The condition is the reference's with its precedence, ((dis > 0.2 || ang > 0.1) && n - kf_num > 1 || n - kf_num > 2) || n <= 1, n =
+ * pose_cloud_frame->points.size() BEFORE this frame's savePoses and kf_num = that size AFTER the savePoses of the last keyframe; ang = 2 acos(w) of quat_last_kF^-1 * q is
+ * NaN for w > 1 and then compares false. */
+enum { LILI_KF_NO = 0, LILI_KF_YES = 1, LILI_KF_FIRST = 2 };
+typedef struct lili_kf_rule_state {
+    double t_last[3], q_last[4];   /* trans_last_kf, quat_last_kF (w, x, y, z) */
+    int64_t n_frames;              /* pose_cloud_frame->points.size() */
+    int64_t kf_num;
+    int32_t kf;                    /* the node's flag */
+    int32_t reserved_;
+} lili_kf_rule_state;
+void lili_kf_rule_reset(lili_kf_rule_state* st);
+int lili_kf_rule_step(lili_kf_rule_state* st, const double t[3], const double q[4], int matched);
+/* computeRelative (L:444-480) in Eigen's order of operations: q_rel = q_prev^-1 * q_cur, t_rel = q_prev^-1 * (t_cur - t_prev), inverse = conjugate / squared norm.
+ * Host code, no context.  LILI_E_ARG for a null pointer. */
+int lili_pose_relative(const double t_prev[3], const double q_prev[4], const double t_cur[3], const double q_cur[4], double t_rel[3], double q_rel[4]);
+
+/* undistortion(cloud, trans, quat) of the odometry node (L:178-199) for up to three clouds in ONE launch.  Per point, with I the float at byte `time_offset[k]` of the row
+ * (intensity = line or ring + time within the scan: 32 in pcl::PointXYZINormal, 16 in pcl::PointXYZI, 12 in the library's float4 rows of the ROT extractor):
+ *     line = (int) I;  ratio = (double)(I - (float) line) / 0.1, at most 1 (no lower bound);  p' = Identity.slerp(ratio, q_rel) * p + ratio * t_rel   in f64, stored as f32.
+ * q_rel NULL or exactly (1, 0, 0, 0) — what publishCloudLast passes — : p' = p + ratio * t_rel, the reference's bits.  Any other q_rel: Eigen 3.3's slerp and q * v.
+ * (int) converts as the reference's x86 build does (NaN and values beyond int: INT_MIN).  A NaN or -inf time channel gives NaN coordinates (+inf clamps to ratio 1); a row with a non-finite coordinate
+ * gives three NaN (Eigen's cross product with it).
+ *   clouds[k]     : NULL or n = 0: nothing for k.  Host (pageable: one staged copy; page-locked: read where it lies) or device memory, any stride that is a multiple of 4;
+ *                   aux_offset = the float that becomes the 4th of the output row (-1: 0) — need not be the time channel (Livox: curvature at 36);
+ *   out[k]        : caller-owned DEVICE buffer of float4 rows (x', y', z', aux): stride 16, mem LILI_MEM_DEVICE, capacity >= clouds[k]->n; count receives n.  The layout
+ *                   lili_voxel_filter, lili_backend_keyframe_prepare and lili_archive_push take.  out[k].data may be clouds[k]->data when that is a device cloud of stride 16.
+ * LILI_E_ARG before anything is enqueued: a stride or offset that is no multiple of 4 or reaches beyond the row, a negative time_offset, capacity too small.
+ * Asynchronous (a pageable host cloud is consumed before the call returns). */
+int lili_keyframe_undistort(lili_ctx* ctx, const lili_cloud* const clouds[3], const int time_offset[3], const double t_rel[3], const double q_rel[4],
+                            lili_feature_out out[3]);
+
+/* publishCloudLast (L:624-650) for the scan of the last lili_frontend_frame / lili_frontend_frame_rot / lili_extract_* on this context (flavour LILI_VARIANT_LIVOX or
+ * LILI_VARIANT_ROT; LILI_E_STATE when there is none): the three clouds the back end receives — /laser_cloud_corner_last, /laser_cloud_surf_last, /full_point_cloud — taken from
+ * the extractor's own device lists (the edge list included, which a Livox frame call does not convert; the true counts after a frame matched with guessed ones) and moved by
+ * undistortion(cloud, t_rel, q_rel) in one launch when `deskew` is set; deskew = 0 (if_to_deskew off, or LILI_KF_FIRST) gives the clouds as they are.  edge / surf / full
+ * receive LILI_MEM_DEVICE clouds of float4 rows (any may be NULL); the 4th float is what lili_extract_*_device carries for edge and surf (Livox: curvature, ROT: intensity) and the
+ * intensity for full.  The views are the library's and stay valid until the next extraction or lili_frontend_keyframe on the context.  Asynchronous.
+ * lili_frontend_keyframe_get copies one of them out (kind 0 = edge, 1 = surf, 2 = full; out->count = its size, at most capacity rows of 16 bytes are written, stride >= 16;
+ * host or device memory).  Blocking. */
+int lili_frontend_keyframe(lili_ctx* ctx, int flavour, const double t_rel[3], const double q_rel[4], int deskew, lili_cloud* edge, lili_cloud* surf, lili_cloud* full);
+int lili_frontend_keyframe_get(lili_ctx* ctx, int kind, lili_feature_out* out);
+
 /* ---- back-end keyframe: everything between "a keyframe has arrived" and ceres::Solve in ONE call ---------------- */
 
 /* Replaces, for one keyframe of the reference's back end (L/src/BackendFusion.cpp:830-980):

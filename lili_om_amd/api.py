@@ -45,6 +45,11 @@ class FrontendOptions(C.Structure):
 
 
 FRAME_SELF_MAP, FRAME_PUSH_EMPTY, FRAME_EXTERNAL_MAP, FRAME_EDGES = 1, 2, 4, 8
+KF_NO, KF_YES, KF_FIRST = 0, 1, 2
+
+
+class KfRuleState(C.Structure):
+    _fields_ = [("t_last", C.c_double * 3), ("q_last", C.c_double * 4), ("n_frames", C.c_int64), ("kf_num", C.c_int64), ("kf", C.c_int32), ("reserved_", C.c_int32)]
 
 
 class FrontendResult(C.Structure):
@@ -258,6 +263,12 @@ _SIGS = {
                                           C.POINTER(FrontendResult)]),
     "lili_backend_keyframe_prepare": (C.c_int, [C.c_void_p, C.POINTER(Cloud), C.POINTER(Cloud), C.c_void_p, C.c_void_p, C.POINTER(Cloud), C.POINTER(Cloud), C.POINTER(C.c_int), C.c_int,
                                                 C.c_void_p, C.c_void_p, C.POINTER(S2MParams), C.POINTER(BackendOptions), C.c_void_p, C.POINTER(BackendResult)]),
+    "lili_kf_rule_reset": (None, [C.POINTER(KfRuleState)]),
+    "lili_kf_rule_step": (C.c_int, [C.POINTER(KfRuleState), C.c_void_p, C.c_void_p, C.c_int]),
+    "lili_pose_relative": (C.c_int, [C.c_void_p] * 6),
+    "lili_keyframe_undistort": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(Cloud)), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.POINTER(FeatureOut)]),
+    "lili_frontend_keyframe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Cloud), C.POINTER(Cloud), C.POINTER(Cloud)]),
+    "lili_frontend_keyframe_get": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FeatureOut)]),
     "lili_frontend_reset": (C.c_int, [C.c_void_p]),
     "lili_frontend_flush": (C.c_int, [C.c_void_p, C.POINTER(S2MParams), C.POINTER(FrontendOptions), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lili_voxel_filter": (C.c_int, [C.c_void_p, C.POINTER(Cloud), C.c_float, C.POINTER(FeatureOut), C.c_void_p]),
@@ -797,6 +808,91 @@ def extract_livox_device(ctx):
     return e, s
 
 
+class KeyframeRule:
+    """The odometry node's keyframe decision (L/src/LidarOdometry.cpp:565-585, 675-676; lili_kf_rule_step): one step() per frame with the pose it ended at.
+    step() returns KF_NO, KF_YES or — the first frame of a sequence, whose clouds go out without deskew and without /odom — KF_FIRST; `flag` is the node's `kf`."""
+
+    def __init__(self):
+        self.lib = load_library()
+        self.st = KfRuleState()
+        self.reset()
+
+    def reset(self):
+        self.lib.lili_kf_rule_reset(C.byref(self.st))
+
+    @property
+    def flag(self):
+        return bool(self.st.kf)
+
+    def step(self, t, q, matched=True):
+        t, q = _f64(t, 3), _f64(q, 4)
+        rc = self.lib.lili_kf_rule_step(C.byref(self.st), _ptr(t), _ptr(q), 1 if matched else 0)
+        if rc < 0:
+            raise LiliError(f"lili_kf_rule_step failed ({rc})")
+        return rc
+
+
+def pose_relative(t_prev, q_prev, t_cur, q_cur):
+    """computeRelative (L/src/LidarOdometry.cpp:444-480): (t_rel, q_rel) of the current pose in the previous one's frame, Eigen's order of operations."""
+    a = [_f64(t_prev, 3), _f64(q_prev, 4), _f64(t_cur, 3), _f64(q_cur, 4)]
+    t, q = np.zeros(3), np.zeros(4)
+    if load_library().lili_pose_relative(*[_ptr(x) for x in a], _ptr(t), _ptr(q)) != OK:
+        raise LiliError("lili_pose_relative failed")
+    return t, q
+
+
+def keyframe_undistort(ctx, clouds, time_offsets, t_rel, q_rel=None, out_ptrs=None):
+    """undistortion(cloud, t_rel, q_rel) (L/src/LidarOdometry.cpp:178-199) of up to three clouds (Cloud or None each) in one launch; time_offsets: the byte
+    offset of the time channel in each cloud's rows.  out_ptrs: device addresses of float4 buffers with room for each cloud (a cloud's own address: in place), or None
+    — the rows then land in torch tensors the returned Clouds keep alive.  Returns three device Clouds (x', y', z', aux).  Asynchronous: ctx.sync() before reading."""
+    arr = (C.POINTER(Cloud) * 3)()
+    offs = (C.c_int * 3)(*[int(v) for v in time_offsets])
+    outs = (FeatureOut * 3)()
+    keep = []
+    for k in range(3):
+        c = clouds[k]
+        n = 0 if c is None else int(c.n)
+        if c is not None:
+            arr[k] = C.pointer(c)
+        if out_ptrs is not None and out_ptrs[k]:
+            outs[k] = FeatureOut(out_ptrs[k], n, 16, MEM_DEVICE, 0)
+            keep.append(None)
+        else:
+            import torch
+            buf = torch.empty((max(n, 1), 4), dtype=torch.float32, device="cuda")
+            outs[k] = FeatureOut(buf.data_ptr(), n, 16, MEM_DEVICE, 0)
+            keep.append(buf)
+    t = _f64(t_rel, 3)
+    q = None if q_rel is None else _f64(q_rel, 4)
+    ctx._chk(ctx.lib.lili_keyframe_undistort(ctx.h, arr, offs, _ptr(t), _ptr(q), outs))
+    res = []
+    for k in range(3):
+        c = Cloud(outs[k].data, outs[k].count, 16, 12, MEM_DEVICE)
+        c._keep = keep[k]
+        res.append(c)
+    return res
+
+
+def frontend_keyframe(ctx, flavour, t_rel=None, q_rel=None, deskew=True):
+    """publishCloudLast (L/src/LidarOdometry.cpp:624-650) for the last frame / extraction of `flavour` (VARIANT_LIVOX or VARIANT_ROT) on the context: (edge, surf, full) device
+    Clouds of float4 rows, valid until the next extraction or keyframe call — usable as new_edge / new_surf of BackendKeyframes.prepare and as `full` of KeyframeArchive.push."""
+    e, s, f = Cloud(), Cloud(), Cloud()
+    t = None if t_rel is None else _f64(t_rel, 3)
+    q = None if q_rel is None else _f64(q_rel, 4)
+    ctx._chk(ctx.lib.lili_frontend_keyframe(ctx.h, int(flavour), _ptr(t), _ptr(q), 1 if deskew else 0, C.byref(e), C.byref(s), C.byref(f)))
+    return e, s, f
+
+
+def frontend_keyframe_get(ctx, kind):
+    """One of the clouds of the last frontend_keyframe (0 edge, 1 surf, 2 full) as (n, 4) float32 rows on the host."""
+    fo = FeatureOut(None, 0, 16, MEM_HOST, 0)
+    ctx._chk(ctx.lib.lili_frontend_keyframe_get(ctx.h, int(kind), C.byref(fo)))
+    out = np.zeros((max(fo.count, 1), 4), np.float32)
+    fo = FeatureOut(out.ctypes.data, out.shape[0], 16, MEM_HOST, 0)
+    ctx._chk(ctx.lib.lili_frontend_keyframe_get(ctx.h, int(kind), C.byref(fo)))
+    return out[:fo.count]
+
+
 def voxel_filter_device(ctx, cloud, leaf, d_out_ptr, capacity):
     """VoxelGrid of a device cloud into a caller-owned device float4 buffer; returns the output device cloud."""
     fo = FeatureOut(d_out_ptr, capacity, 16, MEM_DEVICE, 0)
@@ -1002,6 +1098,13 @@ class FrontendOdometry:
         self.ctx._chk(self.lib.lili_frontend_flush(self.ctx.h, C.byref(self.params), C.byref(self.opt), C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    flavour = VARIANT_LIVOX
+
+    def keyframe(self, t_rel=None, q_rel=None, deskew=True):
+        """The last frame's three clouds as the node's publishCloudLast hands them to the back end (lili_frontend_keyframe): (edge, surf, full) device Clouds, moved by
+        undistortion(cloud, t_rel, q_rel) when deskew is set (the node passes rel_pose's translation and no rotation).  Valid until the next frame."""
+        return frontend_keyframe(self.ctx, self.flavour, t_rel, q_rel, deskew)
+
     def frame(self, scan, t_pred, q_pred, q_imu=(1.0, 0, 0, 0), timing=False):
         """scan: (n,5) float32 rows x, y, z, intensity, curvature (host; page-locked memory is read in place) or a Cloud.  Returns (t, q, info)."""
         if isinstance(scan, Cloud):
@@ -1032,6 +1135,8 @@ class RotFrontendOdometry(FrontendOdometry):
     per spinning-LiDAR scan.  external_map = True: the call for a caller that keeps its own maps (the back end's matcher on one scan, BASELINE configs[0]) — the scan is
     matched against the indices set with ScanToMapMatcher.set_input_cloud, nothing joins the ring; edges = True: the edge features are queries too; leaf_query = 0: the
     surf features themselves are the queries."""
+
+    flavour = VARIANT_ROT
 
     def __init__(self, ctx, params=None, n_scans=64, ds_rate=4, ds_v=0.6, near_range=3.0, q_lb=(1.0, 0, 0, 0), leaf_query=0.4, leaf_map=0.4, width=20, slot=0,
                  scan_match_cnt=6, first_match_cnt=8, reference_startup=True, external_map=False, edges=False):

@@ -192,7 +192,7 @@ struct lili_ctx {
     int rot_atan = 2;            // ROT extractor: 2 = glibc fdlibm float atan / atan2 (the reference build's bits), 1 = f64 functions rounded to f32
     int n_simd = 0;              // SIMDs of the device (CUs x 4)
     // What a module keeps per context, created by its first call (ext_of) and deleted with the context
-    enum { kExtRot, kExtLivox, kExtVoxel /* voxel filter / local-map ring */, kExtLoop, kExtArchive /* keyframe archive and global map */, kExtImu, kExtLocal /* local pose graph */, kExtPoseGraph /* global pose graph */, kExtCount };
+    enum { kExtRot, kExtLivox, kExtVoxel /* voxel filter / local-map ring */, kExtLoop, kExtArchive /* keyframe archive and global map */, kExtImu, kExtLocal /* local pose graph */, kExtPoseGraph /* global pose graph */, kExtKeyframe /* keyframe hand-over: the three published clouds */, kExtCount };
     std::unique_ptr<ExtState> ext[kExtCount];
     bool imu_time = false;                   // option "imu_time": events around k_imu_preintegrate (lili_imu_kernel_ms)
     int archive_max_mb = 0;                  // bound on the archive's slab pool (0: none)
@@ -334,6 +334,11 @@ void lili_extract_rot_prev(lili_ctx* ctx, int* prev_edge, int* prev_surf);
 int lili_extract_rot_complete(lili_ctx* ctx);
 // did the last lili_extract_rot_complete rewrite the lists (second passes)?
 bool lili_extract_rot_redone(lili_ctx* ctx);
+// lili_extract_*.hip -> lili_keyframe.hip: where the last extraction's lists lie, column by column (a Livox list is two float4 arrays: x y z nx | ny nz intensity curvature).
+// src[0] = edge, [1] = surf, [2] = full; `time`: the intensity, `aux`: what the published row carries as its 4th float.  LILI_E_STATE without an extraction.
+struct lili_kf_source { const unsigned char* xyz = nullptr; const unsigned char* time = nullptr; const unsigned char* aux = nullptr; int xyz_stride = 0, time_stride = 0, aux_stride = 0; int n = 0; };
+int lili_extract_livox_kf_sources(lili_ctx* ctx, lili_kf_source src[3]);
+int lili_extract_rot_kf_sources(lili_ctx* ctx, lili_kf_source src[3]);
 // lili_match.hip -> lili_pipeline.hip: a slot sized for a GUESSED number of queries (the producer pads with NaN rows), trimmed once the number is known
 int lili_s2m_set_queries_counted(lili_ctx* ctx, int slot, int kind, int n_guess);
 int lili_s2m_trim_queries(lili_ctx* ctx, int slot, int kind, int n);

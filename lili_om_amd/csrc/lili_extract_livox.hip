@@ -610,6 +610,20 @@ int lili_extract_livox_device(lili_ctx* ctx, lili_cloud* edge, lili_cloud* surf)
 }  // extern "C"
 // (internal, lili_pipeline.hip) convert_edge = false: the edge cloud comes back with its count and NO data — a front-end frame matches surf features only, the edge
 // list's conversion was a launch per frame for nothing
+// (internal, lili_keyframe.hip) the three lists where they lie: x y z in the `a` array, intensity and curvature in the 3rd and 4th float of the `b` array
+int lili_extract_livox_kf_sources(lili_ctx* ctx, lili_kf_source src[3]) {
+    if (!ctx) return LILI_E_ARG;
+    auto* B = livox_of(ctx);
+    if (!B->have) return ctx->fail(LILI_E_STATE, "frontend_keyframe: no Livox extraction on this context yet");
+    const DevBuf* a[3] = {&B->edge_a, &B->surf_a, &B->cut_a};
+    const DevBuf* b[3] = {&B->edge_b, &B->surf_b, &B->cut_b};
+    const int n[3] = {B->host.n_edge, B->host.n_surf, B->host.n_cut};
+    for (int k = 0; k < 3; k++) {
+        src[k].xyz = a[k]->as<unsigned char>(); src[k].time = b[k]->as<unsigned char>() + 8; src[k].aux = b[k]->as<unsigned char>() + (k == 2 ? 8 : 12);
+        src[k].xyz_stride = src[k].time_stride = src[k].aux_stride = 16; src[k].n = n[k];
+    }
+    return LILI_OK;
+}
 int lili_extract_livox_device_ex(lili_ctx* ctx, lili_cloud* edge, lili_cloud* surf, bool convert_edge) {
     if (!ctx) return LILI_E_ARG;
     auto* B = livox_of(ctx);

@@ -1914,3 +1914,17 @@ int lili_extract_rot_device(lili_ctx* ctx, lili_cloud* full, lili_cloud* edge, l
 }
 
 }  // extern "C"
+
+// (internal, lili_keyframe.hip) the three lists where they lie: float4 rows x y z intensity, the intensity both the time channel and the published 4th float
+int lili_extract_rot_kf_sources(lili_ctx* ctx, lili_kf_source src[3]) {
+    if (!ctx) return LILI_E_ARG;
+    auto* R = rot_of(ctx);
+    if (!R->have) return ctx->fail(LILI_E_STATE, "frontend_keyframe: no ROT extraction on this context yet");
+    const DevBuf* a[3] = {&R->edge_pts, &R->surf, &R->full};
+    const int n[3] = {R->host.n_edge, R->host.n_surf, R->host.n_full};
+    for (int k = 0; k < 3; k++) {
+        src[k].xyz = a[k]->as<unsigned char>(); src[k].time = src[k].aux = a[k]->as<unsigned char>() + 12;
+        src[k].xyz_stride = src[k].time_stride = src[k].aux_stride = 16; src[k].n = n[k];
+    }
+    return LILI_OK;
+}

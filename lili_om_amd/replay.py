@@ -12,7 +12,8 @@ Livox configuration, one scan in flight like the reference's `ros::spin` nodes.
 The scan queue follows Preprocessing::cloudHandler (L/src/Preprocessing.cpp:194-215): scan k is processed when scan
 k+2 has arrived, `time_scan_next` = stamp of scan k+1, and only once IMU data reaches that time.  The pose prediction
 is the constant-velocity model of poseInitialization (L/src/LidarOdometry.cpp:415-480).  This is replay tooling around
-the C ABI — the reference's keyframe selection, back-end and loop closure are not part of it."""
+the C ABI.  With keyframes=True the node's keyframe decision and hand-over run too (lili_kf_rule_step, lili_pose_relative, lili_frontend_keyframe: the
+clouds the back end receives, device-resident); the back-end and loop closure are the caller's (on_keyframe)."""
 import numpy as np
 
 from . import api as A
@@ -30,8 +31,10 @@ def _predict(poses):
 
 
 def replay(bag_path, ctx, lidar_topic="/livox/lidar", imu_topic="/imu", first_pose=None, n_outer=6, n_outer_first=12,
-           map_width=20, leaf=0.4, max_scans=None, on_frame=None, staged=False):
-    """Returns a list of dicts (stamp, t, q, n_surf, n_edge, n_query, q_imu) — one per processed scan."""
+           map_width=20, leaf=0.4, max_scans=None, on_frame=None, staged=False, keyframes=False, deskew=False, on_keyframe=None):
+    """Returns a list of dicts (stamp, t, q, n_surf, n_edge, n_query, q_imu) — one per processed scan.  keyframes=True: every record gains `is_kf` (the node's keyframe
+    flag, L/src/LidarOdometry.cpp:565-585) and `rel` = (t_rel, q_rel) of computeRelative, and on_keyframe(rec, edge, surf, full) is called for every keyframe with the three
+    device clouds of publishCloudLast (deskewed by rel's translation when `deskew`, never on the first frame), valid until the next scan is processed."""
     P = A.make_params("frontend")
     ex = A.LivoxExtractor(ctx)
     matcher = A.ScanToMapMatcher(ctx, P)
@@ -42,6 +45,19 @@ def replay(bag_path, ctx, lidar_topic="/livox/lidar", imu_topic="/imu", first_po
     imu_t, imu_w = [], []
     queue, out, poses = [], [], []
     bag = rosbag.Bag(bag_path)
+    rule = A.KeyframeRule() if keyframes else None
+
+    def hand_over(rec, matched):
+        """the seam of LidarOdometry::run behind savePoses: computeRelative, the keyframe flag, publishCloudLast"""
+        if len(poses) > 1:
+            rec["rel"] = A.pose_relative(poses[-2][0], poses[-2][1], poses[-1][0], poses[-1][1])
+        else:
+            rec["rel"] = (np.zeros(3), np.array([1.0, 0, 0, 0]))
+        verdict = rule.step(rec["t"], rec["q"], matched)
+        rec["is_kf"] = verdict != A.KF_NO
+        if rec["is_kf"] and on_keyframe:
+            edge, surf, full = A.frontend_keyframe(ctx, A.VARIANT_LIVOX, rec["rel"][0], None, deskew and verdict == A.KF_YES)
+            on_keyframe(rec, edge, surf, full)
 
     def process(stamp, pts5, t_next):
         q_imu = imu.integrate(np.array(imu_t), np.array(imu_w).reshape(-1, 3), t_next)
@@ -55,6 +71,8 @@ def replay(bag_path, ctx, lidar_topic="/livox/lidar", imu_topic="/imu", first_po
             #  joined the ring at; the staged path below does the same, so trajectory, next prediction and local map agree on such frames)
             poses.append((t, q))
             rec = dict(stamp=stamp, t=t, q=q, n_surf=info["n_surf"], n_edge=info["n_edge"], n_query=info["n_query"], q_imu=q_imu)
+            if keyframes:
+                hand_over(rec, info["matched"])
             out.append(rec)
             if on_frame:
                 on_frame(rec)
@@ -62,10 +80,12 @@ def replay(bag_path, ctx, lidar_topic="/livox/lidar", imu_topic="/imu", first_po
         f = ex.extract(pts5, q_imu)
         surf = np.ascontiguousarray(f["surf"][:, [0, 1, 2, 7]])
         qry, _ = A.voxel_filter(ctx, surf, leaf) if surf.shape[0] else (surf, None)
+        matched = False
         if not poses:
             t, q = first_pose if first_pose is not None else (np.zeros(3), np.array([1.0, 0, 0, 0]))
             t, q = np.asarray(t, np.float64), np.asarray(q, np.float64)
         else:
+            matched = True
             t0, q0 = _predict(poses)
             local.commit()
             matcher.set_queries(0, A.KIND_SURF, qry)
@@ -75,6 +95,8 @@ def replay(bag_path, ctx, lidar_topic="/livox/lidar", imu_topic="/imu", first_po
         poses.append((t, q))
         local.push(qry, t, q)
         rec = dict(stamp=stamp, t=t, q=q, n_surf=int(f["surf"].shape[0]), n_edge=int(f["edge"].shape[0]), n_query=int(qry.shape[0]), q_imu=q_imu)
+        if keyframes:
+            hand_over(rec, matched)
         out.append(rec)
         if on_frame:
             on_frame(rec)
