@@ -130,6 +130,8 @@ int lili_set_debug(lili_ctx* ctx, int keep_neighbors);
  *   archive / map "archive_max_mb" (bound on the keyframe archive's slab pool in MiB; 0 = unlimited, the default; a push beyond it fails), "archive_slab_mb" (size of
  *                 one slab in MiB, default 64; a keyframe larger than a slab gets a slab of its own), "global_map_batch_points" (points lili_global_map places,
  *                 sorts and folds at a time, 1024 .. 2^27, default 2^21: about 100 bytes of work buffers per point next to the table).
+ *   pose graph    "pose_graph_max_loops" (loops the global pose graph accepts, LILI_PG_MAX_LOOPS .. LILI_PG_MAX_LOOPS_EXT, default LILI_PG_MAX_LOOPS; may be
+ *                 raised at any time, lowering it below the graph's loop count is LILI_E_STATE; graphs that fit the default solve to the same bits either way).
  * One knob that DOES choose between two definitions of a result: "rot_atan" — lili_extract_rot's atan / atan2 on float arguments
  * (R/src/Preprocessing.cpp:285-288,315,349): 2 (default) = glibc's float routines statement for statement (atanf / atan2f of
  * every glibc up to 2.40 — the bits a build of the reference produces), 1 = the f64 functions rounded to f32 (libm-independent). */
@@ -927,18 +929,25 @@ int lili_local_graph_kernel_ms(lili_ctx* ctx, float* ms);
  *                            max_iterations (LILI_LM_MAX_ITERATIONS) end it.  summary: iterations = steps computed; cost[k], step_inf[k] = the candidate's cost and
  *                            |delta|inf of iteration k, grad_inf[k] = |g|inf at its linearisation (the first 16).  The elimination is a one-level nested
  *                            dissection: separators = every loop endpoint and every node id that is a multiple of LILI_PG_SEGMENT; the stretches between them are
- *                            eliminated side by side, the reduced system (<= 768 unknowns) by one workgroup.  Every launch of the solve is enqueued up front; one
- *                            synchronisation, one read-back; blocking.  The same graph gives the same bits on every run.
+ *                            eliminated side by side; the reduced system over the separators is factored by one workgroup up to 768 unknowns and by a blocked
+ *                            Cholesky over the whole chip beyond (tiles of 96 unknowns: diagonal tile, panel, trailing update on the f64 matrix units; the two
+ *                            substitutions tile by tile).  Every launch of the solve is enqueued up front; one synchronisation, one read-back; blocking.  The
+ *                            same graph gives the same bits on every run, and a graph of <= 768 reduced unknowns the same bits whatever "pose_graph_max_loops" is.
  *                            The reference's isam->update(graph); isam->update() is nearest to max_iterations = 2.
  * lili_pose_graph_kernel_ms — device time of the last lili_pose_graph_solve's launches in milliseconds; LILI_E_STATE when there is none.
  *
+ * Loops.  A graph takes LILI_PG_MAX_LOOPS loops by default; lili_set_option(ctx, "pose_graph_max_loops", v) with v in LILI_PG_MAX_LOOPS .. LILI_PG_MAX_LOOPS_EXT
+ * moves that bound (any time; LILI_E_STATE when the graph already holds more than v loops).  The tables and work arrays follow the graph's actual size; the dense
+ * reduced system takes 8 (6 K)^2 bytes for K separators (K <= 64 + 2 loops): 4.7 MB at 32 loops, 1.3 GB at 1024 loops (12 672 unknowns).
+ *
  * LILI_E_ARG, with every output and the graph untouched: a null pointer (ctx, poses, meas, var, summary, cost, gradient, diag; sub / loop_blocks where they have
  * entries), a non-finite input, a quaternion more than 1e-6 from unit norm, a non-positive variance, from == to, an id or a range outside the graph, n < 1,
- * more than LILI_PG_MAX_NODES nodes or LILI_PG_MAX_LOOPS loops, append with prev != NULL on an empty graph or prev == NULL on a non-empty one, max_iterations
+ * more than LILI_PG_MAX_NODES nodes or "pose_graph_max_loops" (default LILI_PG_MAX_LOOPS) loops, append with prev != NULL on an empty graph or prev == NULL on a non-empty one, max_iterations
  * outside 1 .. 1000, a tolerance that is negative or not finite.  LILI_E_STATE: evaluate / solve on an empty graph. */
 #define LILI_PG_MAX_NODES 32768
-#define LILI_PG_MAX_LOOPS 32
-#define LILI_PG_SEGMENT 512                /* fixed separators sit at multiples of it: 64 + 2 x 32 separators = 768 reduced unknowns at the caps */
+#define LILI_PG_MAX_LOOPS 32               /* the default of option "pose_graph_max_loops" */
+#define LILI_PG_MAX_LOOPS_EXT 1024         /* the largest value of option "pose_graph_max_loops" */
+#define LILI_PG_SEGMENT 512                /* fixed separators sit at multiples of it: 64 + 2 x 32 separators = 768 reduced unknowns at the default caps */
 #define LILI_PG_MAX_LOG 16
 #define LILI_PG_SMALL_ANGLE 0.1
 #define LILI_PG_COST_INCREASED 7           /* termination, next to the LILI_LM_* codes */

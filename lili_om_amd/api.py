@@ -132,6 +132,9 @@ class LocalGraphSummary(C.Structure):
 
 
 PG_MAX_NODES, PG_MAX_LOOPS, PG_SEGMENT, PG_MAX_LOG, PG_COST_INCREASED = 32768, 32, 512, 16, 7
+PG_MAX_LOOPS_EXT = 1024      # LILI_PG_MAX_LOOPS_EXT: the largest value of option "pose_graph_max_loops" (default PG_MAX_LOOPS)
+PG_MAX_REDUCED = 768         # reduced unknowns (6 per separator) one workgroup factors; beyond, the blocked solve in tiles of PG_REDUCED_TILE (lili_kernels.h: kPgMaxReduced, kPgTile)
+PG_REDUCED_TILE = 96
 
 
 class PgOptions(C.Structure):

@@ -241,6 +241,11 @@ int lili_set_option(lili_ctx* ctx, const char* name, int value) {
         if (value < 1024 || value > (1 << 27)) return ctx->fail(LILI_E_ARG, "global_map_batch_points must be in 1024..2^27");
         ctx->global_map_batch_points = value; return LILI_OK;
     }
+    if (std::strcmp(name, "pose_graph_max_loops") == 0) {      // any time; the graph's tables and work arrays follow its actual size
+        if (value < LILI_PG_MAX_LOOPS || value > LILI_PG_MAX_LOOPS_EXT) return ctx->fail(LILI_E_ARG, "pose_graph_max_loops must be in LILI_PG_MAX_LOOPS..LILI_PG_MAX_LOOPS_EXT");
+        if (value < ctx->pose_graph_loops) return ctx->fail(LILI_E_STATE, "pose_graph_max_loops: the graph holds more loops than that");
+        ctx->pose_graph_max_loops = value; return LILI_OK;
+    }
     if (std::strcmp(name, "max_cells") == 0) { if (value < 1) return ctx->fail(LILI_E_ARG, "max_cells must be positive"); ctx->max_cells = value; return LILI_OK; }
     return ctx->fail(LILI_E_ARG, std::string("unknown option ") + name);
 }

@@ -218,6 +218,8 @@ struct lili_ctx {
         int32_t kind[3 * LILI_WINDOW_MAX_KF] = {}, kf[3 * LILI_WINDOW_MAX_KF] = {};
     } win_res_tab;
     bool local_graph_time = false;           // option "local_graph_time": events around k_local_graph (lili_local_graph_kernel_ms)
+    int pose_graph_max_loops = LILI_PG_MAX_LOOPS;      // option "pose_graph_max_loops": where lili_pose_graph_add_loop refuses
+    int pose_graph_loops = 0;                // the global pose graph's loop count (lili_pose_graph.hip keeps it): the option is not lowered below it
 };
 
 #define HIPCHK(expr)                                                                                         \

@@ -217,21 +217,34 @@ struct LocalGraphOut {
 };
 // Global pose graph (lili_pose_graph.hip).  Factor f of N nodes and L loops: 0 = the prior on node 0, 1 .. N - 1 = the chain factor (f - 1, f),
 // N + l = loop l.  Separator k is node sep[k]; segment k = the nodes between separator k and separator k + 1 (or the end of the chain).
-constexpr int kPgMaxNodes = LILI_PG_MAX_NODES, kPgMaxLoops = LILI_PG_MAX_LOOPS, kPgSegment = LILI_PG_SEGMENT;
-constexpr int kPgMaxSep = kPgMaxNodes / kPgSegment + 2 * kPgMaxLoops, kPgMaxReduced = 6 * kPgMaxSep;
+constexpr int kPgMaxNodes = LILI_PG_MAX_NODES, kPgMaxLoops = LILI_PG_MAX_LOOPS, kPgMaxLoopsExt = LILI_PG_MAX_LOOPS_EXT, kPgSegment = LILI_PG_SEGMENT;
+constexpr int kPgMaxReduced = 768;   // reduced unknowns one workgroup factors (k_pg_reduced_solve): 6 x (64 + 2 x 32 separators), the default caps; beyond, the blocked solve
 constexpr int kPgWide = 1024;        // threads of the single-workgroup stages (gate, reduced system, retract and cost)
 constexpr int kPgCols = 13;          // columns a segment carries through its elimination: the right-hand side, 6 of its left separator, 6 of its right one
 constexpr int kPgGram = kPgCols * kPgCols;
-static_assert(kPgMaxReduced <= 768 && kPgMaxReduced <= kPgWide, "the reduced system is factored by one workgroup, one row per thread");
+static_assert(6 * (kPgMaxNodes / kPgSegment + 2 * kPgMaxLoops) <= kPgMaxReduced && kPgMaxReduced <= kPgWide, "at the default caps the reduced system is factored by one workgroup, one row per thread");
+// The blocked reduced solve: tiles of kPgTile unknowns (a multiple of 6: a separator never straddles two tiles, and of 16: the f64 matrix instruction's edge),
+// the trailing update's operands staged kPgTileK columns at a time, rows padded to kPgTileLd doubles (stride = 32 banks mod 64: the four k-rows a wave reads
+// at once fall on two disjoint halves of the banks)
+constexpr int kPgTile = 96, kPgTileK = 16, kPgTileLd = kPgTile + 16;
+static_assert(kPgTile % 6 == 0 && kPgTile % 16 == 0 && kPgTile % kPgTileK == 0 && kPgTileK % 4 == 0, "tile edge");
 struct PgLoop { int from, to, sep_from, sep_to; double meas[7], w[6]; };      // w = 1 / sqrt(variance)
 struct PgSeg { int left, first, last, right; };      // separator node ids (right = -1: the chain ends first), interior nodes first .. last (first > last: none)
+struct PgBlock { int p, q, begin, end; };            // a block (p, q), p >= q, of the reduced system that can be non-zero; its loops = ent[begin .. end)
+// The fixed part, then the arrays that follow the graph (device pointers into one staged block).  An entry of a loop list is 2 l + side: in node_ent, side 1 =
+// the node is loop l's `to`; in blk_ent, side 1 = the loop's (from, to) block is the transpose of block (p, q).  Every list is in loop order.
 struct PgTables {
     int n, n_loops, n_sep, max_iter;
     double function_tolerance, gradient_tolerance, parameter_tolerance;
     double w_prior[6], w_odom[6];
-    int sep[kPgMaxSep];
-    PgSeg seg[kPgMaxSep];
-    PgLoop loop[kPgMaxLoops];
+    int n_blk, reserved_;
+    const int* sep;                  // n_sep
+    const PgSeg* seg;                // n_sep
+    const PgLoop* loop;              // n_loops
+    const int* node_ptr;             // n + 1: node i's loops = node_ent[node_ptr[i] .. node_ptr[i + 1])
+    const int* node_ent;             // 2 n_loops
+    const PgBlock* blk;              // n_blk: the diagonal blocks, the blocks of adjacent separators, then the other pairs joined by a loop
+    const int* blk_ent;              // n_loops
 };
 struct PgState {
     int done, fail;                  // done: the termination word — every later launch returns at its first instruction; fail: a segment met a non-positive pivot
@@ -248,6 +261,7 @@ struct PgDev {
     double *Ld, *Ls, *Y;             // per eliminated node: Cholesky factor of its pivot block (36), L block (i + 1, i) (36), the carried columns (6 x 13, column by column)
     double *gram;                    // per segment: sum of Y^T Y (13 x 13)
     double *red, *delta;             // the reduced system's lower triangle, column by column ([col * n + row]); the step (6 N)
+    double *rhs;                     // the blocked solve's right-hand side in the reduced system's own order (6 n_sep)
 };
 struct ImuOutDev {                   // lili_window_imu's numbers, then the prediction
     double sum_dt, g[3], delta_p[3], delta_q[4], delta_v[3], lin_ba[3], lin_bg[3], jacobian[225], covariance[225];

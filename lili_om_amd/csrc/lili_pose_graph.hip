@@ -1,18 +1,26 @@
 // Global pose graph over every frame (include/lili_hip.h: lili_pose_graph*): what saveKeyFramesAndFactors, performLoopClosure and correctPoses
 // (L/src/BackendFusion.cpp:1820-1889, 2587-2633, 2177-2311) hand to GTSAM, as a batch Gauss-Newton solve on the device, f64, no contraction.
 //
-// One iteration is eight launches, every one enqueued up front; none waits for another workgroup, every loop is bounded by the graph's size:
+// One iteration is nine launches (more with the blocked reduced solve), every one enqueued up front; none waits for another workgroup, every loop is bounded by the graph's size:
 //   k_pg_linearize         two lanes per factor: the even one the weighted residual and the Jacobian block of the factor's first node, the odd one the second node's;
 //   k_pg_assemble          one lane per entry of H and g, by gather: a node sums its <= 2 chain contributions, then its loop contributions in loop order;
 //   k_pg_gate              one workgroup: |g|inf (and, before the first step, the cost) in a fixed order; sets the termination word at the gradient tolerance;
 //   k_pg_eliminate         one wave per segment: 6 x 6-block Cholesky along the chain between two separators, lane c carrying column c of
 //                          [L block^T | g | columns of the left separator | columns of the right separator] through the forward substitution, and the 13 x 13
 //                          Gram of the carried columns — the segment's Schur contribution;
-//   k_pg_reduced_assemble  one workgroup per block of the reduced system over the separators: diagonal, Schur terms, loop blocks in loop order;
-//   k_pg_reduced_solve     one workgroup: dense left-looking Cholesky (one row per thread, fixed-order sums) and the two substitutions;
+//   k_pg_zero              the reduced system's storage cleared;
+//   k_pg_reduced_assemble  one workgroup per block of the reduced system over the separators that can be non-zero (diagonal, adjacent separators, pairs joined
+//                          by a loop): diagonal, Schur terms, loop blocks in loop order;
+//   k_pg_reduced_solve     up to kPgMaxReduced unknowns.  One workgroup: dense left-looking Cholesky (one row per thread, fixed-order sums) and the two substitutions;
+//   k_pg_chol_*            beyond.  A right-looking blocked Cholesky in tiles of kPgTile unknowns, per tile column k three launches: _diag (one workgroup factors
+//                          the diagonal tile in LDS, checks the pivots, solves its piece of L y = b), _panel (one workgroup per row tile below: L_ik = A_ik L_kk^-T,
+//                          and b_i -= L_ik y_k), _update (one workgroup per lower-triangle tile: A_ij -= L_ik L_jk^T on v_mfma_f64_16x16x4_f64, operands staged in
+//                          LDS); then per tile row i, last first, _back: every workgroup solves x_i = L_ii^-T y_i on the same bits, workgroup k < i takes
+//                          L_ik^T x_i off y_k, workgroup i writes the step.  Every tile and every piece of b has one owner per launch and sums over k ascending;
 //   k_pg_backsub           one wave per segment, every lane the same arithmetic: the interior nodes' step from the separators';
 //   k_pg_retract_cost      one workgroup: the candidate, its cost in a fixed order, the accept / stop decision, the termination word.
-// No atomics anywhere: H, g, the cost and the step are pure functions of the graph.
+// No atomics anywhere: H, g, the cost and the step are pure functions of the graph.  The tables (separators, segments, loops, the loops of each node and of each
+// reduced block) and the work arrays follow the graph's size: the reduced system takes 8 (6 K)^2 bytes, 1.3 GB at 1024 loops (K = 2112).
 #include "lili_launch.h"
 #include "lili_device_math.h"
 
@@ -21,6 +29,7 @@
 #include <cstddef>
 #include <cstring>
 #include <string>
+#include <vector>
 
 namespace lili {
 
@@ -211,10 +220,10 @@ __global__ __launch_bounds__(256) void k_pg_assemble(const PgDev G) {
         const int r = e / 6, c = e - 6 * r;
         double v = pg_atb(Jb, Jb, r, c);
         if (next) v += pg_atb(Ja, Ja, r, c);
-        for (int l = 0; l < L; l++) {
-            const double* Jl = G.fJ + (size_t)(n + l) * 72;
-            if (T.loop[l].from == i) v += pg_atb(Jl, Jl, r, c);
-            if (T.loop[l].to == i) v += pg_atb(Jl + 36, Jl + 36, r, c);
+        for (int u = T.node_ptr[i]; u < T.node_ptr[i + 1]; u++) {      // in loop order
+            const int en = T.node_ent[u];
+            const double* Jl = G.fJ + (size_t)(n + (en >> 1)) * 72 + 36 * (en & 1);
+            v += pg_atb(Jl, Jl, r, c);
         }
         G.D[(size_t)i * 36 + e] = v;
     } else if (e < 72) {
@@ -224,11 +233,9 @@ __global__ __launch_bounds__(256) void k_pg_assemble(const PgDev G) {
         const int c = e - 72;
         double v = pg_atv(Jb, G.fr + (size_t)i * 6, c);
         if (next) v += pg_atv(Ja, G.fr + (size_t)(i + 1) * 6, c);
-        for (int l = 0; l < L; l++) {
-            const double* Jl = G.fJ + (size_t)(n + l) * 72;
-            const double* rl = G.fr + (size_t)(n + l) * 6;
-            if (T.loop[l].from == i) v += pg_atv(Jl, rl, c);
-            if (T.loop[l].to == i) v += pg_atv(Jl + 36, rl, c);
+        for (int u = T.node_ptr[i]; u < T.node_ptr[i + 1]; u++) {
+            const int en = T.node_ent[u], l = en >> 1;
+            v += pg_atv(G.fJ + (size_t)(n + l) * 72 + 36 * (en & 1), G.fr + (size_t)(n + l) * 6, c);
         }
         G.g[(size_t)i * 6 + c] = v;
     }
@@ -372,13 +379,21 @@ __global__ __launch_bounds__(64) void k_pg_eliminate(const PgDev G) {
     if (!ok && c == 0) G.st->fail = 1;
 }
 
-// block (p, q), p >= q, of the reduced system over the separators, and (block (p, p)) its right-hand side g_p minus the Schur terms, kept in delta's rows of the separators
+__global__ __launch_bounds__(256) void k_pg_zero(const PgDev G) {
+    if (G.st->done) return;
+    const size_t nr = 6 * (size_t)G.tab->n_sep, n2 = nr * nr / 2;      // nr is even
+    double2* R = reinterpret_cast<double2*>(G.red);
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n2; e += (size_t)gridDim.x * blockDim.x) R[e] = double2{0.0, 0.0};
+}
+
+// block (p, q), p >= q, of the reduced system over the separators, and (block (p, p)) its right-hand side g_p minus the Schur terms, kept in delta's rows of the
+// separators (and, for the blocked solve, in rhs).  One workgroup per entry of T.blk; every other block stays at k_pg_zero's zeros.
 __global__ __launch_bounds__(64) void k_pg_reduced_assemble(const PgDev G) {
     if (G.st->done) return;
     const PgTables& T = *G.tab;
-    const int K = T.n_sep, nr = 6 * K;
-    const int p = blockIdx.x / K, q = blockIdx.x - K * p;
-    if (p < q) return;
+    const int nr = 6 * T.n_sep;
+    const PgBlock B = T.blk[blockIdx.x];
+    const int p = B.p, q = B.q;
     const int t = threadIdx.x;
     const int sp = T.sep[p], sq = T.sep[q];
     const bool seg_p = T.seg[p].first <= T.seg[p].last;                       // the segment to the right of separator p has nodes
@@ -394,9 +409,9 @@ __global__ __launch_bounds__(64) void k_pg_reduced_assemble(const PgDev G) {
             if (T.seg[q].first <= T.seg[q].last) v = -G.gram[(size_t)q * kPgGram + (7 + r) * kPgCols + (1 + c)];
             else v = G.S[(size_t)sq * 36 + t];
         }
-        for (int l = 0; l < T.n_loops; l++) {
-            if (T.loop[l].sep_from == p && T.loop[l].sep_to == q) v += G.LB[36 * l + 6 * r + c];
-            if (T.loop[l].sep_to == p && T.loop[l].sep_from == q) v += G.LB[36 * l + 6 * c + r];
+        for (int u = B.begin; u < B.end; u++) {      // in loop order
+            const int en = T.blk_ent[u], l = en >> 1;
+            v += (en & 1) ? G.LB[36 * l + 6 * c + r] : G.LB[36 * l + 6 * r + c];
         }
         G.red[(size_t)(6 * q + c) * nr + (6 * p + r)] = v;
     } else if (t < 42 && p == q) {
@@ -405,6 +420,7 @@ __global__ __launch_bounds__(64) void k_pg_reduced_assemble(const PgDev G) {
         if (seg_p) v -= G.gram[(size_t)p * kPgGram + (1 + r) * kPgCols];
         if (seg_l) v -= G.gram[(size_t)(p - 1) * kPgGram + (7 + r) * kPgCols];
         G.delta[(size_t)sp * 6 + r] = v;
+        if (G.rhs) G.rhs[6 * p + r] = v;
     }
 }
 
@@ -453,6 +469,217 @@ __global__ __launch_bounds__(kPgWide) void k_pg_reduced_solve(const PgDev G) {
         __syncthreads();
     }
     if (i < nr) G.delta[(size_t)T.sep[i / 6] * 6 + i % 6] = -sy[i];
+}
+
+// ---- the blocked reduced solve (6 n_sep > kPgMaxReduced).  red holds the lower triangle column by column: element (r, c), r >= c, at red[c * nr + r].  Tile (i, j)
+// covers rows i T .. and columns j T ..; the last tile row / column may overhang the matrix: its loads read zeros, its stores are masked.
+__device__ __forceinline__ int pg_tri(const int r, const int c) { return r * (r + 1) / 2 + c; }      // the packed lower triangle of a tile in LDS, r >= c
+constexpr int kPgPanelCols = 32;      // columns of its row a panel thread holds in registers at a time
+static_assert(kPgTile % kPgPanelCols == 0, "panel columns");
+
+// Tile column k: L_kk = chol(A_kk) in LDS (right-looking, element (r, c) takes its updates over j ascending), then y_k = L_kk^-1 b_k.  A non-positive pivot, or a
+// segment's (PgState::fail), ends the solve.
+__global__ __launch_bounds__(256) void k_pg_chol_diag(const PgDev G, const int k) {
+    if (G.st->done) return;
+    __shared__ double sL[kPgTile * (kPgTile + 1) / 2], sb[kPgTile];
+    const int nr = 6 * G.tab->n_sep, o = k * kPgTile, m = min(kPgTile, nr - o), t = threadIdx.x;
+    double* R = G.red;
+    for (int e = t; e < m * m; e += 256) {
+        const int c = e / m, r = e - c * m;
+        if (r >= c) sL[pg_tri(r, c)] = R[(size_t)(o + c) * nr + (o + r)];
+    }
+    if (t < m) sb[t] = G.rhs[o + t];
+    bool ok = G.st->fail == 0;
+    __syncthreads();
+    // 16 x 16 threads over the triangle: thread (ty, tx) owns the elements (r, c) = (tx + 16 b, ty + 16 a) with c <= r < m, at fixed places of the packed triangle
+    constexpr int kSpan = kPgTile / 16;
+    int trr[kSpan], cc[kSpan];
+#pragma unroll
+    for (int u = 0; u < kSpan; u++) { const int r = (t & 15) + 16 * u; trr[u] = r < m ? r * (r + 1) / 2 : -1; cc[u] = (t >> 4) + 16 * u; }
+    for (int j = 0; j < m && ok; j++) {
+        const double piv = sL[pg_tri(j, j)];
+        ok = piv > 0.0;      // (the same value in every thread)
+        const double l = sqrt(piv);
+        for (int r = j + 1 + t; r < m; r += 256) sL[pg_tri(r, j)] = sL[pg_tri(r, j)] / l;
+        __syncthreads();
+        if (t == 0) sL[pg_tri(j, j)] = l;      // (nobody reads it before the factor is complete)
+        // the trailing update of column j: a thread's reads first, then its writes
+        double lc[kSpan], lr[kSpan], cur[kSpan][kSpan];
+#pragma unroll
+        for (int u = 0; u < kSpan; u++) {
+            lc[u] = cc[u] > j && cc[u] < m ? sL[pg_tri(cc[u], j)] : 0.0;
+            lr[u] = trr[u] >= 0 && (t & 15) + 16 * u > j ? sL[trr[u] + j] : 0.0;
+        }
+#pragma unroll
+        for (int a = 0; a < kSpan; a++)
+#pragma unroll
+            for (int b = 0; b < kSpan; b++) cur[a][b] = cc[a] > j && trr[b] >= 0 && (t & 15) + 16 * b >= cc[a] ? sL[trr[b] + cc[a]] : 0.0;
+#pragma unroll
+        for (int a = 0; a < kSpan; a++)
+#pragma unroll
+            for (int b = 0; b < kSpan; b++)
+                if (cc[a] > j && trr[b] >= 0 && (t & 15) + 16 * b >= cc[a]) sL[trr[b] + cc[a]] = cur[a][b] - lr[b] * lc[a];
+        __syncthreads();
+    }
+    if (!ok) {
+        if (t == 0) { G.st->s.termination = LILI_LM_NUMERICAL_FAILURE; G.st->done = 1; }
+        return;
+    }
+    for (int e = t; e < m * m; e += 256) {
+        const int c = e / m, r = e - c * m;
+        if (r >= c) R[(size_t)(o + c) * nr + (o + r)] = sL[pg_tri(r, c)];
+    }
+    for (int j = 0; j < m; j++) {      // L y = b
+        const double yj = sb[j] / sL[pg_tri(j, j)];
+        __syncthreads();
+        if (t == j) sb[j] = yj;
+        else if (t > j && t < m) sb[t] -= sL[pg_tri(t, j)] * yj;
+        __syncthreads();
+    }
+    if (t < m) G.rhs[o + t] = sb[t];
+}
+
+// Row tile i = k + 1 + blockIdx.x of tile column k, one thread per row: x L_kk^T = a by forward substitution over the columns (the row stays in memory, in place), then
+// b_i -= L_ik y_k
+__global__ __launch_bounds__(128) void k_pg_chol_panel(const PgDev G, const int k) {
+    if (G.st->done) return;
+    __shared__ double sL[kPgTile * (kPgTile + 1) / 2], sy[kPgTile];
+    const int nr = 6 * G.tab->n_sep, o = k * kPgTile, i = k + 1 + blockIdx.x, t = threadIdx.x;
+    double* R = G.red;
+    for (int e = t; e < kPgTile * kPgTile; e += 128) {      // tile column k is not the last one: it is whole
+        const int c = e / kPgTile, r = e - c * kPgTile;
+        if (r >= c) sL[pg_tri(r, c)] = R[(size_t)(o + c) * nr + (o + r)];
+    }
+    if (t < kPgTile) sy[t] = G.rhs[o + t];
+    __syncthreads();
+    const int row = i * kPgTile + t;
+    if (t >= kPgTile || row >= nr) return;
+    double* X = R + (size_t)o * nr + row;      // element c of the row at X[c * nr]
+    double b = G.rhs[row];
+    for (int c0 = 0; c0 < kPgTile; c0 += kPgPanelCols) {      // kPgPanelCols columns at a time in registers; every element sums over q ascending
+        double v[kPgPanelCols];
+#pragma unroll
+        for (int c = 0; c < kPgPanelCols; c++) v[c] = X[(size_t)(c0 + c) * nr];
+#pragma unroll 4
+        for (int q = 0; q < c0; q++) {
+            const double xq = X[(size_t)q * nr];
+#pragma unroll
+            for (int c = 0; c < kPgPanelCols; c++) v[c] -= xq * sL[pg_tri(c0 + c, q)];
+        }
+#pragma unroll
+        for (int c = 0; c < kPgPanelCols; c++) {
+#pragma unroll
+            for (int q = 0; q < c; q++) v[c] -= v[q] * sL[pg_tri(c0 + c, c0 + q)];
+            v[c] = v[c] / sL[pg_tri(c0 + c, c0 + c)];
+        }
+#pragma unroll
+        for (int c = 0; c < kPgPanelCols; c++) { X[(size_t)(c0 + c) * nr] = v[c]; b -= v[c] * sy[c0 + c]; }
+    }
+    G.rhs[row] = b;
+}
+
+// Lower-triangle tile (i, j), k < j <= i, of the trailing matrix: A_ij -= L_ik L_jk^T.  The matrix instruction's rows are the tile's COLUMNS (operand A = L_jk), its
+// columns the tile's rows (operand B = L_ik^T), so that a lane's 16 neighbours store 16 consecutive doubles.  Four waves, each a 48 x 48 quarter as 3 x 3
+// instruction tiles; the f64 result map: column = lane & 15, row = (lane >> 4) + 4 reg.  The sum over the kPgTile columns of tile column k runs in ascending order.
+typedef double pg_d4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void k_pg_chol_update(const PgDev G, const int k) {
+    if (G.st->done) return;
+    __shared__ double sA[kPgTileK * kPgTileLd], sB[kPgTileK * kPgTileLd];
+    const int nr = 6 * G.tab->n_sep, t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
+    const int b = blockIdx.x;
+    int ii = (int)((sqrtf(8.f * (float)b + 1.f) - 1.f) * 0.5f);
+    while (ii * (ii + 1) / 2 > b) ii--;
+    while ((ii + 1) * (ii + 2) / 2 <= b) ii++;
+    const int i = k + 1 + ii, j = k + 1 + (b - ii * (ii + 1) / 2);
+    const bool live = !(i == j && wm > wn);      // a quarter above the diagonal of a diagonal tile
+    double* R = G.red;
+    pg_d4 acc[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) acc[a][c] = pg_d4{0.0, 0.0, 0.0, 0.0};
+    // the operands of a chunk travel memory -> registers -> LDS; the next chunk's loads are in flight while this one is multiplied
+    constexpr int kPer = kPgTileK * kPgTile / 256;
+    static_assert(kPgTileK * kPgTile % 256 == 0, "whole rounds of the 256 threads");
+    double pa[kPer], pb[kPer];
+    auto fetch = [&](const int kc) {
+#pragma unroll
+        for (int u = 0; u < kPer; u++) {
+            const int e = t + 256 * u, kk = e / kPgTile, r = e - kk * kPgTile;
+            const size_t col = (size_t)(k * kPgTile + kc + kk) * nr;
+            const int rj = j * kPgTile + r, ri = i * kPgTile + r;
+            pa[u] = rj < nr ? R[col + rj] : 0.0;
+            pb[u] = ri < nr ? R[col + ri] : 0.0;
+        }
+    };
+    fetch(0);
+    for (int kc = 0; kc < kPgTile; kc += kPgTileK) {
+        __syncthreads();      // the previous chunk has been read
+#pragma unroll
+        for (int u = 0; u < kPer; u++) {
+            const int e = t + 256 * u, kk = e / kPgTile, r = e - kk * kPgTile;
+            sA[kk * kPgTileLd + r] = pa[u];
+            sB[kk * kPgTileLd + r] = pb[u];
+        }
+        __syncthreads();
+        if (kc + kPgTileK < kPgTile) fetch(kc + kPgTileK);
+        if (live) {
+#pragma unroll
+            for (int k4 = 0; k4 < kPgTileK; k4 += 4) {
+                const int kq = (k4 + (lane >> 4)) * kPgTileLd + (lane & 15);
+                double a[3], c[3];
+#pragma unroll
+                for (int u = 0; u < 3; u++) { a[u] = sA[kq + wm * 48 + 16 * u]; c[u] = sB[kq + wn * 48 + 16 * u]; }
+#pragma unroll
+                for (int u = 0; u < 3; u++)
+#pragma unroll
+                    for (int v = 0; v < 3; v++) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], c[v], acc[u][v], 0, 0, 0);
+            }
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int u = 0; u < 3; u++)
+#pragma unroll
+        for (int v = 0; v < 3; v++)
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                const int c = j * kPgTile + wm * 48 + 16 * u + (lane >> 4) + 4 * reg, r = i * kPgTile + wn * 48 + 16 * v + (lane & 15);
+                if (r < nr && c < nr && r >= c) { double* e = R + (size_t)c * nr + r; *e = *e - acc[u][v][reg]; }
+            }
+}
+
+// Tile row i (launched last row first), workgroup kb = blockIdx.x <= i: every workgroup solves L_ii^T x_i = y_i in LDS on the same bits; workgroup kb < i takes
+// L_(i, kb)^T x_i off y_kb (its own piece of rhs), workgroup i writes the separators' step -x_i
+__global__ __launch_bounds__(128) void k_pg_chol_back(const PgDev G, const int i) {
+    if (G.st->done) return;
+    __shared__ double sL[kPgTile * (kPgTile + 1) / 2], sx[kPgTile];
+    const PgTables& T = *G.tab;
+    const int nr = 6 * T.n_sep, o = i * kPgTile, m = min(kPgTile, nr - o), t = threadIdx.x, kb = blockIdx.x;
+    const double* R = G.red;
+    for (int e = t; e < m * m; e += 128) {
+        const int c = e / m, r = e - c * m;
+        if (r >= c) sL[pg_tri(r, c)] = R[(size_t)(o + c) * nr + (o + r)];
+    }
+    if (t < m) sx[t] = G.rhs[o + t];
+    __syncthreads();
+    for (int c = m - 1; c >= 0; c--) {
+        const double xc = sx[c] / sL[pg_tri(c, c)];
+        __syncthreads();
+        if (t == c) sx[c] = xc;
+        else if (t < c) sx[t] -= sL[pg_tri(c, t)] * xc;
+        __syncthreads();
+    }
+    if (kb == i) {
+        if (t < m) G.delta[(size_t)T.sep[(o + t) / 6] * 6 + (o + t) % 6] = -sx[t];
+        return;
+    }
+    if (t >= kPgTile) return;
+    const int col = kb * kPgTile + t;      // tile column kb < i is whole
+    const double* Lc = R + (size_t)col * nr + o;
+    double y = G.rhs[col];
+    for (int r = 0; r < m; r++) y -= Lc[r] * sx[r];
+    G.rhs[col] = y;
 }
 
 __global__ __launch_bounds__(64) void k_pg_backsub(const PgDev G) {
@@ -550,8 +777,8 @@ namespace {
 
 struct PoseGraphState : ExtState {
     int n = 0, n_loops = 0;
-    PgLoop loops[kPgMaxLoops];
-    DevBuf X, Xn, meas, tab, st, stage, fr, fJ, g, D, S, LB, Ld, Ls, Y, gram, red, delta;
+    std::vector<PgLoop> loops;
+    DevBuf X, Xn, meas, tab, tabv, st, stage, fr, fJ, g, D, S, LB, Ld, Ls, Y, gram, red, delta, rhs;
     PinBuf h_tab, h_io;
     Event ev0, ev1;
     float last_ms = -1.f;
@@ -561,29 +788,31 @@ struct PoseGraphState : ExtState {
         HIPCHK(meas.ensure(sizeof(double) * 7 * kPgMaxNodes));
         HIPCHK(tab.ensure(sizeof(PgTables)));
         HIPCHK(st.ensure(sizeof(PgState)));
-        HIPCHK(h_tab.ensure(sizeof(PgTables) + sizeof(PgState)));
         return LILI_OK;
     }
-    // the work arrays of an evaluation (solve: and of the elimination) for the current sizes
+    // the work arrays of an evaluation (solve: and of the elimination) for the current sizes.  The reduced system is dense: 8 (6 n_sep)^2 bytes, 4.7 MB at the
+    // default caps (128 separators), 1.3 GB at LILI_PG_MAX_LOOPS_EXT loops (2112 separators, 12 672 unknowns)
     int work(lili_ctx* ctx, int n_sep, bool solve) {
-        const size_t N = (size_t)n, F = (size_t)n + kPgMaxLoops, d = sizeof(double);
+        const size_t N = (size_t)n, F = (size_t)n + (size_t)n_loops, d = sizeof(double);
         HIPCHK(fr.ensure(F * 6 * d)); HIPCHK(fJ.ensure(F * 72 * d));
-        HIPCHK(g.ensure(N * 6 * d)); HIPCHK(D.ensure(N * 36 * d)); HIPCHK(S.ensure(N * 36 * d)); HIPCHK(LB.ensure((size_t)kPgMaxLoops * 36 * d));
+        HIPCHK(g.ensure(N * 6 * d)); HIPCHK(D.ensure(N * 36 * d)); HIPCHK(S.ensure(N * 36 * d)); HIPCHK(LB.ensure((size_t)std::max(n_loops, 1) * 36 * d));
         if (solve) {
             HIPCHK(Xn.ensure(N * 7 * d));
             HIPCHK(Ld.ensure(N * 36 * d)); HIPCHK(Ls.ensure(N * 36 * d)); HIPCHK(Y.ensure(N * 6 * kPgCols * d));
-            HIPCHK(gram.ensure((size_t)kPgMaxSep * kPgGram * d));
+            HIPCHK(gram.ensure((size_t)n_sep * kPgGram * d));
             HIPCHK(red.ensure((size_t)36 * n_sep * n_sep * d));
             HIPCHK(delta.ensure(N * 6 * d));
+            if (6 * n_sep > kPgMaxReduced) HIPCHK(rhs.ensure((size_t)6 * n_sep * d));
         }
         return LILI_OK;
     }
-    PgDev dev() const {
+    PgDev dev(int n_sep) const {
         PgDev G{};
         G.tab = tab.as<PgTables>(); G.st = st.as<PgState>();
         G.X = X.as<double>(); G.Xn = Xn.as<double>(); G.meas = meas.as<double>();
         G.fr = fr.as<double>(); G.fJ = fJ.as<double>(); G.g = g.as<double>(); G.D = D.as<double>(); G.S = S.as<double>(); G.LB = LB.as<double>();
         G.Ld = Ld.as<double>(); G.Ls = Ls.as<double>(); G.Y = Y.as<double>(); G.gram = gram.as<double>(); G.red = red.as<double>(); G.delta = delta.as<double>();
+        G.rhs = 6 * n_sep > kPgMaxReduced ? rhs.as<double>() : nullptr;
         return G;
     }
 };
@@ -614,37 +843,114 @@ int check_options(lili_ctx* ctx, const lili_pg_options* options, lili_pg_options
         ARGCHK(std::isfinite(opt->prior_var[k]) && std::isfinite(opt->odom_var[k]) && opt->prior_var[k] > 0 && opt->odom_var[k] > 0, "pose_graph: a variance is not positive and finite");
     return LILI_OK;
 }
-// the tables of a solve / an evaluation in the page-locked block, the state behind them; returns the number of separators
-int fill_tables(PoseGraphState* P, const lili_pg_options& opt) {
+// the tables of a solve / an evaluation in the page-locked block: the fixed part, the state, then the arrays that follow the graph (PgTables' pointers are their
+// addresses in tabv); *n_sep, *n_blk = the number of separators and of reduced blocks
+struct PgLayout { size_t loop, seg, blk, sep, node_ptr, node_ent, blk_ent, bytes; };
+int fill_tables(lili_ctx* ctx, PoseGraphState* P, const lili_pg_options& opt, PgLayout* lay, int* n_sep, int* n_blk) {
+    const int n = P->n, L = P->n_loops;
+    std::vector<int> sep;
+    sep.reserve((size_t)n / kPgSegment + 1 + 2 * (size_t)L);
+    for (int s = 0; s < n; s += kPgSegment) sep.push_back(s);
+    for (const PgLoop& l : P->loops) { sep.push_back(l.from); sep.push_back(l.to); }
+    std::sort(sep.begin(), sep.end());
+    sep.erase(std::unique(sep.begin(), sep.end()), sep.end());
+    const int K = (int)sep.size();
+    // the loops of every pair of separators (p > q), in loop order
+    struct Ent { int p, q, en; };
+    std::vector<Ent> ents((size_t)L);
+    std::vector<int> sf((size_t)L), stt((size_t)L);
+    for (int l = 0; l < L; l++) {
+        sf[l] = (int)(std::lower_bound(sep.begin(), sep.end(), P->loops[l].from) - sep.begin());
+        stt[l] = (int)(std::lower_bound(sep.begin(), sep.end(), P->loops[l].to) - sep.begin());
+        ents[l] = sf[l] > stt[l] ? Ent{sf[l], stt[l], 2 * l} : Ent{stt[l], sf[l], 2 * l + 1};
+    }
+    std::sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) { return a.p != b.p ? a.p < b.p : a.q != b.q ? a.q < b.q : a.en < b.en; });
+    std::vector<PgBlock> blk;
+    blk.reserve((size_t)2 * K + L);
+    for (int p = 0; p < K; p++) blk.push_back(PgBlock{p, p, 0, 0});
+    for (int q = 0; q + 1 < K; q++) blk.push_back(PgBlock{q + 1, q, 0, 0});
+    for (int u = 0; u < L;) {
+        int e = u;
+        while (e < L && ents[e].p == ents[u].p && ents[e].q == ents[u].q) e++;
+        if (ents[u].p == ents[u].q + 1) { blk[(size_t)K + ents[u].q].begin = u; blk[(size_t)K + ents[u].q].end = e; }
+        else blk.push_back(PgBlock{ents[u].p, ents[u].q, u, e});
+        u = e;
+    }
+    const int NB = (int)blk.size();
+    auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
+    PgLayout& o = *lay;
+    o.loop = 0;
+    o.seg = o.loop + up8(sizeof(PgLoop) * (size_t)L);
+    o.blk = o.seg + up8(sizeof(PgSeg) * (size_t)K);
+    o.sep = o.blk + up8(sizeof(PgBlock) * (size_t)NB);
+    o.node_ptr = o.sep + up8(sizeof(int) * (size_t)K);
+    o.node_ent = o.node_ptr + up8(sizeof(int) * ((size_t)n + 1));
+    o.blk_ent = o.node_ent + up8(sizeof(int) * 2 * (size_t)L);
+    o.bytes = o.blk_ent + up8(sizeof(int) * (size_t)L) + 8;
+    HIPCHK(P->h_tab.ensure(sizeof(PgTables) + sizeof(PgState) + o.bytes));
+    HIPCHK(P->tabv.ensure(o.bytes));
     PgTables* T = P->h_tab.as<PgTables>();
     std::memset(T, 0, sizeof *T);
-    T->n = P->n; T->n_loops = P->n_loops; T->max_iter = opt.max_iterations;
+    T->n = n; T->n_loops = L; T->n_sep = K; T->n_blk = NB; T->max_iter = opt.max_iterations;
     T->function_tolerance = opt.function_tolerance; T->gradient_tolerance = opt.gradient_tolerance; T->parameter_tolerance = opt.parameter_tolerance;
     for (int k = 0; k < 6; k++) { T->w_prior[k] = 1.0 / std::sqrt(opt.prior_var[k]); T->w_odom[k] = 1.0 / std::sqrt(opt.odom_var[k]); }
-    int K = 0;
-    for (int s = 0; s < P->n; s += kPgSegment) T->sep[K++] = s;
-    for (int l = 0; l < P->n_loops; l++) { T->sep[K++] = P->loops[l].from; T->sep[K++] = P->loops[l].to; }
-    std::sort(T->sep, T->sep + K);
-    K = (int)(std::unique(T->sep, T->sep + K) - T->sep);
-    for (int k = 0; k < K; k++) {
-        const bool more = k + 1 < K;
-        T->seg[k] = PgSeg{T->sep[k], T->sep[k] + 1, more ? T->sep[k + 1] - 1 : P->n - 1, more ? T->sep[k + 1] : -1};
-    }
-    for (int l = 0; l < P->n_loops; l++) {
-        T->loop[l] = P->loops[l];
-        T->loop[l].sep_from = (int)(std::lower_bound(T->sep, T->sep + K, P->loops[l].from) - T->sep);
-        T->loop[l].sep_to = (int)(std::lower_bound(T->sep, T->sep + K, P->loops[l].to) - T->sep);
-    }
-    T->n_sep = K;
     PgState* S = reinterpret_cast<PgState*>(T + 1);
     std::memset(S, 0, sizeof *S);
-    S->s.n_nodes = P->n; S->s.n_loops = P->n_loops;
-    return K;
-}
-int upload_tables(lili_ctx* ctx, PoseGraphState* P) {
-    HIPCHK(hipMemcpyAsync(P->tab.p, P->h_tab.p, sizeof(PgTables), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(P->st.p, P->h_tab.as<PgTables>() + 1, sizeof(PgState), hipMemcpyHostToDevice, ctx->stream));
+    S->s.n_nodes = n; S->s.n_loops = L;
+    char* hv = reinterpret_cast<char*>(S + 1);
+    const char* dv = P->tabv.as<char>();
+    std::memset(hv, 0, o.bytes);
+    PgLoop* h_loop = reinterpret_cast<PgLoop*>(hv + o.loop);
+    PgSeg* h_seg = reinterpret_cast<PgSeg*>(hv + o.seg);
+    int* h_sep = reinterpret_cast<int*>(hv + o.sep);
+    int* h_np = reinterpret_cast<int*>(hv + o.node_ptr);
+    int* h_ne = reinterpret_cast<int*>(hv + o.node_ent);
+    int* h_be = reinterpret_cast<int*>(hv + o.blk_ent);
+    for (int k = 0; k < K; k++) {
+        const bool more = k + 1 < K;
+        h_sep[k] = sep[k];
+        h_seg[k] = PgSeg{sep[k], sep[k] + 1, more ? sep[k + 1] - 1 : n - 1, more ? sep[k + 1] : -1};
+    }
+    for (int l = 0; l < L; l++) { h_loop[l] = P->loops[l]; h_loop[l].sep_from = sf[l]; h_loop[l].sep_to = stt[l]; }
+    if (NB) std::memcpy(hv + o.blk, blk.data(), sizeof(PgBlock) * (size_t)NB);
+    for (int l = 0; l < L; l++) h_be[l] = ents[l].en;
+    // the loops of every node, in loop order: counts, offsets, entries
+    for (int l = 0; l < L; l++) { h_np[P->loops[l].from + 1]++; h_np[P->loops[l].to + 1]++; }
+    for (int i = 0; i < n; i++) h_np[i + 1] += h_np[i];
+    {
+        std::vector<int> fill(sep.size(), 0);      // only separators have loops
+        for (int l = 0; l < L; l++) {
+            h_ne[h_np[P->loops[l].from] + fill[sf[l]]++] = 2 * l;
+            h_ne[h_np[P->loops[l].to] + fill[stt[l]]++] = 2 * l + 1;
+        }
+    }
+    T->loop = reinterpret_cast<const PgLoop*>(dv + o.loop); T->seg = reinterpret_cast<const PgSeg*>(dv + o.seg); T->blk = reinterpret_cast<const PgBlock*>(dv + o.blk);
+    T->sep = reinterpret_cast<const int*>(dv + o.sep); T->node_ptr = reinterpret_cast<const int*>(dv + o.node_ptr);
+    T->node_ent = reinterpret_cast<const int*>(dv + o.node_ent); T->blk_ent = reinterpret_cast<const int*>(dv + o.blk_ent);
+    *n_sep = K; *n_blk = NB;
     return LILI_OK;
+}
+int upload_tables(lili_ctx* ctx, PoseGraphState* P, const PgLayout& lay) {
+    const PgTables* T = P->h_tab.as<PgTables>();
+    const PgState* S = reinterpret_cast<const PgState*>(T + 1);
+    HIPCHK(hipMemcpyAsync(P->tab.p, T, sizeof(PgTables), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(P->st.p, S, sizeof(PgState), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(P->tabv.p, S + 1, lay.bytes, hipMemcpyHostToDevice, ctx->stream));
+    return LILI_OK;
+}
+// the reduced system's solve of one iteration: one workgroup up to kPgMaxReduced unknowns, the blocked Cholesky and its substitutions beyond
+void launch_reduced_solve(lili_ctx* ctx, const PgDev& G, const int n_sep) {
+    const int nr = 6 * n_sep;
+    if (nr <= kPgMaxReduced) { hipLaunchKernelGGL(k_pg_reduced_solve, dim3(1), dim3(kPgWide), 0, ctx->stream, G); return; }
+    const int nt = (nr + kPgTile - 1) / kPgTile;
+    for (int k = 0; k < nt; k++) {
+        hipLaunchKernelGGL(k_pg_chol_diag, dim3(1), dim3(256), 0, ctx->stream, G, k);
+        const int w = nt - k - 1;
+        if (w == 0) break;
+        hipLaunchKernelGGL(k_pg_chol_panel, dim3(w), dim3(128), 0, ctx->stream, G, k);
+        hipLaunchKernelGGL(k_pg_chol_update, dim3(w * (w + 1) / 2), dim3(256), 0, ctx->stream, G, k);
+    }
+    for (int i = nt - 1; i >= 0; i--) hipLaunchKernelGGL(k_pg_chol_back, dim3(i + 1), dim3(128), 0, ctx->stream, G, i);
 }
 void launch_linearize(lili_ctx* ctx, const PoseGraphState* P, const PgDev& G) {
     const int F = P->n + P->n_loops;
@@ -715,6 +1021,8 @@ int lili_pose_graph_reset(lili_ctx* ctx) {
     if (!ctx) return LILI_E_ARG;
     PoseGraphState* P = pg_of(ctx);
     P->n = 0; P->n_loops = 0;
+    P->loops.clear();
+    ctx->pose_graph_loops = 0;
     return LILI_OK;
 }
 
@@ -755,14 +1063,15 @@ int lili_pose_graph_add_loop(lili_ctx* ctx, int from, int to, const double meas[
     PoseGraphState* P = pg_of(ctx);
     ARGCHK(meas && var, "pose_graph_add_loop: null argument");
     ARGCHK(from >= 0 && from < P->n && to >= 0 && to < P->n && from != to, "pose_graph_add_loop: from / to must be two different nodes of the graph");
-    ARGCHK(P->n_loops < kPgMaxLoops, "pose_graph_add_loop: more than LILI_PG_MAX_LOOPS loops");
+    ARGCHK(P->n_loops < ctx->pose_graph_max_loops, "pose_graph_add_loop: more than LILI_PG_MAX_LOOPS loops");      // (option "pose_graph_max_loops")
     ARGCHK(finite_n(var, 6), "pose_graph_add_loop: an input is not finite");
     for (int k = 0; k < 6; k++) ARGCHK(var[k] > 0, "pose_graph_add_loop: a variance is not positive");
     PgLoop l{};
     TRY(check_poses(ctx, "pose_graph_add_loop", meas, 1, l.meas));
     l.from = from; l.to = to;
     for (int k = 0; k < 6; k++) l.w[k] = 1.0 / std::sqrt(var[k]);
-    P->loops[P->n_loops++] = l;
+    P->loops.push_back(l);
+    ctx->pose_graph_loops = P->n_loops = (int)P->loops.size();
     return LILI_OK;
 }
 
@@ -807,9 +1116,11 @@ int lili_pose_graph_evaluate(lili_ctx* ctx, const lili_pg_options* options, doub
     const size_t N = (size_t)P->n, L = (size_t)P->n_loops, d = sizeof(double);
     const size_t o_g = 0, o_D = o_g + 6 * N, o_S = o_D + 36 * N, o_L = o_S + 36 * N, total = o_L + 36 * L;
     HIPCHK(P->h_io.ensure(total * d));
-    fill_tables(P, opt);
-    TRY(upload_tables(ctx, P));
-    const PgDev G = P->dev();
+    PgLayout lay;
+    int K = 0, NB = 0;
+    TRY(fill_tables(ctx, P, opt, &lay, &K, &NB));
+    TRY(upload_tables(ctx, P, lay));
+    const PgDev G = P->dev(0);
     launch_linearize(ctx, P, G);
     hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 1);
     HIPCHK(hipGetLastError());
@@ -838,18 +1149,22 @@ int lili_pose_graph_solve(lili_ctx* ctx, const lili_pg_options* options, lili_pg
     if (P->n == 0) return ctx->fail(LILI_E_STATE, "pose_graph_solve: the graph is empty");
     HIPCHK(hipSetDevice(ctx->device));
     TRY(P->persist(ctx));
-    const int K = fill_tables(P, opt);
+    PgLayout lay;
+    int K = 0, NB = 0;
+    TRY(fill_tables(ctx, P, opt, &lay, &K, &NB));
     TRY(P->work(ctx, K, true));
-    TRY(upload_tables(ctx, P));
-    const PgDev G = P->dev();
+    TRY(upload_tables(ctx, P, lay));
+    const PgDev G = P->dev(K);
+    const int zero_blocks = (int)std::min<size_t>(2048, ((size_t)18 * K * K + 255) / 256);
     HIPCHK(P->ev0.get(hipEventDefault)); HIPCHK(P->ev1.get(hipEventDefault));
     HIPCHK(hipEventRecord(P->ev0, ctx->stream));
     for (int it = 0; it < opt.max_iterations; it++) {
         launch_linearize(ctx, P, G);
         hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 0);
         hipLaunchKernelGGL(k_pg_eliminate, dim3(K), dim3(64), 0, ctx->stream, G);
-        hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(K * K), dim3(64), 0, ctx->stream, G);
-        hipLaunchKernelGGL(k_pg_reduced_solve, dim3(1), dim3(kPgWide), 0, ctx->stream, G);
+        hipLaunchKernelGGL(k_pg_zero, dim3(zero_blocks), dim3(256), 0, ctx->stream, G);
+        hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(NB), dim3(64), 0, ctx->stream, G);
+        launch_reduced_solve(ctx, G, K);
         hipLaunchKernelGGL(k_pg_backsub, dim3(K), dim3(64), 0, ctx->stream, G);
         hipLaunchKernelGGL(k_pg_retract_cost, dim3(1), dim3(kPgWide), 0, ctx->stream, G);
     }

@@ -55,11 +55,18 @@ def correct_poses(solution, keyframe_id_in_frame, slide_window_width, abs_poses,
 
 
 class PoseGraph:
-    """The graph of one context: one node per scan, a prior on node 0, chain factors frozen at append time, loop factors."""
+    """The graph of one context: one node per scan, a prior on node 0, chain factors frozen at append time, loop factors.
+    max_loops: the context's option "pose_graph_max_loops" (api.PG_MAX_LOOPS .. api.PG_MAX_LOOPS_EXT; None leaves it as it is, api.PG_MAX_LOOPS unless it was set)."""
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, max_loops=None):
         self.ctx, self.lib = ctx, ctx.lib
         self.last_summary = None
+        if max_loops is not None:
+            self.set_max_loops(max_loops)
+
+    def set_max_loops(self, max_loops):
+        """raise (any time) or lower (not below the graph's loop count) the number of loops add_loop accepts"""
+        self.ctx.set_option("pose_graph_max_loops", int(max_loops))
 
     def options(self, **kw):
         o = PgOptions()
