@@ -972,6 +972,40 @@ int lili_pose_graph_set(lili_ctx* ctx, int first, int n, const double* poses);
 int lili_pose_graph_evaluate(lili_ctx* ctx, const lili_pg_options* options, double* cost, double* gradient, double* diag, double* sub, double* loop_blocks);
 int lili_pose_graph_solve(lili_ctx* ctx, const lili_pg_options* options, lili_pg_summary* summary);
 int lili_pose_graph_kernel_ms(lili_ctx* ctx, float* ms);
+/* Marginal covariances (gtsam: marginalCovariance / jointMarginalCovariance).  Sigma = H^-1 with H = J^T J of the graph as it is, linearised at the current
+ * estimates: the matrix whose blocks lili_pose_graph_evaluate returns.  Only the variances of `options` are read (NULL = the defaults).  No step is taken: estimates
+ * and measurements are untouched, and a following solve gives the bytes it would have given without the call.  A block is a row-major 6 x 6 in the node's own tangent
+ * (omega, v), rotation first, under X (+) xi above — gtsam::Pose3's convention, the one prior_var / odom_var are expressed in.
+ *   cov   (n x 36):        Sigma(i, i), i = first .. first + n - 1; n may be 0 with cov NULL.  A sub-range equals the slice of the full result bit for bit.
+ *   cross (n_pairs x 36):  Sigma(i, j) of pairs[2 k], pairs[2 k + 1], rows: node i, columns: node j; n_pairs <= LILI_PG_MAX_PAIRS, NULL / 0 for none.  A pair may
+ *                          repeat, take either order (the two blocks are transposes bit for bit) and have i == j (the diagonal block).
+ *   info  (optional):      status 0 or LILI_LM_NUMERICAL_FAILURE, the graph's sizes, the reduced system's unknowns, the device time of the call's launches.
+ * The call repeats the front half of a solve iteration — linearise, assemble, eliminate the segments, assemble and factor the reduced system over the separators,
+ * whatever |g|inf is — and adds the inverse side: the reduced inverse S^-1 (one workgroup per separator: six unit columns through L and L^T, tile by tile; only its
+ * lower triangle is kept and read), then per segment, last node first, W = -L_II^-T Y_E, the diagonal blocks P of the segment's own inverse, and
+ * Sigma(i, i) = P_i + W_i Sigma_sep W_i^T with Sigma_sep the joint block of the segment's two separators; a separator's block is its block of S^-1; a pair is
+ * W_i Sigma_sep(i),sep(j) W_j^T, plus a substitution along the segment when both nodes are interior nodes of one segment.  Every launch is enqueued up front, one
+ * synchronisation, outputs through page-locked staging; no atomics, every sum in a fixed order: the same graph gives the same bytes on every run, and a graph of
+ * <= 768 reduced unknowns the same bytes whatever "pose_graph_max_loops" is.  Memory, allocated by the first call: a second dense array of the reduced system's size
+ * (8 (6 K)^2 bytes: 4.7 MB at 32 loops, 1.3 GB at 1024 loops), 144 doubles per node and the outputs.
+ * LILI_E_ARG, nothing written: a null pointer where entries are expected, a range or an id outside the graph, n < 0, n_pairs < 0 or > LILI_PG_MAX_PAIRS, n == 0
+ * together with n_pairs == 0, a variance that is not positive and finite.  LILI_E_STATE: an empty graph.  A non-positive pivot (H is not positive definite in
+ * double precision): info->status = LILI_LM_NUMERICAL_FAILURE, LILI_E_NUMERIC, cov and cross untouched. */
+#define LILI_PG_MAX_PAIRS 4096
+typedef struct lili_pg_marginals_info {
+    int32_t status;            /* 0, or LILI_LM_NUMERICAL_FAILURE (a non-positive pivot: no output written) */
+    int32_t n_nodes, n_loops, reduced_unknowns;
+    float   kernel_ms;         /* device time of this call's launches */
+    int32_t reserved_;
+} lili_pg_marginals_info;
+int lili_pose_graph_marginals(lili_ctx* ctx, const lili_pg_options* options, int first, int n, double* cov, const int32_t* pairs, int n_pairs, double* cross,
+                              lili_pg_marginals_info* info);
+/* First-order covariance of between(X_i, X_j) in its own tangent, host side, no context:
+ * J_a Sigma_ii J_a^T + J_a Sigma_ij J_b^T + J_b Sigma_ij^T J_a^T + J_b Sigma_jj J_b^T with the between-factor's Jacobians at Z = between(X_i, X_j) (zero residual):
+ * J_b = I, J_a = [-R_Z^T, 0; R_Z^T [t_Z]x, -R_Z^T].  cov_ij = Sigma(i, j), rows: node i.  On a zero-residual chain the result for (i, i + 1) is diag(odom_var).
+ * LILI_E_ARG (cov_rel untouched): a null pointer, a non-finite input, a quaternion more than 1e-6 from unit norm. */
+int lili_pose_relative_covariance(const double pose_i[7], const double pose_j[7], const double cov_ii[36], const double cov_jj[36], const double cov_ij[36],
+                                  double cov_rel[36]);
 /* The loop factor's measurement (L:2587-2615), host side, no context: T_icp (row-major 4 x 4) corrects the latest keyframe's pose, meas = between(T_icp o
  * pose_latest, pose_closest) with both quaternions normalised.  LILI_E_ARG: a null pointer, a non-finite input, a zero quaternion. */
 int lili_loop_measurement(const double T_icp[16], const double pose_latest[7], const double pose_closest[7], double meas[7]);

@@ -153,6 +153,16 @@ class PgSummary(C.Structure):
                     final_cost=self.final_cost, cost=list(self.cost[:k]), step_inf=list(self.step_inf[:k]), grad_inf=list(self.grad_inf[:kg]))
 
 
+PG_MAX_PAIRS = 4096          # LILI_PG_MAX_PAIRS: pairs one lili_pose_graph_marginals call takes
+
+
+class PgMarginalsInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_nodes", C.c_int32), ("n_loops", C.c_int32), ("reduced_unknowns", C.c_int32), ("kernel_ms", C.c_float), ("reserved_", C.c_int32)]
+
+    def as_dict(self):
+        return dict(status=self.status, n_nodes=self.n_nodes, n_loops=self.n_loops, reduced_unknowns=self.reduced_unknowns, kernel_ms=float(self.kernel_ms))
+
+
 class WindowPrior(C.Structure):
     _fields_ = [("n_rows", C.c_int32), ("n_cols", C.c_int32), ("n_blocks", C.c_int32), ("reserved_", C.c_int32), ("block_kind", C.POINTER(C.c_int32)),
                 ("block_keyframe", C.POINTER(C.c_int32)), ("x0", C.POINTER(C.c_double)), ("J0", C.POINTER(C.c_double)), ("r0", C.POINTER(C.c_double))]
@@ -357,6 +367,8 @@ _SIGS = {
     "lili_pose_graph_evaluate": (C.c_int, [C.c_void_p, C.POINTER(PgOptions), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_pose_graph_solve": (C.c_int, [C.c_void_p, C.POINTER(PgOptions), C.POINTER(PgSummary)]),
     "lili_pose_graph_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "lili_pose_graph_marginals": (C.c_int, [C.c_void_p, C.POINTER(PgOptions), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PgMarginalsInfo)]),
+    "lili_pose_relative_covariance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_loop_measurement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_correct_poses": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_marg_add_lidar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),

@@ -262,6 +262,11 @@ struct PgDev {
     double *gram;                    // per segment: sum of Y^T Y (13 x 13)
     double *red, *delta;             // the reduced system's lower triangle, column by column ([col * n + row]); the step (6 N)
     double *rhs;                     // the blocked solve's right-hand side in the reduced system's own order (6 n_sep)
+    // lili_pose_graph_marginals only (null in a solve / an evaluation)
+    double *sinv;                    // the reduced system's inverse, laid out as red; column c holds its rows >= c rounded down to a tile edge: read the lower triangle
+    double *W, *P;                   // per eliminated node: -L_II^-T Y_E (6 x 12, column by column), the diagonal block of the segment's own inverse (36)
+    double *cov, *cross;             // Sigma(i, i) of every node (36 N); Sigma(i, j) of every pair (36 per pair)
+    const int* pairs;                // 2 ids per pair
 };
 struct ImuOutDev {                   // lili_window_imu's numbers, then the prediction
     double sum_dt, g[3], delta_p[3], delta_q[4], delta_v[3], lin_ba[3], lin_bg[3], jacobian[225], covariance[225];

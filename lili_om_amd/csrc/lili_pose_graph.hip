@@ -19,6 +19,10 @@
 //                          L_ik^T x_i off y_k, workgroup i writes the step.  Every tile and every piece of b has one owner per launch and sums over k ascending;
 //   k_pg_backsub           one wave per segment, every lane the same arithmetic: the interior nodes' step from the separators';
 //   k_pg_retract_cost      one workgroup: the candidate, its cost in a fixed order, the accept / stop decision, the termination word.
+// lili_pose_graph_marginals runs the launches up to the reduced factorisation (the gate in its evaluate mode: it decides nothing), then three of its own:
+//   k_pg_marg_inverse      one workgroup per separator: its six columns of the reduced inverse through L and L^T, tile by tile;
+//   k_pg_marg_segments     one wave per segment, last node first: W = -L_II^-T Y_E, the segment's own inverse blocks, Sigma(i, i) of every node;
+//   k_pg_marg_pairs        one wave per requested pair: Sigma(i, j).
 // No atomics anywhere: H, g, the cost and the step are pure functions of the graph.  The tables (separators, segments, loops, the loops of each node and of each
 // reduced block) and the work arrays follow the graph's size: the reduced system takes 8 (6 K)^2 bytes, 1.3 GB at 1024 loops (K = 2112).
 #include "lili_launch.h"
@@ -771,6 +775,258 @@ __global__ __launch_bounds__(kPgWide) void k_pg_retract_cost(const PgDev G) {
     if (s_accept) for (int e = t; e < 7 * n; e += kPgWide) G.X[e] = G.Xn[e];
 }
 
+// ---- marginal covariances (lili_pose_graph_marginals): the inverse-side passes behind one iteration's factorisation.  With the interior nodes I in front of the
+// separators s, H = [A_II E; E^T A_ss], A_II = L_II L_II^T (Ld, Ls), Y_E = L_II^-1 E (Y), S = A_ss - Y_E^T Y_E = L L^T (red):
+//   Sigma_ss = S^-1,   W = -L_II^-T Y_E,   Sigma_Is = W Sigma_ss,   Sigma_II = A_II^-1 + W Sigma_ss W^T.
+// A node's rows of W are non-zero only in the columns of the (at most two) separators that bound its segment, and A_II^-1 is block diagonal by segment.
+//
+// k_pg_marg_inverse: workgroup p = the six columns of S^-1 that belong to separator p, thread (q, r) = column q, the rows r mod kPgTile.  L x = e from the tile that
+// holds row 6 p (x is zero above it), then L^T x = y back down to that tile: only the rows >= 6 p are wanted, the others follow by symmetry.  Tile by tile: the diagonal
+// tile in LDS, its triangular solve there, then every row below (forward) / above (backward) takes its 96 products, summed over the tile in ascending order.  Every
+// element of x has one owner for the whole launch, which reads back only what it wrote itself.
+constexpr int kPgInvThreads = 6 * kPgTile;
+static_assert(kPgInvThreads % 64 == 0 && kPgInvThreads <= 1024, "whole waves, one workgroup");
+__global__ __launch_bounds__(kPgInvThreads) void k_pg_marg_inverse(const PgDev G) {
+    if (G.st->done) return;
+    __shared__ double sL[kPgTile * (kPgTile + 1) / 2], sx[6 * kPgTile];
+    const int nr = 6 * G.tab->n_sep, p = blockIdx.x, t = threadIdx.x, q = t / kPgTile, r = t - q * kPgTile;
+    const int nt = (nr + kPgTile - 1) / kPgTile, k0 = 6 * p / kPgTile;
+    const double* R = G.red;
+    double* X = G.sinv + (size_t)(6 * p + q) * nr;      // this thread's column
+    const double* xq = sx + q * kPgTile;
+    for (int kt = k0; kt < nt; kt++) {      // L y = e
+        const int o = kt * kPgTile, m = min(kPgTile, nr - o);
+        __syncthreads();      // the previous tile's reads of sL and sx
+        for (int e = t; e < m * m; e += kPgInvThreads) {
+            const int c = e / m, rr = e - c * m;
+            if (rr >= c) sL[pg_tri(rr, c)] = R[(size_t)(o + c) * nr + (o + rr)];
+        }
+        if (r < m) sx[t] = kt == k0 ? (o + r == 6 * p + q ? 1.0 : 0.0) : X[o + r];
+        __syncthreads();
+        for (int c = 0; c < m; c++) {
+            const double xc = xq[c] / sL[pg_tri(c, c)];
+            __syncthreads();
+            if (r == c) sx[t] = xc;
+            else if (r > c && r < m) sx[t] -= sL[pg_tri(r, c)] * xc;
+            __syncthreads();
+        }
+        if (r < m) X[o + r] = sx[t];
+        for (int row = o + kPgTile + r; row < nr; row += kPgTile) {      // (rows below: this tile column is whole)
+            const double* Lr = R + (size_t)o * nr + row;
+            double s = kt == k0 ? 0.0 : X[row];
+#pragma unroll 8
+            for (int c = 0; c < kPgTile; c++) s -= Lr[(size_t)c * nr] * xq[c];
+            X[row] = s;
+        }
+    }
+    for (int kt = nt - 1; kt >= k0; kt--) {      // L^T x = y
+        const int o = kt * kPgTile, m = min(kPgTile, nr - o);
+        __syncthreads();
+        for (int e = t; e < m * m; e += kPgInvThreads) {
+            const int c = e / m, rr = e - c * m;
+            if (rr >= c) sL[pg_tri(rr, c)] = R[(size_t)(o + c) * nr + (o + rr)];
+        }
+        if (r < m) sx[t] = X[o + r];
+        __syncthreads();
+        for (int c = m - 1; c >= 0; c--) {
+            const double xc = xq[c] / sL[pg_tri(c, c)];
+            __syncthreads();
+            if (r == c) sx[t] = xc;
+            else if (r < c) sx[t] -= sL[pg_tri(c, r)] * xc;
+            __syncthreads();
+        }
+        if (r < m) X[o + r] = sx[t];
+        for (int row = k0 * kPgTile + r; row < o; row += kPgTile) {      // y_row -= L(o .., row)^T x_tile
+            const double* Lc = R + (size_t)row * nr + o;
+            double s = X[row];
+#pragma unroll 8
+            for (int rr = 0; rr < m; rr++) s -= Lc[rr] * xq[rr];
+            X[row] = s;
+        }
+    }
+}
+
+// element (a, b) of the reduced inverse, from its lower triangle: the same bits for (a, b) and (b, a)
+__device__ __forceinline__ double pg_sinv(const double* X, const int nr, const int a, const int b) { return a >= b ? X[(size_t)b * nr + a] : X[(size_t)a * nr + b]; }
+// x <- Ld^-T x, Ld a row-major lower-triangular 6 x 6 block
+__device__ __forceinline__ void pg_back6(const double* Ld, double x[6]) {
+#pragma unroll
+    for (int k = 5; k >= 0; k--) {
+        double v = x[k];
+#pragma unroll
+        for (int m = k + 1; m < 6; m++) v -= Ld[6 * m + k] * x[m];
+        x[k] = v / Ld[6 * k + k];
+    }
+}
+
+// One wave per segment, last node first.  Lanes 0 .. 11: a column of W_i = Ld_i^-T (-Y_E,i - Ls_i^T W_(i+1)).  Lanes 12 .. 17: a column of the segment's own inverse
+// block P_i = Ld_i^-T (I + Ls_i^T P_(i+1) Ls_i) Ld_i^-1, made symmetric by averaging.  Lanes 0 .. 35: entry (r, c) of Sigma_ii = P_i + W_i Sigma_sep W_i^T, Sigma_sep
+// the 12 x 12 joint block of the segment's two separators (neighbours in the reduced order; the chain's last segment has one, the other half is zero); entries (r, c)
+// and (c, r) evaluate the same expression.  Lanes 0 .. 35 also write the left separator's own block.
+__global__ __launch_bounds__(64) void k_pg_marg_segments(const PgDev G) {
+    if (G.st->done) return;
+    __shared__ double sS[144], sW[72], sP[36], sPn[36];
+    const PgTables& T = *G.tab;
+    const int k = blockIdx.x, c = threadIdx.x, nr = 6 * T.n_sep;
+    const PgSeg sg = T.seg[k];
+    for (int e = c; e < 144; e += 64) {
+        const int a = e / 12, b = e - 12 * a;
+        sS[e] = (sg.right >= 0 || (a < 6 && b < 6)) ? pg_sinv(G.sinv, nr, 6 * k + a, 6 * k + b) : 0.0;
+    }
+    if (c < 36) sP[c] = 0.0;
+    __syncthreads();
+    if (c < 36) G.cov[(size_t)sg.left * 36 + c] = sS[12 * (c / 6) + c % 6];
+    double wn[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = sg.last; i >= sg.first; i--) {
+        const double* Ld = G.Ld + (size_t)i * 36;
+        const double* Ls = G.Ls + (size_t)i * 36;      // L block (i + 1, i), row by row
+        const bool tail = i < sg.last;
+        if (c < 12) {
+            const double* Y = G.Y + (size_t)i * (6 * kPgCols) + 6 * (1 + c);
+            double x[6];
+#pragma unroll
+            for (int kk = 0; kk < 6; kk++) {
+                double s = -Y[kk];
+                if (tail) {
+#pragma unroll
+                    for (int m = 0; m < 6; m++) s -= Ls[6 * m + kk] * wn[m];
+                }
+                x[kk] = s;
+            }
+            pg_back6(Ld, x);
+#pragma unroll
+            for (int kk = 0; kk < 6; kk++) { sW[6 * c + kk] = x[kk]; G.W[(size_t)i * 72 + 6 * c + kk] = x[kk]; wn[kk] = x[kk]; }
+        } else if (c < 18) {
+            const int cc = c - 12;
+            double u[6], x[6];
+#pragma unroll
+            for (int kk = 0; kk < 6; kk++) {      // u = Ld^-1 e_cc
+                double v = kk == cc ? 1.0 : 0.0;
+#pragma unroll
+                for (int m = 0; m < kk; m++) v -= Ld[6 * kk + m] * u[m];
+                u[kk] = v / Ld[6 * kk + kk];
+            }
+            if (tail) {
+                double v[6], pv[6];
+#pragma unroll
+                for (int rr = 0; rr < 6; rr++) {
+                    double s = Ls[6 * rr] * u[0];
+#pragma unroll
+                    for (int m = 1; m < 6; m++) s += Ls[6 * rr + m] * u[m];
+                    v[rr] = s;
+                }
+#pragma unroll
+                for (int rr = 0; rr < 6; rr++) {
+                    double s = sP[6 * rr] * v[0];
+#pragma unroll
+                    for (int m = 1; m < 6; m++) s += sP[6 * rr + m] * v[m];
+                    pv[rr] = s;
+                }
+#pragma unroll
+                for (int kk = 0; kk < 6; kk++) {
+                    double s = u[kk];
+#pragma unroll
+                    for (int rr = 0; rr < 6; rr++) s += Ls[6 * rr + kk] * pv[rr];
+                    x[kk] = s;
+                }
+            } else {
+#pragma unroll
+                for (int kk = 0; kk < 6; kk++) x[kk] = u[kk];
+            }
+            pg_back6(Ld, x);
+#pragma unroll
+            for (int kk = 0; kk < 6; kk++) sPn[6 * kk + cc] = x[kk];
+        }
+        __syncthreads();      // P_(i+1) has been read, the raw columns of P_i are in place
+        if (c < 36) { const int rr = c / 6, qq = c - 6 * rr; sP[c] = 0.5 * (sPn[6 * rr + qq] + sPn[6 * qq + rr]); }
+        __syncthreads();
+        if (c < 36) {
+            const int rr = c / 6, qq = c - 6 * rr, hi = max(rr, qq), lo = min(rr, qq);
+            double s = sP[6 * hi + lo];
+            for (int a = 0; a < 12; a++) {
+                double ta = sS[12 * a] * sW[lo];
+#pragma unroll
+                for (int b = 1; b < 12; b++) ta += sS[12 * a + b] * sW[6 * b + lo];
+                s += sW[6 * a + hi] * ta;
+            }
+            G.cov[(size_t)i * 36 + c] = s;
+            G.P[(size_t)i * 36 + c] = sP[c];
+        }
+        __syncthreads();      // sW and sP have been read
+    }
+}
+
+// the separator at or in front of node i: the largest p with sep[p] <= i (sep[0] = 0)
+__device__ __forceinline__ int pg_sep_at(const PgTables& T, const int i) {
+    int lo = 0, hi = T.n_sep - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (T.sep[mid] <= i) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+// One wave per pair (i, j): Sigma(lo, hi) of the smaller and the larger id, written as it is or transposed, so that the two orders of a pair are transposes bit for
+// bit; i == j copies the node's diagonal block.  Sigma(lo, hi) = Z + W_lo M W_hi^T: W of a separator = the identity on its own six columns, M = the blocks of the
+// reduced inverse between the nodes' separators, Z = the segment's own inverse block (lo, hi) when both are interior nodes of one segment, from the larger node's P
+// by Z_(k, hi) = -Ld_k^-T Ls_k^T Z_(k+1, hi) (lanes 0 .. 5, a column each; at most LILI_PG_SEGMENT - 2 steps).
+__global__ __launch_bounds__(64) void k_pg_marg_pairs(const PgDev G) {
+    if (G.st->done) return;
+    __shared__ double sM[144], sWl[72], sWh[72], sZ[36];
+    const PgTables& T = *G.tab;
+    const int c = threadIdx.x, nr = 6 * T.n_sep;
+    const int i = G.pairs[2 * blockIdx.x], j = G.pairs[2 * blockIdx.x + 1];
+    double* out = G.cross + (size_t)blockIdx.x * 36;
+    if (i == j) {
+        if (c < 36) out[c] = G.cov[(size_t)i * 36 + c];
+        return;
+    }
+    const int lo = min(i, j), hi = max(i, j), pl = pg_sep_at(T, lo), ph = pg_sep_at(T, hi);
+    const bool il = T.sep[pl] != lo, ih = T.sep[ph] != hi;      // interior nodes of segments pl / ph
+    for (int e = c; e < 72; e += 64) {
+        const int a = e / 6, rr = e - 6 * a;
+        sWl[e] = il ? G.W[(size_t)lo * 72 + e] : (a == rr ? 1.0 : 0.0);
+        sWh[e] = ih ? G.W[(size_t)hi * 72 + e] : (a == rr ? 1.0 : 0.0);
+    }
+    for (int e = c; e < 144; e += 64) {
+        const int a = e / 12, b = e - 12 * a;
+        const bool va = a < 6 || (il && pl + 1 < T.n_sep), vb = b < 6 || (ih && ph + 1 < T.n_sep);
+        sM[e] = va && vb ? pg_sinv(G.sinv, nr, 6 * pl + a, 6 * ph + b) : 0.0;
+    }
+    if (c < 36) sZ[c] = 0.0;
+    __syncthreads();
+    if (il && ih && pl == ph && c < 6) {
+        double v[6];
+#pragma unroll
+        for (int rr = 0; rr < 6; rr++) v[rr] = G.P[(size_t)hi * 36 + 6 * rr + c];
+        for (int kn = hi - 1; kn >= lo; kn--) {
+            const double* Ls = G.Ls + (size_t)kn * 36;
+            double x[6];
+#pragma unroll
+            for (int kk = 0; kk < 6; kk++) {
+                double s = Ls[kk] * v[0];
+#pragma unroll
+                for (int rr = 1; rr < 6; rr++) s += Ls[6 * rr + kk] * v[rr];
+                x[kk] = -s;
+            }
+            pg_back6(G.Ld + (size_t)kn * 36, x);
+#pragma unroll
+            for (int kk = 0; kk < 6; kk++) v[kk] = x[kk];
+        }
+#pragma unroll
+        for (int rr = 0; rr < 6; rr++) sZ[6 * rr + c] = v[rr];
+    }
+    __syncthreads();
+    if (c < 36) {
+        const int rr = c / 6, qq = c - 6 * rr;
+        double s = sZ[c];
+        for (int a = 0; a < 12; a++) {
+            double ta = sM[12 * a] * sWh[qq];
+#pragma unroll
+            for (int b = 1; b < 12; b++) ta += sM[12 * a + b] * sWh[6 * b + qq];
+            s += sWl[6 * a + rr] * ta;
+        }
+        out[i < j ? c : 6 * qq + rr] = s;
+    }
+}
+
 }  // namespace lili
 
 namespace {
@@ -779,7 +1035,8 @@ struct PoseGraphState : ExtState {
     int n = 0, n_loops = 0;
     std::vector<PgLoop> loops;
     DevBuf X, Xn, meas, tab, tabv, st, stage, fr, fJ, g, D, S, LB, Ld, Ls, Y, gram, red, delta, rhs;
-    PinBuf h_tab, h_io;
+    DevBuf sinv, W, Pm, cov, cross, pairs;      // lili_pose_graph_marginals only
+    PinBuf h_tab, h_io, h_pairs;
     Event ev0, ev1;
     float last_ms = -1.f;
     // the graph itself is allocated once at the caps (3.7 MB): it has to outlive every call
@@ -806,6 +1063,14 @@ struct PoseGraphState : ExtState {
         }
         return LILI_OK;
     }
+    // what the inverse-side passes add, allocated by the first lili_pose_graph_marginals: a second dense array of the reduced system's size, W and P per node, the outputs
+    int work_marginals(lili_ctx* ctx, int n_sep, int n_pairs) {
+        const size_t N = (size_t)n, d = sizeof(double);
+        HIPCHK(sinv.ensure((size_t)36 * n_sep * n_sep * d));
+        HIPCHK(W.ensure(N * 72 * d)); HIPCHK(Pm.ensure(N * 36 * d)); HIPCHK(cov.ensure(N * 36 * d));
+        HIPCHK(cross.ensure((size_t)std::max(n_pairs, 1) * 36 * d)); HIPCHK(pairs.ensure((size_t)std::max(n_pairs, 1) * 2 * sizeof(int32_t)));
+        return LILI_OK;
+    }
     PgDev dev(int n_sep) const {
         PgDev G{};
         G.tab = tab.as<PgTables>(); G.st = st.as<PgState>();
@@ -813,6 +1078,7 @@ struct PoseGraphState : ExtState {
         G.fr = fr.as<double>(); G.fJ = fJ.as<double>(); G.g = g.as<double>(); G.D = D.as<double>(); G.S = S.as<double>(); G.LB = LB.as<double>();
         G.Ld = Ld.as<double>(); G.Ls = Ls.as<double>(); G.Y = Y.as<double>(); G.gram = gram.as<double>(); G.red = red.as<double>(); G.delta = delta.as<double>();
         G.rhs = 6 * n_sep > kPgMaxReduced ? rhs.as<double>() : nullptr;
+        G.sinv = sinv.as<double>(); G.W = W.as<double>(); G.P = Pm.as<double>(); G.cov = cov.as<double>(); G.cross = cross.as<double>(); G.pairs = pairs.as<int>();
         return G;
     }
 };
@@ -1187,7 +1453,111 @@ int lili_pose_graph_kernel_ms(lili_ctx* ctx, float* ms) {
     return LILI_OK;
 }
 
-int lili_loop_measurement(const double T_icp[16], const double pose_latest[7], const double pose_closest[7], double meas[7]) {
+int lili_pose_graph_marginals(lili_ctx* ctx, const lili_pg_options* options, int first, int n, double* cov, const int32_t* pairs, int n_pairs, double* cross,
+                              lili_pg_marginals_info* info) {
+    if (!ctx) return LILI_E_ARG;
+    PoseGraphState* P = pg_of(ctx);
+    ARGCHK(n >= 0 && n_pairs >= 0 && n_pairs <= LILI_PG_MAX_PAIRS && (n > 0 || n_pairs > 0), "pose_graph_marginals: n or n_pairs is negative, both are zero, or more than LILI_PG_MAX_PAIRS pairs");
+    ARGCHK((cov || n == 0) && ((pairs && cross) || n_pairs == 0), "pose_graph_marginals: null argument");
+    lili_pg_options opt;
+    TRY(check_options(ctx, options, &opt));
+    if (P->n == 0) return ctx->fail(LILI_E_STATE, "pose_graph_marginals: the graph is empty");
+    ARGCHK(n == 0 || (first >= 0 && first < P->n && n <= P->n - first), "pose_graph_marginals: range outside the graph");
+    for (int k = 0; k < 2 * n_pairs; k++) ARGCHK(pairs[k] >= 0 && pairs[k] < P->n, "pose_graph_marginals: a pair names a node outside the graph");
+    HIPCHK(hipSetDevice(ctx->device));
+    TRY(P->persist(ctx));
+    PgLayout lay;
+    int K = 0, NB = 0;
+    TRY(fill_tables(ctx, P, opt, &lay, &K, &NB));
+    TRY(P->work(ctx, K, true));
+    TRY(P->work_marginals(ctx, K, n_pairs));
+    const size_t d = sizeof(double), n_cov = 36 * (size_t)n, n_cross = 36 * (size_t)n_pairs;
+    HIPCHK(P->h_io.ensure((n_cov + n_cross) * d));
+    TRY(upload_tables(ctx, P, lay));
+    if (n_pairs) {
+        HIPCHK(P->h_pairs.ensure(sizeof(int32_t) * 2 * (size_t)n_pairs));
+        std::memcpy(P->h_pairs.p, pairs, sizeof(int32_t) * 2 * (size_t)n_pairs);
+        HIPCHK(hipMemcpyAsync(P->pairs.p, P->h_pairs.p, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const PgDev G = P->dev(K);
+    const int zero_blocks = (int)std::min<size_t>(2048, ((size_t)18 * K * K + 255) / 256);
+    HIPCHK(P->ev0.get(hipEventDefault)); HIPCHK(P->ev1.get(hipEventDefault));
+    HIPCHK(hipEventRecord(P->ev0, ctx->stream));
+    // the front half of a solve iteration; the gate in its evaluate mode: a converged graph is factored like any other
+    launch_linearize(ctx, P, G);
+    hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 1);
+    hipLaunchKernelGGL(k_pg_eliminate, dim3(K), dim3(64), 0, ctx->stream, G);
+    hipLaunchKernelGGL(k_pg_zero, dim3(zero_blocks), dim3(256), 0, ctx->stream, G);
+    hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(NB), dim3(64), 0, ctx->stream, G);
+    launch_reduced_solve(ctx, G, K);
+    // the inverse side
+    hipLaunchKernelGGL(k_pg_marg_inverse, dim3(K), dim3(kPgInvThreads), 0, ctx->stream, G);
+    hipLaunchKernelGGL(k_pg_marg_segments, dim3(K), dim3(64), 0, ctx->stream, G);
+    if (n_pairs) hipLaunchKernelGGL(k_pg_marg_pairs, dim3(n_pairs), dim3(64), 0, ctx->stream, G);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(P->ev1, ctx->stream));
+    double* h = P->h_io.as<double>();
+    PgState* hs = reinterpret_cast<PgState*>(P->h_tab.as<PgTables>() + 1);
+    HIPCHK(hipMemcpyAsync(hs, P->st.p, sizeof(PgState), hipMemcpyDeviceToHost, ctx->stream));
+    if (n) HIPCHK(hipMemcpyAsync(h, P->cov.as<double>() + 36 * (size_t)first, n_cov * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_pairs) HIPCHK(hipMemcpyAsync(h + n_cov, P->cross.p, n_cross * d, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, P->ev0, P->ev1));
+    const bool failed = hs->done != 0;      // only a non-positive pivot sets the termination word here
+    if (info) {
+        info->status = failed ? LILI_LM_NUMERICAL_FAILURE : 0;
+        info->n_nodes = P->n; info->n_loops = P->n_loops; info->reduced_unknowns = 6 * K;
+        info->kernel_ms = ms; info->reserved_ = 0;
+    }
+    if (failed) return ctx->fail(LILI_E_NUMERIC, "pose_graph_marginals: a non-positive pivot: the information matrix is not positive definite in double precision");
+    if (n) std::memcpy(cov, h, n_cov * d);
+    if (n_pairs) std::memcpy(cross, h + n_cov, n_cross * d);
+    return LILI_OK;
+}
+
+int lili_pose_relative_covariance(const double pose_i[7], const double pose_j[7], const double cov_ii[36], const double cov_jj[36], const double cov_ij[36],
+                                  double cov_rel[36]) {
+    if (!pose_i || !pose_j || !cov_ii || !cov_jj || !cov_ij || !cov_rel) return LILI_E_ARG;
+    if (!h_finite(pose_i, 7) || !h_finite(pose_j, 7) || !h_finite(cov_ii, 36) || !h_finite(cov_jj, 36) || !h_finite(cov_ij, 36)) return LILI_E_ARG;
+    const double ni = std::sqrt(((pose_i[3] * pose_i[3] + pose_i[4] * pose_i[4]) + pose_i[5] * pose_i[5]) + pose_i[6] * pose_i[6]);
+    const double nj = std::sqrt(((pose_j[3] * pose_j[3] + pose_j[4] * pose_j[4]) + pose_j[5] * pose_j[5]) + pose_j[6] * pose_j[6]);
+    if (!(std::fabs(ni - 1.0) <= 1e-6) || !(std::fabs(nj - 1.0) <= 1e-6)) return LILI_E_ARG;
+    // Z = between(X_i, X_j): R_Z = R_i^T R_j, t_Z = d = R_i^T (p_j - p_i)
+    const hq qi{pose_i[3] / ni, pose_i[4] / ni, pose_i[5] / ni, pose_i[6] / ni}, qj{pose_j[3] / nj, pose_j[4] / nj, pose_j[5] / nj, pose_j[6] / nj};
+    const hq ci{qi.w, -qi.x, -qi.y, -qi.z};
+    const hv t = h_rot(ci, hv{pose_j[0] - pose_i[0], pose_j[1] - pose_i[1], pose_j[2] - pose_i[2]});
+    const hq z = h_normalized(h_mul(ci, qj));
+    const double R[9] = {1 - 2 * (z.y * z.y + z.z * z.z), 2 * (z.x * z.y - z.w * z.z), 2 * (z.x * z.z + z.w * z.y),
+                         2 * (z.x * z.y + z.w * z.z), 1 - 2 * (z.x * z.x + z.z * z.z), 2 * (z.y * z.z - z.w * z.x),
+                         2 * (z.x * z.z - z.w * z.y), 2 * (z.y * z.z + z.w * z.x), 1 - 2 * (z.x * z.x + z.y * z.y)};
+    const double Sd[9] = {0.0, -t.z, t.y, t.z, 0.0, -t.x, -t.y, t.x, 0.0};
+    // J_a = [-R_Z^T, 0; R_Z^T [t_Z]x, -R_Z^T], J_b = I
+    double Ja[36] = {0.0};
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            Ja[6 * r + c] = -R[3 * c + r];
+            Ja[6 * (3 + r) + 3 + c] = -R[3 * c + r];
+            Ja[6 * (3 + r) + c] = (R[r] * Sd[c] + R[3 + r] * Sd[3 + c]) + R[6 + r] * Sd[6 + c];
+        }
+    double A[36], B[36], out[36];      // A = J_a Sigma_ii, B = J_a Sigma_ij
+    for (int r = 0; r < 6; r++)
+        for (int c = 0; c < 6; c++) {
+            double a = 0.0, b = 0.0;
+            for (int k = 0; k < 6; k++) { a += Ja[6 * r + k] * cov_ii[6 * k + c]; b += Ja[6 * r + k] * cov_ij[6 * k + c]; }
+            A[6 * r + c] = a; B[6 * r + c] = b;
+        }
+    for (int r = 0; r < 6; r++)
+        for (int c = 0; c < 6; c++) {
+            double a = 0.0;
+            for (int k = 0; k < 6; k++) a += A[6 * r + k] * Ja[6 * c + k];
+            out[6 * r + c] = ((a + B[6 * r + c]) + B[6 * c + r]) + cov_jj[6 * r + c];
+        }
+    std::memcpy(cov_rel, out, sizeof out);
+    return LILI_OK;
+}
+
+int lili_loop_measurement(const double T_icp[16],const double pose_latest[7], const double pose_closest[7], double meas[7]) {
     if (!T_icp || !pose_latest || !pose_closest || !meas) return LILI_E_ARG;
     if (!h_finite(T_icp, 16) || !h_finite(pose_latest, 7) || !h_finite(pose_closest, 7)) return LILI_E_ARG;
     // L:2587-2600: quaternionIncre(R), transitionIncre; corrected = incre * toCorrect

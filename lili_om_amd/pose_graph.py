@@ -14,12 +14,15 @@ A full loop closure, with a KeyframeArchive `archive`, a FrameTrajectory `traj` 
         out = correct_poses(graph.poses(), traj.keyframe_id_in_frame, width, abs_poses, np.hstack([ts, qs]))
         traj.rewrite(out["frame_poses"])
         archive.set_poses(0, out["keyframe_poses"][:, 0:3], out["keyframe_poses"][:, 3:7])      # then lili_localmap_repose of the rings
+
+How well the poses are known (gtsam: marginalCovariance / jointMarginalCovariance): graph.marginals() -> the 6 x 6 covariance of every node and of node pairs at the
+current estimates, graph.relative_covariance(i, j) -> the covariance of between(X_i, X_j); INTEGRATION.md §1c says what a loop closure can do with them.
 """
 import ctypes as C
 
 import numpy as np
 
-from .api import LiliError, PgOptions, PgSummary, _ptr, load_library
+from .api import LiliError, PgMarginalsInfo, PgOptions, PgSummary, _ptr, load_library
 
 
 def _f64(a, shape):
@@ -61,6 +64,7 @@ class PoseGraph:
     def __init__(self, ctx, max_loops=None):
         self.ctx, self.lib = ctx, ctx.lib
         self.last_summary = None
+        self.last_marginals = None
         if max_loops is not None:
             self.set_max_loops(max_loops)
 
@@ -140,5 +144,36 @@ class PoseGraph:
         self.ctx._chk(self.lib.lili_pose_graph_kernel_ms(self.ctx.h, C.byref(ms)))
         return float(ms.value)
 
+    def marginals(self, first=0, n=None, pairs=None, options=None):
+        """Marginal covariances at the current estimates (no step is taken) -> cov (n, 6, 6): Sigma(i, i) of nodes first .. first + n - 1 (n None: to the last
+        node), cross (P, 6, 6): Sigma(i, j) of every pair (i, j), rows: node i — or None without pairs.  Blocks are in the node's tangent (omega, v).  The call's
+        info (status, sizes, reduced_unknowns, kernel_ms) is kept in self.last_marginals, also when the call fails on a non-positive pivot."""
+        n = self.info()[0] - int(first) if n is None else int(n)
+        pr = None if pairs is None else np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n_pairs = 0 if pr is None else pr.shape[0]
+        cov = np.zeros((max(n, 0), 6, 6))
+        cross = np.zeros((n_pairs, 6, 6)) if n_pairs else None
+        info = PgMarginalsInfo()
+        rc = self.lib.lili_pose_graph_marginals(self.ctx.h, C.byref(options) if options is not None else None, int(first), n, _ptr(cov) if n > 0 else None,
+                                                _ptr(pr) if n_pairs else None, n_pairs, _ptr(cross) if n_pairs else None, C.byref(info))
+        self.last_marginals = info.as_dict() if rc in (0, -6) else None
+        self.ctx._chk(rc)
+        return cov, cross
 
-__all__ = ["PoseGraph", "correct_poses", "loop_measurement"]
+    def relative_covariance(self, i, j, options=None):
+        """first-order covariance (6, 6) of between(X_i, X_j) in its own tangent: one marginals call for the two nodes and the pair, then the host function"""
+        i, j = int(i), int(j)
+        _, cross = self.marginals(0, 0, [(i, i), (j, j), (i, j)], options)
+        return relative_covariance(self.poses(i, 1)[0], self.poses(j, 1)[0], cross[0], cross[1], cross[2])
+
+
+def relative_covariance(pose_i, pose_j, cov_ii, cov_jj, cov_ij):
+    """lili_pose_relative_covariance: J_a S_ii J_a^T + J_a S_ij + S_ij^T J_a^T + S_jj with the between-factor's Jacobian J_a at Z = between(X_i, X_j) (J_b = I)"""
+    a, b = _f64(pose_i, (7,)), _f64(pose_j, (7,))
+    sii, sjj, sij, out = _f64(cov_ii, (6, 6)), _f64(cov_jj, (6, 6)), _f64(cov_ij, (6, 6)), np.zeros((6, 6))
+    if load_library().lili_pose_relative_covariance(_ptr(a), _ptr(b), _ptr(sii), _ptr(sjj), _ptr(sij), _ptr(out)) != 0:
+        raise LiliError("lili_pose_relative_covariance: bad argument")
+    return out
+
+
+__all__ = ["PoseGraph", "correct_poses", "loop_measurement", "relative_covariance"]
