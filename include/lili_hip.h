@@ -908,7 +908,7 @@ int lili_local_graph_kernel_ms(lili_ctx* ctx, float* ms);
  * Conventions.  A pose is 7 doubles, p (3) then q (w, x, y, z).  The tangent is xi = (omega, v), ROTATION FIRST (gtsam::Pose3's order: the reference's variance
  * vectors apply index for index).  X (+) xi = (p + R v, normalise(q * Exp(omega)));  between(A, B) = (R_A^T (p_B - p_A), q_A^-1 * q_B).
  * Between-factor on nodes (a, b), measurement Z = (t_Z, q_Z), variances s^2 (6):  e = (Log(R_Z^T R_A^T R_B), R_Z^T (R_A^T (p_B - p_A) - t_Z)),  r = e / s.
- * Prior on node 0: e = (Log(R_Z^T R_0), R_Z^T (p_0 - t_Z)).  Cost = 1/2 sum |r|^2, no loss function.  The right Jacobian inverse of SO(3) inside the factor
+ * Prior on node 0: e = (Log(R_Z^T R_0), R_Z^T (p_0 - t_Z)).  Cost = 1/2 sum |r|^2; a loop may carry a robust loss (lili_pose_graph_add_loop_robust below).  The right Jacobian inverse of SO(3) inside the factor
  * Jacobians uses its series below LILI_PG_SMALL_ANGLE (rad) and the closed form above it.
  * Node 0's prior sits at its own pose as given; the chain measurement of node i is between(pose[i - 1], pose[i]) of the poses AS GIVEN AT APPEND TIME and is
  * frozen from then on; the initial estimate of a new node is its given pose.  Quaternions are normalised on entry.
@@ -934,7 +934,7 @@ int lili_local_graph_kernel_ms(lili_ctx* ctx, float* ms);
  *                            substitutions tile by tile).  Every launch of the solve is enqueued up front; one synchronisation, one read-back; blocking.  The
  *                            same graph gives the same bits on every run, and a graph of <= 768 reduced unknowns the same bits whatever "pose_graph_max_loops" is.
  *                            The reference's isam->update(graph); isam->update() is nearest to max_iterations = 2.
- * lili_pose_graph_kernel_ms — device time of the last lili_pose_graph_solve's launches in milliseconds; LILI_E_STATE when there is none.
+ * lili_pose_graph_kernel_ms — device time of the last lili_pose_graph_solve's or lili_pose_graph_solve_lm's launches in milliseconds; LILI_E_STATE when there is none.
  *
  * Loops.  A graph takes LILI_PG_MAX_LOOPS loops by default; lili_set_option(ctx, "pose_graph_max_loops", v) with v in LILI_PG_MAX_LOOPS .. LILI_PG_MAX_LOOPS_EXT
  * moves that bound (any time; LILI_E_STATE when the graph already holds more than v loops).  The tables and work arrays follow the graph's actual size; the dense
@@ -972,6 +972,57 @@ int lili_pose_graph_set(lili_ctx* ctx, int first, int n, const double* poses);
 int lili_pose_graph_evaluate(lili_ctx* ctx, const lili_pg_options* options, double* cost, double* gradient, double* diag, double* sub, double* loop_blocks);
 int lili_pose_graph_solve(lili_ctx* ctx, const lili_pg_options* options, lili_pg_summary* summary);
 int lili_pose_graph_kernel_ms(lili_ctx* ctx, float* ms);
+/* Robust loop factors (GTSAM's noiseModel::Robust on the loop's BetweenFactor).  lili_pose_graph_add_loop_robust is lili_pose_graph_add_loop with a loss kind and
+ * its scale k; lili_pose_graph_add_loop means LILI_PG_LOSS_NONE.  The prior and the chain factors never carry a loss.  With r = e / s the loop's whitened residual,
+ * d^2 = |r|^2 (summed in tangent order) and d = sqrt(d^2):
+ *   Huber          w = 1 if d <= k, else k / d         rho = d^2 / 2 if d <= k, else k (d - k / 2)
+ *   Cauchy         w = k^2 / (k^2 + d^2)               rho = (k^2 / 2) log1p(d^2 / k^2)
+ *   Geman-McClure  w = (k^2 / (k^2 + d^2))^2           rho = (k^2 / 2) d^2 / (k^2 + d^2)
+ * The factor is linearised as sqrt(w) r, sqrt(w) J (iteratively re-weighted least squares, no second-order term) and adds rho to the cost where every other factor
+ * adds |r|^2 / 2: g = J^T W r is the robust cost's exact gradient, H = J^T W J its approximation.  evaluate (cost, gradient, every block), solve, solve_lm and
+ * marginals (Sigma = the inverse of that weighted H) all read the graph this way.
+ * LILI_E_ARG, the graph untouched: what lili_pose_graph_add_loop refuses, a loss that is none of the four, and for a loss other than NONE a scale that is not
+ * positive and finite (the scale of NONE is ignored).
+ *
+ * lili_pose_graph_loop_status — what the loss decided: at the current estimates, d^2 (chi2) and w (weight; 1 for NONE) of loops first .. first + n - 1 in the order
+ * they were added.  One small launch; no step, nothing changes; a sub-range equals the slice of the full result byte for byte.  Only the variances of `options` are
+ * checked (NULL = the defaults).  LILI_E_ARG, outputs untouched: a null pointer, n < 1, a range outside the graph's loops, a variance that is not positive and finite. */
+#define LILI_PG_LOSS_NONE 0
+#define LILI_PG_LOSS_HUBER 1
+#define LILI_PG_LOSS_CAUCHY 2
+#define LILI_PG_LOSS_GEMAN_MCCLURE 3
+int lili_pose_graph_add_loop_robust(lili_ctx* ctx, int from, int to, const double meas[7], const double var[6], int loss, double scale);
+int lili_pose_graph_loop_status(lili_ctx* ctx, const lili_pg_options* options, int first, int n, double* chi2, double* weight);
+/* Levenberg-Marquardt on the same graph, the same elimination and the same robust cost.  Attempt k, k < max_iterations, at the estimate X with the damping lambda
+ * (initial_lambda at first):
+ *   1. linearise at X; |g|inf <= gradient_tolerance ends the solve (LILI_LM_GRADIENT_TOLERANCE);
+ *   2. damp H: diagonal_damping = 0 adds lambda to every diagonal entry of every 6 x 6 diagonal block, diagonal_damping = 1 turns every such entry h into h + lambda h;
+ *   3. solve (segments, reduced system, either reduced path); form X (+) delta and its robust cost;
+ *   4. new cost <= cost: the step is taken, lambda <- max(lambda / lambda_factor, lambda_lower), then the parameter, function and max-iterations tests of
+ *      lili_pose_graph_solve; otherwise X stays, lambda <- lambda * lambda_factor, and lambda > lambda_upper ends the solve (LILI_PG_LAMBDA_LIMIT).  A non-positive
+ *      pivot anywhere is a rejected attempt (as GTSAM treats an indeterminate system), never LILI_LM_NUMERICAL_FAILURE; its cost[k] is the unchanged cost and its
+ *      step_inf[k] is 0.
+ * Summary: base.iterations = attempts; base.cost[k], step_inf[k], grad_inf[k] as in lili_pg_summary; lambda[k] = the lambda attempt k was solved with; accepted[k] = 0 / 1;
+ * base.final_cost and the estimates are those of the last accepted attempt; final_lambda = lambda after the last decision.  Every launch of every attempt is enqueued
+ * up front, the device decides each attempt, one synchronisation, one read-back; no atomics, every sum in a fixed order: the same graph and options give the same
+ * bytes on every run.  The damping exists in this call only: evaluate, marginals and lili_pose_graph_solve are unchanged by it.
+ * LILI_E_ARG, everything untouched: what lili_pose_graph_solve refuses, a null summary, an LM option that is not finite, initial_lambda <= 0, lambda_factor <= 1,
+ * lambda_lower <= 0, lambda_upper < lambda_lower, diagonal_damping other than 0 or 1.  LILI_E_STATE: an empty graph. */
+#define LILI_PG_LAMBDA_LIMIT 8             /* termination: a rejected attempt raised lambda above lambda_upper */
+typedef struct lili_pg_lm_options {
+    double initial_lambda, lambda_factor, lambda_lower, lambda_upper;
+    int32_t diagonal_damping, reserved_;
+} lili_pg_lm_options;
+typedef struct lili_pg_lm_summary {
+    lili_pg_summary base;
+    double lambda[LILI_PG_MAX_LOG];
+    int32_t accepted[LILI_PG_MAX_LOG];
+    int32_t steps_accepted, steps_rejected;
+    double final_lambda;
+} lili_pg_lm_summary;
+/* initial_lambda 1e-5, lambda_factor 10, lambda_lower 1e-10, lambda_upper 1e8, diagonal_damping 0 */
+void lili_pg_lm_default_options(lili_pg_lm_options* opt);
+int lili_pose_graph_solve_lm(lili_ctx* ctx, const lili_pg_options* options, const lili_pg_lm_options* lm_options, lili_pg_lm_summary* summary);
 /* Marginal covariances (gtsam: marginalCovariance / jointMarginalCovariance).  Sigma = H^-1 with H = J^T J of the graph as it is, linearised at the current
  * estimates: the matrix whose blocks lili_pose_graph_evaluate returns.  Only the variances of `options` are read (NULL = the defaults).  No step is taken: estimates
  * and measurements are untouched, and a following solve gives the bytes it would have given without the call.  A block is a row-major 6 x 6 in the node's own tangent

@@ -153,6 +153,28 @@ class PgSummary(C.Structure):
                     final_cost=self.final_cost, cost=list(self.cost[:k]), step_inf=list(self.step_inf[:k]), grad_inf=list(self.grad_inf[:kg]))
 
 
+PG_LOSS_NONE, PG_LOSS_HUBER, PG_LOSS_CAUCHY, PG_LOSS_GEMAN_MCCLURE = 0, 1, 2, 3      # LILI_PG_LOSS_*: the robust loss of a loop factor
+PG_LOSSES = {None: PG_LOSS_NONE, "none": PG_LOSS_NONE, "huber": PG_LOSS_HUBER, "cauchy": PG_LOSS_CAUCHY, "geman_mcclure": PG_LOSS_GEMAN_MCCLURE}
+PG_LAMBDA_LIMIT = 8          # LILI_PG_LAMBDA_LIMIT: lili_pose_graph_solve_lm ended on a rejected attempt that raised lambda above lambda_upper
+
+
+class PgLmOptions(C.Structure):
+    _fields_ = [("initial_lambda", C.c_double), ("lambda_factor", C.c_double), ("lambda_lower", C.c_double), ("lambda_upper", C.c_double),
+                ("diagonal_damping", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class PgLmSummary(C.Structure):
+    _fields_ = [("base", PgSummary), ("lambda_", C.c_double * PG_MAX_LOG), ("accepted", C.c_int32 * PG_MAX_LOG), ("steps_accepted", C.c_int32),
+                ("steps_rejected", C.c_int32), ("final_lambda", C.c_double)]
+
+    def as_dict(self):
+        d = self.base.as_dict()
+        k = min(self.base.iterations, PG_MAX_LOG)
+        d["lambda"], d["accepted"] = list(self.lambda_[:k]), [int(v) for v in self.accepted[:k]]
+        d["steps_accepted"], d["steps_rejected"], d["final_lambda"] = self.steps_accepted, self.steps_rejected, self.final_lambda
+        return d
+
+
 PG_MAX_PAIRS = 4096          # LILI_PG_MAX_PAIRS: pairs one lili_pose_graph_marginals call takes
 
 
@@ -367,6 +389,10 @@ _SIGS = {
     "lili_pose_graph_evaluate": (C.c_int, [C.c_void_p, C.POINTER(PgOptions), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_pose_graph_solve": (C.c_int, [C.c_void_p, C.POINTER(PgOptions), C.POINTER(PgSummary)]),
     "lili_pose_graph_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "lili_pose_graph_add_loop_robust": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
+    "lili_pose_graph_loop_status": (C.c_int, [C.c_void_p, C.POINTER(PgOptions), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "lili_pg_lm_default_options": (None, [C.POINTER(PgLmOptions)]),
+    "lili_pose_graph_solve_lm": (C.c_int, [C.c_void_p, C.POINTER(PgOptions), C.POINTER(PgLmOptions), C.POINTER(PgLmSummary)]),
     "lili_pose_graph_marginals": (C.c_int, [C.c_void_p, C.POINTER(PgOptions), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PgMarginalsInfo)]),
     "lili_pose_relative_covariance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_loop_measurement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

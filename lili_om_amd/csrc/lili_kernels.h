@@ -228,7 +228,7 @@ static_assert(6 * (kPgMaxNodes / kPgSegment + 2 * kPgMaxLoops) <= kPgMaxReduced 
 // at once fall on two disjoint halves of the banks)
 constexpr int kPgTile = 96, kPgTileK = 16, kPgTileLd = kPgTile + 16;
 static_assert(kPgTile % 6 == 0 && kPgTile % 16 == 0 && kPgTile % kPgTileK == 0 && kPgTileK % 4 == 0, "tile edge");
-struct PgLoop { int from, to, sep_from, sep_to; double meas[7], w[6]; };      // w = 1 / sqrt(variance)
+struct PgLoop { int from, to, sep_from, sep_to; double meas[7], w[6]; int loss, reserved_; double scale; };      // w = 1 / sqrt(variance); loss = LILI_PG_LOSS_*, scale = its k
 struct PgSeg { int left, first, last, right; };      // separator node ids (right = -1: the chain ends first), interior nodes first .. last (first > last: none)
 struct PgBlock { int p, q, begin, end; };            // a block (p, q), p >= q, of the reduced system that can be non-zero; its loops = ent[begin .. end)
 // The fixed part, then the arrays that follow the graph (device pointers into one staged block).  An entry of a loop list is 2 l + side: in node_ent, side 1 =
@@ -237,7 +237,7 @@ struct PgTables {
     int n, n_loops, n_sep, max_iter;
     double function_tolerance, gradient_tolerance, parameter_tolerance;
     double w_prior[6], w_odom[6];
-    int n_blk, reserved_;
+    int n_blk, damping;              // damping: 0 = none (every call but lili_pose_graph_solve_lm); 1 = + lambda on H's diagonal, 2 = + lambda h; lambda = PgState::lambda
     const int* sep;                  // n_sep
     const PgSeg* seg;                // n_sep
     const PgLoop* loop;              // n_loops
@@ -250,13 +250,19 @@ struct PgState {
     int done, fail;                  // done: the termination word — every later launch returns at its first instruction; fail: a segment met a non-positive pivot
     double cost, gmax;
     lili_pg_summary s;
+    // lili_pose_graph_solve_lm only: the damping of the attempt in flight, its bounds, and the log next to s
+    double lambda, lambda_factor, lambda_lower, lambda_upper;
+    double lambda_log[LILI_PG_MAX_LOG];
+    int accepted[LILI_PG_MAX_LOG];
+    int steps_accepted, steps_rejected;
 };
 struct PgDev {
     const PgTables* tab;
     PgState* st;
     double *X, *Xn;                  // estimates, candidate (7 per node)
     const double* meas;              // meas[i] = the measurement of factor i (7 per node; 0: the prior's)
-    double *fr, *fJ;                 // per factor: weighted residual (6), Jacobian blocks of its first and second node (2 x 36, row-major)
+    double *fr, *fJ;                 // per factor: weighted residual (6), Jacobian blocks of its first and second node (2 x 36, row-major); a robust loop's carry sqrt(w) too
+    double *lw;                      // per loop: its unweighted d^2 = |r|^2 and the weight w its loss gives it (1 without a loss), written by the linearisation
     double *g, *D, *S, *LB;          // gradient (6 N), diagonal blocks (36 N), sub[i] = chain block (i + 1, i) (36 N), loop blocks (from, to) (36 L)
     double *Ld, *Ls, *Y;             // per eliminated node: Cholesky factor of its pivot block (36), L block (i + 1, i) (36), the carried columns (6 x 13, column by column)
     double *gram;                    // per segment: sum of Y^T Y (13 x 13)

@@ -3,6 +3,8 @@
 //
 // One iteration is nine launches (more with the blocked reduced solve), every one enqueued up front; none waits for another workgroup, every loop is bounded by the graph's size:
 //   k_pg_linearize         two lanes per factor: the even one the weighted residual and the Jacobian block of the factor's first node, the odd one the second node's;
+//                          a loop with a robust loss (lili_pose_graph_add_loop_robust) is scaled by sqrt(w), w from its unweighted d^2 = |r|^2, which both lanes
+//                          compute on the same bits and the even one keeps in lw for the cost;
 //   k_pg_assemble          one lane per entry of H and g, by gather: a node sums its <= 2 chain contributions, then its loop contributions in loop order;
 //   k_pg_gate              one workgroup: |g|inf (and, before the first step, the cost) in a fixed order; sets the termination word at the gradient tolerance;
 //   k_pg_eliminate         one wave per segment: 6 x 6-block Cholesky along the chain between two separators, lane c carrying column c of
@@ -18,7 +20,12 @@
 //                          LDS); then per tile row i, last first, _back: every workgroup solves x_i = L_ii^-T y_i on the same bits, workgroup k < i takes
 //                          L_ik^T x_i off y_k, workgroup i writes the step.  Every tile and every piece of b has one owner per launch and sums over k ascending;
 //   k_pg_backsub           one wave per segment, every lane the same arithmetic: the interior nodes' step from the separators';
-//   k_pg_retract_cost      one workgroup: the candidate, its cost in a fixed order, the accept / stop decision, the termination word.
+//   k_pg_retract_cost      one workgroup: the candidate, its cost in a fixed order (a robust loop adds rho, not half its squared residual), the accept / stop
+//                          decision, the termination word.
+// lili_pose_graph_solve_lm is the same chain with PgTables::damping set: k_pg_eliminate (its kDamped instance) and k_pg_reduced_assemble add PgState::lambda to H's diagonal as they read it
+// (D itself stays undamped), a non-positive pivot raises PgState::fail instead of ending the solve and the launches up to the tail return at once, and the tail is
+//   k_pg_lm_decide         accept (X <- candidate, lambda down) or reject (X stays, lambda up; past its bound the solve ends), the log of the attempt.
+// A rejected attempt linearises again at the unchanged X.  lili_pose_graph_loop_status is one launch, k_pg_loop_status: d^2 and w of a range of loops.
 // lili_pose_graph_marginals runs the launches up to the reduced factorisation (the gate in its evaluate mode: it decides nothing), then three of its own:
 //   k_pg_marg_inverse      one workgroup per separator: its six columns of the reduced inverse through L and L^T, tile by tile;
 //   k_pg_marg_segments     one wave per segment, last node first: W = -L_II^-T Y_E, the segment's own inverse blocks, Sigma(i, i) of every node;
@@ -77,6 +84,25 @@ __device__ __forceinline__ void pg_error(const d3 pa, const dq qa, const d3 pb, 
     e[3] = ev.x; e[4] = ev.y; e[5] = ev.z;
 }
 __device__ __forceinline__ double pg_sq6(const double* r) { return ((((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]) + r[3] * r[3]) + r[4] * r[4]) + r[5] * r[5]; }
+// Robust loss on a loop (GTSAM's mEstimator::Huber / Cauchy / GemanMcClure), d2 = |r|^2 of the whitened residual, k the scale: the weight w = rho'(d) / d ...
+__device__ __forceinline__ double pg_loss_weight(const int loss, const double k, const double d2) {
+    if (loss == LILI_PG_LOSS_HUBER) { const double d = sqrt(d2); return d <= k ? 1.0 : k / d; }
+    const double k2 = k * k, u = k2 / (k2 + d2);
+    return loss == LILI_PG_LOSS_CAUCHY ? u : u * u;
+}
+// ... and 2 rho(d), what the factor adds to twice the cost (a factor without a loss adds d2)
+__device__ __forceinline__ double pg_loss_rho2(const int loss, const double k, const double d2) {
+    if (loss == LILI_PG_LOSS_HUBER) { const double d = sqrt(d2); return d <= k ? d2 : 2.0 * (k * (d - 0.5 * k)); }
+    const double k2 = k * k;
+    return loss == LILI_PG_LOSS_CAUCHY ? k2 * log1p(d2 / k2) : k2 * (d2 / (k2 + d2));
+}
+// the loss of factor f: LILI_PG_LOSS_NONE for the prior and the chain
+__device__ __forceinline__ int pg_loss_of(const PgTables& T, const int f, double& scale) {
+    if (f < T.n) { scale = 0.0; return LILI_PG_LOSS_NONE; }
+    const PgLoop& l = T.loop[f - T.n];
+    scale = l.scale;
+    return l.loss;
+}
 // the two poses, the measurement and the weights of factor f at the estimates x
 struct PgFactorIn { d3 pa, pb; dq qa, qb; const double* Z; const double* w; };
 __device__ __forceinline__ PgFactorIn pg_factor(const PgTables& T, const double* x, const double* meas, const int f) {
@@ -98,7 +124,10 @@ __device__ __forceinline__ double pg_factor_cost(const PgTables& T, const double
     pg_error(F.pa, F.qa, F.pb, F.qb, F.Z, e, qab, d, qe);
 #pragma unroll
     for (int k = 0; k < 6; k++) r[k] = e[k] * F.w[k];
-    return pg_sq6(r);
+    const double d2 = pg_sq6(r);
+    double scale;
+    const int loss = pg_loss_of(T, f, scale);
+    return loss == LILI_PG_LOSS_NONE ? d2 : pg_loss_rho2(loss, scale, d2);
 }
 // sum / maximum over the kPgWide threads of the single-workgroup stages, in a fixed order; every thread gets the result
 __device__ __forceinline__ double pg_block_sum(double v, double* sh) {
@@ -153,11 +182,26 @@ __global__ __launch_bounds__(256) void k_pg_linearize(const PgDev G) {
     dq qab, qe; d3 d;
     pg_error(F.pa, F.qa, F.pb, F.qb, F.Z, e, qab, d, qe);
     pg_jr_inv(e, Jri);
+    // a loop: its unweighted d^2 and the weight of its loss, by both lanes of the factor on the same bits; a robust loop's rows are scaled by sqrt(w)
+    bool robust = false;
+    double sw = 1.0;
+    if (f >= T.n) {
+        double rr[6], scale;
+#pragma unroll
+        for (int k = 0; k < 6; k++) rr[k] = e[k] * F.w[k];
+        const double d2 = pg_sq6(rr);
+        const int loss = pg_loss_of(T, f, scale);
+        robust = loss != LILI_PG_LOSS_NONE;
+        const double wl = robust ? pg_loss_weight(loss, scale, d2) : 1.0;
+        sw = sqrt(wl);
+        if (side == 0) { G.lw[2 * (size_t)(f - T.n)] = d2; G.lw[2 * (size_t)(f - T.n) + 1] = wl; }
+    }
+    auto rw = [&](const double v) { return robust ? v * sw : v; };
     double* J = G.fJ + (size_t)f * 72 + 36 * side;
     if (side == 0) {
         double* r = G.fr + (size_t)f * 6;
 #pragma unroll
-        for (int k = 0; k < 6; k++) r[k] = e[k] * F.w[k];
+        for (int k = 0; k < 6; k++) r[k] = rw(e[k] * F.w[k]);
         // first node: [-Jr^-1 Rab^T, 0; R_Z^T [d]x, -R_Z^T]
         double Rab[9], RabT[9], Rz[9], A[9], Bm[9];
         pg_mat(qab, Rab);
@@ -173,8 +217,8 @@ __global__ __launch_bounds__(256) void k_pg_linearize(const PgDev G) {
         for (int i = 0; i < 3; i++)
 #pragma unroll
             for (int j = 0; j < 3; j++) {
-                J[6 * i + j] = -A[3 * i + j] * F.w[i]; J[6 * i + 3 + j] = 0.0;
-                J[6 * (3 + i) + j] = Bm[3 * i + j] * F.w[3 + i]; J[6 * (3 + i) + 3 + j] = -Rz[3 * i + j] * F.w[3 + i];
+                J[6 * i + j] = rw(-A[3 * i + j] * F.w[i]); J[6 * i + 3 + j] = 0.0;
+                J[6 * (3 + i) + j] = rw(Bm[3 * i + j] * F.w[3 + i]); J[6 * (3 + i) + 3 + j] = rw(-Rz[3 * i + j] * F.w[3 + i]);
             }
     } else {
         // second node: [Jr^-1, 0; 0, R_Z^T R_A^T R_B]
@@ -184,8 +228,8 @@ __global__ __launch_bounds__(256) void k_pg_linearize(const PgDev G) {
         for (int i = 0; i < 3; i++)
 #pragma unroll
             for (int j = 0; j < 3; j++) {
-                J[6 * i + j] = Jri[3 * i + j] * F.w[i]; J[6 * i + 3 + j] = 0.0;
-                J[6 * (3 + i) + j] = 0.0; J[6 * (3 + i) + 3 + j] = Re[3 * i + j] * F.w[3 + i];
+                J[6 * i + j] = rw(Jri[3 * i + j] * F.w[i]); J[6 * i + 3 + j] = 0.0;
+                J[6 * (3 + i) + j] = 0.0; J[6 * (3 + i) + 3 + j] = rw(Re[3 * i + j] * F.w[3 + i]);
             }
     }
 }
@@ -257,7 +301,11 @@ __global__ __launch_bounds__(kPgWide) void k_pg_gate(const PgDev G, const int ev
     double cost = G.st->cost;
     if (it == 0 || evaluate) {
         double c = 0.0;
-        for (int f = t; f < T.n + T.n_loops; f += kPgWide) c += pg_sq6(G.fr + (size_t)f * 6);
+        for (int f = t; f < T.n + T.n_loops; f += kPgWide) {      // a robust loop adds 2 rho of its unweighted d^2, not the square of its weighted residual
+            double scale;
+            const int loss = pg_loss_of(T, f, scale);
+            c += loss == LILI_PG_LOSS_NONE ? pg_sq6(G.fr + (size_t)f * 6) : pg_loss_rho2(loss, scale, G.lw[2 * (size_t)(f - T.n)]);
+        }
         cost = 0.5 * pg_block_sum(c, sh);
     }
     if (t == 0) {
@@ -271,13 +319,19 @@ __global__ __launch_bounds__(kPgWide) void k_pg_gate(const PgDev G, const int ev
     }
 }
 
+// a diagonal entry of H under lili_pose_graph_solve_lm's damping (PgTables::damping != 0 in that call only): + lambda, or + lambda h
+__device__ __forceinline__ double pg_damped(const double h, const int damping, const double lambda) { return damping == 1 ? h + lambda : h + lambda * h; }
+// kDamped: lili_pose_graph_solve_lm's instance.  The pivot block sits on the serial path of the segment (one node after the other on one wave), so the calls
+// that never damp run the instance that has no trace of it
+template <bool kDamped>
 __global__ __launch_bounds__(64) void k_pg_eliminate(const PgDev G) {
     if (G.st->done) return;
     __shared__ double sLs[36];      // L block (i, i - 1), row by row
     __shared__ double sY[6 * kPgCols];      // the carried columns of node i, column by column
     const PgTables& T = *G.tab;
     const PgSeg sg = T.seg[blockIdx.x];
-    const int c = threadIdx.x, n = T.n;
+    const int c = threadIdx.x, n = T.n, damping = kDamped ? T.damping : 0;
+    const double lambda = kDamped ? G.st->lambda : 0.0;
     double yprev[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, acc[3] = {0.0, 0.0, 0.0};
     bool ok = true;
     for (int i = sg.first; i <= sg.last; i++) {
@@ -290,6 +344,7 @@ __global__ __launch_bounds__(64) void k_pg_eliminate(const PgDev G) {
 #pragma unroll
             for (int q = 0; q <= r; q++) {
                 double v = Di[6 * r + q];
+                if (kDamped && r == q) v = pg_damped(v, damping, lambda);
                 if (!first) {
                     double s = sLs[6 * r] * sLs[6 * q];
 #pragma unroll
@@ -407,6 +462,7 @@ __global__ __launch_bounds__(64) void k_pg_reduced_assemble(const PgDev G) {
         double v = 0.0;
         if (p == q) {
             v = G.D[(size_t)sp * 36 + t];
+            if (T.damping && r == c) v = pg_damped(v, T.damping, G.st->lambda);
             if (seg_p) v -= G.gram[(size_t)p * kPgGram + (1 + r) * kPgCols + (1 + c)];
             if (seg_l) v -= G.gram[(size_t)(p - 1) * kPgGram + (7 + r) * kPgCols + (7 + c)];
         } else if (p == q + 1) {
@@ -454,8 +510,8 @@ __global__ __launch_bounds__(kPgWide) void k_pg_reduced_solve(const PgDev G) {
         __syncthreads();      // column j is in front of the next column's reads of it
     }
     __syncthreads();
-    if (!ok) {
-        if (i == 0) { G.st->s.termination = LILI_LM_NUMERICAL_FAILURE; G.st->done = 1; }
+    if (!ok) {      // the damped solve counts it as a rejected attempt: fail stays up until the next gate, the launches in between return at once
+        if (i == 0) { if (T.damping) G.st->fail = 1; else { G.st->s.termination = LILI_LM_NUMERICAL_FAILURE; G.st->done = 1; } }
         return;
     }
     for (int j = 0; j < nr; j++) {      // L y = b
@@ -526,7 +582,7 @@ __global__ __launch_bounds__(256) void k_pg_chol_diag(const PgDev G, const int k
         __syncthreads();
     }
     if (!ok) {
-        if (t == 0) { G.st->s.termination = LILI_LM_NUMERICAL_FAILURE; G.st->done = 1; }
+        if (t == 0) { if (G.tab->damping) G.st->fail = 1; else { G.st->s.termination = LILI_LM_NUMERICAL_FAILURE; G.st->done = 1; } }
         return;
     }
     for (int e = t; e < m * m; e += 256) {
@@ -546,7 +602,7 @@ __global__ __launch_bounds__(256) void k_pg_chol_diag(const PgDev G, const int k
 // Row tile i = k + 1 + blockIdx.x of tile column k, one thread per row: x L_kk^T = a by forward substitution over the columns (the row stays in memory, in place), then
 // b_i -= L_ik y_k
 __global__ __launch_bounds__(128) void k_pg_chol_panel(const PgDev G, const int k) {
-    if (G.st->done) return;
+    if (G.st->done || G.st->fail) return;      // (fail without done: a rejected attempt of the damped solve)
     __shared__ double sL[kPgTile * (kPgTile + 1) / 2], sy[kPgTile];
     const int nr = 6 * G.tab->n_sep, o = k * kPgTile, i = k + 1 + blockIdx.x, t = threadIdx.x;
     double* R = G.red;
@@ -587,7 +643,7 @@ __global__ __launch_bounds__(128) void k_pg_chol_panel(const PgDev G, const int 
 // instruction tiles; the f64 result map: column = lane & 15, row = (lane >> 4) + 4 reg.  The sum over the kPgTile columns of tile column k runs in ascending order.
 typedef double pg_d4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void k_pg_chol_update(const PgDev G, const int k) {
-    if (G.st->done) return;
+    if (G.st->done || G.st->fail) return;      // (fail without done: a rejected attempt of the damped solve)
     __shared__ double sA[kPgTileK * kPgTileLd], sB[kPgTileK * kPgTileLd];
     const int nr = 6 * G.tab->n_sep, t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
     const int b = blockIdx.x;
@@ -656,7 +712,7 @@ __global__ __launch_bounds__(256) void k_pg_chol_update(const PgDev G, const int
 // Tile row i (launched last row first), workgroup kb = blockIdx.x <= i: every workgroup solves L_ii^T x_i = y_i in LDS on the same bits; workgroup kb < i takes
 // L_(i, kb)^T x_i off y_kb (its own piece of rhs), workgroup i writes the separators' step -x_i
 __global__ __launch_bounds__(128) void k_pg_chol_back(const PgDev G, const int i) {
-    if (G.st->done) return;
+    if (G.st->done || G.st->fail) return;      // (fail without done: a rejected attempt of the damped solve)
     __shared__ double sL[kPgTile * (kPgTile + 1) / 2], sx[kPgTile];
     const PgTables& T = *G.tab;
     const int nr = 6 * T.n_sep, o = i * kPgTile, m = min(kPgTile, nr - o), t = threadIdx.x, kb = blockIdx.x;
@@ -687,7 +743,7 @@ __global__ __launch_bounds__(128) void k_pg_chol_back(const PgDev G, const int i
 }
 
 __global__ __launch_bounds__(64) void k_pg_backsub(const PgDev G) {
-    if (G.st->done) return;
+    if (G.st->done || G.st->fail) return;      // (fail without done: a rejected attempt of the damped solve)
     const PgTables& T = *G.tab;
     const PgSeg sg = T.seg[blockIdx.x];
     double xl[6], xr[6], xn[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -728,10 +784,8 @@ __global__ __launch_bounds__(64) void k_pg_backsub(const PgDev G) {
     }
 }
 
-__global__ __launch_bounds__(kPgWide) void k_pg_retract_cost(const PgDev G) {
-    if (G.st->done) return;
-    __shared__ double sh[kPgWide];
-    __shared__ int s_accept;
+// the candidate X (+) delta into Xn, |delta|inf and the candidate's cost, in a fixed order; every thread gets both
+__device__ __forceinline__ void pg_candidate(const PgDev& G, double* sh, double& smax_out, double& cost_out) {
     const PgTables& T = *G.tab;
     const int t = threadIdx.x, n = T.n;
     double smax = 0.0;
@@ -750,10 +804,20 @@ __global__ __launch_bounds__(kPgWide) void k_pg_retract_cost(const PgDev G) {
 #pragma unroll
         for (int k = 0; k < 6; k++) smax = fmax(smax, fabs(dl[k]));
     }
-    smax = pg_block_max(smax, sh);      // (its barriers also put the candidate in front of the reads below)
+    smax_out = pg_block_max(smax, sh);      // (its barriers also put the candidate in front of the reads below)
     double c = 0.0;
     for (int f = t; f < n + T.n_loops; f += kPgWide) c += pg_factor_cost(T, G.Xn, G.meas, f);
-    const double new_cost = 0.5 * pg_block_sum(c, sh);
+    cost_out = 0.5 * pg_block_sum(c, sh);
+}
+
+__global__ __launch_bounds__(kPgWide) void k_pg_retract_cost(const PgDev G) {
+    if (G.st->done) return;
+    __shared__ double sh[kPgWide];
+    __shared__ int s_accept;
+    const PgTables& T = *G.tab;
+    const int t = threadIdx.x, n = T.n;
+    double smax, new_cost;
+    pg_candidate(G, sh, smax, new_cost);
     if (t == 0) {
         PgState& st = *G.st;
         const int it = st.s.iterations;
@@ -773,6 +837,63 @@ __global__ __launch_bounds__(kPgWide) void k_pg_retract_cost(const PgDev G) {
     }
     __syncthreads();
     if (s_accept) for (int e = t; e < 7 * n; e += kPgWide) G.X[e] = G.Xn[e];
+}
+
+// The tail of an attempt of lili_pose_graph_solve_lm: the candidate and its cost, then the decision.  Accepted (new cost <= cost): X <- candidate, lambda falls by
+// the factor down to its lower bound, the stop tests of k_pg_retract_cost.  Rejected (a higher cost, or a non-positive pivot on the way: PgState::fail, no
+// candidate is formed): X stays, lambda rises by the factor, past its upper bound the solve ends.
+__global__ __launch_bounds__(kPgWide) void k_pg_lm_decide(const PgDev G) {
+    if (G.st->done) return;
+    __shared__ double sh[kPgWide];
+    __shared__ int s_accept;
+    const PgTables& T = *G.tab;
+    const int t = threadIdx.x, n = T.n;
+    const bool failed = G.st->fail != 0;
+    double smax = 0.0, new_cost = G.st->cost;
+    if (!failed) pg_candidate(G, sh, smax, new_cost);
+    __syncthreads();      // every thread has read the state
+    if (t == 0) {
+        PgState& st = *G.st;
+        const int it = st.s.iterations;
+        const double cost = st.cost, lambda = st.lambda;
+        const int accept = !failed && new_cost <= cost;
+        if (it < LILI_PG_MAX_LOG) { st.s.cost[it] = new_cost; st.s.step_inf[it] = smax; st.lambda_log[it] = lambda; st.accepted[it] = accept; }
+        st.s.iterations = it + 1;
+        if (accept) {
+            st.steps_accepted++;
+            st.lambda = fmax(lambda / st.lambda_factor, st.lambda_lower);
+            st.cost = new_cost; st.s.final_cost = new_cost;
+            if (smax <= T.parameter_tolerance) { st.s.termination = LILI_LM_PARAMETER_TOLERANCE; st.done = 1; }
+            else if (fabs(cost - new_cost) <= T.function_tolerance * cost) { st.s.termination = LILI_LM_FUNCTION_TOLERANCE; st.done = 1; }
+            else if (it + 1 >= T.max_iter) { st.s.termination = LILI_LM_MAX_ITERATIONS; st.done = 1; }
+        } else {
+            st.steps_rejected++;
+            st.lambda = lambda * st.lambda_factor;
+            if (st.lambda > st.lambda_upper) { st.s.termination = LILI_PG_LAMBDA_LIMIT; st.done = 1; }
+            else if (it + 1 >= T.max_iter) { st.s.termination = LILI_LM_MAX_ITERATIONS; st.done = 1; }
+        }
+        s_accept = accept;
+    }
+    __syncthreads();
+    if (s_accept) for (int e = t; e < 7 * n; e += kPgWide) G.X[e] = G.Xn[e];
+}
+
+// lili_pose_graph_loop_status: d^2 and the weight of loops first .. first + n - 1 at the estimates, the linearisation's arithmetic
+__global__ __launch_bounds__(256) void k_pg_loop_status(const PgDev G, const int first, const int n, double* __restrict__ out) {
+    const PgTables& T = *G.tab;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int f = T.n + first + i;
+    const PgFactorIn F = pg_factor(T, G.X, G.meas, f);
+    double e[6], r[6], scale;
+    dq qab, qe; d3 d;
+    pg_error(F.pa, F.qa, F.pb, F.qb, F.Z, e, qab, d, qe);
+#pragma unroll
+    for (int k = 0; k < 6; k++) r[k] = e[k] * F.w[k];
+    const double d2 = pg_sq6(r);
+    const int loss = pg_loss_of(T, f, scale);
+    out[i] = d2;
+    out[n + i] = loss == LILI_PG_LOSS_NONE ? 1.0 : pg_loss_weight(loss, scale, d2);
 }
 
 // ---- marginal covariances (lili_pose_graph_marginals): the inverse-side passes behind one iteration's factorisation.  With the interior nodes I in front of the
@@ -1034,7 +1155,7 @@ namespace {
 struct PoseGraphState : ExtState {
     int n = 0, n_loops = 0;
     std::vector<PgLoop> loops;
-    DevBuf X, Xn, meas, tab, tabv, st, stage, fr, fJ, g, D, S, LB, Ld, Ls, Y, gram, red, delta, rhs;
+    DevBuf X, Xn, meas, tab, tabv, st, stage, fr, fJ, lw, g, D, S, LB, Ld, Ls, Y, gram, red, delta, rhs;
     DevBuf sinv, W, Pm, cov, cross, pairs;      // lili_pose_graph_marginals only
     PinBuf h_tab, h_io, h_pairs;
     Event ev0, ev1;
@@ -1051,7 +1172,7 @@ struct PoseGraphState : ExtState {
     // default caps (128 separators), 1.3 GB at LILI_PG_MAX_LOOPS_EXT loops (2112 separators, 12 672 unknowns)
     int work(lili_ctx* ctx, int n_sep, bool solve) {
         const size_t N = (size_t)n, F = (size_t)n + (size_t)n_loops, d = sizeof(double);
-        HIPCHK(fr.ensure(F * 6 * d)); HIPCHK(fJ.ensure(F * 72 * d));
+        HIPCHK(fr.ensure(F * 6 * d)); HIPCHK(fJ.ensure(F * 72 * d)); HIPCHK(lw.ensure((size_t)std::max(n_loops, 1) * 2 * d));
         HIPCHK(g.ensure(N * 6 * d)); HIPCHK(D.ensure(N * 36 * d)); HIPCHK(S.ensure(N * 36 * d)); HIPCHK(LB.ensure((size_t)std::max(n_loops, 1) * 36 * d));
         if (solve) {
             HIPCHK(Xn.ensure(N * 7 * d));
@@ -1075,7 +1196,7 @@ struct PoseGraphState : ExtState {
         PgDev G{};
         G.tab = tab.as<PgTables>(); G.st = st.as<PgState>();
         G.X = X.as<double>(); G.Xn = Xn.as<double>(); G.meas = meas.as<double>();
-        G.fr = fr.as<double>(); G.fJ = fJ.as<double>(); G.g = g.as<double>(); G.D = D.as<double>(); G.S = S.as<double>(); G.LB = LB.as<double>();
+        G.fr = fr.as<double>(); G.fJ = fJ.as<double>(); G.lw = lw.as<double>(); G.g = g.as<double>(); G.D = D.as<double>(); G.S = S.as<double>(); G.LB = LB.as<double>();
         G.Ld = Ld.as<double>(); G.Ls = Ls.as<double>(); G.Y = Y.as<double>(); G.gram = gram.as<double>(); G.red = red.as<double>(); G.delta = delta.as<double>();
         G.rhs = 6 * n_sep > kPgMaxReduced ? rhs.as<double>() : nullptr;
         G.sinv = sinv.as<double>(); G.W = W.as<double>(); G.P = Pm.as<double>(); G.cov = cov.as<double>(); G.cross = cross.as<double>(); G.pairs = pairs.as<int>();
@@ -1325,6 +1446,10 @@ int lili_pose_graph_append(lili_ctx* ctx, const double* prev, const double* pose
 }
 
 int lili_pose_graph_add_loop(lili_ctx* ctx, int from, int to, const double meas[7], const double var[6]) {
+    return lili_pose_graph_add_loop_robust(ctx, from, to, meas, var, LILI_PG_LOSS_NONE, 0.0);
+}
+
+int lili_pose_graph_add_loop_robust(lili_ctx* ctx, int from, int to, const double meas[7], const double var[6], int loss, double scale) {
     if (!ctx) return LILI_E_ARG;
     PoseGraphState* P = pg_of(ctx);
     ARGCHK(meas && var, "pose_graph_add_loop: null argument");
@@ -1332,10 +1457,13 @@ int lili_pose_graph_add_loop(lili_ctx* ctx, int from, int to, const double meas[
     ARGCHK(P->n_loops < ctx->pose_graph_max_loops, "pose_graph_add_loop: more than LILI_PG_MAX_LOOPS loops");      // (option "pose_graph_max_loops")
     ARGCHK(finite_n(var, 6), "pose_graph_add_loop: an input is not finite");
     for (int k = 0; k < 6; k++) ARGCHK(var[k] > 0, "pose_graph_add_loop: a variance is not positive");
+    ARGCHK(loss == LILI_PG_LOSS_NONE || loss == LILI_PG_LOSS_HUBER || loss == LILI_PG_LOSS_CAUCHY || loss == LILI_PG_LOSS_GEMAN_MCCLURE, "pose_graph_add_loop_robust: unknown loss");
+    ARGCHK(loss == LILI_PG_LOSS_NONE || (std::isfinite(scale) && scale > 0), "pose_graph_add_loop_robust: the scale of a loss must be positive and finite");
     PgLoop l{};
     TRY(check_poses(ctx, "pose_graph_add_loop", meas, 1, l.meas));
     l.from = from; l.to = to;
     for (int k = 0; k < 6; k++) l.w[k] = 1.0 / std::sqrt(var[k]);
+    l.loss = loss; l.scale = loss == LILI_PG_LOSS_NONE ? 0.0 : scale;
     P->loops.push_back(l);
     ctx->pose_graph_loops = P->n_loops = (int)P->loops.size();
     return LILI_OK;
@@ -1427,7 +1555,7 @@ int lili_pose_graph_solve(lili_ctx* ctx, const lili_pg_options* options, lili_pg
     for (int it = 0; it < opt.max_iterations; it++) {
         launch_linearize(ctx, P, G);
         hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 0);
-        hipLaunchKernelGGL(k_pg_eliminate, dim3(K), dim3(64), 0, ctx->stream, G);
+        hipLaunchKernelGGL((k_pg_eliminate<false>), dim3(K), dim3(64), 0, ctx->stream, G);
         hipLaunchKernelGGL(k_pg_zero, dim3(zero_blocks), dim3(256), 0, ctx->stream, G);
         hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(NB), dim3(64), 0, ctx->stream, G);
         launch_reduced_solve(ctx, G, K);
@@ -1444,11 +1572,96 @@ int lili_pose_graph_solve(lili_ctx* ctx, const lili_pg_options* options, lili_pg
     return LILI_OK;
 }
 
+void lili_pg_lm_default_options(lili_pg_lm_options* o) {
+    if (!o) return;
+    o->initial_lambda = 1e-5; o->lambda_factor = 10.0; o->lambda_lower = 1e-10; o->lambda_upper = 1e8;
+    o->diagonal_damping = 0; o->reserved_ = 0;
+}
+
+int lili_pose_graph_solve_lm(lili_ctx* ctx, const lili_pg_options* options, const lili_pg_lm_options* lm_options, lili_pg_lm_summary* summary) {
+    if (!ctx) return LILI_E_ARG;
+    PoseGraphState* P = pg_of(ctx);
+    ARGCHK(summary, "pose_graph_solve_lm: null summary");
+    lili_pg_options opt;
+    TRY(check_options(ctx, options, &opt));
+    lili_pg_lm_options lm;
+    if (lm_options) lm = *lm_options; else lili_pg_lm_default_options(&lm);
+    ARGCHK(std::isfinite(lm.initial_lambda) && std::isfinite(lm.lambda_factor) && std::isfinite(lm.lambda_lower) && std::isfinite(lm.lambda_upper),
+           "pose_graph_solve_lm: an option is not finite");
+    ARGCHK(lm.initial_lambda > 0 && lm.lambda_factor > 1 && lm.lambda_lower > 0 && lm.lambda_upper >= lm.lambda_lower,
+           "pose_graph_solve_lm: initial_lambda and lambda_lower must be positive, lambda_factor above 1, lambda_upper not below lambda_lower");
+    ARGCHK(lm.diagonal_damping == 0 || lm.diagonal_damping == 1, "pose_graph_solve_lm: diagonal_damping must be 0 or 1");
+    if (P->n == 0) return ctx->fail(LILI_E_STATE, "pose_graph_solve_lm: the graph is empty");
+    HIPCHK(hipSetDevice(ctx->device));
+    TRY(P->persist(ctx));
+    PgLayout lay;
+    int K = 0, NB = 0;
+    TRY(fill_tables(ctx, P, opt, &lay, &K, &NB));
+    PgTables* T = P->h_tab.as<PgTables>();
+    PgState* hs = reinterpret_cast<PgState*>(T + 1);
+    T->damping = lm.diagonal_damping ? 2 : 1;
+    hs->lambda = lm.initial_lambda; hs->lambda_factor = lm.lambda_factor; hs->lambda_lower = lm.lambda_lower; hs->lambda_upper = lm.lambda_upper;
+    TRY(P->work(ctx, K, true));
+    TRY(upload_tables(ctx, P, lay));
+    const PgDev G = P->dev(K);
+    const int zero_blocks = (int)std::min<size_t>(2048, ((size_t)18 * K * K + 255) / 256);
+    HIPCHK(P->ev0.get(hipEventDefault)); HIPCHK(P->ev1.get(hipEventDefault));
+    HIPCHK(hipEventRecord(P->ev0, ctx->stream));
+    for (int it = 0; it < opt.max_iterations; it++) {      // a rejected attempt linearises again at the unchanged X: the same bytes
+        launch_linearize(ctx, P, G);
+        hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 0);
+        hipLaunchKernelGGL((k_pg_eliminate<true>), dim3(K), dim3(64), 0, ctx->stream, G);
+        hipLaunchKernelGGL(k_pg_zero, dim3(zero_blocks), dim3(256), 0, ctx->stream, G);
+        hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(NB), dim3(64), 0, ctx->stream, G);
+        launch_reduced_solve(ctx, G, K);
+        hipLaunchKernelGGL(k_pg_backsub, dim3(K), dim3(64), 0, ctx->stream, G);
+        hipLaunchKernelGGL(k_pg_lm_decide, dim3(1), dim3(kPgWide), 0, ctx->stream, G);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(P->ev1, ctx->stream));
+    HIPCHK(hipMemcpyAsync(hs, P->st.p, sizeof(PgState), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipEventElapsedTime(&P->last_ms, P->ev0, P->ev1));
+    std::memset(summary, 0, sizeof *summary);
+    summary->base = hs->s;
+    std::memcpy(summary->lambda, hs->lambda_log, sizeof summary->lambda);
+    for (int k = 0; k < LILI_PG_MAX_LOG; k++) summary->accepted[k] = hs->accepted[k];
+    summary->steps_accepted = hs->steps_accepted; summary->steps_rejected = hs->steps_rejected;
+    summary->final_lambda = hs->lambda;
+    return LILI_OK;
+}
+
+int lili_pose_graph_loop_status(lili_ctx* ctx, const lili_pg_options* options, int first, int n, double* chi2, double* weight) {
+    if (!ctx) return LILI_E_ARG;
+    PoseGraphState* P = pg_of(ctx);
+    ARGCHK(chi2 && weight, "pose_graph_loop_status: null argument");
+    ARGCHK(first >= 0 && n >= 1 && first <= P->n_loops && n <= P->n_loops - first, "pose_graph_loop_status: range outside the graph's loops");
+    lili_pg_options opt;
+    TRY(check_options(ctx, options, &opt));
+    HIPCHK(hipSetDevice(ctx->device));
+    TRY(P->persist(ctx));
+    PgLayout lay;
+    int K = 0, NB = 0;
+    TRY(fill_tables(ctx, P, opt, &lay, &K, &NB));
+    const size_t bytes = sizeof(double) * 2 * (size_t)n;
+    HIPCHK(P->h_io.ensure(bytes));
+    HIPCHK(P->stage.ensure(bytes));
+    TRY(upload_tables(ctx, P, lay));
+    const PgDev G = P->dev(0);
+    hipLaunchKernelGGL(k_pg_loop_status, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, G, first, n, P->stage.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(P->h_io.p, P->stage.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(chi2, P->h_io.p, sizeof(double) * (size_t)n);
+    std::memcpy(weight, P->h_io.as<double>() + n, sizeof(double) * (size_t)n);
+    return LILI_OK;
+}
+
 int lili_pose_graph_kernel_ms(lili_ctx* ctx, float* ms) {
     if (!ctx) return LILI_E_ARG;
     ARGCHK(ms, "pose_graph_kernel_ms: null argument");
     const PoseGraphState* P = static_cast<const PoseGraphState*>(ctx->ext[lili_ctx::kExtPoseGraph].get());
-    if (!P || P->last_ms < 0.f) return ctx->fail(LILI_E_STATE, "pose_graph_kernel_ms: no lili_pose_graph_solve yet");
+    if (!P || P->last_ms < 0.f) return ctx->fail(LILI_E_STATE, "pose_graph_kernel_ms: no lili_pose_graph_solve or lili_pose_graph_solve_lm yet");
     *ms = P->last_ms;
     return LILI_OK;
 }
@@ -1486,7 +1699,7 @@ int lili_pose_graph_marginals(lili_ctx* ctx, const lili_pg_options* options, int
     // the front half of a solve iteration; the gate in its evaluate mode: a converged graph is factored like any other
     launch_linearize(ctx, P, G);
     hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 1);
-    hipLaunchKernelGGL(k_pg_eliminate, dim3(K), dim3(64), 0, ctx->stream, G);
+    hipLaunchKernelGGL((k_pg_eliminate<false>), dim3(K), dim3(64), 0, ctx->stream, G);
     hipLaunchKernelGGL(k_pg_zero, dim3(zero_blocks), dim3(256), 0, ctx->stream, G);
     hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(NB), dim3(64), 0, ctx->stream, G);
     launch_reduced_solve(ctx, G, K);

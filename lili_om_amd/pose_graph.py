@@ -17,12 +17,16 @@ A full loop closure, with a KeyframeArchive `archive`, a FrameTrajectory `traj` 
 
 How well the poses are known (gtsam: marginalCovariance / jointMarginalCovariance): graph.marginals() -> the 6 x 6 covariance of every node and of node pairs at the
 current estimates, graph.relative_covariance(i, j) -> the covariance of between(X_i, X_j); INTEGRATION.md §1c says what a loop closure can do with them.
+
+A false closure (an ICP that passed lc_icp_thres on a repeated corridor): add_loop / add_loop_from_icp take loss="huber" | "cauchy" | "geman_mcclure" and its scale
+(GTSAM's noiseModel::Robust on the loop factor), graph.loop_status() -> every loop's chi2 and the weight its loss leaves it, graph.solve_lm() is the damped
+(Levenberg-Marquardt) solve for a graph that starts far from its minimum.
 """
 import ctypes as C
 
 import numpy as np
 
-from .api import LiliError, PgMarginalsInfo, PgOptions, PgSummary, _ptr, load_library
+from .api import PG_LOSSES, LiliError, PgLmOptions, PgLmSummary, PgMarginalsInfo, PgOptions, PgSummary, _ptr, load_library
 
 
 def _f64(a, shape):
@@ -99,16 +103,40 @@ class PoseGraph:
         self.ctx._chk(self.lib.lili_pose_graph_append(self.ctx.h, _ptr(pv), _ptr(p), p.shape[0], C.byref(first)))
         return first.value
 
-    def add_loop(self, node_from, node_to, meas, var):
+    def add_loop(self, node_from, node_to, meas, var, loss=None, scale=None):
+        """loss: None / "none", "huber", "cauchy", "geman_mcclure" (or an api.PG_LOSS_* code); scale: the loss's k in units of the whitened residual (None = 1)"""
         m = _f64(meas, (7,))
         v = np.full(6, float(var)) if np.ndim(var) == 0 else _f64(var, (6,))
-        self.ctx._chk(self.lib.lili_pose_graph_add_loop(self.ctx.h, int(node_from), int(node_to), _ptr(m), _ptr(v)))
+        if loss is None and scale is None:
+            self.ctx._chk(self.lib.lili_pose_graph_add_loop(self.ctx.h, int(node_from), int(node_to), _ptr(m), _ptr(v)))
+            return
+        if isinstance(loss, str) and loss not in PG_LOSSES:
+            raise LiliError(f"unknown loss {loss!r}: one of {sorted(k for k in PG_LOSSES if k)}")
+        kind = PG_LOSSES[loss] if loss is None or isinstance(loss, str) else int(loss)
+        self.ctx._chk(self.lib.lili_pose_graph_add_loop_robust(self.ctx.h, int(node_from), int(node_to), _ptr(m), _ptr(v), kind, 1.0 if scale is None else float(scale)))
 
-    def add_loop_from_icp(self, node_from, node_to, T_icp, pose_latest, pose_closest, fitness):
-        """performLoopClosure's factor (L:2587-2625): the measurement from the ICP transform and the two keyframe poses, all six variances = the fitness"""
+    def add_loop_from_icp(self, node_from, node_to, T_icp, pose_latest, pose_closest, fitness, loss=None, scale=None):
+        """performLoopClosure's factor (L:2587-2625): the measurement from the ICP transform and the two keyframe poses, all six variances = the fitness;
+        loss / scale as in add_loop"""
         m = loop_measurement(T_icp, pose_latest, pose_closest)
-        self.add_loop(node_from, node_to, m, float(fitness))
+        self.add_loop(node_from, node_to, m, float(fitness), loss, scale)
         return m
+
+    def loop_status(self, first=0, n=None, options=None):
+        """what the loss decided at the current estimates -> chi2 (n,), weight (n,) of loops first .. first + n - 1 in the order they were added (weight 1 without
+        a loss); no step is taken"""
+        n = self.info()[1] - int(first) if n is None else int(n)
+        chi2, weight = np.zeros(max(n, 0)), np.zeros(max(n, 0))
+        if n > 0:
+            self.ctx._chk(self.lib.lili_pose_graph_loop_status(self.ctx.h, C.byref(options) if options is not None else None, int(first), n, _ptr(chi2), _ptr(weight)))
+        return chi2, weight
+
+    def lm_options(self, **kw):
+        o = PgLmOptions()
+        self.lib.lili_pg_lm_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
 
     def poses(self, first=0, n=None):
         n = self.info()[0] - first if n is None else int(n)
@@ -136,6 +164,19 @@ class PoseGraph:
             options = self.options(**kw)
         s = PgSummary()
         self.ctx._chk(self.lib.lili_pose_graph_solve(self.ctx.h, C.byref(options) if options is not None else None, C.byref(s)))
+        self.last_summary = s
+        return s.as_dict()
+
+    def solve_lm(self, options=None, lm=None, **kw):
+        """Levenberg-Marquardt on the device -> summary dict: solve()'s entries per attempt, plus lambda and accepted (one per attempt), steps_accepted,
+        steps_rejected, final_lambda.  kw: the fields of either option structure (used where options / lm is None)"""
+        lm_names = {f[0] for f in PgLmOptions._fields_}
+        if options is None and any(k not in lm_names for k in kw):
+            options = self.options(**{k: v for k, v in kw.items() if k not in lm_names})
+        if lm is None and any(k in lm_names for k in kw):
+            lm = self.lm_options(**{k: v for k, v in kw.items() if k in lm_names})
+        s = PgLmSummary()
+        self.ctx._chk(self.lib.lili_pose_graph_solve_lm(self.ctx.h, C.byref(options) if options is not None else None, C.byref(lm) if lm is not None else None, C.byref(s)))
         self.last_summary = s
         return s.as_dict()
 
