@@ -39,6 +39,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -61,13 +62,18 @@ __device__ __forceinline__ void pg_log(dq q, double phi[3]) {
     if (n2 > 0.0) { const double n = sqrt(n2); k = 2.0 * atan2(n, q.w) / n; }
     phi[0] = k * q.x; phi[1] = k * q.y; phi[2] = k * q.z;
 }
+// S = [v]x, row-major (host too: lili_pose_relative_covariance)
+__host__ __device__ __forceinline__ void pg_skew(const double x, const double y, const double z, double S[9]) {
+    S[0] = 0.0; S[1] = -z; S[2] = y; S[3] = z; S[4] = 0.0; S[5] = -x; S[6] = -y; S[7] = x; S[8] = 0.0;
+}
 // the inverse of SO(3)'s right Jacobian: I + [phi]x / 2 + c [phi]x^2, c by its series below LILI_PG_SMALL_ANGLE
 __device__ __forceinline__ void pg_jr_inv(const double phi[3], double M[9]) {
     const double t2 = (phi[0] * phi[0] + phi[1] * phi[1]) + phi[2] * phi[2];
     double c;
     if (t2 < LILI_PG_SMALL_ANGLE * LILI_PG_SMALL_ANGLE) c = 1.0 / 12.0 + t2 * (1.0 / 720.0 + t2 * (1.0 / 30240.0 + t2 * (1.0 / 1209600.0)));
     else { const double t = sqrt(t2); c = 1.0 / t2 - (1.0 + cos(t)) / (2.0 * t * sin(t)); }
-    const double S[9] = {0.0, -phi[2], phi[1], phi[2], 0.0, -phi[0], -phi[1], phi[0], 0.0};
+    double S[9];
+    pg_skew(phi[0], phi[1], phi[2], S);
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -117,36 +123,54 @@ __device__ __forceinline__ PgFactorIn pg_factor(const PgTables& T, const double*
     F.pb = d3{B[0], B[1], B[2]}; F.qb = pg_quat(B);
     return F;
 }
-__device__ __forceinline__ double pg_factor_cost(const PgTables& T, const double* x, const double* meas, const int f) {
-    const PgFactorIn F = pg_factor(T, x, meas, f);
-    double e[6], r[6];
-    dq qab, qe; d3 d;
-    pg_error(F.pa, F.qa, F.pb, F.qb, F.Z, e, qab, d, qe);
+// d^2 = |r|^2 of a factor's whitened error: one text for the cost, the linearisation's weight and lili_pose_graph_loop_status
+__device__ __forceinline__ double pg_whitened_d2(const PgFactorIn& F, const double e[6]) {
+    double r[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) r[k] = e[k] * F.w[k];
-    const double d2 = pg_sq6(r);
+    return pg_sq6(r);
+}
+__device__ __forceinline__ double pg_factor_cost(const PgTables& T, const double* x, const double* meas, const int f) {
+    const PgFactorIn F = pg_factor(T, x, meas, f);
+    double e[6];
+    dq qab, qe; d3 d;
+    pg_error(F.pa, F.qa, F.pb, F.qb, F.Z, e, qab, d, qe);
+    const double d2 = pg_whitened_d2(F, e);
     double scale;
     const int loss = pg_loss_of(T, f, scale);
     return loss == LILI_PG_LOSS_NONE ? d2 : pg_loss_rho2(loss, scale, d2);
 }
-// sum / maximum over the kPgWide threads of the single-workgroup stages, in a fixed order; every thread gets the result
-__device__ __forceinline__ double pg_block_sum(double v, double* sh) {
+// Op (PgSum / PgMax) over the kPgWide threads of the single-workgroup stages, in a fixed order; every thread gets the result
+struct PgSum { __device__ double operator()(const double a, const double b) const { return a + b; } };
+struct PgMax { __device__ double operator()(const double a, const double b) const { return fmax(a, b); } };
+template <class Op>
+__device__ __forceinline__ double pg_block_reduce(double v, double* sh) {
     const int t = threadIdx.x;
     sh[t] = v;
     __syncthreads();
-    for (int s = kPgWide / 2; s > 0; s >>= 1) { if (t < s) sh[t] = sh[t] + sh[t + s]; __syncthreads(); }
+    for (int s = kPgWide / 2; s > 0; s >>= 1) { if (t < s) sh[t] = Op()(sh[t], sh[t + s]); __syncthreads(); }
     const double r = sh[0];
     __syncthreads();
     return r;
 }
-__device__ __forceinline__ double pg_block_max(double v, double* sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = kPgWide / 2; s > 0; s >>= 1) { if (t < s) sh[t] = fmax(sh[t], sh[t + s]); __syncthreads(); }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
+// x <- L^-1 x and x <- L^-T x, L a row-major lower-triangular 6 x 6 block
+__device__ __forceinline__ void pg_fwd6(const double* L, double x[6]) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        double v = x[k];
+#pragma unroll
+        for (int m = 0; m < k; m++) v -= L[6 * k + m] * x[m];
+        x[k] = v / L[6 * k + k];
+    }
+}
+__device__ __forceinline__ void pg_back6(const double* L, double x[6]) {
+#pragma unroll
+    for (int k = 5; k >= 0; k--) {
+        double v = x[k];
+#pragma unroll
+        for (int m = k + 1; m < 6; m++) v -= L[6 * m + k] * x[m];
+        x[k] = v / L[6 * k + k];
+    }
 }
 
 // new nodes first .. first + n - 1 from the staged rows (row 0 = prev, rows 1 .. n = the poses): estimates and frozen measurements
@@ -186,10 +210,8 @@ __global__ __launch_bounds__(256) void k_pg_linearize(const PgDev G) {
     bool robust = false;
     double sw = 1.0;
     if (f >= T.n) {
-        double rr[6], scale;
-#pragma unroll
-        for (int k = 0; k < 6; k++) rr[k] = e[k] * F.w[k];
-        const double d2 = pg_sq6(rr);
+        double scale;
+        const double d2 = pg_whitened_d2(F, e);
         const int loss = pg_loss_of(T, f, scale);
         robust = loss != LILI_PG_LOSS_NONE;
         const double wl = robust ? pg_loss_weight(loss, scale, d2) : 1.0;
@@ -211,7 +233,8 @@ __global__ __launch_bounds__(256) void k_pg_linearize(const PgDev G) {
 #pragma unroll
             for (int j = 0; j < 3; j++) RabT[3 * i + j] = Rab[3 * j + i];
         pg_mm3(Jri, RabT, A);
-        const double Sd[9] = {0.0, -d.z, d.y, d.z, 0.0, -d.x, -d.y, d.x, 0.0};
+        double Sd[9];
+        pg_skew(d.x, d.y, d.z, Sd);
         pg_mm3(Rz, Sd, Bm);
 #pragma unroll
         for (int i = 0; i < 3; i++)
@@ -297,7 +320,7 @@ __global__ __launch_bounds__(kPgWide) void k_pg_gate(const PgDev G, const int ev
     const int t = threadIdx.x, it = G.st->s.iterations;
     double m = 0.0;
     for (int i = t; i < 6 * T.n; i += kPgWide) m = fmax(m, fabs(G.g[i]));
-    m = pg_block_max(m, sh);
+    m = pg_block_reduce<PgMax>(m, sh);
     double cost = G.st->cost;
     if (it == 0 || evaluate) {
         double c = 0.0;
@@ -306,7 +329,7 @@ __global__ __launch_bounds__(kPgWide) void k_pg_gate(const PgDev G, const int ev
             const int loss = pg_loss_of(T, f, scale);
             c += loss == LILI_PG_LOSS_NONE ? pg_sq6(G.fr + (size_t)f * 6) : pg_loss_rho2(loss, scale, G.lw[2 * (size_t)(f - T.n)]);
         }
-        cost = 0.5 * pg_block_sum(c, sh);
+        cost = 0.5 * pg_block_reduce<PgSum>(c, sh);
     }
     if (t == 0) {
         PgState& st = *G.st;
@@ -399,13 +422,7 @@ __global__ __launch_bounds__(64) void k_pg_eliminate(const PgDev G) {
                 z[k] -= s;
             }
         }
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            double v = z[k];
-#pragma unroll
-            for (int m = 0; m < k; m++) v -= A[6 * k + m] * z[m];
-            z[k] = v / A[6 * k + k];
-        }
+        pg_fwd6(A, z);
         __syncthreads();      // every lane has read sLs and sY of the previous node
         if (c < 6) {
 #pragma unroll
@@ -484,6 +501,11 @@ __global__ __launch_bounds__(64) void k_pg_reduced_assemble(const PgDev G) {
     }
 }
 
+// a non-positive pivot ends the solve; the damped solve counts it as a rejected attempt: fail stays up until the next gate, the launches in between return at once
+__device__ __forceinline__ void pg_pivot_failed(const PgTables& T, PgState& st) {
+    if (T.damping) st.fail = 1; else { st.s.termination = LILI_LM_NUMERICAL_FAILURE; st.done = 1; }
+}
+
 __global__ __launch_bounds__(kPgWide) void k_pg_reduced_solve(const PgDev G) {
     if (G.st->done) return;
     __shared__ double sy[kPgMaxReduced], srow[kPgMaxReduced];
@@ -510,8 +532,8 @@ __global__ __launch_bounds__(kPgWide) void k_pg_reduced_solve(const PgDev G) {
         __syncthreads();      // column j is in front of the next column's reads of it
     }
     __syncthreads();
-    if (!ok) {      // the damped solve counts it as a rejected attempt: fail stays up until the next gate, the launches in between return at once
-        if (i == 0) { if (T.damping) G.st->fail = 1; else { G.st->s.termination = LILI_LM_NUMERICAL_FAILURE; G.st->done = 1; } }
+    if (!ok) {
+        if (i == 0) pg_pivot_failed(T, *G.st);
         return;
     }
     for (int j = 0; j < nr; j++) {      // L y = b
@@ -534,7 +556,22 @@ __global__ __launch_bounds__(kPgWide) void k_pg_reduced_solve(const PgDev G) {
 // ---- the blocked reduced solve (6 n_sep > kPgMaxReduced).  red holds the lower triangle column by column: element (r, c), r >= c, at red[c * nr + r].  Tile (i, j)
 // covers rows i T .. and columns j T ..; the last tile row / column may overhang the matrix: its loads read zeros, its stores are masked.
 __device__ __forceinline__ int pg_tri(const int r, const int c) { return r * (r + 1) / 2 + c; }      // the packed lower triangle of a tile in LDS, r >= c
-constexpr int kPgPanelCols = 32;      // columns of its row a panel thread holds in registers at a time
+// the lower triangle of the diagonal tile at o (m of its rows inside the matrix) into LDS and back, by the kThreads threads of the workgroup
+template <int kThreads>
+__device__ __forceinline__ void pg_load_tile(double* sL, const double* R, const int nr, const int o, const int m) {
+    for (int e = threadIdx.x; e < m * m; e += kThreads) {
+        const int c = e / m, r = e - c * m;
+        if (r >= c) sL[pg_tri(r, c)] = R[(size_t)(o + c) * nr + (o + r)];
+    }
+}
+template <int kThreads>
+__device__ __forceinline__ void pg_store_tile(const double* sL, double* R, const int nr, const int o, const int m) {
+    for (int e = threadIdx.x; e < m * m; e += kThreads) {
+        const int c = e / m, r = e - c * m;
+        if (r >= c) R[(size_t)(o + c) * nr + (o + r)] = sL[pg_tri(r, c)];
+    }
+}
+constexpr int kPgPanelCols = 32;     // columns of its row a panel thread holds in registers at a time
 static_assert(kPgTile % kPgPanelCols == 0, "panel columns");
 
 // Tile column k: L_kk = chol(A_kk) in LDS (right-looking, element (r, c) takes its updates over j ascending), then y_k = L_kk^-1 b_k.  A non-positive pivot, or a
@@ -544,10 +581,7 @@ __global__ __launch_bounds__(256) void k_pg_chol_diag(const PgDev G, const int k
     __shared__ double sL[kPgTile * (kPgTile + 1) / 2], sb[kPgTile];
     const int nr = 6 * G.tab->n_sep, o = k * kPgTile, m = min(kPgTile, nr - o), t = threadIdx.x;
     double* R = G.red;
-    for (int e = t; e < m * m; e += 256) {
-        const int c = e / m, r = e - c * m;
-        if (r >= c) sL[pg_tri(r, c)] = R[(size_t)(o + c) * nr + (o + r)];
-    }
+    pg_load_tile<256>(sL, R, nr, o, m);
     if (t < m) sb[t] = G.rhs[o + t];
     bool ok = G.st->fail == 0;
     __syncthreads();
@@ -582,13 +616,10 @@ __global__ __launch_bounds__(256) void k_pg_chol_diag(const PgDev G, const int k
         __syncthreads();
     }
     if (!ok) {
-        if (t == 0) { if (G.tab->damping) G.st->fail = 1; else { G.st->s.termination = LILI_LM_NUMERICAL_FAILURE; G.st->done = 1; } }
+        if (t == 0) pg_pivot_failed(*G.tab, *G.st);
         return;
     }
-    for (int e = t; e < m * m; e += 256) {
-        const int c = e / m, r = e - c * m;
-        if (r >= c) R[(size_t)(o + c) * nr + (o + r)] = sL[pg_tri(r, c)];
-    }
+    pg_store_tile<256>(sL, R, nr, o, m);
     for (int j = 0; j < m; j++) {      // L y = b
         const double yj = sb[j] / sL[pg_tri(j, j)];
         __syncthreads();
@@ -606,10 +637,7 @@ __global__ __launch_bounds__(128) void k_pg_chol_panel(const PgDev G, const int 
     __shared__ double sL[kPgTile * (kPgTile + 1) / 2], sy[kPgTile];
     const int nr = 6 * G.tab->n_sep, o = k * kPgTile, i = k + 1 + blockIdx.x, t = threadIdx.x;
     double* R = G.red;
-    for (int e = t; e < kPgTile * kPgTile; e += 128) {      // tile column k is not the last one: it is whole
-        const int c = e / kPgTile, r = e - c * kPgTile;
-        if (r >= c) sL[pg_tri(r, c)] = R[(size_t)(o + c) * nr + (o + r)];
-    }
+    pg_load_tile<128>(sL, R, nr, o, kPgTile);      // tile column k is not the last one: it is whole
     if (t < kPgTile) sy[t] = G.rhs[o + t];
     __syncthreads();
     const int row = i * kPgTile + t;
@@ -717,10 +745,7 @@ __global__ __launch_bounds__(128) void k_pg_chol_back(const PgDev G, const int i
     const PgTables& T = *G.tab;
     const int nr = 6 * T.n_sep, o = i * kPgTile, m = min(kPgTile, nr - o), t = threadIdx.x, kb = blockIdx.x;
     const double* R = G.red;
-    for (int e = t; e < m * m; e += 128) {
-        const int c = e / m, r = e - c * m;
-        if (r >= c) sL[pg_tri(r, c)] = R[(size_t)(o + c) * nr + (o + r)];
-    }
+    pg_load_tile<128>(sL, R, nr, o, m);
     if (t < m) sx[t] = G.rhs[o + t];
     __syncthreads();
     for (int c = m - 1; c >= 0; c--) {
@@ -768,13 +793,7 @@ __global__ __launch_bounds__(64) void k_pg_backsub(const PgDev G) {
             }
             x[k] = s;
         }
-#pragma unroll
-        for (int k = 5; k >= 0; k--) {
-            double v = x[k];
-#pragma unroll
-            for (int m = k + 1; m < 6; m++) v -= Ld[6 * m + k] * x[m];
-            x[k] = v / Ld[6 * k + k];
-        }
+        pg_back6(Ld, x);
         if (threadIdx.x == 0) {
 #pragma unroll
             for (int k = 0; k < 6; k++) G.delta[(size_t)i * 6 + k] = x[k];
@@ -804,21 +823,31 @@ __device__ __forceinline__ void pg_candidate(const PgDev& G, double* sh, double&
 #pragma unroll
         for (int k = 0; k < 6; k++) smax = fmax(smax, fabs(dl[k]));
     }
-    smax_out = pg_block_max(smax, sh);      // (its barriers also put the candidate in front of the reads below)
+    smax_out = pg_block_reduce<PgMax>(smax, sh);      // (its barriers also put the candidate in front of the reads below)
     double c = 0.0;
     for (int f = t; f < n + T.n_loops; f += kPgWide) c += pg_factor_cost(T, G.Xn, G.meas, f);
-    cost_out = 0.5 * pg_block_sum(c, sh);
+    cost_out = 0.5 * pg_block_reduce<PgSum>(c, sh);
+}
+// thread 0, an accepted step: the new cost, then the stop tests (parameter tolerance, function tolerance, the iteration cap)
+__device__ __forceinline__ void pg_accept_step(PgState& st, const PgTables& T, const int it, const double cost, const double new_cost, const double smax) {
+    st.cost = new_cost; st.s.final_cost = new_cost;
+    if (smax <= T.parameter_tolerance) { st.s.termination = LILI_LM_PARAMETER_TOLERANCE; st.done = 1; }
+    else if (fabs(cost - new_cost) <= T.function_tolerance * cost) { st.s.termination = LILI_LM_FUNCTION_TOLERANCE; st.done = 1; }
+    else if (it + 1 >= T.max_iter) { st.s.termination = LILI_LM_MAX_ITERATIONS; st.done = 1; }
+}
+// X <- the candidate, by the whole workgroup
+__device__ __forceinline__ void pg_commit(const PgDev& G, const int n) {
+    for (int e = threadIdx.x; e < 7 * n; e += kPgWide) G.X[e] = G.Xn[e];
 }
 
 __global__ __launch_bounds__(kPgWide) void k_pg_retract_cost(const PgDev G) {
     if (G.st->done) return;
     __shared__ double sh[kPgWide];
     __shared__ int s_accept;
-    const PgTables& T = *G.tab;
-    const int t = threadIdx.x, n = T.n;
+    const int n = G.tab->n;
     double smax, new_cost;
     pg_candidate(G, sh, smax, new_cost);
-    if (t == 0) {
+    if (threadIdx.x == 0) {
         PgState& st = *G.st;
         const int it = st.s.iterations;
         const double cost = st.cost;
@@ -826,17 +855,11 @@ __global__ __launch_bounds__(kPgWide) void k_pg_retract_cost(const PgDev G) {
         st.s.iterations = it + 1;
         int accept = 0;
         if (!(new_cost <= cost)) { st.s.termination = LILI_PG_COST_INCREASED; st.done = 1; }
-        else {
-            accept = 1;
-            st.cost = new_cost; st.s.final_cost = new_cost;
-            if (smax <= T.parameter_tolerance) { st.s.termination = LILI_LM_PARAMETER_TOLERANCE; st.done = 1; }
-            else if (fabs(cost - new_cost) <= T.function_tolerance * cost) { st.s.termination = LILI_LM_FUNCTION_TOLERANCE; st.done = 1; }
-            else if (it + 1 >= T.max_iter) { st.s.termination = LILI_LM_MAX_ITERATIONS; st.done = 1; }
-        }
+        else { accept = 1; pg_accept_step(st, *G.tab, it, cost, new_cost, smax); }
         s_accept = accept;
     }
     __syncthreads();
-    if (s_accept) for (int e = t; e < 7 * n; e += kPgWide) G.X[e] = G.Xn[e];
+    if (s_accept) pg_commit(G, n);
 }
 
 // The tail of an attempt of lili_pose_graph_solve_lm: the candidate and its cost, then the decision.  Accepted (new cost <= cost): X <- candidate, lambda falls by
@@ -847,12 +870,12 @@ __global__ __launch_bounds__(kPgWide) void k_pg_lm_decide(const PgDev G) {
     __shared__ double sh[kPgWide];
     __shared__ int s_accept;
     const PgTables& T = *G.tab;
-    const int t = threadIdx.x, n = T.n;
+    const int n = T.n;
     const bool failed = G.st->fail != 0;
     double smax = 0.0, new_cost = G.st->cost;
     if (!failed) pg_candidate(G, sh, smax, new_cost);
     __syncthreads();      // every thread has read the state
-    if (t == 0) {
+    if (threadIdx.x == 0) {
         PgState& st = *G.st;
         const int it = st.s.iterations;
         const double cost = st.cost, lambda = st.lambda;
@@ -862,10 +885,7 @@ __global__ __launch_bounds__(kPgWide) void k_pg_lm_decide(const PgDev G) {
         if (accept) {
             st.steps_accepted++;
             st.lambda = fmax(lambda / st.lambda_factor, st.lambda_lower);
-            st.cost = new_cost; st.s.final_cost = new_cost;
-            if (smax <= T.parameter_tolerance) { st.s.termination = LILI_LM_PARAMETER_TOLERANCE; st.done = 1; }
-            else if (fabs(cost - new_cost) <= T.function_tolerance * cost) { st.s.termination = LILI_LM_FUNCTION_TOLERANCE; st.done = 1; }
-            else if (it + 1 >= T.max_iter) { st.s.termination = LILI_LM_MAX_ITERATIONS; st.done = 1; }
+            pg_accept_step(st, T, it, cost, new_cost, smax);
         } else {
             st.steps_rejected++;
             st.lambda = lambda * st.lambda_factor;
@@ -875,7 +895,7 @@ __global__ __launch_bounds__(kPgWide) void k_pg_lm_decide(const PgDev G) {
         s_accept = accept;
     }
     __syncthreads();
-    if (s_accept) for (int e = t; e < 7 * n; e += kPgWide) G.X[e] = G.Xn[e];
+    if (s_accept) pg_commit(G, n);
 }
 
 // lili_pose_graph_loop_status: d^2 and the weight of loops first .. first + n - 1 at the estimates, the linearisation's arithmetic
@@ -885,12 +905,10 @@ __global__ __launch_bounds__(256) void k_pg_loop_status(const PgDev G, const int
     if (i >= n) return;
     const int f = T.n + first + i;
     const PgFactorIn F = pg_factor(T, G.X, G.meas, f);
-    double e[6], r[6], scale;
+    double e[6], scale;
     dq qab, qe; d3 d;
     pg_error(F.pa, F.qa, F.pb, F.qb, F.Z, e, qab, d, qe);
-#pragma unroll
-    for (int k = 0; k < 6; k++) r[k] = e[k] * F.w[k];
-    const double d2 = pg_sq6(r);
+    const double d2 = pg_whitened_d2(F, e);
     const int loss = pg_loss_of(T, f, scale);
     out[i] = d2;
     out[n + i] = loss == LILI_PG_LOSS_NONE ? 1.0 : pg_loss_weight(loss, scale, d2);
@@ -918,10 +936,7 @@ __global__ __launch_bounds__(kPgInvThreads) void k_pg_marg_inverse(const PgDev G
     for (int kt = k0; kt < nt; kt++) {      // L y = e
         const int o = kt * kPgTile, m = min(kPgTile, nr - o);
         __syncthreads();      // the previous tile's reads of sL and sx
-        for (int e = t; e < m * m; e += kPgInvThreads) {
-            const int c = e / m, rr = e - c * m;
-            if (rr >= c) sL[pg_tri(rr, c)] = R[(size_t)(o + c) * nr + (o + rr)];
-        }
+        pg_load_tile<kPgInvThreads>(sL, R, nr, o, m);
         if (r < m) sx[t] = kt == k0 ? (o + r == 6 * p + q ? 1.0 : 0.0) : X[o + r];
         __syncthreads();
         for (int c = 0; c < m; c++) {
@@ -943,10 +958,7 @@ __global__ __launch_bounds__(kPgInvThreads) void k_pg_marg_inverse(const PgDev G
     for (int kt = nt - 1; kt >= k0; kt--) {      // L^T x = y
         const int o = kt * kPgTile, m = min(kPgTile, nr - o);
         __syncthreads();
-        for (int e = t; e < m * m; e += kPgInvThreads) {
-            const int c = e / m, rr = e - c * m;
-            if (rr >= c) sL[pg_tri(rr, c)] = R[(size_t)(o + c) * nr + (o + rr)];
-        }
+        pg_load_tile<kPgInvThreads>(sL, R, nr, o, m);
         if (r < m) sx[t] = X[o + r];
         __syncthreads();
         for (int c = m - 1; c >= 0; c--) {
@@ -969,16 +981,6 @@ __global__ __launch_bounds__(kPgInvThreads) void k_pg_marg_inverse(const PgDev G
 
 // element (a, b) of the reduced inverse, from its lower triangle: the same bits for (a, b) and (b, a)
 __device__ __forceinline__ double pg_sinv(const double* X, const int nr, const int a, const int b) { return a >= b ? X[(size_t)b * nr + a] : X[(size_t)a * nr + b]; }
-// x <- Ld^-T x, Ld a row-major lower-triangular 6 x 6 block
-__device__ __forceinline__ void pg_back6(const double* Ld, double x[6]) {
-#pragma unroll
-    for (int k = 5; k >= 0; k--) {
-        double v = x[k];
-#pragma unroll
-        for (int m = k + 1; m < 6; m++) v -= Ld[6 * m + k] * x[m];
-        x[k] = v / Ld[6 * k + k];
-    }
-}
 
 // One wave per segment, last node first.  Lanes 0 .. 11: a column of W_i = Ld_i^-T (-Y_E,i - Ls_i^T W_(i+1)).  Lanes 12 .. 17: a column of the segment's own inverse
 // block P_i = Ld_i^-T (I + Ls_i^T P_(i+1) Ls_i) Ld_i^-1, made symmetric by averaging.  Lanes 0 .. 35: entry (r, c) of Sigma_ii = P_i + W_i Sigma_sep W_i^T, Sigma_sep
@@ -1021,12 +1023,8 @@ __global__ __launch_bounds__(64) void k_pg_marg_segments(const PgDev G) {
             const int cc = c - 12;
             double u[6], x[6];
 #pragma unroll
-            for (int kk = 0; kk < 6; kk++) {      // u = Ld^-1 e_cc
-                double v = kk == cc ? 1.0 : 0.0;
-#pragma unroll
-                for (int m = 0; m < kk; m++) v -= Ld[6 * kk + m] * u[m];
-                u[kk] = v / Ld[6 * kk + kk];
-            }
+            for (int kk = 0; kk < 6; kk++) u[kk] = kk == cc ? 1.0 : 0.0;
+            pg_fwd6(Ld, u);      // u = Ld^-1 e_cc
             if (tail) {
                 double v[6], pv[6];
 #pragma unroll
@@ -1160,6 +1158,8 @@ struct PoseGraphState : ExtState {
     PinBuf h_tab, h_io, h_pairs;
     Event ev0, ev1;
     float last_ms = -1.f;
+    // the host copy of the state, behind the fixed tables in the page-locked block: a call's read-back lands there
+    PgState* host_state() const { return reinterpret_cast<PgState*>(h_tab.as<PgTables>() + 1); }
     // the graph itself is allocated once at the caps (3.7 MB): it has to outlive every call
     int persist(lili_ctx* ctx) {
         HIPCHK(X.ensure(sizeof(double) * 7 * kPgMaxNodes));
@@ -1205,17 +1205,19 @@ struct PoseGraphState : ExtState {
 };
 PoseGraphState* pg_of(lili_ctx* ctx) { return ext_of<PoseGraphState>(ctx, lili_ctx::kExtPoseGraph); }
 
-// n poses: finite, quaternions within 1e-6 of unit norm; out = the poses with the quaternions normalised
+// the norm of a pose's quaternion; false where it is more than 1e-6 from 1 (or not a number)
+bool unit_quaternion(const double* pose, double* nq) {
+    const double* q = pose + 3;
+    *nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    return std::fabs(*nq - 1.0) <= 1e-6;
+}
+// n poses: finite, quaternions within 1e-6 of unit norm; out (scratch) = the poses with the quaternions normalised
 int check_poses(lili_ctx* ctx, const char* who, const double* poses, size_t n, double* out) {
     ARGCHK(finite_n(poses, 7 * n), std::string(who) + ": an input is not finite");
     for (size_t i = 0; i < n; i++) {
-        const double* q = poses + 7 * i + 3;
-        const double nq = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-        ARGCHK(std::fabs(nq - 1.0) <= 1e-6, std::string(who) + ": a quaternion is more than 1e-6 from unit norm");
-    }
-    for (size_t i = 0; i < n; i++) {
         const double* p = poses + 7 * i;
-        const double nq = std::sqrt(((p[3] * p[3] + p[4] * p[4]) + p[5] * p[5]) + p[6] * p[6]);
+        double nq;
+        ARGCHK(unit_quaternion(p, &nq), std::string(who) + ": a quaternion is more than 1e-6 from unit norm");
         for (int k = 0; k < 3; k++) out[7 * i + k] = p[k];
         for (int k = 3; k < 7; k++) out[7 * i + k] = p[k] / nq;
     }
@@ -1281,7 +1283,7 @@ int fill_tables(lili_ctx* ctx, PoseGraphState* P, const lili_pg_options& opt, Pg
     T->n = n; T->n_loops = L; T->n_sep = K; T->n_blk = NB; T->max_iter = opt.max_iterations;
     T->function_tolerance = opt.function_tolerance; T->gradient_tolerance = opt.gradient_tolerance; T->parameter_tolerance = opt.parameter_tolerance;
     for (int k = 0; k < 6; k++) { T->w_prior[k] = 1.0 / std::sqrt(opt.prior_var[k]); T->w_odom[k] = 1.0 / std::sqrt(opt.odom_var[k]); }
-    PgState* S = reinterpret_cast<PgState*>(T + 1);
+    PgState* S = P->host_state();
     std::memset(S, 0, sizeof *S);
     S->s.n_nodes = n; S->s.n_loops = L;
     char* hv = reinterpret_cast<char*>(S + 1);
@@ -1319,7 +1321,7 @@ int fill_tables(lili_ctx* ctx, PoseGraphState* P, const lili_pg_options& opt, Pg
 }
 int upload_tables(lili_ctx* ctx, PoseGraphState* P, const PgLayout& lay) {
     const PgTables* T = P->h_tab.as<PgTables>();
-    const PgState* S = reinterpret_cast<const PgState*>(T + 1);
+    const PgState* S = P->host_state();
     HIPCHK(hipMemcpyAsync(P->tab.p, T, sizeof(PgTables), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(P->st.p, S, sizeof(PgState), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(P->tabv.p, S + 1, lay.bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -1343,6 +1345,68 @@ void launch_linearize(lili_ctx* ctx, const PoseGraphState* P, const PgDev& G) {
     const int F = P->n + P->n_loops;
     hipLaunchKernelGGL(k_pg_linearize, dim3(nblocks(2 * (int64_t)F, 256)), dim3(256), 0, ctx->stream, G);
     hipLaunchKernelGGL(k_pg_assemble, dim3(nblocks((int64_t)P->n * 78 + 36 * P->n_loops, 256)), dim3(256), 0, ctx->stream, G);
+}
+
+// ---- what the calls that run kernels on the graph share.  PgNeeds: the work arrays of nothing (loop_status), of an evaluation, of the elimination too
+enum PgNeeds { kPgTablesOnly, kPgEvaluation, kPgElimination };
+struct PgCall { PoseGraphState* P; lili_pg_options opt{}; PgLayout lay{}; int K = 0, NB = 0; PgDev G{}; };
+using PgStep = std::function<int()>;
+// The prologue, in the order of its refusals: the options, own_checks (the caller's argument checks behind the options' and in front of the empty graph's refusal),
+// the empty graph.  before_upload edits the host tables and state, or allocates what the device view needs.  Without the elimination the view is that of K = 0 (no rhs)
+int prepare_call(lili_ctx* ctx, const char* who, const lili_pg_options* options, const PgNeeds needs, PgCall* c, const PgStep& own_checks = nullptr,
+                 const PgStep& before_upload = nullptr) {
+    PoseGraphState* P = c->P;
+    TRY(check_options(ctx, options, &c->opt));
+    if (own_checks) TRY(own_checks());
+    if (P->n == 0) return ctx->fail(LILI_E_STATE, std::string(who) + ": the graph is empty");
+    HIPCHK(hipSetDevice(ctx->device));
+    TRY(P->persist(ctx));
+    TRY(fill_tables(ctx, P, c->opt, &c->lay, &c->K, &c->NB));
+    if (before_upload) TRY(before_upload());
+    const int K = needs == kPgElimination ? c->K : 0;
+    if (needs != kPgTablesOnly) TRY(P->work(ctx, K, needs == kPgElimination));
+    TRY(upload_tables(ctx, P, c->lay));
+    c->G = P->dev(K);
+    return LILI_OK;
+}
+int zero_blocks(const int K) { return (int)std::min<size_t>(2048, ((size_t)18 * K * K + 255) / 256); }
+// The front of an iteration, up to the separators' step.  damped: k_pg_eliminate's kDamped instance; gate_mode 1 (marginals): a converged graph is factored like any other
+void enqueue_factorisation(lili_ctx* ctx, const PgCall& c, const bool damped, const int gate_mode) {
+    const PgDev& G = c.G;
+    launch_linearize(ctx, c.P, G);
+    hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, gate_mode);
+    if (damped) hipLaunchKernelGGL((k_pg_eliminate<true>), dim3(c.K), dim3(64), 0, ctx->stream, G);
+    else hipLaunchKernelGGL((k_pg_eliminate<false>), dim3(c.K), dim3(64), 0, ctx->stream, G);
+    hipLaunchKernelGGL(k_pg_zero, dim3(zero_blocks(c.K)), dim3(256), 0, ctx->stream, G);
+    hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(c.NB), dim3(64), 0, ctx->stream, G);
+    launch_reduced_solve(ctx, G, c.K);
+}
+// the events around a call's kernels; close: the launches' status, the closing event, the state's read-back enqueued
+int open_bracket(lili_ctx* ctx, PoseGraphState* P) {
+    HIPCHK(P->ev0.get(hipEventDefault)); HIPCHK(P->ev1.get(hipEventDefault));
+    HIPCHK(hipEventRecord(P->ev0, ctx->stream));
+    return LILI_OK;
+}
+int close_bracket(lili_ctx* ctx, PoseGraphState* P) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(P->ev1, ctx->stream));
+    HIPCHK(hipMemcpyAsync(P->host_state(), P->st.p, sizeof(PgState), hipMemcpyDeviceToHost, ctx->stream));
+    return LILI_OK;
+}
+// every iteration enqueued up front (damped: a rejected attempt linearises again at the unchanged X: the same bytes); the state lands in P->host_state()
+int run_solve(lili_ctx* ctx, const PgCall& c, const bool damped) {
+    PoseGraphState* P = c.P;
+    TRY(open_bracket(ctx, P));
+    for (int it = 0; it < c.opt.max_iterations; it++) {
+        enqueue_factorisation(ctx, c, damped, 0);
+        hipLaunchKernelGGL(k_pg_backsub, dim3(c.K), dim3(64), 0, ctx->stream, c.G);
+        if (damped) hipLaunchKernelGGL(k_pg_lm_decide, dim3(1), dim3(kPgWide), 0, ctx->stream, c.G);
+        else hipLaunchKernelGGL(k_pg_retract_cost, dim3(1), dim3(kPgWide), 0, ctx->stream, c.G);
+    }
+    TRY(close_bracket(ctx, P));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipEventElapsedTime(&P->last_ms, P->ev0, P->ev1));
+    return LILI_OK;
 }
 
 // ---- host-side quaternion algebra as Eigen 3.3 evaluates it (q = w, x, y, z)
@@ -1391,7 +1455,6 @@ hq h_from_matrix(const double* m) {
     }
     return hq{q[0], q[1], q[2], q[3]};
 }
-bool h_finite(const double* p, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false; return true; }
 
 }  // namespace
 
@@ -1499,27 +1562,18 @@ int lili_pose_graph_set(lili_ctx* ctx, int first, int n, const double* poses) {
 
 int lili_pose_graph_evaluate(lili_ctx* ctx, const lili_pg_options* options, double* cost, double* gradient, double* diag, double* sub, double* loop_blocks) {
     if (!ctx) return LILI_E_ARG;
-    PoseGraphState* P = pg_of(ctx);
+    PgCall c{pg_of(ctx)};
+    PoseGraphState* P = c.P;
     ARGCHK(cost && gradient && diag && (sub || P->n <= 1) && (loop_blocks || P->n_loops == 0), "pose_graph_evaluate: null argument");
-    lili_pg_options opt;
-    TRY(check_options(ctx, options, &opt));
-    if (P->n == 0) return ctx->fail(LILI_E_STATE, "pose_graph_evaluate: the graph is empty");
-    HIPCHK(hipSetDevice(ctx->device));
-    TRY(P->persist(ctx));
-    TRY(P->work(ctx, 0, false));
+    TRY(prepare_call(ctx, "pose_graph_evaluate", options, kPgEvaluation, &c));
     const size_t N = (size_t)P->n, L = (size_t)P->n_loops, d = sizeof(double);
     const size_t o_g = 0, o_D = o_g + 6 * N, o_S = o_D + 36 * N, o_L = o_S + 36 * N, total = o_L + 36 * L;
     HIPCHK(P->h_io.ensure(total * d));
-    PgLayout lay;
-    int K = 0, NB = 0;
-    TRY(fill_tables(ctx, P, opt, &lay, &K, &NB));
-    TRY(upload_tables(ctx, P, lay));
-    const PgDev G = P->dev(0);
-    launch_linearize(ctx, P, G);
-    hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 1);
+    launch_linearize(ctx, P, c.G);
+    hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, c.G, 1);
     HIPCHK(hipGetLastError());
     double* h = P->h_io.as<double>();
-    PgState* hs = reinterpret_cast<PgState*>(P->h_tab.as<PgTables>() + 1);
+    PgState* hs = P->host_state();
     HIPCHK(hipMemcpyAsync(hs, P->st.p, sizeof(PgState), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(h + o_g, P->g.p, 6 * N * d, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(h + o_D, P->D.p, 36 * N * d, hipMemcpyDeviceToHost, ctx->stream));
@@ -1536,39 +1590,11 @@ int lili_pose_graph_evaluate(lili_ctx* ctx, const lili_pg_options* options, doub
 
 int lili_pose_graph_solve(lili_ctx* ctx, const lili_pg_options* options, lili_pg_summary* summary) {
     if (!ctx) return LILI_E_ARG;
-    PoseGraphState* P = pg_of(ctx);
+    PgCall c{pg_of(ctx)};
     ARGCHK(summary, "pose_graph_solve: null summary");
-    lili_pg_options opt;
-    TRY(check_options(ctx, options, &opt));
-    if (P->n == 0) return ctx->fail(LILI_E_STATE, "pose_graph_solve: the graph is empty");
-    HIPCHK(hipSetDevice(ctx->device));
-    TRY(P->persist(ctx));
-    PgLayout lay;
-    int K = 0, NB = 0;
-    TRY(fill_tables(ctx, P, opt, &lay, &K, &NB));
-    TRY(P->work(ctx, K, true));
-    TRY(upload_tables(ctx, P, lay));
-    const PgDev G = P->dev(K);
-    const int zero_blocks = (int)std::min<size_t>(2048, ((size_t)18 * K * K + 255) / 256);
-    HIPCHK(P->ev0.get(hipEventDefault)); HIPCHK(P->ev1.get(hipEventDefault));
-    HIPCHK(hipEventRecord(P->ev0, ctx->stream));
-    for (int it = 0; it < opt.max_iterations; it++) {
-        launch_linearize(ctx, P, G);
-        hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 0);
-        hipLaunchKernelGGL((k_pg_eliminate<false>), dim3(K), dim3(64), 0, ctx->stream, G);
-        hipLaunchKernelGGL(k_pg_zero, dim3(zero_blocks), dim3(256), 0, ctx->stream, G);
-        hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(NB), dim3(64), 0, ctx->stream, G);
-        launch_reduced_solve(ctx, G, K);
-        hipLaunchKernelGGL(k_pg_backsub, dim3(K), dim3(64), 0, ctx->stream, G);
-        hipLaunchKernelGGL(k_pg_retract_cost, dim3(1), dim3(kPgWide), 0, ctx->stream, G);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(P->ev1, ctx->stream));
-    PgState* hs = reinterpret_cast<PgState*>(P->h_tab.as<PgTables>() + 1);
-    HIPCHK(hipMemcpyAsync(hs, P->st.p, sizeof(PgState), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipEventElapsedTime(&P->last_ms, P->ev0, P->ev1));
-    *summary = hs->s;
+    TRY(prepare_call(ctx, "pose_graph_solve", options, kPgElimination, &c));
+    TRY(run_solve(ctx, c, false));
+    *summary = c.P->host_state()->s;
     return LILI_OK;
 }
 
@@ -1580,48 +1606,28 @@ void lili_pg_lm_default_options(lili_pg_lm_options* o) {
 
 int lili_pose_graph_solve_lm(lili_ctx* ctx, const lili_pg_options* options, const lili_pg_lm_options* lm_options, lili_pg_lm_summary* summary) {
     if (!ctx) return LILI_E_ARG;
-    PoseGraphState* P = pg_of(ctx);
+    PgCall c{pg_of(ctx)};
+    PoseGraphState* P = c.P;
     ARGCHK(summary, "pose_graph_solve_lm: null summary");
-    lili_pg_options opt;
-    TRY(check_options(ctx, options, &opt));
     lili_pg_lm_options lm;
     if (lm_options) lm = *lm_options; else lili_pg_lm_default_options(&lm);
-    ARGCHK(std::isfinite(lm.initial_lambda) && std::isfinite(lm.lambda_factor) && std::isfinite(lm.lambda_lower) && std::isfinite(lm.lambda_upper),
-           "pose_graph_solve_lm: an option is not finite");
-    ARGCHK(lm.initial_lambda > 0 && lm.lambda_factor > 1 && lm.lambda_lower > 0 && lm.lambda_upper >= lm.lambda_lower,
-           "pose_graph_solve_lm: initial_lambda and lambda_lower must be positive, lambda_factor above 1, lambda_upper not below lambda_lower");
-    ARGCHK(lm.diagonal_damping == 0 || lm.diagonal_damping == 1, "pose_graph_solve_lm: diagonal_damping must be 0 or 1");
-    if (P->n == 0) return ctx->fail(LILI_E_STATE, "pose_graph_solve_lm: the graph is empty");
-    HIPCHK(hipSetDevice(ctx->device));
-    TRY(P->persist(ctx));
-    PgLayout lay;
-    int K = 0, NB = 0;
-    TRY(fill_tables(ctx, P, opt, &lay, &K, &NB));
-    PgTables* T = P->h_tab.as<PgTables>();
-    PgState* hs = reinterpret_cast<PgState*>(T + 1);
-    T->damping = lm.diagonal_damping ? 2 : 1;
-    hs->lambda = lm.initial_lambda; hs->lambda_factor = lm.lambda_factor; hs->lambda_lower = lm.lambda_lower; hs->lambda_upper = lm.lambda_upper;
-    TRY(P->work(ctx, K, true));
-    TRY(upload_tables(ctx, P, lay));
-    const PgDev G = P->dev(K);
-    const int zero_blocks = (int)std::min<size_t>(2048, ((size_t)18 * K * K + 255) / 256);
-    HIPCHK(P->ev0.get(hipEventDefault)); HIPCHK(P->ev1.get(hipEventDefault));
-    HIPCHK(hipEventRecord(P->ev0, ctx->stream));
-    for (int it = 0; it < opt.max_iterations; it++) {      // a rejected attempt linearises again at the unchanged X: the same bytes
-        launch_linearize(ctx, P, G);
-        hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 0);
-        hipLaunchKernelGGL((k_pg_eliminate<true>), dim3(K), dim3(64), 0, ctx->stream, G);
-        hipLaunchKernelGGL(k_pg_zero, dim3(zero_blocks), dim3(256), 0, ctx->stream, G);
-        hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(NB), dim3(64), 0, ctx->stream, G);
-        launch_reduced_solve(ctx, G, K);
-        hipLaunchKernelGGL(k_pg_backsub, dim3(K), dim3(64), 0, ctx->stream, G);
-        hipLaunchKernelGGL(k_pg_lm_decide, dim3(1), dim3(kPgWide), 0, ctx->stream, G);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(P->ev1, ctx->stream));
-    HIPCHK(hipMemcpyAsync(hs, P->st.p, sizeof(PgState), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipEventElapsedTime(&P->last_ms, P->ev0, P->ev1));
+    const auto check_lm = [&]() -> int {
+        ARGCHK(std::isfinite(lm.initial_lambda) && std::isfinite(lm.lambda_factor) && std::isfinite(lm.lambda_lower) && std::isfinite(lm.lambda_upper),
+               "pose_graph_solve_lm: an option is not finite");
+        ARGCHK(lm.initial_lambda > 0 && lm.lambda_factor > 1 && lm.lambda_lower > 0 && lm.lambda_upper >= lm.lambda_lower,
+               "pose_graph_solve_lm: initial_lambda and lambda_lower must be positive, lambda_factor above 1, lambda_upper not below lambda_lower");
+        ARGCHK(lm.diagonal_damping == 0 || lm.diagonal_damping == 1, "pose_graph_solve_lm: diagonal_damping must be 0 or 1");
+        return LILI_OK;
+    };
+    const auto set_damping = [&]() -> int {
+        PgState* hs = P->host_state();
+        P->h_tab.as<PgTables>()->damping = lm.diagonal_damping ? 2 : 1;
+        hs->lambda = lm.initial_lambda; hs->lambda_factor = lm.lambda_factor; hs->lambda_lower = lm.lambda_lower; hs->lambda_upper = lm.lambda_upper;
+        return LILI_OK;
+    };
+    TRY(prepare_call(ctx, "pose_graph_solve_lm", options, kPgElimination, &c, check_lm, set_damping));
+    TRY(run_solve(ctx, c, true));
+    const PgState* hs = P->host_state();
     std::memset(summary, 0, sizeof *summary);
     summary->base = hs->s;
     std::memcpy(summary->lambda, hs->lambda_log, sizeof summary->lambda);
@@ -1633,22 +1639,15 @@ int lili_pose_graph_solve_lm(lili_ctx* ctx, const lili_pg_options* options, cons
 
 int lili_pose_graph_loop_status(lili_ctx* ctx, const lili_pg_options* options, int first, int n, double* chi2, double* weight) {
     if (!ctx) return LILI_E_ARG;
-    PoseGraphState* P = pg_of(ctx);
+    PgCall c{pg_of(ctx)};
+    PoseGraphState* P = c.P;
     ARGCHK(chi2 && weight, "pose_graph_loop_status: null argument");
-    ARGCHK(first >= 0 && n >= 1 && first <= P->n_loops && n <= P->n_loops - first, "pose_graph_loop_status: range outside the graph's loops");
-    lili_pg_options opt;
-    TRY(check_options(ctx, options, &opt));
-    HIPCHK(hipSetDevice(ctx->device));
-    TRY(P->persist(ctx));
-    PgLayout lay;
-    int K = 0, NB = 0;
-    TRY(fill_tables(ctx, P, opt, &lay, &K, &NB));
+    ARGCHK(first >= 0 && n >= 1 && first <= P->n_loops && n <= P->n_loops - first, "pose_graph_loop_status: range outside the graph's loops");      // (a loop: not empty)
+    TRY(prepare_call(ctx, "pose_graph_loop_status", options, kPgTablesOnly, &c));
     const size_t bytes = sizeof(double) * 2 * (size_t)n;
     HIPCHK(P->h_io.ensure(bytes));
     HIPCHK(P->stage.ensure(bytes));
-    TRY(upload_tables(ctx, P, lay));
-    const PgDev G = P->dev(0);
-    hipLaunchKernelGGL(k_pg_loop_status, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, G, first, n, P->stage.as<double>());
+    hipLaunchKernelGGL(k_pg_loop_status, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, c.G, first, n, P->stage.as<double>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(P->h_io.p, P->stage.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1669,49 +1668,35 @@ int lili_pose_graph_kernel_ms(lili_ctx* ctx, float* ms) {
 int lili_pose_graph_marginals(lili_ctx* ctx, const lili_pg_options* options, int first, int n, double* cov, const int32_t* pairs, int n_pairs, double* cross,
                               lili_pg_marginals_info* info) {
     if (!ctx) return LILI_E_ARG;
-    PoseGraphState* P = pg_of(ctx);
+    PgCall c{pg_of(ctx)};
+    PoseGraphState* P = c.P;
     ARGCHK(n >= 0 && n_pairs >= 0 && n_pairs <= LILI_PG_MAX_PAIRS && (n > 0 || n_pairs > 0), "pose_graph_marginals: n or n_pairs is negative, both are zero, or more than LILI_PG_MAX_PAIRS pairs");
     ARGCHK((cov || n == 0) && ((pairs && cross) || n_pairs == 0), "pose_graph_marginals: null argument");
-    lili_pg_options opt;
-    TRY(check_options(ctx, options, &opt));
-    if (P->n == 0) return ctx->fail(LILI_E_STATE, "pose_graph_marginals: the graph is empty");
-    ARGCHK(n == 0 || (first >= 0 && first < P->n && n <= P->n - first), "pose_graph_marginals: range outside the graph");
-    for (int k = 0; k < 2 * n_pairs; k++) ARGCHK(pairs[k] >= 0 && pairs[k] < P->n, "pose_graph_marginals: a pair names a node outside the graph");
-    HIPCHK(hipSetDevice(ctx->device));
-    TRY(P->persist(ctx));
-    PgLayout lay;
-    int K = 0, NB = 0;
-    TRY(fill_tables(ctx, P, opt, &lay, &K, &NB));
-    TRY(P->work(ctx, K, true));
-    TRY(P->work_marginals(ctx, K, n_pairs));
     const size_t d = sizeof(double), n_cov = 36 * (size_t)n, n_cross = 36 * (size_t)n_pairs;
+    const auto check_range = [&]() -> int {      // on an empty graph no range is judged: the prologue's refusal of the empty graph comes first
+        if (P->n == 0) return LILI_OK;
+        ARGCHK(n == 0 || (first >= 0 && first < P->n && n <= P->n - first), "pose_graph_marginals: range outside the graph");
+        for (int k = 0; k < 2 * n_pairs; k++) ARGCHK(pairs[k] >= 0 && pairs[k] < P->n, "pose_graph_marginals: a pair names a node outside the graph");
+        return LILI_OK;
+    };
+    const auto own_arrays = [&]() -> int { return P->work_marginals(ctx, c.K, n_pairs); };      // (in front of the device view)
+    TRY(prepare_call(ctx, "pose_graph_marginals", options, kPgElimination, &c, check_range, own_arrays));
     HIPCHK(P->h_io.ensure((n_cov + n_cross) * d));
-    TRY(upload_tables(ctx, P, lay));
+    const int K = c.K;
     if (n_pairs) {
         HIPCHK(P->h_pairs.ensure(sizeof(int32_t) * 2 * (size_t)n_pairs));
         std::memcpy(P->h_pairs.p, pairs, sizeof(int32_t) * 2 * (size_t)n_pairs);
         HIPCHK(hipMemcpyAsync(P->pairs.p, P->h_pairs.p, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
     }
-    const PgDev G = P->dev(K);
-    const int zero_blocks = (int)std::min<size_t>(2048, ((size_t)18 * K * K + 255) / 256);
-    HIPCHK(P->ev0.get(hipEventDefault)); HIPCHK(P->ev1.get(hipEventDefault));
-    HIPCHK(hipEventRecord(P->ev0, ctx->stream));
-    // the front half of a solve iteration; the gate in its evaluate mode: a converged graph is factored like any other
-    launch_linearize(ctx, P, G);
-    hipLaunchKernelGGL(k_pg_gate, dim3(1), dim3(kPgWide), 0, ctx->stream, G, 1);
-    hipLaunchKernelGGL((k_pg_eliminate<false>), dim3(K), dim3(64), 0, ctx->stream, G);
-    hipLaunchKernelGGL(k_pg_zero, dim3(zero_blocks), dim3(256), 0, ctx->stream, G);
-    hipLaunchKernelGGL(k_pg_reduced_assemble, dim3(NB), dim3(64), 0, ctx->stream, G);
-    launch_reduced_solve(ctx, G, K);
+    TRY(open_bracket(ctx, P));
+    enqueue_factorisation(ctx, c, false, 1);
     // the inverse side
-    hipLaunchKernelGGL(k_pg_marg_inverse, dim3(K), dim3(kPgInvThreads), 0, ctx->stream, G);
-    hipLaunchKernelGGL(k_pg_marg_segments, dim3(K), dim3(64), 0, ctx->stream, G);
-    if (n_pairs) hipLaunchKernelGGL(k_pg_marg_pairs, dim3(n_pairs), dim3(64), 0, ctx->stream, G);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(P->ev1, ctx->stream));
+    hipLaunchKernelGGL(k_pg_marg_inverse, dim3(K), dim3(kPgInvThreads), 0, ctx->stream, c.G);
+    hipLaunchKernelGGL(k_pg_marg_segments, dim3(K), dim3(64), 0, ctx->stream, c.G);
+    if (n_pairs) hipLaunchKernelGGL(k_pg_marg_pairs, dim3(n_pairs), dim3(64), 0, ctx->stream, c.G);
+    TRY(close_bracket(ctx, P));
     double* h = P->h_io.as<double>();
-    PgState* hs = reinterpret_cast<PgState*>(P->h_tab.as<PgTables>() + 1);
-    HIPCHK(hipMemcpyAsync(hs, P->st.p, sizeof(PgState), hipMemcpyDeviceToHost, ctx->stream));
+    const PgState* hs = P->host_state();
     if (n) HIPCHK(hipMemcpyAsync(h, P->cov.as<double>() + 36 * (size_t)first, n_cov * d, hipMemcpyDeviceToHost, ctx->stream));
     if (n_pairs) HIPCHK(hipMemcpyAsync(h + n_cov, P->cross.p, n_cross * d, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1732,10 +1717,9 @@ int lili_pose_graph_marginals(lili_ctx* ctx, const lili_pg_options* options, int
 int lili_pose_relative_covariance(const double pose_i[7], const double pose_j[7], const double cov_ii[36], const double cov_jj[36], const double cov_ij[36],
                                   double cov_rel[36]) {
     if (!pose_i || !pose_j || !cov_ii || !cov_jj || !cov_ij || !cov_rel) return LILI_E_ARG;
-    if (!h_finite(pose_i, 7) || !h_finite(pose_j, 7) || !h_finite(cov_ii, 36) || !h_finite(cov_jj, 36) || !h_finite(cov_ij, 36)) return LILI_E_ARG;
-    const double ni = std::sqrt(((pose_i[3] * pose_i[3] + pose_i[4] * pose_i[4]) + pose_i[5] * pose_i[5]) + pose_i[6] * pose_i[6]);
-    const double nj = std::sqrt(((pose_j[3] * pose_j[3] + pose_j[4] * pose_j[4]) + pose_j[5] * pose_j[5]) + pose_j[6] * pose_j[6]);
-    if (!(std::fabs(ni - 1.0) <= 1e-6) || !(std::fabs(nj - 1.0) <= 1e-6)) return LILI_E_ARG;
+    if (!finite_n(pose_i, 7) || !finite_n(pose_j, 7) || !finite_n(cov_ii, 36) || !finite_n(cov_jj, 36) || !finite_n(cov_ij, 36)) return LILI_E_ARG;
+    double ni, nj;
+    if (!unit_quaternion(pose_i, &ni) || !unit_quaternion(pose_j, &nj)) return LILI_E_ARG;
     // Z = between(X_i, X_j): R_Z = R_i^T R_j, t_Z = d = R_i^T (p_j - p_i)
     const hq qi{pose_i[3] / ni, pose_i[4] / ni, pose_i[5] / ni, pose_i[6] / ni}, qj{pose_j[3] / nj, pose_j[4] / nj, pose_j[5] / nj, pose_j[6] / nj};
     const hq ci{qi.w, -qi.x, -qi.y, -qi.z};
@@ -1744,7 +1728,8 @@ int lili_pose_relative_covariance(const double pose_i[7], const double pose_j[7]
     const double R[9] = {1 - 2 * (z.y * z.y + z.z * z.z), 2 * (z.x * z.y - z.w * z.z), 2 * (z.x * z.z + z.w * z.y),
                          2 * (z.x * z.y + z.w * z.z), 1 - 2 * (z.x * z.x + z.z * z.z), 2 * (z.y * z.z - z.w * z.x),
                          2 * (z.x * z.z - z.w * z.y), 2 * (z.y * z.z + z.w * z.x), 1 - 2 * (z.x * z.x + z.y * z.y)};
-    const double Sd[9] = {0.0, -t.z, t.y, t.z, 0.0, -t.x, -t.y, t.x, 0.0};
+    double Sd[9];
+    lili::pg_skew(t.x, t.y, t.z, Sd);
     // J_a = [-R_Z^T, 0; R_Z^T [t_Z]x, -R_Z^T], J_b = I
     double Ja[36] = {0.0};
     for (int r = 0; r < 3; r++)
@@ -1772,7 +1757,7 @@ int lili_pose_relative_covariance(const double pose_i[7], const double pose_j[7]
 
 int lili_loop_measurement(const double T_icp[16],const double pose_latest[7], const double pose_closest[7], double meas[7]) {
     if (!T_icp || !pose_latest || !pose_closest || !meas) return LILI_E_ARG;
-    if (!h_finite(T_icp, 16) || !h_finite(pose_latest, 7) || !h_finite(pose_closest, 7)) return LILI_E_ARG;
+    if (!finite_n(T_icp, 16) || !finite_n(pose_latest, 7) || !finite_n(pose_closest, 7)) return LILI_E_ARG;
     // L:2587-2600: quaternionIncre(R), transitionIncre; corrected = incre * toCorrect
     const double R[9] = {T_icp[0], T_icp[1], T_icp[2], T_icp[4], T_icp[5], T_icp[6], T_icp[8], T_icp[9], T_icp[10]};
     const hq q_inc = h_from_matrix(R);
@@ -1799,7 +1784,7 @@ int lili_correct_poses(const double* solution, int n_frames, const int32_t* keyf
     const int w = slide_window_width;
     if (n_frames < 1 || n_keyframes < 1 || n_abs < 1 || w < 2 || w > n_abs || w > n_keyframes || n_abs > n_keyframes + 1 || n_keyframes - w + 2 > n_abs) return LILI_E_ARG;
     for (int i = 0; i <= n_keyframes - w; i++) if (keyframe_id_in_frame[i] < 0 || keyframe_id_in_frame[i] >= n_frames) return LILI_E_ARG;
-    if (!h_finite(solution, 7 * (size_t)n_frames) || !h_finite(abs_poses, 7 * (size_t)n_abs)) return LILI_E_ARG;
+    if (!finite_n(solution, 7 * (size_t)n_frames) || !finite_n(abs_poses, 7 * (size_t)n_abs)) return LILI_E_ARG;
     auto A = [&](int i) { return abs_poses + 7 * (size_t)i; };
     auto pos = [&](double v) { return f32_positions ? (double)(float)v : v; };
     // L:2186-2209: the relative transforms of the window's tail

@@ -207,6 +207,14 @@ def test_refusals_leave_everything_untouched(pg, gpu_ctx):
     s = api.PgSummary()
     C.memset(C.byref(s), 0x5A, C.sizeof(s))
     assert lib.lili_pose_graph_solve(h, None, C.byref(s)) == -3 and bytes(s) == b"\x5a" * C.sizeof(s)
+    # ... refuses evaluate too; a null argument and the options are judged in front of it
+    cost, g1, bad = C.c_double(7.5), np.full((1, 36), 7.5), pg.options(max_iterations=0)
+    assert lib.lili_pose_graph_evaluate(h, None, C.byref(cost), ptr(g1), ptr(g1), None, None) == -3 and b"pose_graph_evaluate: the graph is empty" in lib.lili_last_error(h)
+    assert lib.lili_pose_graph_evaluate(h, C.byref(bad), C.byref(cost), ptr(g1), ptr(g1), None, None) == -1 and b"max_iterations" in lib.lili_last_error(h)
+    assert lib.lili_pose_graph_evaluate(h, C.byref(bad), None, ptr(g1), ptr(g1), None, None) == -1 and b"null argument" in lib.lili_last_error(h)
+    assert lib.lili_pose_graph_solve(h, C.byref(bad), C.byref(s)) == -1 and b"max_iterations" in lib.lili_last_error(h)
+    assert lib.lili_pose_graph_solve(h, C.byref(bad), None) == -1 and b"null summary" in lib.lili_last_error(h)
+    assert cost.value == 7.5 and (g1 == 7.5).all() and bytes(s) == b"\x5a" * C.sizeof(s) and pg.info() == (0, 0) and pg.poses().shape == (0, 7)
     _load(pg, c)
     n, nl = pg.info()
     X0, cost0 = pg.poses(), pg.evaluate()[0]

@@ -212,8 +212,20 @@ def test_refusals(pg, gpu_ctx):
     # an empty graph
     rc, cov, cross, _ = _raw(pg, 0, 1, [])
     assert rc == -3 and (cov == -7.5).all()
+    # ... which is judged behind the options and in front of the range and the pairs
+    buf, pr, o = np.full((3, 36), -7.5), np.array([[0, 5]], np.int32), pg.options()
+    o.odom_var[2] = 0.0
+    assert lib.lili_pose_graph_marginals(h, C.byref(o), 0, 1, ptr(buf), None, 0, None, None) == -1 and b"a variance is not positive" in lib.lili_last_error(h)
+    assert lib.lili_pose_graph_marginals(h, None, 4, 1, ptr(buf), ptr(pr), 1, ptr(buf), None) == -3 and b"pose_graph_marginals: the graph is empty" in lib.lili_last_error(h)
+    assert (buf == -7.5).all() and pg.info() == (0, 0)
     c = BY["n3_loop_2_0"]
     _load(pg, c)
+    X0, cost0 = pg.poses(), pg.evaluate()[0]
+    # the options in front of the range, the range in front of the pairs
+    assert lib.lili_pose_graph_marginals(h, C.byref(o), 4, 1, ptr(buf), ptr(pr), 1, ptr(buf), None) == -1 and b"a variance is not positive" in lib.lili_last_error(h)
+    assert lib.lili_pose_graph_marginals(h, None, 4, 1, ptr(buf), ptr(pr), 1, ptr(buf), None) == -1 and b"range outside the graph" in lib.lili_last_error(h)
+    assert lib.lili_pose_graph_marginals(h, None, 0, 1, ptr(buf), ptr(pr), 1, ptr(buf), None) == -1 and b"a pair names a node outside the graph" in lib.lili_last_error(h)
+    assert (buf == -7.5).all() and pg.info() == (3, 1) and pg.poses().tobytes() == X0.tobytes() and pg.evaluate()[0] == cost0
     for first, n, pairs in ((0, 4, []), (3, 1, []), (-1, 1, []), (2, 2, []), (0, -1, [(0, 1)]), (0, 0, []), (0, 1, [(0, 3)]), (0, 1, [(-1, 0)]), (0, 3, [(1, 2), (3, 3)])):
         rc, cov, cross, _ = _raw(pg, first, n, pairs)
         assert rc == -1 and (cov == -7.5).all() and (cross == -7.5).all(), (first, n, pairs)

@@ -269,6 +269,12 @@ def test_refusals_leave_everything_untouched(pg, gpu_ctx):
     assert lib.lili_pose_graph_solve_lm(h, None, None, C.byref(s)) == -3 and bytes(s) == b"\x5a" * C.sizeof(s)
     out = np.full((2, 4), 7.5)
     assert lib.lili_pose_graph_loop_status(h, None, 0, 1, ptr(out[0]), ptr(out[1])) == -1 and (out == 7.5).all()
+    # ... comes behind solve_lm's own options, and those behind the options of lili_pose_graph_solve; a null summary in front of all
+    bad, bad_lm = pg.options(max_iterations=0), pg.lm_options(lambda_factor=1.0)
+    assert lib.lili_pose_graph_solve_lm(h, None, C.byref(bad_lm), C.byref(s)) == -1 and b"lambda_factor above 1" in lib.lili_last_error(h)
+    assert lib.lili_pose_graph_solve_lm(h, C.byref(bad), C.byref(bad_lm), C.byref(s)) == -1 and b"max_iterations" in lib.lili_last_error(h)
+    assert lib.lili_pose_graph_solve_lm(h, C.byref(bad), C.byref(bad_lm), None) == -1 and b"null summary" in lib.lili_last_error(h)
+    assert bytes(s) == b"\x5a" * C.sizeof(s) and pg.info() == (0, 0) and pg.poses().shape == (0, 7)
     _load(pg, c)
     n, nl = pg.info()
     X0, cost0, st0 = pg.poses(), pg.evaluate()[0], pg.loop_status()
@@ -308,7 +314,9 @@ def test_refusals_leave_everything_untouched(pg, gpu_ctx):
         assert lib.lili_pose_graph_loop_status(h, None, first, cnt, ptr(out[0]), ptr(out[1])) == -1
     assert lib.lili_pose_graph_loop_status(h, None, 0, 1, None, ptr(out[1])) == -1 and lib.lili_pose_graph_loop_status(h, None, 0, 1, ptr(out[0]), None) == -1
     o = pg.options(odom_var=[1, 1, 0, 1, 1, 1])
-    assert lib.lili_pose_graph_loop_status(h, C.byref(o), 0, 1, ptr(out[0]), ptr(out[1])) == -1
+    assert lib.lili_pose_graph_loop_status(h, C.byref(o), 0, 1, ptr(out[0]), ptr(out[1])) == -1 and b"a variance is not positive" in lib.lili_last_error(h)
+    assert lib.lili_pose_graph_loop_status(h, C.byref(o), nl, 1, ptr(out[0]), ptr(out[1])) == -1 and b"range outside the graph's loops" in lib.lili_last_error(h)      # the range first
+    assert lib.lili_pose_graph_loop_status(h, C.byref(o), nl, 1, None, ptr(out[1])) == -1 and b"null argument" in lib.lili_last_error(h)
     assert (out == 7.5).all() and unchanged()
     # solve_lm: the options of lili_pose_graph_solve, then its own
     C.memset(C.byref(s), 0x5A, C.sizeof(s))
