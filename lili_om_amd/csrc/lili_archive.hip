@@ -147,6 +147,31 @@ __global__ void k_gm_centroid(const float4* __restrict__ tsum, const int* __rest
 
 }  // namespace lili
 
+// `count` float4 rows of device memory into a caller's lili_feature_out (declared in lili_launch.h): out->count = count, the first min(count, capacity) rows are
+// copied at out->stride (0: 16 bytes) on ctx->stream.  copy_rows_enqueue only enqueues and reports the rows the copy covers (0: nothing was enqueued);
+// copy_rows_out synchronises the stream behind it, whether or not a row was copied.
+int copy_rows_enqueue(lili_ctx* ctx, const void* d_rows, size_t count, lili_feature_out* out, const char* what, size_t* copied) {
+    out->count = count;
+    const size_t k = std::min(out->count, out->capacity);
+    *copied = 0;
+    if (out->data && k) {
+        const size_t stride = out->stride ? out->stride : 16;
+        if (stride < 16) return ctx->fail(LILI_E_ARG, std::string(what) + ": stride must be >= 16");
+        const hipMemcpyKind kind = out->mem == LILI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (stride == 16) HIPCHK(hipMemcpyAsync(out->data, d_rows, k * 16, kind, ctx->stream));
+        else HIPCHK(hipMemcpy2DAsync(out->data, stride, d_rows, 16, 16, k, kind, ctx->stream));
+        *copied = k;
+    }
+    return LILI_OK;
+}
+int copy_rows_out(lili_ctx* ctx, const void* d_rows, size_t count, lili_feature_out* out, const char* what) {
+    size_t copied = 0;
+    const int rc = copy_rows_enqueue(ctx, d_rows, count, out, what, &copied);
+    if (rc != LILI_OK) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return LILI_OK;
+}
+
 namespace {
 
 constexpr int kKinds = 3;
@@ -302,20 +327,6 @@ int push_keyframe(lili_ctx* ctx, const lili_cloud* const clouds[kKinds], const f
     map_pose(kf.t_po, kf.q_po, A->t_bl, A->q_bl, kf.t_map, kf.q_map);
     if (id) *id = (int)A->kf.size();
     A->kf.push_back(kf);
-    return LILI_OK;
-}
-
-int copy_rows_out(lili_ctx* ctx, const void* d_rows, size_t count, lili_feature_out* out, const char* what) {
-    out->count = count;
-    const size_t k = std::min(out->count, out->capacity);
-    if (out->data && k) {
-        const size_t stride = out->stride ? out->stride : 16;
-        if (stride < 16) return ctx->fail(LILI_E_ARG, std::string(what) + ": stride must be >= 16");
-        const hipMemcpyKind kind = out->mem == LILI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (stride == 16) HIPCHK(hipMemcpyAsync(out->data, d_rows, k * 16, kind, ctx->stream));
-        else HIPCHK(hipMemcpy2DAsync(out->data, stride, d_rows, 16, 16, k, kind, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     return LILI_OK;
 }
 

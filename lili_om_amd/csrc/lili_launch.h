@@ -61,6 +61,9 @@ __global__ void k_pg_retract_cost(PgDev);
 
 // lili_map.hip: the three-kernel exclusive scan (k_scan_block_sums, k_scan_sums, k_scan_apply) of n words into out[0 .. n]; in == out is allowed
 int lili_scan_exclusive3(lili_ctx* ctx, const int* in, int64_t n, lili_detail::DevBuf& sums, int* out);
+// lili_archive.hip: float4 rows of device memory into a caller's lili_feature_out — enqueued only (*copied: the rows covered), or with the stream synchronised behind it
+int copy_rows_enqueue(lili_ctx* ctx, const void* d_rows, size_t count, lili_feature_out* out, const char* what, size_t* copied);
+int copy_rows_out(lili_ctx* ctx, const void* d_rows, size_t count, lili_feature_out* out, const char* what);
 // lili_match.hip -> lili_window.hip (the lidar blocks of the joint window)
 int lili_match_window_records(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const double* t, const double* q, double* d_gram);
 int lili_match_lm_args(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, const lili_lm_options* options, int max_blocks, lili::LmArgs* out);

@@ -6,6 +6,7 @@
 //     kernels behind the end return at their first instruction; one host synchronisation per batch.
 // A context owns one source, one target and its index (LoopState): nothing here touches the matcher's maps, the local map or the voxel filter's state.
 #include "lili_ctx.h"
+#include "lili_launch.h"
 #include "lili_device_math.h"
 
 #include <cfloat>
@@ -507,16 +508,10 @@ int lili_icp_get_cloud(lili_ctx* ctx, int which, lili_feature_out* out) {
     LoopState* L = loop_of(ctx);
     if (!L->has[which]) return ctx->fail(LILI_E_STATE, "icp_get_cloud: no such cloud yet");
     HIPCHK(hipSetDevice(ctx->device));
-    out->count = (size_t)L->n[which];
-    const size_t k = std::min(out->count, out->capacity);
-    if (out->data && k) {
-        const size_t stride = out->stride ? out->stride : 16;
-        ARGCHK(stride >= 16, "icp_get_cloud: stride must be >= 16");
-        const hipMemcpyKind kind = out->mem == LILI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (stride == 16) HIPCHK(hipMemcpyAsync(out->data, L->cloud[which].p, k * 16, kind, ctx->stream));
-        else HIPCHK(hipMemcpy2DAsync(out->data, stride, L->cloud[which].p, 16, 16, k, kind, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
+    size_t k = 0;
+    const int rc = copy_rows_enqueue(ctx, L->cloud[which].p, (size_t)L->n[which], out, "icp_get_cloud", &k);
+    if (rc != LILI_OK) return rc;
+    if (k) HIPCHK(hipStreamSynchronize(ctx->stream));
     return LILI_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "lili_launch.h"
 #include "lili_device_math.h"
 #include "lili_device_cloud.h"
+#include "lili_localmap_plan.h"
 
 namespace lili_detail { struct ConcatSeg { const float4* src; long long first; }; }      // one keyframe of the ring: its points and where they start in the concatenation
 
@@ -532,24 +533,26 @@ __global__ __launch_bounds__(64 * kRankWaves) void k_rank_count(const float4* __
     for (int w = 0; w < kRankWaves; w++) r += part[w][lane];
     if (r) atomicAdd(&rank[e], r);
 }
-__global__ void k_rank_scatter(const float4* __restrict__ pts, int n, float inv_leaf, unsigned seq, const int* __restrict__ rank, float4* __restrict__ out_pt,
-                               unsigned long long* __restrict__ out_key, unsigned* __restrict__ out_seq) {
+// `segs` (may be null): the cloud is the concatenation of several keyframes and an entry takes its keyframe's sequence number (k_sorted_gather); else `seq_const`
+__global__ void k_rank_scatter(const float4* __restrict__ pts, int n, float inv_leaf, unsigned seq_const, const lili_detail::ConcatSeg* __restrict__ segs, const unsigned* __restrict__ seg_seq,
+                               int n_seg, const int* __restrict__ rank, float4* __restrict__ out_pt, unsigned long long* __restrict__ out_key, unsigned* __restrict__ out_seq) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
+    unsigned sq = seq_const;
+    if (segs) sq = seg_seq[seg_of(segs, n_seg, e)];
     const float4 p = pts[e];
     const int r = rank[e];
-    out_pt[r] = p; out_key[r] = abs_voxel_key(p, inv_leaf); out_seq[r] = seq;
+    out_pt[r] = p; out_key[r] = abs_voxel_key(p, inv_leaf); out_seq[r] = sq;
 }
 
-struct DropSeqs { unsigned s[4]; int n; };
-__global__ void k_keep_flags(const unsigned* __restrict__ seq, long long n, DropSeqs d, int* __restrict__ flags) {
+// The keep rule of every merge: the ring's sequence numbers rise in ring order (pushes take the next number, lili_localmap_repose renumbers its suffix upwards), so the
+// entries that stay are exactly those of ONE range [keep_lo, keep_hi] of sequence numbers — the popped keyframes lie below it, the re-posed ones (under their old
+// numbers) above; no limit on the number of keyframes dropped.
+__global__ void k_keep_range_flags(const unsigned* __restrict__ seq, long long n, unsigned keep_lo, unsigned keep_hi, int* __restrict__ flags) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const unsigned q = seq[i];
-    bool drop = false;
-#pragma unroll
-    for (int k = 0; k < 4; k++) drop = drop || (k < d.n && q == d.s[k]);
-    flags[i] = drop ? 0 : 1;
+    flags[i] = (q >= keep_lo && q <= keep_hi) ? 1 : 0;
 }
 // kept entry i of the old list goes to (kept entries before it) + (new entries with a SMALLER key: new ones follow old ones of the same voxel)
 __device__ __forceinline__ void merge_old_item(const unsigned long long* __restrict__ key, const float4* __restrict__ pt, const unsigned* __restrict__ seq, bool keep,
@@ -571,49 +574,12 @@ __device__ __forceinline__ void merge_new_item(const unsigned long long* __restr
     const long long pos = (long long)j + (long long)rank[lo];
     okey[pos] = k; opt[pos] = npt[j]; oseq[pos] = nseq;
 }
-// both halves of the merge in ONE launch: threads [0, n) place the old list's entries, threads [n, n + n_new) the new keyframe's.  `flags` (the keep flags in memory) or,
-// when null, the keyframes dropped (`drop`: the scan derived the flags itself, k_scan_flags<kScanKeep>)
-__global__ void k_merge(const unsigned long long* __restrict__ key, const float4* __restrict__ pt, const unsigned* __restrict__ seq, const int* __restrict__ flags, DropSeqs drop,
-                        const int* __restrict__ rank, long long n, const unsigned long long* __restrict__ nkey, const float4* __restrict__ npt, int n_new, unsigned nseq,
-                        unsigned long long* __restrict__ okey, float4* __restrict__ opt, unsigned* __restrict__ oseq) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        bool keep;
-        if (flags) keep = flags[i] != 0;
-        else {
-            const unsigned q = seq[i];
-            bool d = false;
-#pragma unroll
-            for (int k = 0; k < 4; k++) d = d || (k < drop.n && q == drop.s[k]);
-            keep = !d;
-        }
-        merge_old_item(key, pt, seq, keep, rank, i, nkey, n_new, okey, opt, oseq);
-    } else if (i < n + n_new) merge_new_item(nkey, npt, (int)(i - n), nseq, key, rank, n, okey, opt, oseq);
-}
-
-// ---- the commit after lili_localmap_repose: the re-posed suffix of the ring and the pending pushes are merged in as ONE list (several keyframes, a sequence number
-// per entry).  The ring's sequence numbers rise in ring order, so the entries that stay are exactly those of ONE range [keep_lo, keep_hi] of sequence numbers: the
-// popped keyframes lie below it, the re-posed ones (renumbered) above — no limit on the number of keyframes dropped.
-__global__ void k_keep_range_flags(const unsigned* __restrict__ seq, long long n, unsigned keep_lo, unsigned keep_hi, int* __restrict__ flags) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const unsigned q = seq[i];
-    flags[i] = (q >= keep_lo && q <= keep_hi) ? 1 : 0;
-}
-// k_rank_scatter for the concatenation of several keyframes: the sequence number of an entry is its keyframe's, found by bisection over the segments (k_sorted_gather)
-__global__ void k_rank_scatter_segs(const float4* __restrict__ pts, int n, float inv_leaf, const lili_detail::ConcatSeg* __restrict__ segs, const unsigned* __restrict__ seg_seq, int n_seg,
-                                    const int* __restrict__ rank, float4* __restrict__ out_pt, unsigned long long* __restrict__ out_key, unsigned* __restrict__ out_seq) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int lo = seg_of(segs, n_seg, e);
-    const float4 p = pts[e];
-    const int r = rank[e];
-    out_pt[r] = p; out_key[r] = abs_voxel_key(p, inv_leaf); out_seq[r] = seg_seq[lo];
-}
-// k_merge with the keep rule of the range and a sequence number per new entry (all of them newer than every kept entry: new after old inside a voxel stays the rule)
-__global__ void k_merge_seqs(const unsigned long long* __restrict__ key, const float4* __restrict__ pt, const unsigned* __restrict__ seq, const int* __restrict__ flags, unsigned keep_lo,
-                             unsigned keep_hi, const int* __restrict__ rank, long long n, const unsigned long long* __restrict__ nkey, const float4* __restrict__ npt,
-                             const unsigned* __restrict__ nseq, int n_new, unsigned long long* __restrict__ okey, float4* __restrict__ opt, unsigned* __restrict__ oseq) {
+// both halves of the merge in ONE launch: threads [0, n) place the old list's entries, threads [n, n + n_new) the new ones (one keyframe or several, a sequence number
+// per entry; all of them newer than every kept entry: new after old inside a voxel is the rule).  `flags` (the keep flags in memory) or, when null, the range itself
+// (the scan derived the flags from it too, k_scan_flags<kScanKeepRange>)
+__global__ void k_merge(const unsigned long long* __restrict__ key, const float4* __restrict__ pt, const unsigned* __restrict__ seq, const int* __restrict__ flags, unsigned keep_lo,
+                        unsigned keep_hi, const int* __restrict__ rank, long long n, const unsigned long long* __restrict__ nkey, const float4* __restrict__ npt,
+                        const unsigned* __restrict__ nseq, int n_new, unsigned long long* __restrict__ okey, float4* __restrict__ opt, unsigned* __restrict__ oseq) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         const unsigned q = seq[i];
@@ -684,22 +650,12 @@ __global__ void k_vox_centroid64(const unsigned long long* __restrict__ keys, co
 }
 
 // (transform_point, the one expression that places a keyframe in the map frame, lives in lili_device_math.h: lili_archive.hip places keyframes with it too)
-// `src`: the rows as pushed (LiDAR frame), kept by the ring for lili_localmap_repose
-__global__ void k_transform_cloud(const float4* __restrict__ in, int n, dq q, d3 t, float4* __restrict__ out, float4* __restrict__ src) {
+// `src`: the rows as pushed (LiDAR frame), kept by the ring for lili_localmap_repose.  `st` (may be null): the pose is read from a slot's device state instead of
+// (q, t) (lili_frontend_frame: the keyframe is pushed at the pose the matcher has just reached, before the host has seen it) — same expression, same operands
+__global__ void k_transform_cloud(const float4* __restrict__ in, int n, dq q, d3 t, const SlotState* __restrict__ st, float4* __restrict__ out, float4* __restrict__ src) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float4 p = in[i];
-    out[i] = transform_point(p, q, t);
-    src[i] = p;
-}
-
-// the same with the pose read from a slot's device state (lili_frontend_frame: the keyframe is pushed at the pose the matcher has just reached, before the
-// host has seen it) — same expression, same operands
-__global__ void k_transform_cloud_state(const float4* __restrict__ in, int n, const SlotState* __restrict__ st, float4* __restrict__ out, float4* __restrict__ src) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const dq q{st->pose[3], st->pose[4], st->pose[5], st->pose[6]};
-    const d3 t{st->pose[0], st->pose[1], st->pose[2]};
+    if (st) { q = dq{st->pose[3], st->pose[4], st->pose[5], st->pose[6]}; t = d3{st->pose[0], st->pose[1], st->pose[2]}; }
     float4 p = in[i];
     out[i] = transform_point(p, q, t);
     src[i] = p;
@@ -734,7 +690,7 @@ namespace lili_detail {
 // allocation per keyframe, as before it kept them: a hipMalloc / hipFree is a device-wide synchronisation); `t` / `q`: the pose `pts` was placed at, unknown
 // (pose_known false) for a push at a pose read on the device (lili_localmap_push_dev)
 struct Keyframe { DevBuf pts; float4* src = nullptr; int n = 0; unsigned seq = 0; double t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0}; bool pose_known = false; };
-// the ring of one kind, sorted by absolute voxel key (older keyframes first inside a voxel): see k_merge_old / k_merge_new
+// the ring of one kind, sorted by absolute voxel key (older keyframes first inside a voxel): see k_merge
 struct SortedRing {
     DevBuf key[2], pt[2], seq[2];
     int cur = 0;
@@ -838,14 +794,13 @@ __global__ __launch_bounds__(256) void k_scan_tiles(const int* __restrict__ in, 
     if (blockIdx.x == gridDim.x - 1 && tid == 0) out[n] = (w_front[0] + w_front[1]) + (w_front[2] + w_front[3]) + tile_total;
 }
 // k_scan_tiles over flags that are never stored (round 5): the launches that only wrote a flag per item for the scan to read are folded into it.  MODE
-//   kScanKeep   : item i of the sorted ring survives the merge (its keyframe is not one of `drop`)                       — was k_keep_flags + scan
+//   kScanKeepRange : item i of the sorted ring survives the merge (its sequence number lies in [keep_lo, keep_hi])         — was k_keep_range_flags + scan
 //   kScanHead64 : item i starts a voxel of the sorted ring (64-bit absolute keys); head_pos[its slot] = i on the way      — was k_vox_heads64 + scan + k_vox_head_pos
 //   kScanHead32 : item i starts a voxel of a sorted cloud (32-bit keys, `sentinel` = no voxel); spts[i] = pts[vals[i]]     — was k_vox_heads + scan
 // Same tiles, same sums; the items in front of a tile are re-derived from the keys (the same bytes the flags would have been, twice for 64-bit keys).
-//   kScanKeepRange : item i of the sorted ring survives the merge after a repose (its sequence number lies in [keep_lo, keep_hi]) — was k_keep_range_flags + scan
-enum { kScanKeep = 1, kScanHead64 = 2, kScanHead32 = 3, kScanKeepRange = 4 };
-constexpr bool scan_keep_mode(int m) { return m == kScanKeep || m == kScanKeepRange; }
-struct ScanFlagArgs { const void* a; DropSeqs drop; unsigned sentinel; const int* vals; const float4* pts; float4* spts; int* head_pos; unsigned keep_lo, keep_hi; };
+enum { kScanHead64 = 2, kScanHead32 = 3, kScanKeepRange = 4 };
+constexpr bool scan_keep_mode(int m) { return m == kScanKeepRange; }
+struct ScanFlagArgs { const void* a; unsigned sentinel; const int* vals; const float4* pts; float4* spts; int* head_pos; unsigned keep_lo, keep_hi; };
 // the raw words behind four consecutive flags (two steps, so that a caller can request several groups before it looks at any: a load behind a branch, or mixed with
 // the arithmetic of the previous group, waits for its own round trip)
 struct ScanRaw { uint4 a, b; unsigned long long prev; };
@@ -863,16 +818,7 @@ template <int MODE> __device__ __forceinline__ ScanRaw scan_flags_load(const Sca
 }
 // v[k] = flag of item i + k; endm (head modes) = bit k set where item i + k is the FIRST item that is no voxel (non-finite points sort last): where the last voxel ends
 template <int MODE> __device__ __forceinline__ void scan_flags_eval(const ScanFlagArgs& A, const ScanRaw& r, int i, int n, int v[4], unsigned* endm = nullptr) {
-    if (MODE == kScanKeep) {
-        const unsigned s[4] = {r.a.x, r.a.y, r.a.z, r.a.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            bool drop = false;
-#pragma unroll
-            for (int d = 0; d < 4; d++) drop = drop || (d < A.drop.n && s[k] == A.drop.s[d]);
-            v[k] = (i + k < n && !drop) ? 1 : 0;
-        }
-    } else if (MODE == kScanKeepRange) {
+    if (MODE == kScanKeepRange) {
         const unsigned s[4] = {r.a.x, r.a.y, r.a.z, r.a.w};
 #pragma unroll
         for (int k = 0; k < 4; k++) v[k] = (i + k < n && s[k] >= A.keep_lo && s[k] <= A.keep_hi) ? 1 : 0;
@@ -984,6 +930,12 @@ template <int MODE> __global__ __launch_bounds__(kScanFlagThreads) void k_scan_f
 }
 constexpr long long kScanFlagsMax = 65536;      // (beyond: flags in memory and the three-kernel scan)
 
+// the bounding box of a device cloud into the six ordered-uint words `d_mm`: arm them, then reduce
+static void launch_bbox(lili_ctx* ctx, const float4* pts, int n, unsigned* d_mm) {
+    hipLaunchKernelGGL(k_box_init, dim3(1), dim3(64), 0, ctx->stream, d_mm);
+    hipLaunchKernelGGL(k_bbox, dim3(std::min(nblocks(n, kBlock), 512)), dim3(kBlock), 0, ctx->stream, pts, n, d_mm);
+}
+
 static int exclusive_scan(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const int* in, int64_t n, int* out /*[n+1]*/) {
     if (n <= 65536) {
         hipLaunchKernelGGL(k_scan_tiles, dim3(std::max(1, nblocks(n, kScanTile))), dim3(256), 0, ctx->stream, in, (int)n, out);
@@ -1048,8 +1000,7 @@ static int radix_sort(lili_ctx* ctx, lili_detail::VoxelBuffers* V, int n, int bi
 // `status` / `box` (lili_voxel_sort_dev): the two refusals come back as *status = 2 / 3 with LILI_OK instead of an error, and the finite rows' box as floats
 static int voxel_sort(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const float4* d_pts, int n, float leaf, VoxDev& P, bool alt = false, int* status = nullptr, float* box = nullptr) {
     unsigned* d_mm = ctx->misc.as<unsigned>();
-    hipLaunchKernelGGL(k_box_init, dim3(1), dim3(64), 0, ctx->stream, d_mm);
-    hipLaunchKernelGGL(k_bbox, dim3(std::min(nblocks(n, kBlock), 512)), dim3(kBlock), 0, ctx->stream, d_pts, n, d_mm);
+    launch_bbox(ctx, d_pts, n, d_mm);
     unsigned mm[6];
     TRY(lili_readback_now(ctx, mm, d_mm, sizeof(mm)));
     P = VoxDev{};
@@ -1141,10 +1092,7 @@ static int voxel_filter_enqueue(lili_ctx* ctx, lili_detail::VoxelBuffers* V, con
         if (ride) HIPCHK(V->hist.ensure((size_t)passes * 256 * nb_sort * sizeof(int)));
         if (box_zeroed) hipLaunchKernelGGL(k_bbox_z, dim3(std::min(nblocks(n, 256), 512)), dim3(256), 0, ctx->stream, d_pts, n, d_mm, ride ? V->hist.as<int>() : (int*)nullptr,
                                            ride ? passes * 256 * nb_sort : 0);
-        else {
-            hipLaunchKernelGGL(k_box_init, dim3(1), dim3(64), 0, ctx->stream, d_mm);
-            hipLaunchKernelGGL(k_bbox, dim3(std::min(nblocks(n, kBlock), 512)), dim3(kBlock), 0, ctx->stream, d_pts, n, d_mm);
-        }
+        else launch_bbox(ctx, d_pts, n, d_mm);
         HIPCHK(V->keys_a.ensure((size_t)n * 4)); HIPCHK(V->vals_a.ensure((size_t)n * 4));
         hipLaunchKernelGGL(k_vox_key_dev, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, d_pts, n, 1.0f / leaf, (const unsigned*)d_mm, box_zeroed ? 1 : 0, bits, V->keys_a.as<unsigned>(),
                            V->vals_a.as<int>(), d_res, ride ? V->hist.as<int>() : (int*)nullptr, nb_sort, kSortBlock * items8);
@@ -1204,14 +1152,10 @@ int lili_voxel_filter(lili_ctx* ctx, const lili_cloud* cloud, float leaf, lili_f
     if (rc != LILI_OK) return rc;
     rc = voxel_filter_device(ctx, V, V->in.as<float4>(), (int)cloud->n, leaf);
     if (rc != LILI_OK) return rc;
-    out->count = (size_t)V->n_out;
-    size_t k = std::min(out->count, out->capacity);
-    if (out->data && k) {
-        size_t stride = out->stride ? out->stride : 16;
-        ARGCHK(stride >= 16, "voxel_filter: stride must be >= 16");
-        const hipMemcpyKind kind = out->mem == LILI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (stride == 16) HIPCHK(hipMemcpyAsync(out->data, V->out.p, k * 16, kind, ctx->stream));
-        else HIPCHK(hipMemcpy2DAsync(out->data, stride, V->out.p, 16, 16, k, kind, ctx->stream));
+    size_t k = 0;
+    rc = copy_rows_enqueue(ctx, V->out.p, (size_t)V->n_out, out, "voxel_filter", &k);
+    if (rc != LILI_OK) return rc;
+    if (k) {
         if (counts) HIPCHK(hipMemcpyAsync(counts, V->out_cnt.p, k * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
@@ -1243,9 +1187,8 @@ static int localmap_push_f4(lili_ctx* ctx, int kind, const float4* d_in, int n, 
         hipError_t e = kf->pts.ensure((size_t)kf->n * 32);      // map-frame rows, then the rows as pushed
         if (e != hipSuccess) return ctx->fail(LILI_E_HIP, "localmap_push: allocation failed");
         kf->src = kf->pts.as<float4>() + kf->n;
-        if (d_state) hipLaunchKernelGGL(k_transform_cloud_state, dim3(nblocks(kf->n, 256)), dim3(256), 0, ctx->stream, d_in, kf->n, d_state, kf->pts.as<float4>(), kf->src);
-        else hipLaunchKernelGGL(k_transform_cloud, dim3(nblocks(kf->n, 256)), dim3(256), 0, ctx->stream, d_in, kf->n,
-                                dq{q[0], q[1], q[2], q[3]}, d3{t[0], t[1], t[2]}, kf->pts.as<float4>(), kf->src);
+        hipLaunchKernelGGL(k_transform_cloud, dim3(nblocks(kf->n, 256)), dim3(256), 0, ctx->stream, d_in, kf->n, d_state ? dq{} : dq{q[0], q[1], q[2], q[3]},
+                           d_state ? d3{} : d3{t[0], t[1], t[2]}, d_state, kf->pts.as<float4>(), kf->src);
         hipError_t le = hipGetLastError();
         if (le != hipSuccess) return ctx->fail(LILI_E_HIP, std::string("localmap_push: ") + hipGetErrorString(le));
     }
@@ -1326,103 +1269,60 @@ int lili_localmap_repose(lili_ctx* ctx, int kind_mask, int n, const double* t, c
     return LILI_OK;
 }
 
-// One keyframe step on the sorted ring: drop the entries of the keyframes in `drop`, merge the keyframe `add` (may be null) in.
-static int sorted_ring_step(lili_ctx* ctx, lili_detail::VoxelBuffers* V, lili_detail::SortedRing& S, const DropSeqs& drop, long long n_drop, lili_detail::Keyframe* add, float leaf,
-                            unsigned* d_bad) {
-    int n_new = add ? add->n : 0;
-    if (n_new > 0 && n_new <= kVoxSmallMax && ctx->voxel_small) {      // a frame's worth of features: one launch (k_sort_keyframe_small)
-        HIPCHK(V->kf_key.ensure((size_t)n_new * 8)); HIPCHK(V->kf_pt.ensure((size_t)n_new * 16)); HIPCHK(V->flags.ensure((size_t)std::max<long long>(n_new, S.n) * 4));
-        // (`rank`: the scan-status words of a map build, idle during a commit; lili_localmap_commit zeroes them together with *bad)
-        int* d_rank = reinterpret_cast<int*>(ctx->misc.as<char>() + kRankOff);
-        const int slices = nblocks(n_new, 64);
-        hipLaunchKernelGGL(k_rank_count, dim3(slices, nblocks(slices, kRankWaves)), dim3(64 * kRankWaves), 0, ctx->stream, add->pts.as<float4>(), n_new, 1.0f / leaf, d_rank, d_bad);
-        hipLaunchKernelGGL(k_rank_scatter, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, add->pts.as<float4>(), n_new, 1.0f / leaf, add->seq, (const int*)d_rank,
-                           V->kf_pt.as<float4>(), V->kf_key.as<unsigned long long>(), V->flags.as<unsigned>());
-        HIPCHK(hipGetLastError());
-    } else
-    if (n_new > 0) {       // the new keyframe alone, sorted by voxel (stable): 20 k points, no host round trip (the bounding box stays on the device)
-        unsigned* d_mm = ctx->misc.as<unsigned>();
-        hipLaunchKernelGGL(k_box_init, dim3(1), dim3(64), 0, ctx->stream, d_mm);
-        hipLaunchKernelGGL(k_bbox, dim3(std::min(nblocks(n_new, kBlock), 512)), dim3(kBlock), 0, ctx->stream, add->pts.as<float4>(), n_new, d_mm);
-        HIPCHK(V->keys_a.ensure((size_t)n_new * 4)); HIPCHK(V->vals_a.ensure((size_t)n_new * 4));
-        hipLaunchKernelGGL(k_vox_key_packed, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, add->pts.as<float4>(), n_new, 1.0f / leaf, (const unsigned*)d_mm,
-                           V->keys_a.as<unsigned>(), V->vals_a.as<int>(), d_bad);
-        int rc = radix_sort(ctx, V, n_new, 32);
-        if (rc != LILI_OK) return rc;
-        HIPCHK(V->kf_key.ensure((size_t)n_new * 8)); HIPCHK(V->kf_pt.ensure((size_t)n_new * 16)); HIPCHK(V->flags.ensure((size_t)std::max<long long>(n_new, S.n) * 4));
-        hipLaunchKernelGGL(k_sorted_gather, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, add->pts.as<float4>(), V->vals_a.as<int>(), n_new, 1.0f / leaf, add->seq,
-                           (const lili_detail::ConcatSeg*)nullptr, (const unsigned*)nullptr, 0, V->kf_pt.as<float4>(), V->kf_key.as<unsigned long long>(), V->flags.as<unsigned>(), d_bad);
-    }
-    const long long n_old = S.n, n_out = n_old - n_drop + n_new;
-    const int dst = 1 - S.cur;
-    HIPCHK(S.key[dst].ensure((size_t)std::max<long long>(n_out, 1) * 8)); HIPCHK(S.pt[dst].ensure((size_t)std::max<long long>(n_out, 1) * 16)); HIPCHK(S.seq[dst].ensure((size_t)std::max<long long>(n_out, 1) * 4));
-    HIPCHK(V->flags.ensure((size_t)std::max<long long>(n_old, 1) * 4)); HIPCHK(V->slots.ensure(((size_t)n_old + 1) * 4));
-    const bool fused_flags = n_old <= kScanFlagsMax;      // the scan derives the keep flags itself; the merge does too
-    if (n_old > 0) {
-        if (fused_flags) {
-            ScanFlagArgs A{}; A.a = S.seq[S.cur].p; A.drop = drop;
-            hipLaunchKernelGGL(k_scan_flags<kScanKeep>, dim3(nblocks(n_old, kScanTile)), dim3(kScanFlagThreads), 0, ctx->stream, A, (int)n_old, V->slots.as<int>());
-        } else {
-            hipLaunchKernelGGL(k_keep_flags, dim3(nblocks(n_old, 256)), dim3(256), 0, ctx->stream, S.seq[S.cur].as<unsigned>(), n_old, drop, V->flags.as<int>());
-            int rc = exclusive_scan(ctx, V, V->flags.as<int>(), n_old, V->slots.as<int>());
-            if (rc != LILI_OK) return rc;
-        }
-    } else HIPCHK(hipMemsetAsync(V->slots.p, 0, 4, ctx->stream));
-    if (n_old + n_new > 0)
-        hipLaunchKernelGGL(k_merge, dim3(nblocks(n_old + n_new, 256)), dim3(256), 0, ctx->stream, S.key[S.cur].as<unsigned long long>(), S.pt[S.cur].as<float4>(), S.seq[S.cur].as<unsigned>(),
-                           fused_flags ? (const int*)nullptr : (const int*)V->flags.as<int>(), drop, (const int*)V->slots.as<int>(), n_old, V->kf_key.as<unsigned long long>(), V->kf_pt.as<float4>(),
-                           n_new, add ? add->seq : 0u, S.key[dst].as<unsigned long long>(), S.pt[dst].as<float4>(), S.seq[dst].as<unsigned>());
-    HIPCHK(hipGetLastError());
-    S.cur = dst; S.n = n_out;
-    return LILI_OK;
-}
-
-// The commit after lili_localmap_repose as ONE merge step: the entries outside the sequence range [keep_lo, keep_hi] go (popped keyframes, the re-posed suffix under its
-// old numbers), the keyframes `add` (the re-posed suffix under fresh numbers, then the pending pushes: ring order) come in, concatenated and stably sorted by key as one
-// list — (key, ring position, point order), the order a full rebuild gives them — and merged behind the kept entries of their voxel.
-constexpr size_t kResuffixMaxAdd = 8;      // keyframes merged in at once; more (a long re-posed suffix, a loop closure) take the full rebuild
-static int sorted_ring_resuffix(lili_ctx* ctx, lili_detail::VoxelBuffers* V, lili_detail::SortedRing& S, unsigned keep_lo, unsigned keep_hi, long long n_drop,
-                                const std::vector<lili_detail::Keyframe*>& add, float leaf, unsigned* d_bad) {
+// ---- One merge step on the sorted ring, in three pieces.
+// 1. The keyframes `add` (ring order) as ONE list sorted by absolute key — (key, ring position, point order), the order a full rebuild gives them — in V->kf_pt / kf_key /
+//    kf_seq.  A single non-empty keyframe is read where it lies; several are concatenated and an entry finds its keyframe's number in the segment table.
+static int sort_added(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const std::vector<lili_detail::Keyframe*>& add, float leaf, unsigned* d_bad, int* n_added) {
     std::vector<lili_detail::ConcatSeg>& segs = V->seg_host;      // members, not locals: hipMemcpyAsync may read them after this call
     std::vector<unsigned>& sseq = V->seg_seq_host;
     segs.clear(); sseq.clear();
-    long long n_new = 0;
-    for (auto* k : add) { if (k->n) { segs.push_back({k->pts.as<float4>(), n_new}); sseq.push_back(k->seq); } n_new += k->n; }
+    long long total = 0;
+    for (auto* k : add) { if (k->n) { segs.push_back({k->pts.as<float4>(), total}); sseq.push_back(k->seq); } total += k->n; }
+    const int n = *n_added = (int)total;      // (the commit has checked that the whole ring stays below 2^31 points)
+    if (n == 0) return LILI_OK;
+    HIPCHK(V->kf_key.ensure((size_t)n * 8)); HIPCHK(V->kf_pt.ensure((size_t)n * 16)); HIPCHK(V->kf_seq.ensure((size_t)n * 4));
     const float inv_leaf = 1.0f / leaf;
-    if (n_new > 0) {
-        HIPCHK(V->concat.ensure((size_t)n_new * 16)); HIPCHK(V->concat_tab.ensure(segs.size() * sizeof(lili_detail::ConcatSeg))); HIPCHK(V->seg_seq.ensure(sseq.size() * 4));
-        HIPCHK(V->kf_key.ensure((size_t)n_new * 8)); HIPCHK(V->kf_pt.ensure((size_t)n_new * 16)); HIPCHK(V->kf_seq.ensure((size_t)n_new * 4));
+    const float4* pts = segs[0].src;
+    const lili_detail::ConcatSeg* d_segs = nullptr;
+    const unsigned* d_sseq = nullptr;
+    if (segs.size() > 1) {
+        HIPCHK(V->concat.ensure((size_t)n * 16)); HIPCHK(V->concat_tab.ensure(segs.size() * sizeof(lili_detail::ConcatSeg))); HIPCHK(V->seg_seq.ensure(sseq.size() * 4));
         HIPCHK(hipMemcpyAsync(V->concat_tab.p, segs.data(), segs.size() * sizeof(lili_detail::ConcatSeg), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(V->seg_seq.p, sseq.data(), sseq.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        const auto* d_segs = V->concat_tab.as<lili_detail::ConcatSeg>();
-        hipLaunchKernelGGL(k_concat, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, d_segs, (int)segs.size(), n_new, V->concat.as<float4>());
-        const float4* cat = V->concat.as<float4>();
-        if (n_new <= kVoxSmallMax && ctx->voxel_small) {      // counting sort of the whole list (k_rank_count; the rank words were zeroed by the commit)
-            int* d_rank = reinterpret_cast<int*>(ctx->misc.as<char>() + kRankOff);
-            const int slices = nblocks(n_new, 64);
-            hipLaunchKernelGGL(k_rank_count, dim3(slices, nblocks(slices, kRankWaves)), dim3(64 * kRankWaves), 0, ctx->stream, cat, (int)n_new, inv_leaf, d_rank, d_bad);
-            hipLaunchKernelGGL(k_rank_scatter_segs, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, cat, (int)n_new, inv_leaf, d_segs, V->seg_seq.as<unsigned>(), (int)segs.size(),
-                               (const int*)d_rank, V->kf_pt.as<float4>(), V->kf_key.as<unsigned long long>(), V->kf_seq.as<unsigned>());
-        } else {      // the radix path of sorted_ring_step on the concatenation; the gather finds every entry's keyframe in the segment table
-            unsigned* d_mm = ctx->misc.as<unsigned>();
-            hipLaunchKernelGGL(k_box_init, dim3(1), dim3(64), 0, ctx->stream, d_mm);
-            hipLaunchKernelGGL(k_bbox, dim3(std::min(nblocks(n_new, kBlock), 512)), dim3(kBlock), 0, ctx->stream, cat, (int)n_new, d_mm);
-            HIPCHK(V->keys_a.ensure((size_t)n_new * 4)); HIPCHK(V->vals_a.ensure((size_t)n_new * 4));
-            hipLaunchKernelGGL(k_vox_key_packed, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, cat, (int)n_new, inv_leaf, (const unsigned*)d_mm, V->keys_a.as<unsigned>(),
-                               V->vals_a.as<int>(), d_bad);
-            const int rc = radix_sort(ctx, V, (int)n_new, 32);
-            if (rc != LILI_OK) return rc;
-            hipLaunchKernelGGL(k_sorted_gather, dim3(nblocks(n_new, 256)), dim3(256), 0, ctx->stream, cat, V->vals_a.as<int>(), (int)n_new, inv_leaf, 0u, d_segs,
-                               V->seg_seq.as<unsigned>(), (int)segs.size(), V->kf_pt.as<float4>(), V->kf_key.as<unsigned long long>(), V->kf_seq.as<unsigned>(), d_bad);
-        }
-        HIPCHK(hipGetLastError());
+        d_segs = V->concat_tab.as<lili_detail::ConcatSeg>(); d_sseq = V->seg_seq.as<unsigned>();
+        hipLaunchKernelGGL(k_concat, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, d_segs, (int)segs.size(), (long long)n, V->concat.as<float4>());
+        pts = V->concat.as<float4>();
     }
-    const long long n_old = S.n, n_out = n_old - n_drop + n_new;
-    const int dst = 1 - S.cur;
-    HIPCHK(S.key[dst].ensure((size_t)std::max<long long>(n_out, 1) * 8)); HIPCHK(S.pt[dst].ensure((size_t)std::max<long long>(n_out, 1) * 16)); HIPCHK(S.seq[dst].ensure((size_t)std::max<long long>(n_out, 1) * 4));
+    const unsigned seq_const = d_segs ? 0u : sseq[0];
+    const int n_seg = d_segs ? (int)segs.size() : 0;
+    if (n <= kVoxSmallMax && ctx->voxel_small) {      // a frame's worth of features: sorted by counting (k_rank_count)
+        // (`rank`: the scan-status words of a map build, idle during a commit; lili_localmap_commit zeroes them together with *bad)
+        int* d_rank = reinterpret_cast<int*>(ctx->misc.as<char>() + kRankOff);
+        const int slices = nblocks(n, 64);
+        hipLaunchKernelGGL(k_rank_count, dim3(slices, nblocks(slices, kRankWaves)), dim3(64 * kRankWaves), 0, ctx->stream, pts, n, inv_leaf, d_rank, d_bad);
+        hipLaunchKernelGGL(k_rank_scatter, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, pts, n, inv_leaf, seq_const, d_segs, d_sseq, n_seg, (const int*)d_rank, V->kf_pt.as<float4>(),
+                           V->kf_key.as<unsigned long long>(), V->kf_seq.as<unsigned>());
+    } else {       // sorted by voxel (stable) with the radix sort: 20 k points a keyframe, no host round trip (the bounding box stays on the device)
+        unsigned* d_mm = ctx->misc.as<unsigned>();
+        launch_bbox(ctx, pts, n, d_mm);
+        HIPCHK(V->keys_a.ensure((size_t)n * 4)); HIPCHK(V->vals_a.ensure((size_t)n * 4));
+        hipLaunchKernelGGL(k_vox_key_packed, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, pts, n, inv_leaf, (const unsigned*)d_mm, V->keys_a.as<unsigned>(), V->vals_a.as<int>(), d_bad);
+        const int rc = radix_sort(ctx, V, n, 32);
+        if (rc != LILI_OK) return rc;
+        hipLaunchKernelGGL(k_sorted_gather, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, pts, V->vals_a.as<int>(), n, inv_leaf, seq_const, d_segs, d_sseq, n_seg, V->kf_pt.as<float4>(),
+                           V->kf_key.as<unsigned long long>(), V->kf_seq.as<unsigned>(), d_bad);
+    }
+    HIPCHK(hipGetLastError());
+    return LILI_OK;
+}
+// 2. The keep flags of the old list (sequence number inside [keep_lo, keep_hi]) and their exclusive scan in V->slots.  *fused: the scan derived the flags itself and
+//    the merge has to as well; else they lie in V->flags.
+static int keep_flags_scan(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const lili_detail::SortedRing& S, unsigned keep_lo, unsigned keep_hi, bool* fused) {
+    const long long n_old = S.n;
     HIPCHK(V->flags.ensure((size_t)std::max<long long>(n_old, 1) * 4)); HIPCHK(V->slots.ensure(((size_t)n_old + 1) * 4));
-    const bool fused_flags = n_old <= kScanFlagsMax;
-    if (fused_flags) {
+    *fused = n_old <= kScanFlagsMax;
+    if (n_old == 0) HIPCHK(hipMemsetAsync(V->slots.p, 0, 4, ctx->stream));
+    else if (*fused) {
         ScanFlagArgs A{}; A.a = S.seq[S.cur].p; A.keep_lo = keep_lo; A.keep_hi = keep_hi;
         hipLaunchKernelGGL(k_scan_flags<kScanKeepRange>, dim3(nblocks(n_old, kScanTile)), dim3(kScanFlagThreads), 0, ctx->stream, A, (int)n_old, V->slots.as<int>());
     } else {
@@ -1430,11 +1330,139 @@ static int sorted_ring_resuffix(lili_ctx* ctx, lili_detail::VoxelBuffers* V, lil
         const int rc = exclusive_scan(ctx, V, V->flags.as<int>(), n_old, V->slots.as<int>());
         if (rc != LILI_OK) return rc;
     }
-    hipLaunchKernelGGL(k_merge_seqs, dim3(nblocks(n_old + n_new, 256)), dim3(256), 0, ctx->stream, S.key[S.cur].as<unsigned long long>(), S.pt[S.cur].as<float4>(), S.seq[S.cur].as<unsigned>(),
-                       fused_flags ? (const int*)nullptr : (const int*)V->flags.as<int>(), keep_lo, keep_hi, (const int*)V->slots.as<int>(), n_old, V->kf_key.as<unsigned long long>(),
-                       V->kf_pt.as<float4>(), V->kf_seq.as<unsigned>(), (int)n_new, S.key[dst].as<unsigned long long>(), S.pt[dst].as<float4>(), S.seq[dst].as<unsigned>());
+    return LILI_OK;
+}
+// 3. The merge launch and the flip: the entries outside [keep_lo, keep_hi] go (`n_drop` of them: popped keyframes, a re-posed suffix under its old numbers), the
+//    keyframes `add` (may be none) come in behind the kept entries of their voxel.
+static int sorted_ring_merge(lili_ctx* ctx, lili_detail::VoxelBuffers* V, lili_detail::SortedRing& S, unsigned keep_lo, unsigned keep_hi, long long n_drop,
+                             const std::vector<lili_detail::Keyframe*>& add, float leaf, unsigned* d_bad) {
+    int n_new = 0;
+    int rc = sort_added(ctx, V, add, leaf, d_bad, &n_new);
+    if (rc != LILI_OK) return rc;
+    bool fused_flags = false;
+    rc = keep_flags_scan(ctx, V, S, keep_lo, keep_hi, &fused_flags);
+    if (rc != LILI_OK) return rc;
+    const long long n_old = S.n, n_out = n_old - n_drop + n_new;
+    const int dst = 1 - S.cur;
+    HIPCHK(S.key[dst].ensure((size_t)std::max<long long>(n_out, 1) * 8)); HIPCHK(S.pt[dst].ensure((size_t)std::max<long long>(n_out, 1) * 16)); HIPCHK(S.seq[dst].ensure((size_t)std::max<long long>(n_out, 1) * 4));
+    if (n_old + n_new > 0)
+        hipLaunchKernelGGL(k_merge, dim3(nblocks(n_old + n_new, 256)), dim3(256), 0, ctx->stream, S.key[S.cur].as<unsigned long long>(), S.pt[S.cur].as<float4>(), S.seq[S.cur].as<unsigned>(),
+                           fused_flags ? (const int*)nullptr : (const int*)V->flags.as<int>(), keep_lo, keep_hi, (const int*)V->slots.as<int>(), n_old, V->kf_key.as<unsigned long long>(),
+                           V->kf_pt.as<float4>(), V->kf_seq.as<unsigned>(), n_new, S.key[dst].as<unsigned long long>(), S.pt[dst].as<float4>(), S.seq[dst].as<unsigned>());
     HIPCHK(hipGetLastError());
     S.cur = dst; S.n = n_out;
+    return LILI_OK;
+}
+
+// The incremental commit: the merge step(s) of `plan`, then the centroid pass over the sorted ring.  *done false with LILI_OK: the map is not made, the full rebuild
+// takes over (the sorted ring is then invalid).
+static int commit_incremental(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const std::vector<std::unique_ptr<lili_detail::Keyframe>>& ring, lili_detail::SortedRing& S,
+                              const lili_detail::LocalmapPlan& plan, size_t total, float leaf, unsigned* d_bad, bool* done, bool* have_box) {
+    *done = false; *have_box = false;
+    { const int rl = lili_lazy_sources_clear_of(ctx, d_bad, kRankOff - 256 + (size_t)kVoxSmallMax * 4); if (rl != LILI_OK) return rl; }
+    HIPCHK(hipMemsetAsync(d_bad, 0, kRankOff - 256 + (size_t)kVoxSmallMax * 4, ctx->stream));      // *bad ... the rank words of k_rank_count: one fill
+    std::vector<lili_detail::Keyframe*> add;
+    for (size_t i = plan.first_add; i < ring.size(); i++) add.push_back(ring[i].get());
+    int rc = LILI_OK;
+    if (plan.after_repose || add.size() <= 1) rc = sorted_ring_merge(ctx, V, S, plan.keep_lo, plan.keep_hi, plan.n_drop, add, leaf, d_bad);
+    else for (size_t i = 0; i < add.size() && rc == LILI_OK; i++) {      // the plain route: one step per pending keyframe; the first drops, the later ones keep everything
+        if (i > 0) HIPCHK(hipMemsetAsync(ctx->misc.as<char>() + kRankOff, 0, (size_t)kVoxSmallMax * 4, ctx->stream));      // (a second pending keyframe counts from zero again)
+        rc = sorted_ring_merge(ctx, V, S, i == 0 ? plan.keep_lo : 0u, i == 0 ? plan.keep_hi : 0xffffffffu, i == 0 ? plan.n_drop : 0, {add[i]}, leaf, d_bad);
+    }
+    if (rc != LILI_OK) return rc;
+    S.members.clear();
+    for (const auto& k : ring) S.members.push_back({k->seq, k->n});
+    const long long n = S.n;
+    V->n_out = 0;
+    unsigned bad = 0;
+    static_assert(2048 + kBoxBanks * 128 <= 8192, "box banks of the commit inside the first 8 KB of ctx->misc");
+    unsigned box_banks[kBoxBanks * 32];
+    bool box_read = false;
+    if (n > 0) {
+        HIPCHK(V->flags.ensure((size_t)n * 4)); HIPCHK(V->slots.ensure(((size_t)n + 1) * 4));
+        HIPCHK(V->out.ensure((size_t)n * 16)); HIPCHK(V->out_cnt.ensure((size_t)n * 4));
+        HIPCHK(V->head_pos.ensure(((size_t)n + 1) * 4));
+        if (n <= kScanFlagsMax) {      // heads, their scan and the compaction of the heads' positions in one launch
+            ScanFlagArgs A{}; A.a = S.key[S.cur].p; A.head_pos = V->head_pos.as<int>();
+            hipLaunchKernelGGL(k_scan_flags<kScanHead64>, dim3(nblocks(n, kScanTile)), dim3(kScanFlagThreads), 0, ctx->stream, A, (int)n, V->slots.as<int>());
+        } else {
+            hipLaunchKernelGGL(k_vox_heads64, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, S.key[S.cur].as<unsigned long long>(), n, V->flags.as<int>());
+            rc = exclusive_scan(ctx, V, V->flags.as<int>(), n, V->slots.as<int>());
+            if (rc != LILI_OK) return rc;
+            hipLaunchKernelGGL(k_vox_head_pos, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, V->flags.as<int>(), V->slots.as<int>(), n, V->head_pos.as<int>());
+        }
+        // one thread per voxel: the grid covers the upper bound (every point its own voxel), threads beyond the count on the device leave at once
+        // the bounding box of the centroids falls out of the centroid pass and travels with their count: the index build starts without a read-back of its own
+        unsigned* d_box = reinterpret_cast<unsigned*>(ctx->misc.as<char>() + 2048);      // (kBoxBanks x 128 bytes, zeroed with *bad above)
+        hipLaunchKernelGGL(k_vox_centroid64, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, S.key[S.cur].as<unsigned long long>(), S.pt[S.cur].as<float4>(), V->head_pos.as<int>(),
+                           n <= kScanFlagsMax ? 1 : 0, (const int*)(V->slots.as<int>() + n), n, V->out.as<float4>(), V->out_cnt.as<int>(), d_box);
+        HIPCHK(hipGetLastError());
+        rc = lili_readback_add(ctx, &V->n_out, V->slots.as<int>() + n, sizeof(int));
+        if (rc == LILI_OK) { rc = lili_readback_add(ctx, box_banks, d_box, sizeof(box_banks)); box_read = rc == LILI_OK; }
+    }
+    if (rc == LILI_OK) rc = lili_readback_add(ctx, &bad, d_bad, 4);
+    { const int rb = lili_readback_finish(ctx); if (rc != LILI_OK) return rc; if (rb != LILI_OK) return rb; }
+    if (box_read) {      // fold the banks; the minima travel inverted (k_vox_centroid64)
+        unsigned w[6] = {0, 0, 0, 0, 0, 0};
+        for (int b = 0; b < kBoxBanks; b++) for (int k = 0; k < 6; k++) w[k] = std::max(w[k], box_banks[b * 32 + k]);
+        for (int k = 0; k < 3; k++) { V->out_box[k] = ~w[k]; V->out_box[3 + k] = w[3 + k]; }
+    }
+    if (bad) { S.valid = false; return LILI_OK; }      // a point beyond the absolute key range: the box-relative rebuild handles it
+    // The guards of the full rebuild (voxel_sort: "no finite point", PCL's int32 voxel-index overflow) apply to the same ring content whichever
+    // way the map is produced: no centroid at all, or a box of centroids whose voxel count — with one voxel of slack per side and axis,
+    // a centroid may round across its voxel's face — would not fit int32, hands the commit to the rebuild, which decides exactly and reports the
+    // error a first commit would report.
+    bool guard = total > 0 && V->n_out == 0;
+    if (!guard && box_read) {
+        const float inv_leaf = 1.0f / leaf;
+        double cells = 1.0;
+        for (int k = 0; k < 3; k++) cells *= (double)((long long)std::floor(ord2f(V->out_box[3 + k]) * inv_leaf) - (long long)std::floor(ord2f(V->out_box[k]) * inv_leaf) + 3);
+        guard = !(cells <= 2147483647.0);
+    }
+    if (guard) { S.valid = false; return LILI_OK; }
+    V->incremental_commits++;
+    *done = true; *have_box = box_read;
+    return LILI_OK;
+}
+
+// The full rebuild: concatenate, sort, reduce; then the sorted ring for the following commits is seeded from the order the sort has produced.
+static int commit_rebuild(lili_ctx* ctx, lili_detail::VoxelBuffers* V, const std::vector<std::unique_ptr<lili_detail::Keyframe>>& ring, lili_detail::SortedRing& S, size_t total, float leaf,
+                          unsigned* d_bad) {
+    HIPCHK(V->concat.ensure(std::max<size_t>(total, 1) * 16));
+    // *surf_local_map += *recent_surf_keyframes[i] (L:1479-1483): ONE gather launch over a table of (source, first output position) per keyframe —
+    // fifty device-to-device copies of ~300 KB cost ~2 us each on the stream (0.12 ms per commit)
+    std::vector<lili_detail::ConcatSeg>& segs = V->seg_host;      // members, not locals: hipMemcpyAsync may read them after this call
+    std::vector<unsigned>& sseq = V->seg_seq_host;
+    segs.clear(); sseq.clear();
+    size_t off = 0;
+    for (const auto& k : ring) { if (k->n) { segs.push_back({k->pts.as<float4>(), (long long)off}); sseq.push_back(k->seq); } off += (size_t)k->n; }
+    if (!segs.empty()) {
+        HIPCHK(V->concat_tab.ensure(segs.size() * sizeof(lili_detail::ConcatSeg)));
+        HIPCHK(hipMemcpyAsync(V->concat_tab.p, segs.data(), segs.size() * sizeof(lili_detail::ConcatSeg), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_concat, dim3(nblocks((int64_t)total, 256)), dim3(256), 0, ctx->stream, V->concat_tab.as<lili_detail::ConcatSeg>(), (int)segs.size(),
+                           (long long)total, V->concat.as<float4>());
+        HIPCHK(hipGetLastError());
+    }
+    int rc = voxel_filter_device(ctx, V, V->concat.as<float4>(), (int)total, leaf, true);   // ds_filter_*_map.filter (L:1488-1492); the sorted ring below needs the order
+    if (rc != LILI_OK) return rc;
+    V->full_commits++;
+    // the sorted ring for the following steps: the order the sort has just produced, with absolute keys and the keyframe of every point
+    S.valid = false;
+    if (ctx->localmap_incremental && total > 0 && total < (1ull << 31) && !segs.empty()) {
+        HIPCHK(S.key[0].ensure(total * 8)); HIPCHK(S.pt[0].ensure(total * 16)); HIPCHK(S.seq[0].ensure(total * 4));
+        HIPCHK(V->seg_seq.ensure(sseq.size() * 4));
+        HIPCHK(hipMemcpyAsync(V->seg_seq.p, sseq.data(), sseq.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemsetAsync(d_bad, 0, 4, ctx->stream));
+        hipLaunchKernelGGL(k_sorted_gather, dim3(nblocks((int64_t)total, 256)), dim3(256), 0, ctx->stream, V->concat.as<float4>(), V->vals_a.as<int>(), (int)total, 1.0f / leaf, 0u,
+                           V->concat_tab.as<lili_detail::ConcatSeg>(), V->seg_seq.as<unsigned>(), (int)segs.size(), S.pt[0].as<float4>(), S.key[0].as<unsigned long long>(),
+                           S.seq[0].as<unsigned>(), d_bad);
+        HIPCHK(hipGetLastError());
+        unsigned bad = 0;
+        TRY(lili_readback_now(ctx, &bad, d_bad, 4));
+        S.cur = 0; S.n = (long long)total; S.leaf = leaf; S.valid = bad == 0;
+        S.members.clear();
+        for (const auto& k : ring) S.members.push_back({k->seq, k->n});
+    }
     return LILI_OK;
 }
 
@@ -1449,142 +1477,21 @@ int lili_localmap_commit(lili_ctx* ctx, int kind, float leaf, double max_sq_radi
     for (const auto& k : ring) total += (size_t)k->n;
     if (n_raw) *n_raw = (int64_t)total;
     unsigned* d_bad = reinterpret_cast<unsigned*>(ctx->misc.as<char>() + 256);      // (the bounding-box words of voxel_sort live in the first 24 bytes)
-    // ---- what changed since the sorted ring was built: keyframes popped at the front, keyframes pushed at the back
-    bool inc = ctx->localmap_incremental && S.valid && S.leaf == leaf && S.n > 0 && !ring.empty() && total < (1ull << 31);
-    DropSeqs drop{}; long long n_drop = 0;
-    std::vector<lili_detail::Keyframe*> add;
-    bool resuffix = false;      // lili_localmap_repose renumbered a suffix of the ring: one merge step of several keyframes (sorted_ring_resuffix)
-    unsigned keep_lo = 0, keep_hi = 0;
-    if (inc) {
-        size_t f = 0, m = 0;
-        while (f < S.members.size() && S.members[f].first != ring.front()->seq) f++;
-        if (f < S.members.size()) while (f + m < S.members.size() && m < ring.size() && S.members[f + m].first == ring[m]->seq) m++;
-        if (f < S.members.size() && f + m < S.members.size()) {
-            // members behind the kept ones that the ring no longer holds under their numbers: a re-posed suffix (its fresh numbers are above every member's)
-            if (m < ring.size() && ring[m]->seq > S.members.back().first && ring.size() - m <= kResuffixMaxAdd) {
-                resuffix = true;
-                keep_lo = S.members[f].first; keep_hi = S.members[f + m - 1].first;
-                for (size_t i = 0; i < S.members.size(); i++) if (i < f || i >= f + m) n_drop += S.members[i].second;
-                for (size_t i = m; i < ring.size(); i++) add.push_back(ring[i].get());
-                long long n_add = 0;
-                for (auto* k : add) n_add += k->n;
-                if (S.n - n_drop + n_add != (long long)total) inc = false;      // (the merge writes exactly the ring's points; anything else is not this case)
-            } else inc = false;
-        } else
-        if (f == S.members.size() || f > 4) inc = false;
-        else {
-            for (size_t i = 0; i < f; i++) { drop.s[i] = S.members[i].first; n_drop += S.members[i].second; }
-            drop.n = (int)f;
-            size_t m = 0;
-            while (f + m < S.members.size() && m < ring.size() && S.members[f + m].first == ring[m]->seq) m++;
-            if (f + m != S.members.size()) inc = false;                    // the ring is not "old members, then new keyframes"
-            for (size_t i = m; i < ring.size(); i++) add.push_back(ring[i].get());
-            if (add.size() > 2) inc = false;                               // several pending keyframes: the rebuild is cheaper than as many merge passes
-        }
+    // ---- the plan: what changed since the sorted ring was built — keyframes popped at the front, pushed at the back, a suffix renumbered by lili_localmap_repose
+    lili_detail::LocalmapPlan plan;
+    if (ctx->localmap_incremental && S.valid && S.leaf == leaf && S.n > 0 && total < (1ull << 31)) {
+        std::vector<lili_detail::SeqCount> now;
+        for (const auto& k : ring) now.push_back({k->seq, k->n});
+        plan = lili_detail::localmap_plan(S.members, now);
     }
-    bool have_box = false;
-    if (inc) {
-        // ---- incremental step(s): the merge, then the centroid pass over the sorted ring
-        { const int rl = lili_lazy_sources_clear_of(ctx, d_bad, kRankOff - 256 + (size_t)kVoxSmallMax * 4); if (rl != LILI_OK) return rl; }
-        HIPCHK(hipMemsetAsync(d_bad, 0, kRankOff - 256 + (size_t)kVoxSmallMax * 4, ctx->stream));      // *bad ... the rank words of k_rank_count: one fill
-        int rc = LILI_OK;
-        if (resuffix) rc = sorted_ring_resuffix(ctx, V, S, keep_lo, keep_hi, n_drop, add, leaf, d_bad);
-        else if (add.empty()) rc = sorted_ring_step(ctx, V, S, drop, n_drop, nullptr, leaf, d_bad);
-        for (size_t i = 0; i < add.size() && rc == LILI_OK && !resuffix; i++) {
-            if (i > 0) HIPCHK(hipMemsetAsync(ctx->misc.as<char>() + kRankOff, 0, (size_t)kVoxSmallMax * 4, ctx->stream));      // (a second pending keyframe counts from zero again)
-            rc = sorted_ring_step(ctx, V, S, i == 0 ? drop : DropSeqs{}, i == 0 ? n_drop : 0, add[i], leaf, d_bad);
-        }
+    bool done = false, have_box = false;
+    if (plan.merge) {
+        const int rc = commit_incremental(ctx, V, ring, S, plan, total, leaf, d_bad, &done, &have_box);
         if (rc != LILI_OK) { S.valid = false; return rc; }
-        S.members.clear();
-        for (const auto& k : ring) S.members.push_back({k->seq, k->n});
-        const long long n = S.n;
-        V->n_out = 0;
-        unsigned bad = 0;
-        static_assert(2048 + kBoxBanks * 128 <= 8192, "box banks of the commit inside the first 8 KB of ctx->misc");
-        unsigned box_banks[kBoxBanks * 32];
-        if (n > 0) {
-            HIPCHK(V->flags.ensure((size_t)n * 4)); HIPCHK(V->slots.ensure(((size_t)n + 1) * 4));
-            HIPCHK(V->out.ensure((size_t)n * 16)); HIPCHK(V->out_cnt.ensure((size_t)n * 4));
-            HIPCHK(V->head_pos.ensure(((size_t)n + 1) * 4));
-            if (n <= kScanFlagsMax) {      // heads, their scan and the compaction of the heads' positions in one launch
-                ScanFlagArgs A{}; A.a = S.key[S.cur].p; A.head_pos = V->head_pos.as<int>();
-                hipLaunchKernelGGL(k_scan_flags<kScanHead64>, dim3(nblocks(n, kScanTile)), dim3(kScanFlagThreads), 0, ctx->stream, A, (int)n, V->slots.as<int>());
-            } else {
-                hipLaunchKernelGGL(k_vox_heads64, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, S.key[S.cur].as<unsigned long long>(), n, V->flags.as<int>());
-                rc = exclusive_scan(ctx, V, V->flags.as<int>(), n, V->slots.as<int>());
-                if (rc != LILI_OK) return rc;
-                hipLaunchKernelGGL(k_vox_head_pos, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, V->flags.as<int>(), V->slots.as<int>(), n, V->head_pos.as<int>());
-            }
-            // one thread per voxel: the grid covers the upper bound (every point its own voxel), threads beyond the count on the device leave at once
-            // the bounding box of the centroids falls out of the centroid pass and travels with their count: the index build below starts without a read-back of its own
-            unsigned* d_box = reinterpret_cast<unsigned*>(ctx->misc.as<char>() + 2048);      // (kBoxBanks x 128 bytes, zeroed with *bad above)
-            hipLaunchKernelGGL(k_vox_centroid64, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, S.key[S.cur].as<unsigned long long>(), S.pt[S.cur].as<float4>(), V->head_pos.as<int>(),
-                               n <= kScanFlagsMax ? 1 : 0, (const int*)(V->slots.as<int>() + n), n, V->out.as<float4>(), V->out_cnt.as<int>(), d_box);
-            HIPCHK(hipGetLastError());
-            rc = lili_readback_add(ctx, &V->n_out, V->slots.as<int>() + n, sizeof(int));
-            if (rc == LILI_OK) { rc = lili_readback_add(ctx, box_banks, d_box, sizeof(box_banks)); have_box = rc == LILI_OK; }
-        }
-        if (rc == LILI_OK) rc = lili_readback_add(ctx, &bad, d_bad, 4);
-        { const int rb = lili_readback_finish(ctx); if (rc != LILI_OK) return rc; if (rb != LILI_OK) return rb; }
-        if (have_box) {      // fold the banks; the minima travel inverted (k_vox_centroid64)
-            unsigned w[6] = {0, 0, 0, 0, 0, 0};
-            for (int b = 0; b < kBoxBanks; b++) for (int k = 0; k < 6; k++) w[k] = std::max(w[k], box_banks[b * 32 + k]);
-            for (int k = 0; k < 3; k++) { V->out_box[k] = ~w[k]; V->out_box[3 + k] = w[3 + k]; }
-        }
-        if (bad) { S.valid = false; inc = false; have_box = false; }      // a point beyond the absolute key range: the box-relative rebuild below handles it
-        else {
-            // The guards of the full rebuild (voxel_sort: "no finite point", PCL's int32 voxel-index overflow) apply to the same ring content whichever
-            // way the map is produced: no centroid at all, or a box of centroids whose voxel count — with one voxel of slack per side and axis,
-            // a centroid may round across its voxel's face — would not fit int32, hands the commit to the rebuild, which decides exactly and reports the
-            // error a first commit would report.
-            bool guard = total > 0 && V->n_out == 0;
-            if (!guard && have_box) {
-                const float inv_leaf = 1.0f / leaf;
-                double cells = 1.0;
-                for (int k = 0; k < 3; k++) cells *= (double)((long long)std::floor(ord2f(V->out_box[3 + k]) * inv_leaf) - (long long)std::floor(ord2f(V->out_box[k]) * inv_leaf) + 3);
-                guard = !(cells <= 2147483647.0);
-            }
-            if (guard) { S.valid = false; inc = false; have_box = false; }
-            else V->incremental_commits++;
-        }
     }
-    if (!inc) {
-        // ---- full rebuild: concatenate, sort, reduce
-        HIPCHK(V->concat.ensure(std::max<size_t>(total, 1) * 16));
-        // *surf_local_map += *recent_surf_keyframes[i] (L:1479-1483): ONE gather launch over a table of (source, first output position) per keyframe —
-        // fifty device-to-device copies of ~300 KB cost ~2 us each on the stream (0.12 ms per commit)
-        std::vector<lili_detail::ConcatSeg>& segs = V->seg_host;      // members, not locals: hipMemcpyAsync may read them after this block
-        std::vector<unsigned>& sseq = V->seg_seq_host;
-        segs.clear(); sseq.clear();
-        size_t off = 0;
-        for (const auto& k : ring) { if (k->n) { segs.push_back({k->pts.as<float4>(), (long long)off}); sseq.push_back(k->seq); } off += (size_t)k->n; }
-        if (!segs.empty()) {
-            HIPCHK(V->concat_tab.ensure(segs.size() * sizeof(lili_detail::ConcatSeg)));
-            HIPCHK(hipMemcpyAsync(V->concat_tab.p, segs.data(), segs.size() * sizeof(lili_detail::ConcatSeg), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_concat, dim3(nblocks((int64_t)total, 256)), dim3(256), 0, ctx->stream, V->concat_tab.as<lili_detail::ConcatSeg>(), (int)segs.size(),
-                               (long long)total, V->concat.as<float4>());
-            HIPCHK(hipGetLastError());
-        }
-        int rc = voxel_filter_device(ctx, V, V->concat.as<float4>(), (int)total, leaf, true);   // ds_filter_*_map.filter (L:1488-1492); the sorted ring below needs the order
+    if (!done) {
+        const int rc = commit_rebuild(ctx, V, ring, S, total, leaf, d_bad);
         if (rc != LILI_OK) return rc;
-        V->full_commits++;
-        // the sorted ring for the following steps: the order the sort has just produced, with absolute keys and the keyframe of every point
-        S.valid = false;
-        if (ctx->localmap_incremental && total > 0 && total < (1ull << 31) && !segs.empty()) {
-            HIPCHK(S.key[0].ensure(total * 8)); HIPCHK(S.pt[0].ensure(total * 16)); HIPCHK(S.seq[0].ensure(total * 4));
-            HIPCHK(V->seg_seq.ensure(sseq.size() * 4));
-            HIPCHK(hipMemcpyAsync(V->seg_seq.p, sseq.data(), sseq.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(hipMemsetAsync(d_bad, 0, 4, ctx->stream));
-            hipLaunchKernelGGL(k_sorted_gather, dim3(nblocks((int64_t)total, 256)), dim3(256), 0, ctx->stream, V->concat.as<float4>(), V->vals_a.as<int>(), (int)total, 1.0f / leaf, 0u,
-                               V->concat_tab.as<lili_detail::ConcatSeg>(), V->seg_seq.as<unsigned>(), (int)segs.size(), S.pt[0].as<float4>(), S.key[0].as<unsigned long long>(),
-                               S.seq[0].as<unsigned>(), d_bad);
-            HIPCHK(hipGetLastError());
-            unsigned bad = 0;
-            TRY(lili_readback_now(ctx, &bad, d_bad, 4));
-            S.cur = 0; S.n = (long long)total; S.leaf = leaf; S.valid = bad == 0;
-            S.members.clear();
-            for (const auto& k : ring) S.members.push_back({k->seq, k->n});
-        }
     }
     if (n_map) *n_map = V->n_out;
     lili_cloud c{V->out.p, (size_t)V->n_out, 16, 12, LILI_MEM_DEVICE};
@@ -1606,16 +1513,10 @@ int lili_localmap_get(lili_ctx* ctx, lili_feature_out* out) {
     ARGCHK(out, "localmap_get: null out");
     HIPCHK(hipSetDevice(ctx->device));
     auto* V = vox_of(ctx);
-    out->count = (size_t)V->n_out;
-    const size_t k = std::min(out->count, out->capacity);
-    if (out->data && k) {
-        const size_t stride = out->stride ? out->stride : 16;
-        ARGCHK(stride >= 16, "localmap_get: stride must be >= 16");
-        const hipMemcpyKind kind = out->mem == LILI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (stride == 16) HIPCHK(hipMemcpyAsync(out->data, V->out.p, k * 16, kind, ctx->stream));
-        else HIPCHK(hipMemcpy2DAsync(out->data, stride, V->out.p, 16, 16, k, kind, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
+    size_t k = 0;
+    const int rc = copy_rows_enqueue(ctx, V->out.p, (size_t)V->n_out, out, "localmap_get", &k);
+    if (rc != LILI_OK) return rc;
+    if (k) HIPCHK(hipStreamSynchronize(ctx->stream));
     return LILI_OK;
 }
 

@@ -64,12 +64,17 @@ def _repose_c(ctx, mask, t, q, n=None):
     return ctx.lib.lili_localmap_repose(ctx.h, mask, t.shape[0] if n is None else n, t.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p))
 
 
+def _ring(rng, sizes):
+    """Keyframes of `sizes` surf points (a quarter as many edge points) and their poses."""
+    surf = [_cloud(rng, n, 0.3) for n in sizes]
+    edge = [_cloud(rng, max(n // 4, 1), 1.0) for n in sizes]
+    poses = [_pose(rng, k) for k in range(len(sizes))]
+    return surf, edge, poses
+
+
 def _ring_of_seven(rng, n_pts):
     """Seven keyframes pushed into a ring of six with a commit after each (the sorted ring is live, one keyframe has been popped)."""
-    surf = [_cloud(rng, n_pts, 0.3) for _ in range(7)]
-    edge = [_cloud(rng, max(n_pts // 4, 1), 1.0) for _ in range(7)]
-    poses = [_pose(rng, k) for k in range(7)]
-    return surf, edge, poses
+    return _ring(rng, [n_pts] * 7)
 
 
 def _feed(lms, surf, edge, poses, ks, commit=True):
@@ -79,34 +84,41 @@ def _feed(lms, surf, edge, poses, ks, commit=True):
             _commit_get(lms)
 
 
-CASES = {"none": [], "last": [5], "suffix3": [3, 4, 5], "all": [0, 1, 2, 3, 4, 5], "gaps": [1, 4]}
+# (ring width, changed ring positions, (incremental, full) commits of the two kinds together).  A changed set extends to the suffix from its first position; the suffix is
+# merged back in one step per kind while it holds at most 8 keyframes and a keyframe in front of it stays.
+CASES = {"none": (W6, [], (2, 0)), "last": (W6, [5], (2, 0)), "suffix3": (W6, [3, 4, 5], (2, 0)), "all": (W6, [0, 1, 2, 3, 4, 5], (0, 2)), "gaps": (W6, [1, 4], (2, 0)),
+         "suffix8of9": (9, list(range(1, 9)), (2, 0)), "all9": (9, list(range(9)), (0, 2)), "suffix9of10": (10, list(range(1, 10)), (0, 2)), "last8": (8, [7], (2, 0))}
+# surf points of the width + 1 keyframes pushed, where not the same for all: the sizes at which the merge switches routes (tests/test_voxel_gpu.py, _AT_THRESHOLD) —
+# 65 536 old entries and 8 192 re-posed ones (flags fused into the scan, counting sort), 65 537 and 8 193 (flags in memory, radix sort)
+SIZES = {"8x8192": [8192] * 9, "7x8192+8193": [8192] * 8 + [8193]}
 
 
-@pytest.mark.parametrize("n_pts", [1500, 12000])
-@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("case,n_pts", [(c, n) for n in (1500, 12000) for c in CASES if c != "last8"] + [("last8", s) for s in SIZES],
+                         ids=lambda v: str(v))
 def test_repose_equals_reset_and_repush(n_pts, case):
-    rng = np.random.default_rng(11 + n_pts)
-    surf, edge, poses = _ring_of_seven(rng, n_pts)
+    width, changed, commits = CASES[case]
+    sizes = SIZES[n_pts] if n_pts in SIZES else [n_pts] * (width + 1)
+    rng = np.random.default_rng(11 + sizes[0])
+    surf, edge, poses = _ring(rng, sizes)
+    ring = range(1, width + 1)                       # ring position j holds keyframe 1 + j
     ca, cb = L.Context(0), L.Context(0)
     try:
-        la = _lms(ca)
-        _feed(la, surf, edge, poses, range(7))
+        la = _lms(ca, width)
+        _feed(la, surf, edge, poses, range(width + 1))
         new = list(poses)
-        for j in CASES[case]:
-            new[1 + j] = _pose(rng, 1 + j)           # ring position j holds keyframe 1 + j
+        for j in changed:
+            new[1 + j] = _pose(rng, 1 + j)
         inc0, full0 = la[0].stats()
-        assert _repose_c(ca, L.MASK_SURF | L.MASK_EDGE, [new[k][0] for k in range(1, 7)], [new[k][1] for k in range(1, 7)]) == L.api.OK
+        assert _repose_c(ca, L.MASK_SURF | L.MASK_EDGE, [new[k][0] for k in ring], [new[k][1] for k in ring]) == L.api.OK
         ma = _commit_get(la)
         inc1, full1 = la[0].stats()
-        if case == "all":
-            assert (inc1 - inc0, full1 - full0) == (0, 2)      # nothing left to merge with: the full rebuild
-        else:
-            assert (inc1 - inc0, full1 - full0) == (2, 0)      # suffix ({1, 4} extends to 1 .. 5): one merge step per kind
-        lb = _lms(cb)
-        _feed(lb, surf, edge, new, range(1, 7), commit=False)
+        assert (inc1 - inc0, full1 - full0) == commits
+        cb.set_option("localmap_incremental", 0)
+        lb = _lms(cb, width)
+        _feed(lb, surf, edge, new, ring, commit=False)
         mb = _commit_get(lb)
         _same_maps(ma, mb)
-        assert ma[0][0] == sum(surf[k].shape[0] for k in range(1, 7))
+        assert ma[0][0] == sum(surf[k].shape[0] for k in ring)
     finally:
         ca.close(); cb.close()
 

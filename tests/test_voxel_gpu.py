@@ -155,50 +155,80 @@ def test_device_resident_pipeline_equals_host_round_trip(gpu_ctx, oracle):
     assert np.linalg.norm(t_d - tb) < 0.5 * np.linalg.norm(t0 - tb)
 
 
-def test_incremental_local_map_equals_full_rebuild(gpu_ctx):
-    """lili_localmap_commit keeps the ring sorted by voxel and merges ONE keyframe per step (the reference pops / pushes one
-    keyframe per step, L/src/BackendFusion.cpp:1407-1477).  A/B against the rebuild-every-time path (option localmap_incremental = 0): the
-    same map, bit for bit and in the same order, at every step — while the ring fills, in the pop / push steady state, with keyframes of
-    different sizes, an empty one, NaN points, two keyframes pushed between commits, a leaf change, and with both radix digit widths."""
+def _life_keyframes():
     rng = np.random.default_rng(5)
 
     def keyframe(k):
-        n = int(rng.integers(300, 4000)) if k != 6 else 0
+        n = int(rng.integers(300, 4000)) if k not in (6, 20) else 0
         pts = np.concatenate([rng.uniform(-12, 12, (n, 2)) + [0.9 * k, -0.4 * k], rng.uniform(-1.5, 2.5, (n, 1)), rng.uniform(0, 30, (n, 1))], 1).astype(np.float32)
         if n and k % 4 == 1:
             pts[rng.integers(0, n, 5), rng.integers(0, 3, 5)] = np.nan
         ang = 0.07 * k
         return pts, np.array([0.5 * k, 0.2 * k, 0.01 * k]), np.array([np.cos(ang / 2), 0.0, 0.0, np.sin(ang / 2)])
-    kfs = [keyframe(k) for k in range(18)]
-    # schedule: (keyframes pushed before this commit, leaf)
-    sched = [(1, 0.4)] * 3 + [(2, 0.4)] + [(1, 0.4)] * 6 + [(1, 0.2)] + [(1, 0.2)] * 2 + [(3, 0.2)]
+    return [keyframe(k) for k in range(23)]
+
+
+def _sized_keyframes(sizes):
+    rng = np.random.default_rng(sum(sizes))
+    return [(np.concatenate([rng.uniform(-12, 12, (n, 2)) + [0.9 * k, -0.4 * k], rng.uniform(-1.5, 2.5, (n, 1)), rng.uniform(0, 30, (n, 1))], 1).astype(np.float32),
+             np.array([0.5 * k, 0.2 * k, 0.01 * k]), np.array([np.cos(0.035 * k), 0.0, 0.0, np.sin(0.035 * k)])) for k, n in enumerate(sizes)]
+
+
+# A commit of the schedules: (keyframes pushed before it, leaf, ring width at those pushes, how the incremental context serves it: "I" one incremental commit, "F" a full rebuild).
+# The life of a ring of five: it fills; pop / push steady state (keyframe 6 is empty: its push pops a keyframe and adds no point); two keyframes pending; a leaf change;
+# three pending (rebuild); then the width changes — the ring grows again, a width lowered by one pops two at once, an empty keyframe's push pops one and adds
+# nothing (the API pops only in a push: the nearest there is to a commit of pops alone), and a width lowered by five pops six of seven, more than a merge drops.
+_LIFE = ([(1, 0.4, 5, "F")] + [(1, 0.4, 5, "I")] * 2 + [(2, 0.4, 5, "I")] + [(1, 0.4, 5, "I")] * 6 + [(1, 0.2, 5, "F")] + [(1, 0.2, 5, "I")] * 2 + [(3, 0.2, 5, "F")]
+         + [(1, 0.2, 7, "I")] * 2 + [(1, 0.2, 6, "I")] * 2 + [(1, 0.2, 7, "I"), (1, 0.2, 2, "F")])
+# The exact sizes at which the merge switches routes, the smallest shapes that take each: a ring of eight keyframes joined by a ninth (which pops the first).
+#   65 536 old entries and 8 192 new ones: the keep flags fused into their scan (<= 65 536), the new keyframe sorted by counting (<= 8 192 points, voxel_small on);
+#   65 537 old entries and 8 193 new ones: the flags in memory and the three-kernel scan, the radix sort.
+_AT_THRESHOLD = {"65536": [8192] * 9, "65537": [8192] * 7 + [8193] * 2}
+_THRESHOLD_SCHED = [(8, 0.4, 8, "F"), (1, 0.4, 8, "I")]
+
+
+@pytest.mark.parametrize("scenario,digits,small", [("life", 8, 1), ("life", 4, 1)] + [(s, d, v) for s in _AT_THRESHOLD for d in (8, 4) for v in (1, 0)])
+def test_incremental_local_map_equals_full_rebuild(gpu_ctx, scenario, digits, small):
+    """lili_localmap_commit keeps the ring sorted by voxel and merges the keyframes that came in (the reference pops / pushes one
+    keyframe per step, L/src/BackendFusion.cpp:1407-1477).  A/B against the rebuild-every-time path (option localmap_incremental = 0): the
+    same map, bit for bit and in the same order, at every commit of the schedule (_LIFE, _AT_THRESHOLD), with both radix digit widths and with and without the
+    counting sort — and every commit is served the way the schedule states: a merge that fell back to a rebuild would give the same map."""
+    if scenario == "life":
+        kfs, sched = _life_keyframes(), _LIFE
+    else:
+        kfs, sched = _sized_keyframes(_AT_THRESHOLD[scenario]), _THRESHOLD_SCHED
     runs = {}
     try:
-        for mode, digits in (("full", 8), ("incremental", 8), ("incremental4", 4)):
+        gpu_ctx.set_option("sort_digit_bits", digits)
+        gpu_ctx.set_option("voxel_small", small)
+        for mode in ("full", "incremental"):
             gpu_ctx.set_option("localmap_incremental", 0 if mode == "full" else 1)
-            gpu_ctx.set_option("sort_digit_bits", digits)
             lm = L.LocalMap(gpu_ctx, L.KIND_SURF, width=5, leaf=0.4, max_sq_radius=1.0)
-            inc0, full0 = lm.stats()
-            k, maps = 0, []
-            for n_push, leaf in sched:
+            k, maps, routes = 0, [], ""
+            for n_push, leaf, width, _ in sched:
+                lm.width = width
                 for _ in range(n_push):
                     lm.push(*kfs[k]); k += 1
                 lm.leaf = leaf
+                inc0, full0 = lm.stats()
                 n_raw, n_map = lm.commit()
-                maps.append((n_raw, lm.get(n_map + 1)))
-            inc1, full1 = lm.stats()
-            runs[mode] = (maps, inc1 - inc0, full1 - full0)
+                inc1, full1 = lm.stats()
+                routes += {(1, 0): "I", (0, 1): "F"}[(inc1 - inc0, full1 - full0)]
+                maps.append((n_raw, n_map, lm.get(n_map + 1)))
+            assert k == len(kfs)
+            runs[mode] = (maps, routes)
     finally:
         gpu_ctx.set_option("localmap_incremental", 1)
         gpu_ctx.set_option("sort_digit_bits", 8)
-    ref, n_inc_ref, n_full_ref = runs["full"]
-    assert n_inc_ref == 0 and n_full_ref == len(sched)
-    for mode in ("incremental", "incremental4"):
-        maps, n_inc, n_full = runs[mode]
-        assert n_inc >= 9 and n_full <= 5, (n_inc, n_full)              # rebuilds only: first commit, leaf change, three keyframes pending (+ nothing else)
-        for (ra, a), (rb, b) in zip(ref, maps):
-            assert ra == rb and a.shape == b.shape and a.shape[0] > 100
-            assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+        gpu_ctx.set_option("voxel_small", 1)
+    ref, ref_routes = runs["full"]
+    maps, routes = runs["incremental"]
+    print(scenario, digits, small, routes)
+    assert ref_routes == "F" * len(sched)
+    assert routes == "".join(s[3] for s in sched)
+    for (ra, na, a), (rb, nb, b) in zip(ref, maps):
+        assert ra == rb and na == nb and a.shape == b.shape and a.shape[0] == na > 100
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def test_index_behind_an_incremental_commit_equals_a_plain_map_set(gpu_ctx):
