@@ -174,6 +174,27 @@ int lili_map_info(lili_ctx* ctx, int kind, int64_t* n_points, int64_t* n_cells, 
  * down-sampled at L:1488-1511 — leaf sizes down to centimetres make a gate-sized cell hold hundreds of points). */
 int lili_map_density(lili_ctx* ctx, int kind, double* mean_occupancy, double* fine_cell_edge, double* fine_sq_radius);
 
+/* The current index itself, for tests that check it cell by cell (read-only, blocking; nothing in the context changes).  `which`: 0 = the gate-sized index,
+ * 1 = the fine index of a dense map. */
+typedef struct lili_map_index_info {
+    int32_t nx, ny, nz;                       /* cells per axis */
+    int32_t bx0, by0, bz0, bnx, bny, bnz;     /* the box of cells that has super cells */
+    int32_t n_points, reach;
+    int32_t has_aux;                          /* the index carries the sorted auxiliary floats */
+    int32_t has_super;                        /* the index has the super-row copy */
+    int32_t narrow;                           /* built from the 8-bit count table */
+    int32_t narrow_overflows, scan_fallbacks; /* the context's counters: builds repeated with 32-bit counters / with the three-kernel scan */
+    double ox, oy, oz, inv_cell, cell;        /* origin, 1 / edge, 1 / (1 / edge) as the kernels use them */
+    int64_t n_cells;                          /* nx * ny * nz */
+    int64_t n_super;                          /* entries of the super-row copy (0 without one) */
+} lili_map_index_info;
+/* Fills `info` and copies, into every buffer that is not NULL: cell_start (n_cells + 1 words), base (n_points rows of four floats: x, y, z, original index as
+ * int bits), aux (n_points floats, if has_aux), cell_start9 (bnx * bny * bnz + 1 words, if has_super), super / super_aux (n_super rows / floats, if has_super /
+ * and has_aux).  Capacities count words, rows and floats.  LILI_E_STATE: no map set, an empty map, or no such index; LILI_E_ARG: NULL ctx or info, bad kind or
+ * `which`, or a buffer too small for its array — then `info` holds the sizes and NO buffer is written. */
+int lili_map_debug_index(lili_ctx* ctx, int kind, int which, lili_map_index_info* info, int32_t* cell_start, size_t cell_start_cap, float* base, size_t base_cap,
+                         float* aux, size_t aux_cap, int32_t* cell_start9, size_t cell_start9_cap, float* super, size_t super_cap, float* super_aux, size_t super_aux_cap);
+
 /* Performance hint (no reference counterpart: pcl::KdTreeFLANN indexes the whole cloud it is given, L/src/BackendFusion.cpp:839-840): a local
  * map may cover far more ground than one scan reaches.  lili_map_set stores, next to the cell-sorted points, a "super-row" copy in which the
  * 27-cell neighbourhood of a query is one contiguous run (option "super_rows", 9x the points); with a focus, that copy is built only for the

@@ -28,6 +28,16 @@ class Cloud(C.Structure):
     _fields_ = [("data", C.c_void_p), ("n", C.c_size_t), ("stride", C.c_size_t), ("aux_offset", C.c_int), ("mem", C.c_int)]
 
 
+class MapIndexInfo(C.Structure):
+    """lili_map_index_info: the scalars of an index as lili_map_debug_index reports them."""
+    _fields_ = [(k, C.c_int32) for k in ("nx", "ny", "nz", "bx0", "by0", "bz0", "bnx", "bny", "bnz", "n_points", "reach", "has_aux", "has_super", "narrow",
+                                         "narrow_overflows", "scan_fallbacks")] + \
+               [(k, C.c_double) for k in ("ox", "oy", "oz", "inv_cell", "cell")] + [("n_cells", C.c_int64), ("n_super", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FeatureOut(C.Structure):
     _fields_ = [("data", C.c_void_p), ("capacity", C.c_size_t), ("stride", C.c_size_t), ("mem", C.c_int), ("count", C.c_size_t)]
 
@@ -316,6 +326,7 @@ _SIGS = {
     "lili_voxel_filter_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lili_map_set": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Cloud), C.c_double]),
     "lili_map_density": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lili_map_debug_index": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(MapIndexInfo)] + [C.c_void_p, C.c_size_t] * 6),
     "lili_s2m_linearize_window": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_s2m_associate_window": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_map_set_begin": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Cloud), C.c_double]),
@@ -623,6 +634,24 @@ class ScanToMapMatcher:
         a, b, c = C.c_double(), C.c_double(), C.c_double()
         self.ctx._chk(self.lib.lili_map_density(self.ctx.h, kind, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def map_debug_index(self, kind, which=0):
+        """The index itself (lili_map_debug_index; which: 0 = gate-sized, 1 = fine): dict(info=MapIndexInfo, cell_start, base (n, 4) float32 whose column 3
+        holds the original index as int bits, aux or None, cell_start9 / super / super_aux or None).  Two calls: the sizes, then the arrays."""
+        info = MapIndexInfo()
+        self.ctx._chk(self.lib.lili_map_debug_index(self.ctx.h, kind, which, C.byref(info), *([None, 0] * 6)))
+        n, n9, nc9 = info.n_points, info.n_super, info.bnx * info.bny * info.bnz
+        cs = np.zeros(info.n_cells + 1, np.int32)
+        base = np.zeros((n, 4), np.float32)
+        aux = np.zeros(n, np.float32) if info.has_aux else None
+        cs9 = np.zeros(nc9 + 1, np.int32) if info.has_super else None
+        sup = np.zeros((n9, 4), np.float32) if info.has_super else None
+        sup_aux = np.zeros(n9, np.float32) if info.has_super and info.has_aux else None
+        args = []
+        for a, cap in ((cs, cs.size), (base, n), (aux, n), (cs9, nc9 + 1), (sup, n9), (sup_aux, n9)):
+            args += [_ptr(a), cap if a is not None else 0]
+        self.ctx._chk(self.lib.lili_map_debug_index(self.ctx.h, kind, which, C.byref(info), *args))
+        return dict(info=info, cell_start=cs, base=base, aux=aux, cell_start9=cs9, super=sup, super_aux=sup_aux)
 
     # -- queries --------------------------------------------------------------------------------
     def set_queries(self, slot, kind, cloud):

@@ -26,6 +26,7 @@ struct MapIndex {
     GridView view{};
     DevBuf sorted, aux_sorted, cell_start, cell_tmp, pt_cell /* rank of every point inside its cell (int), between the count and the scatter pass */, block_sums, cell_start9, row9;
     bool has_aux = false;
+    bool narrow = false;         // the gate-sized index came out of the 8-bit count table (lili_map_debug_index reports it)
     // density adaptation: a second index with cells sized from the measured density (dense maps only) — the ONLY one the association of a dense map searches (lili_s2m_dense.hip)
     bool has_fine = false;
     GridView fview{};
@@ -36,7 +37,7 @@ struct MapIndex {
         std::swap(valid, o.valid); std::swap(n, o.n); std::swap(n_cells, o.n_cells); std::swap(cell, o.cell); std::swap(view, o.view);
         sorted.swap(o.sorted); aux_sorted.swap(o.aux_sorted); cell_start.swap(o.cell_start); cell_tmp.swap(o.cell_tmp); pt_cell.swap(o.pt_cell);
         block_sums.swap(o.block_sums); cell_start9.swap(o.cell_start9); row9.swap(o.row9);
-        std::swap(has_aux, o.has_aux); std::swap(has_fine, o.has_fine); std::swap(fview, o.fview);
+        std::swap(has_aux, o.has_aux); std::swap(narrow, o.narrow); std::swap(has_fine, o.has_fine); std::swap(fview, o.fview);
         sorted_f.swap(o.sorted_f); aux_sorted_f.swap(o.aux_sorted_f); cell_start_f.swap(o.cell_start_f); cell_start9_f.swap(o.cell_start9_f);
         std::swap(fbound, o.fbound); std::swap(fine_cell, o.fine_cell); std::swap(mean_occupancy, o.mean_occupancy);
     }

@@ -1,4 +1,4 @@
-// C-ABI of liblili_hip.so, map index part (include/lili_hip.h: lili_map_set*, lili_map_focus, lili_map_info, lili_map_density, lili_map_build_stats).
+// C-ABI of liblili_hip.so, map index part (include/lili_hip.h: lili_map_set*, lili_map_focus, lili_map_info, lili_map_density, lili_map_build_stats, lili_map_debug_index).
 // Host code only; the kernels live in lili_s2m.hip.  Replaces pcl::KdTreeFLANN::setInputCloud at L/src/LidarOdometry.cpp:490, L/src/BackendFusion.cpp:1258-1259.
 #include "lili_launch.h"
 #include "lili_device_cloud.h"
@@ -242,6 +242,7 @@ static int map_set_impl(lili_ctx* ctx, int kind, const lili_cloud* cloud, double
         decode_box(mm);
     }
     m.has_fine = false; m.fview = GridView{}; m.fbound = 0.f; m.fine_cell = 0; m.mean_occupancy = 0;
+    m.narrow = narrow;
     constexpr size_t kRankBanks = 64;                       // k_cell_count: one bank per 128 bytes
     unsigned long long* d_rank = reinterpret_cast<unsigned long long*>(ctx->misc.as<char>() + kMiscDensityOff);
     unsigned scan_err = 0;
@@ -444,6 +445,56 @@ int lili_map_density(lili_ctx* ctx, int kind, double* mean_occupancy, double* fi
     if (mean_occupancy) *mean_occupancy = m.mean_occupancy;
     if (fine_cell_edge) *fine_cell_edge = m.has_fine ? m.fine_cell : 0.0;
     if (fine_sq_radius) *fine_sq_radius = m.has_fine ? (double)m.fbound : 0.0;
+    return LILI_OK;
+}
+
+// The index as it lies in device memory, for the tests that check it cell by cell (tests/test_map_index_gpu.py).  Read-only and synchronous, as lili_extract_rot_debug;
+// the 8 slack entries behind the sorted array are nobody's business and stay here.
+int lili_map_debug_index(lili_ctx* ctx, int kind, int which, lili_map_index_info* info, int32_t* cell_start, size_t cell_start_cap, float* base, size_t base_cap,
+                         float* aux, size_t aux_cap, int32_t* cell_start9, size_t cell_start9_cap, float* super, size_t super_cap, float* super_aux, size_t super_aux_cap) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(kind == LILI_KIND_SURF || kind == LILI_KIND_EDGE, "map_debug_index: bad kind");
+    ARGCHK(which == 0 || which == 1, "map_debug_index: which must be 0 (gate-sized index) or 1 (fine index)");
+    ARGCHK(info, "map_debug_index: null info");
+    const MapIndex& m = ctx->map[kind];
+    if (!m.valid) return ctx->fail(LILI_E_STATE, "map_debug_index: no map set");
+    if (m.n == 0) return ctx->fail(LILI_E_STATE, "map_debug_index: the map is empty and has no index");
+    if (which == 1 && !m.has_fine) return ctx->fail(LILI_E_STATE, "map_debug_index: this map has no fine index");
+    HIPCHK(hipSetDevice(ctx->device));
+    const GridView& g = which ? m.fview : m.view;
+    const size_t n = (size_t)g.n_points, nc = (size_t)g.nx * (size_t)g.ny * (size_t)g.nz, nc9 = (size_t)g.bnx * (size_t)g.bny * (size_t)g.bnz;
+    int end9 = g.n_points;
+    if (g.cell_start9) {          // the copy's length is the last word of its own start array
+        HIPCHK(hipMemcpyAsync(&end9, g.cell_start9 + nc9, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    const size_t n9 = (size_t)(end9 - g.n_points);
+    lili_map_index_info I{};
+    I.nx = g.nx; I.ny = g.ny; I.nz = g.nz;
+    I.bx0 = g.bx0; I.by0 = g.by0; I.bz0 = g.bz0; I.bnx = g.bnx; I.bny = g.bny; I.bnz = g.bnz;
+    I.n_points = g.n_points; I.reach = g.reach;
+    I.has_aux = g.aux ? 1 : 0; I.has_super = g.cell_start9 ? 1 : 0; I.narrow = which == 0 && m.narrow ? 1 : 0;
+    I.narrow_overflows = ctx->narrow_overflows; I.scan_fallbacks = ctx->scan_fallbacks;
+    I.ox = g.ox; I.oy = g.oy; I.oz = g.oz; I.inv_cell = g.inv_cell; I.cell = g.cell;
+    I.n_cells = (int64_t)nc; I.n_super = (int64_t)n9;
+    *info = I;
+    // nothing is copied unless everything asked for fits
+    ARGCHK(!cell_start || cell_start_cap >= nc + 1, "map_debug_index: cell_start buffer too small (info holds the sizes)");
+    ARGCHK(!base || base_cap >= n, "map_debug_index: base buffer too small (info holds the sizes)");
+    ARGCHK(!(aux && g.aux) || aux_cap >= n, "map_debug_index: aux buffer too small (info holds the sizes)");
+    ARGCHK(!(cell_start9 && g.cell_start9) || cell_start9_cap >= nc9 + 1, "map_debug_index: cell_start9 buffer too small (info holds the sizes)");
+    ARGCHK(!(super && g.cell_start9) || super_cap >= n9, "map_debug_index: super buffer too small (info holds the sizes)");
+    ARGCHK(!(super_aux && g.cell_start9 && g.aux) || super_aux_cap >= n9, "map_debug_index: super_aux buffer too small (info holds the sizes)");
+    auto dl = [&](void* dst, const void* src, size_t bytes) -> hipError_t { return (dst && src && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
+    HIPCHK(dl(cell_start, g.cell_start, (nc + 1) * sizeof(int)));
+    HIPCHK(dl(base, g.pts, n * sizeof(float4)));
+    HIPCHK(dl(aux, g.aux, n * sizeof(float)));
+    if (g.cell_start9) {
+        HIPCHK(dl(cell_start9, g.cell_start9, (nc9 + 1) * sizeof(int)));
+        HIPCHK(dl(super, g.pts + n, n9 * sizeof(float4)));
+        HIPCHK(dl(super_aux, g.aux ? g.aux + n : nullptr, n9 * sizeof(float)));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return LILI_OK;
 }
 

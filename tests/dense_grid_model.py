@@ -70,6 +70,21 @@ def build_grid(mn, mx, cell, max_cells=MAX_CELLS):
     return Grid(float(mn[0]), float(mn[1]), float(mn[2]), inv, 1.0 / inv, cell, int(nx), int(ny), int(nz))
 
 
+def focus_box(g, focus=None, radius=0.0):
+    """build_grid's b0 / b1 arithmetic: (bx0, by0, bz0, bnx, bny, bnz), the box of cells that gets super cells — the whole grid, or with lili_map_focus the
+    cells within `radius` (+ two cells) of `focus`, clamped into the grid.  The division is by the edge after coarsening, as in the library."""
+    dims = (g.nx, g.ny, g.nz)
+    b0, b1 = [0, 0, 0], [d - 1 for d in dims]
+    if focus is not None and radius > 0:
+        mn = (g.ox, g.oy, g.oz)
+        for k in range(3):
+            lo = (float(focus[k]) - float(radius) - mn[k]) / g.cell_used - 2.0
+            hi = (float(focus[k]) + float(radius) - mn[k]) / g.cell_used + 2.0
+            b0[k] = int(min(max(math.floor(lo), 0.0), float(dims[k] - 1)))
+            b1[k] = int(min(max(math.floor(hi), float(b0[k])), float(dims[k] - 1)))
+    return (b0[0], b0[1], b0[2], b1[0] - b0[0] + 1, b1[1] - b0[1] + 1, b1[2] - b0[2] + 1)
+
+
 def uncoarsened_fine_cell(occ, cell):
     fc = cell * math.sqrt(3.0 / occ)
     return min(max(fc, cell / 16.0), cell / 1.5)

@@ -51,7 +51,8 @@ def test_every_struct_mirror_matches_the_header(tmp_path):
     import subprocess
     pairs = [("lili_cloud", L.api.Cloud), ("lili_feature_out", L.api.FeatureOut), ("lili_rot_params", L.api.RotParams), ("lili_livox_params", L.api.LivoxParams),
              ("lili_frontend_options", L.api.FrontendOptions), ("lili_frontend_result", L.api.FrontendResult), ("lili_lm_options", L.api.LmOptions),
-             ("lili_lm_iteration", L.api.LmIteration), ("lili_lm_summary", L.api.LmSummary), ("lili_s2m_params", L.api.S2MParams), ("lili_imu_state", L.api.ImuState)]
+             ("lili_lm_iteration", L.api.LmIteration), ("lili_lm_summary", L.api.LmSummary), ("lili_s2m_params", L.api.S2MParams), ("lili_imu_state", L.api.ImuState),
+             ("lili_map_index_info", L.api.MapIndexInfo)]
     lines, expect = [], []
     for cname, T in pairs:
         lines.append(f'printf("%zu\\n", sizeof({cname}));')

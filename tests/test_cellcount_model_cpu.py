@@ -2,7 +2,8 @@
 round 4") — a wave-by-wave Python restatement of its bookkeeping: four 8-bit counters per 32-bit word, lanes of one WORD RUN sharing one atomic whose
 return value carries the four old counts, a lane's rank = the old count of its cell + the lanes of its run before it in the same cell, the overflow
 flag for a cell that would pass 255 — and of the row-wise single-pass scan that turns the byte table into `cell_start` (k_scan_lookback_t<true>).
-It tests the ARGUMENT, not the GPU (that is tests/test_map_build_gpu.py): whatever order the waves' atomics are served in, the ranks of every
+It tests the ARGUMENT, not the GPU (that is tests/test_map_index_gpu.py, which reads the device's index back and compares it cell by cell with
+tests/map_index_model.py on the designed clouds of tests/map_index_cases.py; tests/test_map_build_gpu.py judges the index through its searches): whatever order the waves' atomics are served in, the ranks of every
 cell are a permutation of 0 .. count-1, the table equals the plain histogram, and the scatter positions `cell_start[cell] + rank` are a
 permutation of 0 .. n-1 that keeps every point inside its cell's range.  Replaces kd_tree->setInputCloud, L/src/BackendFusion.cpp:839-840."""
 import numpy as np
