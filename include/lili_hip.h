@@ -1233,6 +1233,67 @@ int lili_global_map_stats(lili_ctx* ctx, int32_t* incremental, int32_t* rebuilds
 /* device memory of the global map: the table and the work buffers of a batch (bytes) */
 int lili_global_map_info(lili_ctx* ctx, int64_t* table_bytes, int64_t* work_bytes);
 
+/* ---- place recognition: polar descriptors over the archive (lili_place.hip) -------------------------------
+ * Appearance-based loop candidates in the manner of Scan Context (Kim & Kim, IROS 2018): per keyframe an n_sector x n_ring image
+ * of maximum heights, compared column-wise under every circular shift.  Not in the reference, whose detectLoopClosure searches
+ * keyframe POSITIONS (lili_loop_detect) and so finds a loop only while the drift is below its radius.
+ * The descriptor, exactly (all f32, every operation rounded on its own).  A point with a non-finite coordinate is skipped;
+ * r2 = x x + y y; a point with r2 > max_radius max_radius is skipped.  Ring = number of k in 1 .. n_ring - 1 with r2 > b_k b_k,
+ * b_k = (max_radius (float)k) / (float)n_ring (a point on a boundary belongs to the inner ring).  Quadrant q: x >= 0, y >= 0 -> 0;
+ * x < 0, y >= 0 -> 1; x < 0, y < 0 -> 2; otherwise 3.  (u, v) = the point turned back by q quarter turns: (x, y), (y, -x), (-x, -y),
+ * (-y, x).  j = number of m in 1 .. n_sector / 4 - 1 with v C_m >= u S_m, C_m / S_m = cos / sin(2 pi m / n_sector) computed in f64 and
+ * rounded to f32.  Sector = q n_sector / 4 + j.  Cell (sector, ring) = the maximum of z + lidar_height over its points, 0 without
+ * one; stored sector-major: desc[sector * n_ring + ring].  A maximum does not depend on order: the descriptor is the same bytes
+ * on every run and for every split of the work (integer atomics on an order-preserving word; no floating-point atomics).
+ * Descriptors live in a buffer of their own that grows by half; it is NOT counted against "archive_max_mb". */
+typedef struct lili_place_params {
+    int32_t n_ring;        /* 1 .. 32, default 20 */
+    int32_t n_sector;      /* a multiple of 4 in 4 .. 64, default 60 */
+    float max_radius;      /* default 80 */
+    float lidar_height;    /* default 2 */
+    int32_t kind;          /* LILI_ARCHIVE_*: the cloud described, default LILI_ARCHIVE_FULL */
+    int32_t reserved_;
+} lili_place_params;
+typedef struct lili_place_query {
+    int32_t id;            /* an archived, described keyframe, or -1: `desc` */
+    int32_t max_id;        /* candidates c <= max_id only */
+    const float* desc;     /* id = -1: n_sector * n_ring floats on the host (the parameters of the last lili_place_update) */
+    double time;           /* the query's time */
+    double min_time_gap;   /* candidates with |time_c - time| > min_time_gap only (time_c: the archive's) */
+} lili_place_query;
+typedef struct lili_place_match { int32_t id, shift; double distance; } lili_place_match;
+void lili_place_default_params(lili_place_params* p);
+/* the tables the kernels decide by, host code without a context: ring_r2[k] = b_k b_k for k < n_ring, sec_cos[m] / sec_sin[m] = C_m /
+ * S_m for m < n_sector / 4, zeros behind them.  LILI_E_ARG on parameters outside the ranges above. */
+int lili_place_layout(const lili_place_params* params, float ring_r2[32], float sec_cos[16], float sec_sin[16]);
+/* Describes every archived keyframe that has no descriptor yet from its cloud of params->kind (absent: all zeros) — one launch
+ * over a table of the keyframes' rows, however many there are.  A descriptor depends on the cloud alone: lili_archive_set_poses
+ * and _set_extrinsic invalidate nothing; lili_archive_reset drops all descriptors; other `params` than the last call's rebuild all.
+ * n_built (optional): descriptors built by this call.  Blocking. */
+int lili_place_update(lili_ctx* ctx, const lili_place_params* params, int* n_built);
+/* the descriptor of any cloud (host, page-locked host or device rows, any stride; lili_archive_push's checks) into
+ * desc[n_sector * n_ring] on the host: bit for bit what lili_place_update builds from the same rows.  Blocking. */
+int lili_place_describe(lili_ctx* ctx, const lili_cloud* cloud, const lili_place_params* params, float* desc);
+/* keyframe id's descriptor into desc[n_sector * n_ring] on the host.  Blocking. */
+int lili_place_get(lili_ctx* ctx, int id, float* desc);
+/* described keyframes, the parameters they were built with (the defaults before the first update), device bytes of the store */
+int lili_place_info(lili_ctx* ctx, int* n_described, lili_place_params* params, int64_t* bytes);
+/* The k best candidates of each of n_q queries (1 <= n_q <= 64, 1 <= k <= 16) among ALL described keyframes at ALL shifts: no
+ * pre-selection, the exact minimum.  Candidate c is eligible iff c <= max_id, |time_c - time| > min_time_gap, c is not the query
+ * itself and c has a descriptor.  With unit columns a_j = A_j / |A_j| (f64, from the f32 cells),
+ *   d(s) = 1 - mean over { j : |A_j| > 0 and |B_(j+s) mod n_sector| > 0 } of a_j . b_(j+s),     +inf when the set is empty;
+ * a pair's distance = min_s d(s), its shift = the smallest s that attains it.  Column j of the query matches column j + s of the
+ * candidate: the candidate's scan is the query's turned by +s sectors about the LiDAR z axis.  matches[q * k + i], i < n_found[q]
+ * <= k, ascend by (distance, id); pairs at +inf are never reported.  A pair's distance and shift depend on the two descriptors
+ * alone — not on the candidate's place in the archive nor on the rest of the batch — and are the same bytes on every run.
+ * Without a described keyframe every n_found is 0.  One synchronisation, one read-back.  Blocking. */
+int lili_place_search(lili_ctx* ctx, const lili_place_query* queries, int n_q, int k, lili_place_match* matches, int* n_found);
+/* The ICP's initial guess from a match, host code without a context: poses are LiDAR map poses (p then q w x y z; the archive's
+ * (q_po q_bl, q_po t_bl + t_po)), T = M_dst Rz(2 pi shift / n_sector) M_src^-1 row-major — the transform that puts the source
+ * keyframe on the candidate with the matched yaw, as lili_icp_align's `guess` wants it.  LILI_E_ARG: a null pointer, a non-finite
+ * input, a zero quaternion, n_sector < 1. */
+int lili_place_guess(const double pose_src[7], const double pose_dst[7], int shift, int n_sector, double T[16]);
+
 #ifdef __cplusplus
 }
 #endif

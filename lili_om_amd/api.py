@@ -250,6 +250,18 @@ class IcpResult(C.Structure):
                 ("fitness", C.c_double), ("stage_us", C.c_double * 4), ("it", IcpIteration * ICP_MAX_LOG)]
 
 
+class PlaceParams(C.Structure):
+    _fields_ = [("n_ring", C.c_int32), ("n_sector", C.c_int32), ("max_radius", C.c_float), ("lidar_height", C.c_float), ("kind", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class PlaceQuery(C.Structure):
+    _fields_ = [("id", C.c_int32), ("max_id", C.c_int32), ("desc", C.c_void_p), ("time", C.c_double), ("min_time_gap", C.c_double)]
+
+
+class PlaceMatch(C.Structure):
+    _fields_ = [("id", C.c_int32), ("shift", C.c_int32), ("distance", C.c_double)]
+
+
 def make_params(variant="rot", **kw):
     """Matcher parameters of the reference configs:
     L/config/config_fr_iosb.yaml ('livox'), R/config/config_fr_iosb.yaml ('rot'),
@@ -434,6 +446,14 @@ _SIGS = {
     "lili_global_map_get": (C.c_int, [C.c_void_p, C.POINTER(FeatureOut), C.c_void_p]),
     "lili_global_map_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "lili_global_map_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lili_place_default_params": (None, [C.POINTER(PlaceParams)]),
+    "lili_place_layout": (C.c_int, [C.POINTER(PlaceParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lili_place_update": (C.c_int, [C.c_void_p, C.POINTER(PlaceParams), C.POINTER(C.c_int)]),
+    "lili_place_describe": (C.c_int, [C.c_void_p, C.POINTER(Cloud), C.POINTER(PlaceParams), C.c_void_p]),
+    "lili_place_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "lili_place_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(PlaceParams), C.POINTER(C.c_int64)]),
+    "lili_place_search": (C.c_int, [C.c_void_p, C.POINTER(PlaceQuery), C.c_int, C.c_int, C.POINTER(PlaceMatch), C.POINTER(C.c_int)]),
+    "lili_place_guess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "lili_window_sqrt_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lili_window_evaluate": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_window_solve": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.POINTER(LmOptions), C.c_void_p, C.POINTER(LmSummary)]),

@@ -40,6 +40,7 @@ class KeyframeArchive:
     def set_extrinsic(self, t_bl, q_bl):
         t, q = _f64(t_bl, 3), _f64(q_bl, 4)
         self.ctx._chk(self.lib.lili_archive_set_extrinsic(self.ctx.h, _ptr(t), _ptr(q)))
+        self.t_bl, self.q_bl = t.copy(), q.copy()
 
     def push(self, edge, surf, full, time, t_po, q_po):
         """Appends a keyframe; returns its id."""

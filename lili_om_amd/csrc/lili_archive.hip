@@ -216,6 +216,7 @@ struct ArchiveState : ExtState {
     std::vector<lili_cloud> view_tmp;
     std::vector<double> pose_tmp;
     GlobalMap gm;
+    unsigned long long resets = 0;      // lili_archive_reset calls so far (lili_place.hip: descriptors of an earlier archive are dropped)
     void free_slabs() { for (auto& s : slabs) if (s.p) (void)hipFree(s.p); slabs.clear(); bytes = 0; }
     ~ArchiveState() override { free_slabs(); }
 };
@@ -408,6 +409,16 @@ int fold_batch(lili_ctx* ctx, GlobalMap& G, int total) {
 
 }  // namespace
 
+int lili_archive_size(lili_ctx* ctx) { return (int)archive_of(ctx)->kf.size(); }
+unsigned long long lili_archive_resets(lili_ctx* ctx) { return archive_of(ctx)->resets; }
+lili_archive_rows lili_archive_rows_of(lili_ctx* ctx, int id, int kind) {
+    const ArcKeyframe& kf = archive_of(ctx)->kf[id];
+    lili_archive_rows r;
+    r.p = kf.c[kind].p; r.n = kf.c[kind].n; r.time = kf.time;
+    return r;
+}
+int lili_archive_check_cloud(lili_ctx* ctx, const lili_cloud* c) { return check_cloud(ctx, c); }
+
 extern "C" {
 
 int lili_archive_reset(lili_ctx* ctx) {
@@ -419,6 +430,7 @@ int lili_archive_reset(lili_ctx* ctx) {
     A->kf.clear();
     for (auto& n : A->n_points) n = 0;
     A->gm.clear_table();      // (the extrinsic, the options and the statistics stay)
+    A->resets++;
     return LILI_OK;
 }
 

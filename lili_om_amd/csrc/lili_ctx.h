@@ -193,7 +193,7 @@ struct lili_ctx {
     int rot_atan = 2;            // ROT extractor: 2 = glibc fdlibm float atan / atan2 (the reference build's bits), 1 = f64 functions rounded to f32
     int n_simd = 0;              // SIMDs of the device (CUs x 4)
     // What a module keeps per context, created by its first call (ext_of) and deleted with the context
-    enum { kExtRot, kExtLivox, kExtVoxel /* voxel filter / local-map ring */, kExtLoop, kExtArchive /* keyframe archive and global map */, kExtImu, kExtLocal /* local pose graph */, kExtPoseGraph /* global pose graph */, kExtKeyframe /* keyframe hand-over: the three published clouds */, kExtCount };
+    enum { kExtRot, kExtLivox, kExtVoxel /* voxel filter / local-map ring */, kExtLoop, kExtArchive /* keyframe archive and global map */, kExtImu, kExtLocal /* local pose graph */, kExtPoseGraph /* global pose graph */, kExtKeyframe /* keyframe hand-over: the three published clouds */, kExtPlace /* place recognition: descriptors of the archive */, kExtCount };
     std::unique_ptr<ExtState> ext[kExtCount];
     bool imu_time = false;                   // option "imu_time": events around k_imu_preintegrate (lili_imu_kernel_ms)
     int archive_max_mb = 0;                  // bound on the archive's slab pool (0: none)

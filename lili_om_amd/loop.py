@@ -138,6 +138,28 @@ class LoopClosure:
                 return None
         return pos.shape[0] - self.slide_window_width, his
 
+    def detect_appearance(self, place, t_now=None, *, max_distance):
+        """(latest_idx, his_idx, shift, distance) or None: the candidate by APPEARANCE (place: a PlaceRecognition on this closure's archive) — the best
+        match of the latest keyframe's descriptor among the keyframes whose time differs from t_now (None: the latest keyframe's) by more than the variant's
+        threshold (global_lc_time_thres / lc_time_thres), at every yaw shift, wherever the odometry believes them to be.  latest = n - slide_window_width as
+        in detect; ROT: none within 0.2 s of the last loop.  A match counts when distance <= max_distance.  The paper (Kim & Kim, IROS 2018) reports 0.13
+        for its data; that is the paper's value, not one measured with this project's sensors: there is no default."""
+        if self.archive is None or place.archive is not self.archive:
+            raise ValueError("detect_appearance needs the archive the PlaceRecognition describes")
+        latest = len(self.archive) - self.slide_window_width
+        if latest < 0:
+            return None
+        place.update()
+        t_now = self.archive.pose(latest)[2] if t_now is None else float(t_now)
+        if self.variant == "rot" and abs(self.time_last_loop - t_now) < 0.2:
+            return None
+        thr = self.global_lc_time_thres if self.variant == "livox" else self.lc_time_thres
+        found = place.search([latest], k=1, min_time_gap=thr, max_id=latest, times=t_now)[0]
+        if not found or not found[0][2] <= max_distance:
+            return None
+        his, shift, dist = found[0]
+        return latest, his, shift, dist
+
     def source_keyframes(self, latest_idx):
         """L: the latest keyframe; ROT: latest, latest - 1, ..., latest - 5 (in that order, R:2267)."""
         ks = [latest_idx] if self.variant == "livox" else [latest_idx - j for j in range(6)]
@@ -186,23 +208,39 @@ class LoopClosure:
         self.last = _result_dict(r)
         return self.last
 
-    def perform(self, positions, times, select_pose, t_now, ts_po=None, qs_po=None, edge_frames=None, surf_frames=None):
+    def perform(self, positions, times, select_pose, t_now, ts_po=None, qs_po=None, edge_frames=None, surf_frames=None, detector="position", place=None,
+                max_distance=None):
         """performLoopClosure up to the BetweenFactor: None, or (latest_idx, his_idx, pose_from, pose_to, between, noise_score) with poses as (t (3,), q (4,) wxyz):
         pose_from = the latest keyframe's pose corrected by the ICP transform, pose_to = the candidate's, between = pose_from^-1 pose_to; noise_score = the
         fitness (the variances of the reference's Diagonal noise model).  The caller adds BetweenFactor(latest, his, between, noise) and updates iSAM2.
-        With an archive: the keyframes' clouds, poses and (where None) positions and times are the archive's."""
+        With an archive: the keyframes' clouds, poses and (where None) positions and times are the archive's.
+        detector="appearance" (archive only; place, max_distance as detect_appearance takes them; positions and select_pose are not read): the candidate is
+        detect_appearance's, the same submaps are assembled, and the ICP starts from place.guess — the source put on the candidate with the matched yaw —
+        instead of the identity."""
+        if detector not in ("position", "appearance"):
+            raise ValueError("detector must be 'position' or 'appearance'")
         if self.archive is not None and edge_frames is None:
             ts_po, qs_po, a_tm = self.archive.poses()
             positions = ts_po if positions is None else positions
             times = a_tm if times is None else times
-        det = self.detect(positions, times, select_pose, t_now)
-        if det is None:
-            return None
-        latest, his = det
+        guess = None
+        if detector == "appearance":
+            if place is None or max_distance is None or edge_frames is not None:
+                raise ValueError("detector='appearance' needs an archive, place and max_distance")
+            det = self.detect_appearance(place, t_now, max_distance=max_distance)
+            if det is None:
+                return None
+            latest, his = det[:2]
+            guess = place.guess(latest, his, det[2])
+        else:
+            det = self.detect(positions, times, select_pose, t_now)
+            if det is None:
+                return None
+            latest, his = det
         ts_po = np.asarray(ts_po, np.float64).reshape(-1, 3)
         qs_po = np.asarray(qs_po, np.float64).reshape(-1, 4)
         self.assemble(latest, his, ts_po, qs_po, edge_frames, surf_frames)
-        res = self.align()
+        res = self.align(guess)
         if not res["converged"] or res["fitness"] > self.lc_icp_thres:
             return None
         T = res["transform"]
