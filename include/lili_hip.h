@@ -1269,7 +1269,8 @@ int lili_place_layout(const lili_place_params* params, float ring_r2[32], float 
 /* Describes every archived keyframe that has no descriptor yet from its cloud of params->kind (absent: all zeros) — one launch
  * over a table of the keyframes' rows, however many there are.  A descriptor depends on the cloud alone: lili_archive_set_poses
  * and _set_extrinsic invalidate nothing; lili_archive_reset drops all descriptors; other `params` than the last call's rebuild all.
- * n_built (optional): descriptors built by this call.  Blocking. */
+ * (In a submap setting — lili_place_set_submap below — a descriptor also depends on its window's poses: see the rebuild rule there.)
+ * n_built (optional): descriptors built (or rebuilt) by this call.  Blocking. */
 int lili_place_update(lili_ctx* ctx, const lili_place_params* params, int* n_built);
 /* the descriptor of any cloud (host, page-locked host or device rows, any stride; lili_archive_push's checks) into
  * desc[n_sector * n_ring] on the host: bit for bit what lili_place_update builds from the same rows.  Blocking. */
@@ -1293,6 +1294,49 @@ int lili_place_search(lili_ctx* ctx, const lili_place_query* queries, int n_q, i
  * keyframe on the candidate with the matched yaw, as lili_icp_align's `guess` wants it.  LILI_E_ARG: a null pointer, a non-finite
  * input, a zero quaternion, n_sector < 1. */
 int lili_place_guess(const double pose_src[7], const double pose_dst[7], int shift, int n_sector, double T[16]);
+
+/* ---- levelled submap descriptors (a narrow-field LiDAR sees a wedge: one keyframe does not describe a place) -------------
+ * With a setting other than all zeros a keyframe's descriptor is the image of the rows of a WINDOW of keyframes, placed in
+ * the frame F_i of the keyframe it belongs to.  All zeros (the default): today's descriptor of the keyframe's own rows, byte for byte.
+ * Window of keyframe i in an archive of n: max(0, i - back) .. min(n - 1, i + fwd), by index (not by time).
+ * Frame F_i from the keyframe's LiDAR map pose (q_i, t_i) (the archive's (q_po q_bl, q_po t_bl + t_po)), host f64 (lili_place_frame):
+ *   level = 0: F_i = (q_i, t_i) as they are.
+ *   level = 1: origin t_i, z = the map's z (the back end's gravity is (0, 0, 9.805) in the map frame), x = the horizontal projection of
+ *     the LiDAR's x axis.  (w, x, y, z) = q_i / sqrt(((w w + x x) + y y) + z z); R00 = 1 - 2 (y y + z z); R10 = 2 (x y + w z);
+ *     h = sqrt(R00 R00 + R10 R10); h < 1e-9 (x axis vertical): c = 1, s = 0; otherwise c = R00 / h clamped to [-1, 1], s = R10 / h;
+ *     F_i.q = (sqrt((1 + c) / 2), 0, 0, sqrt((1 - c) / 2)), the last negated iff s < 0.  At c = -1 (a half turn) s is +-0 and the
+ *     comparison s < 0 is false for both zeros: the frame is (0, 0, 0, +1).
+ * Placement of member k (lili_place_relative, host f64): f = F_i.q / |F_i.q|, f' = its conjugate, p = q_k / |q_k|,
+ *   q_rel = f' (x) p (Hamilton product, the sums left to right), t_rel = f' . (t_k - t_i) as v + w (2 u x v) + u x (2 u x v).
+ *   On the device a row becomes (float)(q_rel . (double)p + t_rel) — the ONE transform every kernel places a keyframe with — and
+ *   is then binned exactly as above.  With level = 0 the centre keyframe's own rows are read untransformed (its segment carries
+ *   an identity flag): back = fwd = level = 0 is today's descriptor.  A maximum is order-free: the bytes do not depend on the run,
+ *   on the split into tiles or on the batches of an update.
+ * Rebuild rule: a descriptor remembers its BUILD KEY, the list of (member id, identity flag, q_rel, t_rel) it was built from.
+ *   lili_place_update builds every descriptor without a key and rebuilds every descriptor whose key, recomputed from the archive
+ *   as it is now, differs in any byte: a new successor inside a window, lili_archive_set_poses, lili_archive_set_extrinsic.  In the
+ *   all-zero setting the key never changes and nothing is rebuilt.  n_built counts built plus rebuilt descriptors. */
+#define LILI_PLACE_TILE_ROWS 2048      /* rows of a descriptor's concatenation one workgroup bins into its LDS image */
+typedef struct lili_place_submap {
+    int32_t back;          /* 0 .. 64 predecessors */
+    int32_t fwd;           /* 0 .. 16 successors */
+    int32_t level;         /* 0 or 1 */
+    int32_t reserved_;
+} lili_place_submap;
+/* another setting than the current one drops every descriptor; NULL = all zeros.  LILI_E_ARG (state untouched) outside the ranges. */
+int lili_place_set_submap(lili_ctx* ctx, const lili_place_submap* s);
+int lili_place_get_submap(lili_ctx* ctx, lili_place_submap* s);
+/* the window keyframe id's descriptor was built from (id .. id in the all-zero setting).  LILI_E_ARG: id has no descriptor. */
+int lili_place_window(lili_ctx* ctx, int id, int* first, int* last);
+/* F of a LiDAR map pose (p then q w x y z), host code without a context.  LILI_E_ARG: null, non-finite, zero quaternion, level not 0 / 1. */
+int lili_place_frame(const double pose[7], int level, double frame[7]);
+/* (q_rel, t_rel) of a member at `pose` in `frame`, host code without a context.  LILI_E_ARG: null, non-finite, a zero quaternion. */
+int lili_place_relative(const double frame[7], const double pose[7], double q_rel[4], double t_rel[3]);
+/* The descriptor of n clouds (1 <= n <= 81; host, page-locked or device rows, any stride; lili_archive_push's checks) placed at
+ * q_rel[4 i ..], t_rel[3 i ..] into desc[n_sector * n_ring] on the host — the kernel and the bytes of the archive path.  A cloud whose
+ * q_rel is four zeros is read untransformed (the identity flag); q_rel = t_rel = NULL: every cloud is.  Blocking. */
+int lili_place_describe_submap(lili_ctx* ctx, const lili_cloud* clouds, int n, const double* q_rel, const double* t_rel, const lili_place_params* params,
+                               float* desc);
 
 #ifdef __cplusplus
 }

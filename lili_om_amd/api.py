@@ -262,6 +262,13 @@ class PlaceMatch(C.Structure):
     _fields_ = [("id", C.c_int32), ("shift", C.c_int32), ("distance", C.c_double)]
 
 
+class PlaceSubmap(C.Structure):
+    _fields_ = [("back", C.c_int32), ("fwd", C.c_int32), ("level", C.c_int32), ("reserved_", C.c_int32)]
+
+
+PLACE_TILE_ROWS = 2048      # LILI_PLACE_TILE_ROWS: rows of a descriptor's concatenation one workgroup bins
+
+
 def make_params(variant="rot", **kw):
     """Matcher parameters of the reference configs:
     L/config/config_fr_iosb.yaml ('livox'), R/config/config_fr_iosb.yaml ('rot'),
@@ -454,6 +461,12 @@ _SIGS = {
     "lili_place_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(PlaceParams), C.POINTER(C.c_int64)]),
     "lili_place_search": (C.c_int, [C.c_void_p, C.POINTER(PlaceQuery), C.c_int, C.c_int, C.POINTER(PlaceMatch), C.POINTER(C.c_int)]),
     "lili_place_guess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "lili_place_set_submap": (C.c_int, [C.c_void_p, C.POINTER(PlaceSubmap)]),
+    "lili_place_get_submap": (C.c_int, [C.c_void_p, C.POINTER(PlaceSubmap)]),
+    "lili_place_window": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lili_place_frame": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "lili_place_relative": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lili_place_describe_submap": (C.c_int, [C.c_void_p, C.POINTER(Cloud), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PlaceParams), C.c_void_p]),
     "lili_window_sqrt_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lili_window_evaluate": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_window_solve": (C.c_int, [C.c_void_p, C.POINTER(WindowProblem), C.POINTER(S2MParams), C.POINTER(LmOptions), C.c_void_p, C.POINTER(LmSummary)]),

@@ -418,6 +418,11 @@ lili_archive_rows lili_archive_rows_of(lili_ctx* ctx, int id, int kind) {
     return r;
 }
 int lili_archive_check_cloud(lili_ctx* ctx, const lili_cloud* c) { return check_cloud(ctx, c); }
+void lili_archive_map_pose_of(lili_ctx* ctx, int id, double pose[7]) {
+    const ArcKeyframe& kf = archive_of(ctx)->kf[id];
+    for (int k = 0; k < 3; k++) pose[k] = kf.t_map[k];
+    for (int k = 0; k < 4; k++) pose[3 + k] = kf.q_map[k];
+}
 
 extern "C" {
 

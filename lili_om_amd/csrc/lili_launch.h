@@ -71,6 +71,7 @@ int lili_archive_size(lili_ctx* ctx);
 unsigned long long lili_archive_resets(lili_ctx* ctx);
 lili_archive_rows lili_archive_rows_of(lili_ctx* ctx, int id, int kind);
 int lili_archive_check_cloud(lili_ctx* ctx, const lili_cloud* c);
+void lili_archive_map_pose_of(lili_ctx* ctx, int id, double pose[7]);      // keyframe id's LiDAR map pose (p, then q w x y z) as the archive holds it now
 // lili_match.hip -> lili_window.hip (the lidar blocks of the joint window)
 int lili_match_window_records(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const double* t, const double* q, double* d_gram);
 int lili_match_lm_args(lili_ctx* ctx, int slot, int kind_mask, const lili_s2m_params* params, const lili_lm_options* options, int max_blocks, lili::LmArgs* out);

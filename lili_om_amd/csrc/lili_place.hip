@@ -4,6 +4,8 @@
 //   * the descriptor: ring and sector of a point by comparisons against tables the host computes once (no arctangent, no square root: lili_place_layout), the cell's
 //     maximum by integer atomics on the ordered-uint form of the height.  A maximum does not depend on order: the descriptor is the same bytes on every run and for
 //     every split of the work.  One launch over a segment table describes any number of keyframes (k_place_cells), one more turns the words into floats;
+//   * levelled submap descriptors (lili_place_set_submap): a keyframe described by the rows of a window of keyframes placed in its levelled frame — one workgroup bins
+//     a tile of rows into an image in LDS and merges it once (k_place_cells_sub); a descriptor is rebuilt when its build key (members and relative placements) changes;
 //   * the search: a wave holds one candidate, a lane one sector's column as a unit vector in f64; the query's unit columns lie ring-major in LDS, so that at shift s lane l
 //     reads column l - s without a bank conflict.  The per-lane cosines of sixteen shifts are parked in LDS and summed per shift in a fixed order (four lanes a shift,
 //     sixteen terms each, then the four parts): a pair's distance and shift depend on the two descriptors alone, never on where the candidate lies or what else is in
@@ -12,6 +14,7 @@
 // No floating-point atomics anywhere.
 #include "lili_launch.h"
 #include "lili_device_cloud.h"
+#include "lili_device_math.h"
 
 #include <climits>
 
@@ -47,6 +50,9 @@ __device__ __forceinline__ int place_cell(const PlaceLayout& L, float x, float y
 
 // a run of rows (any stride; x, y, z at a row's start) whose points go into image `slot`; `first`: the run's position in the concatenation
 struct PlSeg { const unsigned char* src; long long first; int stride, slot; };
+// the same with the placement k_place_cells_sub applies first: transform_point by (q, t), or none where `ident` is set (the row is read as it is).  A type of its
+// own: k_place_cells keeps PlSeg's 24-byte stride and with it its address arithmetic, instruction for instruction.
+struct PlSubSeg : PlSeg { dq q; d3 t; int ident, pad_; };
 
 // every point of the concatenation offers its height to its cell: atomicMax on the ordered-uint form (0 = no point yet: below every float's word).  The plain read in
 // front of the atomic may be stale, but a cell's word only grows: a stale word costs an atomic, never a maximum.
@@ -62,6 +68,70 @@ __global__ void k_place_cells(const PlSeg* __restrict__ segs, int n_seg, long lo
     unsigned* a = img + (size_t)s.slot * cells + cell;
     if (*reinterpret_cast<volatile unsigned*>(a) < w) atomicMax(a, w);
 }
+
+// Submap descriptors: a descriptor's concatenation holds the rows of a whole window of keyframes, about twenty times a keyframe's, and k_place_cells' global atomics
+// slow down as the rows per image grow.  Here ONE WORKGROUP bins one TILE — at most kPlTileRows rows of ONE descriptor's concatenation — into an image
+// in LDS and offers the global image only the tile's non-zero cells, once.  The tile table comes from the host with the tile's first segment in it: a thread's rows
+// ascend, so it walks the segment table forward from there and never bisects.  A row is placed by transform_point (lili_device_math.h) unless its segment carries the
+// identity flag; place_cell and the ordered-uint maximum are k_place_cells'.  The maximum is order-free: tiles, batches and runs cannot change a byte.
+constexpr int kPlTileRows = LILI_PLACE_TILE_ROWS;
+struct PlTile { long long first; int n, seg, slot, pad_; };      // rows [first, first + n) of the concatenation, the segment that holds `first`, the image
+
+__global__ __launch_bounds__(256) void k_place_cells_sub(const PlSubSeg* __restrict__ segs, int n_seg, const PlTile* __restrict__ tiles, PlaceLayout L, unsigned* img, int cells) {
+    __shared__ unsigned s_img[kPlMaxSector * kPlMaxRing];
+    const int tid = threadIdx.x;
+    for (int c = tid; c < cells; c += 256) s_img[c] = 0u;
+    const PlTile tile = tiles[blockIdx.x];
+    __syncthreads();
+    int si = tile.seg;
+    PlSubSeg s = segs[si];
+    for (int k = tid; k < tile.n; k += 256) {
+        const long long i = tile.first + k;
+        if (si + 1 < n_seg && segs[si + 1].first <= i) {      // (the tile ends inside its descriptor: the walk stays among that descriptor's segments)
+            do si++; while (si + 1 < n_seg && segs[si + 1].first <= i);
+            s = segs[si];
+        }
+        const float* p = reinterpret_cast<const float*>(s.src + (size_t)(i - s.first) * (size_t)s.stride);
+        float x = p[0], y = p[1], z = p[2];
+        if (!s.ident) {
+            const float4 r = transform_point(make_float4(x, y, z, 0.f), s.q, s.t);
+            x = r.x; y = r.y; z = r.z;
+        }
+        float val;
+        const int cell = place_cell(L, x, y, z, &val);
+        if (cell < 0) continue;
+        const unsigned w = f2ord(val);
+        if (*reinterpret_cast<volatile unsigned*>(&s_img[cell]) < w) atomicMax(&s_img[cell], w);
+    }
+    __syncthreads();
+    unsigned* out = img + (size_t)tile.slot * cells;
+    for (int c = tid; c < cells; c += 256) {
+        const unsigned w = s_img[c];
+        if (w && *reinterpret_cast<volatile unsigned*>(out + c) < w) atomicMax(out + c, w);
+    }
+}
+
+#ifdef LILI_PLACE_PROBE_GLOBAL
+// tools/place_time.py's probe build only (never the shipped library): the same segment table in k_place_cells' form — a thread a row, the segment by bisection, the
+// maximum straight into the global image — to time the LDS form against.  The same bytes: the maximum is order-free.
+__global__ void k_place_cells_sub_global(const PlSubSeg* __restrict__ segs, int n_seg, long long total, PlaceLayout L, unsigned* img, int cells) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const PlSubSeg s = segs[seg_of(segs, n_seg, i)];
+    const float* p = reinterpret_cast<const float*>(s.src + (size_t)(i - s.first) * (size_t)s.stride);
+    float x = p[0], y = p[1], z = p[2];
+    if (!s.ident) {
+        const float4 r = transform_point(make_float4(x, y, z, 0.f), s.q, s.t);
+        x = r.x; y = r.y; z = r.z;
+    }
+    float val;
+    const int cell = place_cell(L, x, y, z, &val);
+    if (cell < 0) return;
+    const unsigned w = f2ord(val);
+    unsigned* a = img + (size_t)s.slot * cells + cell;
+    if (*reinterpret_cast<volatile unsigned*>(a) < w) atomicMax(a, w);
+}
+#endif
 
 // ordered-uint words -> the descriptor's floats, in place (no point: 0)
 __global__ void k_place_finish(unsigned* img, long long n) {
@@ -223,6 +293,9 @@ namespace {
 using lili::PlaceLayout;
 using lili::PlQuery;
 using lili::PlSeg;
+using lili::PlSubSeg;
+using lili::PlTile;
+using lili::kPlTileRows;
 using lili::kPlMaxK;
 using lili::kPlMaxQuery;
 using lili::kPlMaxRing;
@@ -251,18 +324,66 @@ PlaceLayout layout_of(const lili_place_params& p) {
     return L;
 }
 
+constexpr int kPlMaxBack = 64, kPlMaxFwd = 16, kPlMaxMembers = kPlMaxBack + kPlMaxFwd + 1;
+constexpr long long kPlBatchRows = 1ll << 26;      // rows of one launch of a submap update (a batch holds whole descriptors, one at least)
+
+// one member of a descriptor's build key: 64 bytes without padding, compared bytewise
+struct PlKey { int id, ident; double q[4], t[3]; };
+static_assert(sizeof(PlKey) == 64, "PlKey is compared bytewise: no padding");
+
+bool submap_ok(const lili_place_submap& s) { return s.back >= 0 && s.back <= kPlMaxBack && s.fwd >= 0 && s.fwd <= kPlMaxFwd && (s.level == 0 || s.level == 1); }
+bool submap_plain(const lili_place_submap& s) { return s.back == 0 && s.fwd == 0 && s.level == 0; }
+
+double quat_norm(const double q[4]) { return std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]); }
+
+// the frame of a LiDAR map pose (include/lili_hip.h "levelled submap descriptors"), statement by statement as the header words it
+void frame_of(const double pose[7], int level, double frame[7]) {
+    for (int k = 0; k < 7; k++) frame[k] = pose[k];
+    if (!level) return;
+    const double n = quat_norm(pose + 3);
+    const double w = pose[3] / n, x = pose[4] / n, y = pose[5] / n, z = pose[6] / n;
+    const double r00 = 1.0 - 2.0 * (y * y + z * z), r10 = 2.0 * (x * y + w * z);
+    const double h = std::sqrt(r00 * r00 + r10 * r10);
+    double c = 1.0, s = 0.0;
+    if (!(h < 1e-9)) { c = r00 / h; s = r10 / h; }
+    c = c > 1.0 ? 1.0 : c < -1.0 ? -1.0 : c;
+    const double qz = std::sqrt((1.0 - c) / 2.0);
+    frame[3] = std::sqrt((1.0 + c) / 2.0); frame[4] = 0.0; frame[5] = 0.0; frame[6] = s < 0.0 ? -qz : qz;
+}
+
+// (q_rel, t_rel) of a member at `pose` in `frame`: f' (x) p and f' . (t_k - t_i), f' the unit frame quaternion's conjugate
+void relative_of(const double frame[7], const double pose[7], double q_rel[4], double t_rel[3]) {
+    const double nf = quat_norm(frame + 3), np = quat_norm(pose + 3);
+    const double a[4] = {frame[3] / nf, -(frame[4] / nf), -(frame[5] / nf), -(frame[6] / nf)};
+    const double b[4] = {pose[3] / np, pose[4] / np, pose[5] / np, pose[6] / np};
+    q_rel[0] = ((a[0] * b[0] - a[1] * b[1]) - a[2] * b[2]) - a[3] * b[3];
+    q_rel[1] = ((a[0] * b[1] + a[1] * b[0]) + a[2] * b[3]) - a[3] * b[2];
+    q_rel[2] = ((a[0] * b[2] + a[2] * b[0]) + a[3] * b[1]) - a[1] * b[3];
+    q_rel[3] = ((a[0] * b[3] + a[3] * b[0]) + a[1] * b[2]) - a[2] * b[1];
+    const double v[3] = {pose[0] - frame[0], pose[1] - frame[1], pose[2] - frame[2]}, u[3] = {a[1], a[2], a[3]};
+    double uv[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+    for (int k = 0; k < 3; k++) uv[k] = uv[k] + uv[k];
+    const double cr[3] = {u[1] * uv[2] - u[2] * uv[1], u[2] * uv[0] - u[0] * uv[2], u[0] * uv[1] - u[1] * uv[0]};
+    for (int k = 0; k < 3; k++) t_rel[k] = (v[k] + a[0] * uv[k]) + cr[k];
+}
+
+bool pose_ok(const double pose[7]) { return pose && finite_n(pose, 7) && quat_norm(pose + 3) > 0.0 && std::isfinite(quat_norm(pose + 3)); }
+
 struct PlaceState : ExtState {
     bool has_params = false;
     lili_place_params params{};
+    lili_place_submap sub{};            // all zeros: a keyframe's own rows (the plain path)
+    std::vector<std::vector<PlKey>> keys;      // submap setting: the build key of every described keyframe
+    DevBuf tiles;
     unsigned long long resets = 0;      // the archive's reset count the descriptors belong to
     int n_desc = 0, cap = 0;            // keyframes 0 .. n_desc - 1 are described; room for `cap`
     DevBuf desc, times;                 // [cap][n_sector * n_ring] f32, [cap] f64
     DevBuf one;                         // lili_place_describe: the image of a caller's cloud (staged rows of a pageable one: the context's staging)
     DevBuf segs, qs, ext, qcols, qmask, dist, shift, out;
-    PinBuf h_in, h_out;
+    PinBuf h_in, h_out, h_tab;          // h_tab: the segment and tile tables of a k_place_cells_sub launch
     size_t cells() const { return (size_t)params.n_sector * params.n_ring; }
     size_t bytes() const { return desc.cap + times.cap; }
-    void drop() { n_desc = 0; }
+    void drop() { n_desc = 0; keys.clear(); }
 };
 
 PlaceState* place_of(lili_ctx* ctx) {
@@ -304,6 +425,122 @@ int build_images(lili_ctx* ctx, PlaceState* P, const lili_place_params& prm, con
     const long long words = (long long)n_img * (long long)cells;
     hipLaunchKernelGGL(lili::k_place_finish, dim3(nblocks(words, 256)), dim3(256), 0, ctx->stream, img, words);
     HIPCHK(hipGetLastError());
+    return LILI_OK;
+}
+
+// the tile table of a segment table (segments of one image adjacent, no empty segment): every image's rows cut into runs of at most kPlTileRows, none across two images
+void tiles_of(const std::vector<PlSubSeg>& segs, long long total, std::vector<PlTile>& tiles) {
+    tiles.clear();
+    for (size_t i = 0; i < segs.size();) {
+        size_t j = i;
+        while (j + 1 < segs.size() && segs[j + 1].slot == segs[i].slot) j++;
+        const long long end = j + 1 < segs.size() ? segs[j + 1].first : total;
+        size_t si = i;
+        for (long long at = segs[i].first; at < end; at += kPlTileRows) {
+            while (si < j && segs[si + 1].first <= at) si++;
+            PlTile t{};
+            t.first = at; t.n = (int)std::min<long long>(kPlTileRows, end - at); t.seg = (int)si; t.slot = segs[i].slot;
+            tiles.push_back(t);
+        }
+        i = j + 1;
+    }
+}
+
+// build_images through k_place_cells_sub: the segment and tile tables go up together through P->h_tab (nothing of an earlier call may still be in flight from it).  Enqueued only.
+int build_images_sub(lili_ctx* ctx, PlaceState* P, const lili_place_params& prm, const std::vector<PlSubSeg>& segs, long long total, unsigned* img, int n_img) {
+    const size_t cells = (size_t)prm.n_sector * prm.n_ring;
+    HIPCHK(hipMemsetAsync(img, 0, (size_t)n_img * cells * 4, ctx->stream));
+    if (total > 0) {
+        std::vector<PlTile> tiles;
+        tiles_of(segs, total, tiles);
+        const size_t sb = segs.size() * sizeof(PlSubSeg), tb = tiles.size() * sizeof(PlTile);
+        HIPCHK(P->segs.ensure(sb)); HIPCHK(P->tiles.ensure(tb)); HIPCHK(P->h_tab.ensure(sb + tb));
+        std::memcpy(P->h_tab.as<unsigned char>(), segs.data(), sb);
+        std::memcpy(P->h_tab.as<unsigned char>() + sb, tiles.data(), tb);
+        HIPCHK(hipMemcpyAsync(P->segs.p, P->h_tab.as<unsigned char>(), sb, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(P->tiles.p, P->h_tab.as<unsigned char>() + sb, tb, hipMemcpyHostToDevice, ctx->stream));
+#ifdef LILI_PLACE_PROBE_GLOBAL
+        hipLaunchKernelGGL(lili::k_place_cells_sub_global, dim3(nblocks(total, 256)), dim3(256), 0, ctx->stream, (const PlSubSeg*)P->segs.as<PlSubSeg>(), (int)segs.size(), total,
+                           layout_of(prm), img, (int)cells);
+#else
+        hipLaunchKernelGGL(lili::k_place_cells_sub, dim3((unsigned)tiles.size()), dim3(256), 0, ctx->stream, (const PlSubSeg*)P->segs.as<PlSubSeg>(), (int)segs.size(),
+                           (const PlTile*)P->tiles.as<PlTile>(), layout_of(prm), img, (int)cells);
+#endif
+    }
+    const long long words = (long long)n_img * (long long)cells;
+    hipLaunchKernelGGL(lili::k_place_finish, dim3(nblocks(words, 256)), dim3(256), 0, ctx->stream, img, words);
+    HIPCHK(hipGetLastError());
+    return LILI_OK;
+}
+
+// keyframe i's build key from the archive as it is now
+void key_of(lili_ctx* ctx, const lili_place_submap& sub, int i, int n, std::vector<PlKey>& key) {
+    const int first = std::max(0, i - sub.back), last = std::min(n - 1, i + sub.fwd);
+    double pose_i[7], frame[7], pose_k[7];
+    lili_archive_map_pose_of(ctx, i, pose_i);
+    frame_of(pose_i, sub.level, frame);
+    key.clear();
+    for (int k = first; k <= last; k++) {
+        PlKey e{};
+        e.id = k;
+        if (k == i && !sub.level) e.ident = 1;      // the centre's own rows in its own frame: read as they are
+        else { lili_archive_map_pose_of(ctx, k, pose_k); relative_of(frame, pose_k, e.q, e.t); }
+        key.push_back(e);
+    }
+}
+
+// the submap setting's lili_place_update: every descriptor whose key is missing or no longer the archive's is built, run by run of adjacent keyframes, in batches of
+// whole descriptors of about kPlBatchRows rows
+int update_submap(lili_ctx* ctx, PlaceState* P, int* n_built) {
+    const int n = lili_archive_size(ctx);
+    if (n_built) *n_built = 0;
+    if (n <= 0) return LILI_OK;
+    for (int i = 0; i < n; i++) {
+        double pose[7];
+        lili_archive_map_pose_of(ctx, i, pose);
+        ARGCHK(pose_ok(pose), "place_update: a keyframe's map pose is not finite or its quaternion is zero");
+    }
+    TRY(reserve(ctx, P, n));
+    P->keys.resize((size_t)n);
+    std::vector<std::vector<PlKey>> fresh((size_t)n);
+    std::vector<int> todo;
+    for (int i = 0; i < n; i++) {
+        key_of(ctx, P->sub, i, n, fresh[i]);
+        const std::vector<PlKey>& old = P->keys[i];
+        if (old.size() != fresh[i].size() || std::memcmp(old.data(), fresh[i].data(), old.size() * sizeof(PlKey)) != 0) todo.push_back(i);
+    }
+    std::vector<PlSubSeg> segs;
+    size_t at = 0;
+    while (at < todo.size()) {
+        const int first = todo[at];
+        long long total = 0;
+        size_t end = at;
+        segs.clear();
+        while (end < todo.size() && todo[end] == first + (int)(end - at) && (end == at || total < kPlBatchRows)) {
+            const int i = todo[end];
+            for (const PlKey& e : fresh[i]) {
+                const lili_archive_rows r = lili_archive_rows_of(ctx, e.id, P->params.kind);
+                if (r.n <= 0) continue;      // absent or empty: offers nothing
+                PlSubSeg s{};
+                s.src = reinterpret_cast<const unsigned char*>(r.p); s.first = total; s.stride = 16; s.slot = i - first; s.ident = e.ident;
+                s.q = lili::dq{e.q[0], e.q[1], e.q[2], e.q[3]}; s.t = lili::d3{e.t[0], e.t[1], e.t[2]};
+                segs.push_back(s);
+                total += r.n;
+            }
+            end++;
+        }
+        const int n_img = (int)(end - at);
+        HIPCHK(P->h_in.ensure((size_t)n_img * 8));
+        double* h_times = P->h_in.as<double>();
+        for (int j = 0; j < n_img; j++) h_times[j] = lili_archive_rows_of(ctx, first + j, P->params.kind).time;
+        HIPCHK(hipMemcpyAsync(P->times.as<double>() + first, h_times, (size_t)n_img * 8, hipMemcpyHostToDevice, ctx->stream));
+        TRY(build_images_sub(ctx, P, P->params, segs, total, P->desc.as<unsigned>() + (size_t)first * P->cells(), n_img));
+        HIPCHK(hipStreamSynchronize(ctx->stream));      // (the next batch reuses the pinned tables)
+        for (size_t j = at; j < end; j++) P->keys[todo[j]].swap(fresh[todo[j]]);
+        at = end;
+    }
+    P->n_desc = n;
+    if (n_built) *n_built = (int)todo.size();
     return LILI_OK;
 }
 
@@ -364,9 +601,10 @@ int lili_place_update(lili_ctx* ctx, const lili_place_params* params, int* n_bui
     if (!P->has_params || !same_params(P->params, *params)) {      // other parameters: every descriptor is rebuilt (the store is sized for the new cells)
         HIPCHK(hipStreamSynchronize(ctx->stream));
         P->desc.release(); P->times.release();
-        P->cap = 0; P->n_desc = 0;
+        P->cap = 0; P->drop();
         P->params = *params; P->params.reserved_ = 0; P->has_params = true;
     }
+    if (!submap_plain(P->sub)) return update_submap(ctx, P, n_built);
     const int n = lili_archive_size(ctx), first = P->n_desc, n_new = n - first;
     if (n_built) *n_built = 0;
     if (n_new <= 0) return LILI_OK;
@@ -420,6 +658,94 @@ int lili_place_describe(lili_ctx* ctx, const lili_cloud* cloud, const lili_place
         segs.push_back(s);
     }
     TRY(build_images(ctx, P, *params, segs, (long long)cloud->n, P->one.as<unsigned>(), 1, 0));
+    HIPCHK(hipMemcpyAsync(P->h_out.p, P->one.p, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(desc, P->h_out.p, cells * 4);
+    return LILI_OK;
+}
+
+int lili_place_frame(const double pose[7], int level, double frame[7]) {
+    if (!pose_ok(pose) || !frame || (level != 0 && level != 1)) return LILI_E_ARG;
+    frame_of(pose, level, frame);
+    return LILI_OK;
+}
+
+int lili_place_relative(const double frame[7], const double pose[7], double q_rel[4], double t_rel[3]) {
+    if (!pose_ok(frame) || !pose_ok(pose) || !q_rel || !t_rel) return LILI_E_ARG;
+    relative_of(frame, pose, q_rel, t_rel);
+    return LILI_OK;
+}
+
+int lili_place_set_submap(lili_ctx* ctx, const lili_place_submap* s) {
+    if (!ctx) return LILI_E_ARG;
+    lili_place_submap v{};
+    if (s) v = *s;
+    v.reserved_ = 0;
+    ARGCHK(submap_ok(v), "place_set_submap: back must be in 0..64, fwd in 0..16, level 0 or 1");
+    PlaceState* P = place_of(ctx);
+    if (v.back != P->sub.back || v.fwd != P->sub.fwd || v.level != P->sub.level) { P->drop(); P->sub = v; }
+    return LILI_OK;
+}
+
+int lili_place_get_submap(lili_ctx* ctx, lili_place_submap* s) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(s, "place_get_submap: null argument");
+    *s = place_of(ctx)->sub;
+    return LILI_OK;
+}
+
+int lili_place_window(lili_ctx* ctx, int id, int* first, int* last) {
+    if (!ctx) return LILI_E_ARG;
+    PlaceState* P = place_of(ctx);
+    ARGCHK(first && last, "place_window: null argument");
+    ARGCHK(id >= 0 && id < P->n_desc, "place_window: the keyframe has no descriptor (lili_place_update first)");
+    if (submap_plain(P->sub)) { *first = *last = id; return LILI_OK; }
+    *first = P->keys[(size_t)id].front().id; *last = P->keys[(size_t)id].back().id;
+    return LILI_OK;
+}
+
+int lili_place_describe_submap(lili_ctx* ctx, const lili_cloud* clouds, int n, const double* q_rel, const double* t_rel, const lili_place_params* params, float* desc) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(clouds && desc, "place_describe_submap: null argument");
+    ARGCHK(n >= 1 && n <= kPlMaxMembers, "place_describe_submap: 1..81 clouds");
+    ARGCHK((q_rel == nullptr) == (t_rel == nullptr), "place_describe_submap: q_rel and t_rel are both given or both NULL");
+    ARGCHK(params_ok(params), "place_describe_submap: bad parameters (n_ring 1..32, n_sector a multiple of 4 in 4..64, max_radius > 0, kind an archive kind)");
+    size_t stage_bytes = 0;
+    for (int i = 0; i < n; i++) {
+        TRY(lili_archive_check_cloud(ctx, clouds + i));
+        ARGCHK(clouds[i].stride <= (size_t)INT_MAX, "place_describe_submap: stride too large");
+        if (q_rel) ARGCHK(finite_n(q_rel + 4 * i, 4) && finite_n(t_rel + 3 * i, 3), "place_describe_submap: a transform is not finite");
+        if (clouds[i].n && clouds[i].mem == LILI_MEM_HOST && !lili_pinned_dev_ptr(clouds[i].data, 4)) stage_bytes += (clouds[i].n * clouds[i].stride + 255) / 256 * 256;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    PlaceState* P = place_of(ctx);
+    const size_t cells = (size_t)params->n_sector * params->n_ring;
+    HIPCHK(P->one.ensure(cells * 4));
+    HIPCHK(P->h_out.ensure((size_t)kPlMaxSector * kPlMaxRing * 4));
+    if (stage_bytes) HIPCHK(ctx->staging.ensure(stage_bytes));
+    std::vector<PlSubSeg> segs;
+    long long total = 0;
+    size_t staged = 0;
+    for (int i = 0; i < n; i++) {
+        const lili_cloud& c = clouds[i];
+        if (!c.n) continue;
+        PlSubSeg s{};
+        s.src = static_cast<const unsigned char*>(c.data); s.first = total; s.stride = (int)c.stride; s.slot = 0;
+        if (c.mem == LILI_MEM_HOST) {      // page-locked rows are read where they lie, pageable ones are staged as they are
+            if (void* d = lili_pinned_dev_ptr(c.data, 4)) s.src = static_cast<const unsigned char*>(d);
+            else {
+                s.src = ctx->staging.as<unsigned char>() + staged;
+                HIPCHK(hipMemcpyAsync(ctx->staging.as<unsigned char>() + staged, c.data, c.n * c.stride, hipMemcpyHostToDevice, ctx->stream));
+                staged += (c.n * c.stride + 255) / 256 * 256;
+            }
+        }
+        const double* q = q_rel ? q_rel + 4 * i : nullptr;
+        if (!q || (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)) s.ident = 1;
+        else { s.q = lili::dq{q[0], q[1], q[2], q[3]}; s.t = lili::d3{t_rel[3 * i], t_rel[3 * i + 1], t_rel[3 * i + 2]}; }
+        segs.push_back(s);
+        total += (long long)c.n;
+    }
+    TRY(build_images_sub(ctx, P, *params, segs, total, P->one.as<unsigned>(), 1));
     HIPCHK(hipMemcpyAsync(P->h_out.p, P->one.p, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     std::memcpy(desc, P->h_out.p, cells * 4);

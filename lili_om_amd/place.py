@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .api import Cloud, PlaceMatch, PlaceParams, PlaceQuery, _f64, _ptr, cloud_from_numpy, keyframe_map_pose, load_library
+from .api import Cloud, PlaceMatch, PlaceParams, PlaceQuery, PlaceSubmap, _f64, _ptr, cloud_from_numpy, keyframe_map_pose, load_library
 from .archive import ARCHIVE_FULL
 
 INT32_MAX = 2 ** 31 - 1
@@ -33,6 +33,23 @@ def place_guess(pose_src, pose_dst, shift, n_sector):
     return T.reshape(4, 4)
 
 
+def place_frame(pose, level):
+    """F of a LiDAR map pose (7 doubles: p, then q w x y z): the pose itself (level false) or its levelled frame — origin p, z the map's z, x the horizontal
+    projection of the LiDAR's x axis (host code, no context)."""
+    a, f = _f64(pose, 7), np.zeros(7)
+    if load_library().lili_place_frame(_ptr(a), int(level), _ptr(f)) != 0:
+        raise ValueError("place_frame: bad argument")
+    return f
+
+
+def place_relative(frame, pose):
+    """(q_rel (4,), t_rel (3,)) f64: where a member at LiDAR map pose `pose` lies in `frame` — what the device places its rows by (host code, no context)."""
+    a, b, q, t = _f64(frame, 7), _f64(pose, 7), np.zeros(4), np.zeros(3)
+    if load_library().lili_place_relative(_ptr(a), _ptr(b), _ptr(q), _ptr(t)) != 0:
+        raise ValueError("place_relative: bad argument")
+    return q, t
+
+
 def _as_cloud(a):
     if isinstance(a, Cloud):
         return a
@@ -43,8 +60,11 @@ def _as_cloud(a):
 class PlaceRecognition:
     """Descriptors of a KeyframeArchive's keyframes and their search.  A descriptor is an (n_sector, n_ring) float32 array (a sector's column is a row of it)."""
 
-    def __init__(self, archive, n_ring=None, n_sector=None, max_radius=None, lidar_height=None, kind=ARCHIVE_FULL):
+    def __init__(self, archive, n_ring=None, n_sector=None, max_radius=None, lidar_height=None, kind=ARCHIVE_FULL, back=0, fwd=0, level=False):
+        """back / fwd / level: the submap setting (all zero: a keyframe's own rows in the LiDAR frame).  Otherwise keyframe i is described by the rows of keyframes
+        i - back .. i + fwd placed in its frame, levelled to the map's z if `level`; a window is counted in keyframes, by index."""
         self.archive, self.ctx, self.lib = archive, archive.ctx, archive.ctx.lib
+        self.submap = PlaceSubmap(int(back), int(fwd), int(level), 0)
         p = default_place_params()
         for k, v in (("n_ring", n_ring), ("n_sector", n_sector), ("max_radius", max_radius), ("lidar_height", lidar_height), ("kind", kind)):
             if v is not None:
@@ -55,8 +75,14 @@ class PlaceRecognition:
     def shape(self):
         return self.params.n_sector, self.params.n_ring
 
+    def _set(self):
+        """this object's submap setting becomes the context's (another one than the context holds drops every descriptor)"""
+        self.ctx._chk(self.lib.lili_place_set_submap(self.ctx.h, C.byref(self.submap)))
+
     def update(self):
-        """Describes every archived keyframe that has no descriptor yet; returns how many it built."""
+        """Describes every archived keyframe that has no descriptor yet and, in a submap setting, every keyframe whose window or relative poses changed; returns
+        how many it built."""
+        self._set()
         n = C.c_int(0)
         self.ctx._chk(self.lib.lili_place_update(self.ctx.h, C.byref(self.params), C.byref(n)))
         return n.value
@@ -64,6 +90,34 @@ class PlaceRecognition:
     def descriptor(self, kid):
         out = np.zeros(self.shape, np.float32)
         self.ctx._chk(self.lib.lili_place_get(self.ctx.h, int(kid), _ptr(out)))
+        return out
+
+    def window(self, kid):
+        """(first, last): the keyframes descriptor kid was built from"""
+        a, b = C.c_int(0), C.c_int(0)
+        self.ctx._chk(self.lib.lili_place_window(self.ctx.h, int(kid), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def frame_pose(self, kid):
+        """the frame keyframe kid's descriptor is built in, as 7 doubles: its LiDAR map pose, levelled if the setting says so"""
+        return place_frame(self.map_pose(kid), self.submap.level)
+
+    def describe_submap(self, clouds, frame=None, poses=None, rel=None):
+        """The descriptor of a list of clouds (as describe takes them) whose LiDAR map poses are `poses`, in `frame` (7 doubles each) — or placed by rel[i] =
+        (q_rel, t_rel) directly.  A pose or rel entry of None — or neither poses nor rel — reads that cloud untransformed.  The kernel and the bytes of the
+        archive path."""
+        cs = [_as_cloud(c) for c in clouds]
+        arr = (Cloud * max(len(cs), 1))(*cs)
+        if rel is None and frame is not None and poses is not None:
+            rel = [None if p is None else place_relative(frame, p) for p in poses]
+        q = t = None
+        if rel is not None:
+            q, t = np.zeros((len(cs), 4)), np.zeros((len(cs), 3))
+            for i, r in enumerate(rel):
+                if r is not None:
+                    q[i], t[i] = r
+        out = np.zeros(self.shape, np.float32)
+        self.ctx._chk(self.lib.lili_place_describe_submap(self.ctx.h, arr, len(cs), _ptr(q), _ptr(t), C.byref(self.params), _ptr(out)))
         return out
 
     def describe(self, cloud):
@@ -115,7 +169,8 @@ class PlaceRecognition:
         return np.concatenate([t, q])
 
     def guess(self, src, dst, shift):
-        """align's guess for source keyframe `src` matched to candidate `dst` at `shift`; src / dst are keyframe ids or 7-double LiDAR map poses."""
-        a = self.map_pose(src) if isinstance(src, (int, np.integer)) else src
-        b = self.map_pose(dst) if isinstance(dst, (int, np.integer)) else dst
+        """align's guess for source keyframe `src` matched to candidate `dst` at `shift`; src / dst are keyframe ids or 7-double frame poses (frame_pose: the
+        LiDAR map poses unless the descriptors are levelled)."""
+        a = self.frame_pose(src) if isinstance(src, (int, np.integer)) else src
+        b = self.frame_pose(dst) if isinstance(dst, (int, np.integer)) else dst
         return place_guess(a, b, shift, self.params.n_sector)

@@ -5,9 +5,16 @@
   b. lili_place_search at 1 000 and 10 000 described keyframes, with 1 and 64 queries, k = 10;
   c. for comparison the same exact search (all candidates, all shifts) in numpy on the host: unit columns, one batched matrix product per query, the wrapped
      diagonals gathered by index.
+  d. (--submap) levelled submap descriptors at back 20 / fwd 2: the update of the whole archive (two parameter sets alternate, as in a.), the steady-state update of
+     one new keyframe (fwd + 1 descriptors), and the full rebuild after every pose of a 1 000-keyframe archive changed.  --build-probe compiles the library once more
+     with k_place_cells_sub replaced by the global-atomic form (a tool-only build, never shipped) into tools/_probe/place_global/; run --submap with
+     LILI_HIP_LIBRARY pointing there to time that form on the same segment tables.
 No number here is a gate.
 
     python tools/place_time.py [--reps 7] [--out profiles/place_time.json]
+    python tools/place_time.py --build-probe
+    python tools/place_time.py --submap [--out FILE]
+    LILI_HIP_LIBRARY=tools/_probe/place_global/liblili_hip.so python tools/place_time.py --submap [--out FILE]
 """
 import argparse
 import json
@@ -63,11 +70,86 @@ def host_search(descs, query, k):
     return order, shift[order], best[order]
 
 
+def build_probe():
+    """the library with lili_place.hip compiled under -DLILI_PLACE_PROBE_GLOBAL, every other object as built -> tools/_probe/place_global/liblili_hip.so"""
+    import glob
+    import subprocess
+    cs, out = os.path.join(ROOT, "lili_om_amd", "csrc"), os.path.join(ROOT, "tools", "_probe", "place_global")
+    os.makedirs(out, exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    obj = os.path.join(out, "lili_place_global.o")
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
+                           "-DLILI_PLACE_PROBE_GLOBAL", "-c", os.path.join(cs, "lili_place.hip"), "-o", obj])
+    others = [o for o in sorted(glob.glob(os.path.join(cs, "*.o"))) if os.path.basename(o) != "lili_place.o"]
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(out, "liblili_hip.so"), obj] + others)
+    print(os.path.join(out, "liblili_hip.so"))
+
+
+def submap_times(a):
+    """d.: keyframes 2 m apart down a street, a few degrees of roll and pitch each, described at back 20 / fwd 2, levelled"""
+    rng = np.random.default_rng(9)
+    form = "global" if "place_global" in os.environ.get("LILI_HIP_LIBRARY", "") else "lds"
+    result = dict(form=form, back=20, fwd=2, level=1)
+
+    def pose(k):
+        r, p = np.radians(rng.uniform(-3, 3, 2))
+        q = np.array([1.0, r / 2, p / 2, np.radians(rng.uniform(-5, 5)) / 2])
+        return [2.0 * k, rng.uniform(-0.5, 0.5), 0.0], q / np.linalg.norm(q)
+
+    for name, rows, n_kf in (("livox_24k", 24_000, 400), ("rot_130k", 130_000, 100), ("livox_24k_1000", 24_000, 1000)):
+        ctx = L.Context(0)
+        arch = L.KeyframeArchive(ctx)
+        pool = [cloud(rng, rows) for _ in range(8)]
+        for k in range(n_kf):
+            arch.push(None, None, pool[k % 8], 0.1 * k, *pose(k))
+        pr = [L.PlaceRecognition(arch, lidar_height=h, back=20, fwd=2, level=True) for h in (2.0, 1.9)]
+        flip = [0]
+        rec = dict(rows_per_keyframe=rows, keyframes=n_kf, rows_binned_in_a_full_update=int(sum(min(n_kf - 1, i + 2) - max(0, i - 20) + 1 for i in range(n_kf))) * rows)
+        if n_kf < 1000:
+            def rebuild():
+                flip[0] ^= 1
+                return pr[flip[0]].update()
+            built, all_ms = timed(rebuild, a.reps)
+            assert built == n_kf
+            one_ms = []
+            for r in range(a.reps + 1):
+                arch.push(None, None, pool[r % 8], 0.1 * (n_kf + r), *pose(n_kf + r))
+                t0 = time.perf_counter()
+                assert pr[flip[0]].update() == 3
+                if r:
+                    one_ms.append((time.perf_counter() - t0) * 1e3)
+            rec.update(update_all_ms=all_ms, update_all_ms_median=float(np.median(all_ms)), update_one_ms=one_ms, update_one_ms_median=float(np.median(one_ms)),
+                       g_rows_per_s_in_a_full_update=rec["rows_binned_in_a_full_update"] / float(np.median(all_ms)) * 1e-6)
+        else:
+            assert pr[0].update() == n_kf
+            ts, qs, _ = arch.poses()
+
+            def correct():
+                ts[:, 1] += 0.01 * np.arange(n_kf) / n_kf      # a pose correction that grows along the trajectory: every relative placement changes
+                arch.set_poses(0, ts, qs)
+            built, ms = timed(pr[0].update, a.reps, before=correct)
+            assert built == n_kf
+            rec.update(rebuild_after_set_poses_ms=ms, rebuild_after_set_poses_ms_median=float(np.median(ms)))
+        result["submap_" + name] = rec
+        print("submap", form, name, json.dumps(rec), flush=True)
+        ctx.close()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--submap", action="store_true")
+    ap.add_argument("--build-probe", action="store_true")
     a = ap.parse_args()
+    if a.build_probe:
+        return build_probe()
+    if a.submap:
+        return submap_times(a)
     rng = np.random.default_rng(9)
     result = {}
     # a. update
