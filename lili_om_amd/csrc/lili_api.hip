@@ -83,7 +83,6 @@ int lili_readback_now(lili_ctx* ctx, void* dst, const void* d_src, size_t bytes,
     return lili_readback_finish(ctx, stream);
 }
 
-// copies / converts a described cloud into a device float4 array (x, y, z, aux)
 // The device-side address of a caller's PAGE-LOCKED host buffer (lili_host_alloc / hipHostMalloc / hipHostRegister), or nullptr: pageable memory, or not aligned to
 // `align` bytes.  Asked on EVERY call that wants to let a kernel read or write the buffer across PCIe (0.06-0.16 us: tools/ptr_attr_cost.hip) — a cached "page-locked"
 // would outlive the buffer: the address of a freed page-locked buffer can come back from malloc as pageable memory, and a kernel would fault on it.
@@ -97,27 +96,39 @@ void* lili_pinned_dev_ptr(const void* host, size_t align) {
     return nullptr;
 }
 
+int lili_cloud_check(lili_ctx* ctx, const lili_cloud& c, const char* who) {
+    if (const char* fault = cloud_fault(c)) return ctx->fail(LILI_E_ARG, std::string(who) + ": " + fault);
+    return LILI_OK;
+}
+// Round 4: a PAGE-LOCKED cloud (a driver's DMA buffer, lili_host_alloc) is read by the consuming kernel where it lies, across PCIe — no copy-engine transfer,
+// no wait for its completion signal before the kernel may start.  Measured (tools/rot_host_time.py, tools/livox_timeline.py): a 1.15 MB Livox scan -28 us per call;
+// a 3.2 MB ROT scan +9 us (the kernel reads PCIe at ~41 GB/s, the copy engine at ~55) — but the call then takes the same time from the first scan on, where a
+// copy-engine upload next to a download of the same call ran 0.35-0.45 ms for its first fifty-odd calls (the bench's bimodal extract_rot).  Pageable memory:
+// one staged transfer of the rows as they are.
+int lili_cloud_sources(lili_ctx* ctx, DevBuf& stage, const lili_cloud* clouds, int n, SourcePolicy policy, const unsigned char** src) {
+    CloudSource one;
+    std::vector<CloudSource> many(n > 1 ? n : 0);
+    CloudSource* plan = n > 1 ? many.data() : &one;
+    const size_t total = plan_sources(clouds, n, policy, [](const void* p) { return lili_pinned_dev_ptr(p, 4); }, plan);
+    if (total > 0) HIPCHK(stage.ensure(total));
+    for (int i = 0; i < n; i++) {
+        src[i] = static_cast<const unsigned char*>(plan[i].kind == CloudSource::kPinned ? plan[i].pinned : clouds[i].data);
+        if (plan[i].kind != CloudSource::kStaged) continue;
+        unsigned char* at = stage.as<unsigned char>() + plan[i].offset;
+        HIPCHK(hipMemcpyAsync(at, clouds[i].data, clouds[i].n * clouds[i].stride, hipMemcpyHostToDevice, ctx->stream));
+        src[i] = at;
+    }
+    return LILI_OK;
+}
+
+// copies / converts a described cloud into a device float4 array (x, y, z, aux)
 int lili_ingest_cloud(lili_ctx* ctx, const lili_cloud* c, DevBuf& out_f4, unsigned* d_bbox) {
-    ARGCHK(c && (c->n == 0 || c->data), "cloud: null data");
-    ARGCHK(c->stride >= 12 && c->stride % 4 == 0, "cloud: stride must be a multiple of 4 and >= 12");
-    ARGCHK(c->aux_offset < 0 || (size_t)c->aux_offset + 4 <= c->stride, "cloud: aux_offset outside the point");
-    ARGCHK(c->n < (size_t)1 << 31, "cloud: too many points");
+    ARGCHK(c, "cloud: null data");
+    TRY(lili_cloud_check(ctx, *c, "cloud"));
     if (c->n == 0) return LILI_OK;
     HIPCHK(out_f4.ensure(c->n * sizeof(float4)));
-    const unsigned char* src = reinterpret_cast<const unsigned char*>(c->data);
-    if (c->mem == LILI_MEM_HOST) {
-        // Round 4: a PAGE-LOCKED cloud (a driver's DMA buffer, lili_host_alloc) is read by the conversion kernel where it lies, across PCIe — no copy-engine transfer,
-        // no wait for its completion signal before the kernel may start.  Measured (tools/rot_host_time.py, tools/livox_timeline.py): a 1.15 MB Livox scan -28 us per call;
-        // a 3.2 MB ROT scan +9 us (the kernel reads PCIe at ~41 GB/s, the copy engine at ~55) — but the call then takes the same time from the first scan on, where a
-        // copy-engine upload next to a download of the same call ran 0.35-0.45 ms for its first fifty-odd calls (the bench's bimodal extract_rot).  Pageable memory:
-        // one staged transfer of the rows as they are.
-        if (void* d = lili_pinned_dev_ptr(c->data, 4)) src = static_cast<const unsigned char*>(d);
-        else {
-            HIPCHK(ctx->staging.ensure(c->n * c->stride));
-            HIPCHK(hipMemcpyAsync(ctx->staging.p, c->data, c->n * c->stride, hipMemcpyHostToDevice, ctx->stream));
-            src = ctx->staging.as<unsigned char>();
-        }
-    } else ARGCHK(c->mem == LILI_MEM_DEVICE, "cloud: bad mem");
+    const unsigned char* src = nullptr;
+    TRY(lili_cloud_sources(ctx, ctx->staging, c, 1, kReadPinnedInPlace, &src));
     // with a bounding box: a bounded grid (grid-stride loop) so that the box costs a few thousand atomics, not one set per 256 points
     const int nb = d_bbox ? std::min(nblocks((int64_t)c->n, kBlock), 4096) : nblocks((int64_t)c->n, kBlock);
     hipLaunchKernelGGL(k_cloud_to_f4, dim3(nb), dim3(kBlock), 0, ctx->stream, src, (int)c->n, (int)c->stride, c->aux_offset, out_f4.as<float4>(), d_bbox);

@@ -238,16 +238,6 @@ void map_pose(const double t_po[3], const double a[4], const double t_bl[3], con
 
 size_t round256(size_t b) { return (b + 255) / 256 * 256; }
 
-int check_cloud(lili_ctx* ctx, const lili_cloud* c) {
-    if (!c) return LILI_OK;
-    ARGCHK(c->n == 0 || c->data, "archive_push: null data");
-    ARGCHK(c->stride >= 12 && c->stride % 4 == 0, "archive_push: stride must be a multiple of 4 and >= 12");
-    ARGCHK(c->aux_offset < 0 || (size_t)c->aux_offset + 4 <= c->stride, "archive_push: aux_offset outside the point");
-    ARGCHK(c->mem == LILI_MEM_HOST || c->mem == LILI_MEM_DEVICE, "archive_push: bad mem");
-    ARGCHK(c->n < (size_t)1 << 31, "archive_push: too many points");
-    return LILI_OK;
-}
-
 // room for `need` bytes in one piece: the last slab, or a new one (the keyframe's three clouds share one piece, so a push opens at most one slab).  The archive is
 // changed only by commit_room, once nothing of the push can fail any more.
 struct Room { int slab = -1; size_t off = 0; void* fresh = nullptr; size_t fresh_cap = 0; };
@@ -272,15 +262,8 @@ void commit_room(ArchiveState* A, const Room& r, size_t need) {
 // the rows of a described cloud into `dst` (float4 rows), enqueued on the context's stream
 int ingest_rows(lili_ctx* ctx, const lili_cloud* c, float4* dst) {
     if (c->n == 0) return LILI_OK;
-    const unsigned char* src = static_cast<const unsigned char*>(c->data);
-    if (c->mem == LILI_MEM_HOST) {
-        if (void* d = lili_pinned_dev_ptr(c->data, 4)) src = static_cast<const unsigned char*>(d);
-        else {
-            HIPCHK(ctx->staging.ensure(c->n * c->stride));
-            HIPCHK(hipMemcpyAsync(ctx->staging.p, c->data, c->n * c->stride, hipMemcpyHostToDevice, ctx->stream));
-            src = ctx->staging.as<unsigned char>();
-        }
-    }
+    const unsigned char* src = nullptr;
+    TRY(lili_cloud_sources(ctx, ctx->staging, c, 1, kReadPinnedInPlace, &src));
     hipLaunchKernelGGL(lili::k_arc_rows, dim3(nblocks((int64_t)c->n, 256)), dim3(256), 0, ctx->stream, src, (int)c->n, (int)c->stride, c->aux_offset, dst);
     HIPCHK(hipGetLastError());
     return LILI_OK;
@@ -290,7 +273,7 @@ int ingest_rows(lili_ctx* ctx, const lili_cloud* c, float4* dst) {
 int push_keyframe(lili_ctx* ctx, const lili_cloud* const clouds[kKinds], const float4* const dev[kKinds], const int dev_n[kKinds], double time, const double t_po[3],
                   const double q_po[4], int* id) {
     ARGCHK(t_po && q_po, "archive_push: null pose");
-    for (int k = 0; k < kKinds; k++) { const int rc = check_cloud(ctx, clouds[k]); if (rc != LILI_OK) return rc; }
+    for (int k = 0; k < kKinds; k++) if (clouds[k]) TRY(lili_cloud_check(ctx, *clouds[k], "archive_push"));
     HIPCHK(hipSetDevice(ctx->device));
     ArchiveState* A = archive_of(ctx);
     ARGCHK(A->kf.size() < (size_t)INT_MAX, "archive_push: too many keyframes");
@@ -417,7 +400,6 @@ lili_archive_rows lili_archive_rows_of(lili_ctx* ctx, int id, int kind) {
     r.p = kf.c[kind].p; r.n = kf.c[kind].n; r.time = kf.time;
     return r;
 }
-int lili_archive_check_cloud(lili_ctx* ctx, const lili_cloud* c) { return check_cloud(ctx, c); }
 void lili_archive_map_pose_of(lili_ctx* ctx, int id, double pose[7]) {
     const ArcKeyframe& kf = archive_of(ctx)->kf[id];
     for (int k = 0; k < 3; k++) pose[k] = kf.t_map[k];

@@ -1,6 +1,7 @@
 // Internal: context and buffer types shared by the translation units of liblili_hip.so (not part of the ABI).
 #pragma once
 #include "../../include/lili_hip.h"
+#include "lili_cloud_source.h"
 #include "lili_kernels.h"
 #include "lili_own.h"
 
@@ -308,6 +309,10 @@ int lili_readback_now(lili_ctx* ctx, void* dst, const void* d_src, size_t bytes,
 // the library — a hook or a commit that clears words another stage has yet to deliver), LILI_OK otherwise.  Host-side, a loop over at most twelve items.
 int lili_lazy_sources_clear_of(lili_ctx* ctx, const void* p, size_t bytes);
 void* lili_pinned_dev_ptr(const void* host, size_t align = 4);      // device-side address of a PAGE-LOCKED host buffer, or nullptr (pageable / misaligned); asked per call: ~0.1 us
+// A caller's cloud (lili_cloud_source.h): LILI_E_ARG "<who>: <fault>" for a bad description; src[i] = where a kernel reads the rows of clouds[i] — pageable rows are
+// copied into `stage` on the context's stream, in cloud order.  Enqueues those copies and nothing else: the caller synchronises where it did.
+int lili_cloud_check(lili_ctx* ctx, const lili_cloud& c, const char* who);
+int lili_cloud_sources(lili_ctx* ctx, lili_detail::DevBuf& stage, const lili_cloud* clouds, int n, lili_detail::SourcePolicy policy, const unsigned char** src);
 int lili_ingest_cloud(lili_ctx* ctx, const lili_cloud* c, lili_detail::DevBuf& out_f4, unsigned* d_bbox = nullptr);   // d_bbox: also reduce the bounding box (6 ordered-uint words, initialised by the caller)
 // lili_p2p.hip: the view of the NEXT exchange of a communicator (advances its sequence number); usable = connected and on this context
 lili::P2PView lili_p2p_next_view(lili_p2p* c);

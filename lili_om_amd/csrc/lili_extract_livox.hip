@@ -412,25 +412,14 @@ static int extract_livox_impl(lili_ctx* ctx, const lili_cloud* scan, int curvatu
     HIPCHK(hipSetDevice(ctx->device));
     auto* B = livox_of(ctx);
     B->have = false; B->pending = false;
-    ARGCHK(scan->n == 0 || scan->data, "cloud: null data");
-    ARGCHK(scan->stride >= 12 && scan->stride % 4 == 0 && (size_t)scan->aux_offset + 4 <= scan->stride, "cloud: stride must be a multiple of 4 and >= 12, offsets inside the point");
-    ARGCHK(scan->n < (size_t)1 << 31, "cloud: too many points");
-    ARGCHK(scan->mem == LILI_MEM_HOST || scan->mem == LILI_MEM_DEVICE, "cloud: bad mem");
+    TRY(lili_cloud_check(ctx, *scan, "cloud"));
     int rc = LILI_OK;
     const int n = (int)scan->n;
-    const unsigned char* raw = static_cast<const unsigned char*>(scan->data);
-    if (scan->mem == LILI_MEM_HOST && n > 0) {
-        // A PAGE-LOCKED scan (a driver's DMA buffer, lili_host_alloc) is read by k_livox_prep where it lies, across PCIe (round 4: the copy engine's transfer + the
-        // ~11 us before a kernel sees its completion were 28 us of the call; the kernel reads the same 1.15 MB in its own time).  Pageable memory: ONE transfer of the
-        // rows as they are; k_livox_prep picks the fields.
-        void* d = lili_pinned_dev_ptr(scan->data, 4);
-        if (d) raw = static_cast<const unsigned char*>(d);
-        else {
-            HIPCHK(ctx->staging.ensure(scan->n * scan->stride));
-            HIPCHK(hipMemcpyAsync(ctx->staging.p, scan->data, scan->n * scan->stride, hipMemcpyHostToDevice, ctx->stream));
-            raw = ctx->staging.as<unsigned char>();
-        }
-    }
+    // A PAGE-LOCKED scan (a driver's DMA buffer, lili_host_alloc) is read by k_livox_prep where it lies, across PCIe (round 4: the copy engine's transfer + the
+    // ~11 us before a kernel sees its completion were 28 us of the call; the kernel reads the same 1.15 MB in its own time).  Pageable memory: ONE transfer of the
+    // rows as they are; k_livox_prep picks the fields.
+    const unsigned char* raw = nullptr;
+    TRY(lili_cloud_sources(ctx, ctx->staging, scan, 1, kReadPinnedInPlace, &raw));
     HIPCHK(B->state.ensure(sizeof(LivoxState))); HIPCHK(B->owner.ensure(kLvCells * 4));
     HIPCHK(B->cell_pt.ensure(kLvCells * 16)); HIPCHK(B->cell_curv.ensure(kLvCells * 4)); HIPCHK(B->cell_src.ensure(kLvCells * 4));
     HIPCHK(B->blk_nedge.ensure(kLvBlocks * 4)); HIPCHK(B->blk_edge_cell.ensure(kLvBlocks * kLvLines * 4)); HIPCHK(B->blk_edge_dir.ensure(kLvBlocks * 12));

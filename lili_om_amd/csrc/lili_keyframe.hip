@@ -151,12 +151,9 @@ int lili_keyframe_undistort(lili_ctx* ctx, const lili_cloud* const clouds[3], co
     for (int k = 0; k < 3; k++) {
         const lili_cloud* c = clouds[k];
         if (!c || c->n == 0) continue;
-        ARGCHK(c->data, "keyframe_undistort: null data");
-        ARGCHK(c->mem == LILI_MEM_HOST || c->mem == LILI_MEM_DEVICE, "keyframe_undistort: bad mem");
-        ARGCHK(c->stride >= 12 && c->stride % 4 == 0, "keyframe_undistort: stride must be a multiple of 4 and >= 12");
-        ARGCHK(c->aux_offset < 0 || (c->aux_offset % 4 == 0 && (size_t)c->aux_offset + 4 <= c->stride), "keyframe_undistort: aux_offset outside the point or no multiple of 4");
+        TRY(lili_cloud_check(ctx, *c, "keyframe_undistort"));
+        ARGCHK(c->aux_offset < 0 || c->aux_offset % 4 == 0, "keyframe_undistort: aux_offset outside the point or no multiple of 4");
         ARGCHK(time_offset[k] >= 0 && time_offset[k] % 4 == 0 && (size_t)time_offset[k] + 4 <= c->stride, "keyframe_undistort: time_offset outside the point or no multiple of 4");
-        ARGCHK(c->n < (size_t)1 << 31, "keyframe_undistort: too many points");
         ARGCHK((reinterpret_cast<uintptr_t>(c->data) & 3) == 0, "keyframe_undistort: cloud not 4-byte aligned");
         ARGCHK(out[k].data && out[k].mem == LILI_MEM_DEVICE && out[k].stride == 16 && out[k].capacity >= c->n, "keyframe_undistort: out must be a device buffer of 16-byte rows with room for the cloud");
         ARGCHK((reinterpret_cast<uintptr_t>(out[k].data) & 15) == 0, "keyframe_undistort: out not 16-byte aligned");
@@ -169,15 +166,8 @@ int lili_keyframe_undistort(lili_ctx* ctx, const lili_cloud* const clouds[3], co
         const lili_cloud* c = clouds[k];
         out[k].count = 0;
         if (!c || c->n == 0) continue;
-        const unsigned char* base = static_cast<const unsigned char*>(c->data);
-        if (c->mem == LILI_MEM_HOST) {
-            if (void* d = lili_pinned_dev_ptr(c->data, 4)) base = static_cast<const unsigned char*>(d);      // page-locked: read where it lies
-            else {
-                HIPCHK(K->stage[k].ensure(c->n * c->stride));
-                HIPCHK(hipMemcpyAsync(K->stage[k].p, c->data, c->n * c->stride, hipMemcpyHostToDevice, ctx->stream));
-                base = K->stage[k].as<unsigned char>();
-            }
-        }
+        const unsigned char* base = nullptr;
+        TRY(lili_cloud_sources(ctx, K->stage[k], c, 1, kReadPinnedInPlace, &base));
         src[k].xyz = base; src[k].time = base + time_offset[k]; src[k].aux = c->aux_offset >= 0 ? base + c->aux_offset : nullptr;
         src[k].xyz_stride = src[k].time_stride = src[k].aux_stride = (int)c->stride; src[k].n = (int)c->n;
         dst[k] = static_cast<float4*>(out[k].data);

@@ -65,12 +65,11 @@ int lili_scan_exclusive3(lili_ctx* ctx, const int* in, int64_t n, lili_detail::D
 int copy_rows_enqueue(lili_ctx* ctx, const void* d_rows, size_t count, lili_feature_out* out, const char* what, size_t* copied);
 int copy_rows_out(lili_ctx* ctx, const void* d_rows, size_t count, lili_feature_out* out, const char* what);
 // lili_archive.hip -> lili_place.hip: what place recognition reads of the archive — its size, its reset count (a descriptor outlives no reset), a keyframe's rows of one kind
-// (device float4 rows, complete once the context's stream has been synchronised) and time, and archive_push's checks of a caller's cloud
+// (device float4 rows, complete once the context's stream has been synchronised) and time
 struct lili_archive_rows { const float4* p = nullptr; int n = 0; double time = 0; };
 int lili_archive_size(lili_ctx* ctx);
 unsigned long long lili_archive_resets(lili_ctx* ctx);
 lili_archive_rows lili_archive_rows_of(lili_ctx* ctx, int id, int kind);
-int lili_archive_check_cloud(lili_ctx* ctx, const lili_cloud* c);
 void lili_archive_map_pose_of(lili_ctx* ctx, int id, double pose[7]);      // keyframe id's LiDAR map pose (p, then q w x y z) as the archive holds it now
 // lili_match.hip -> lili_window.hip (the lidar blocks of the joint window)
 int lili_match_window_records(lili_ctx* ctx, const int* slots, int n_slots, int kind_mask, const lili_s2m_params* params, const double* t, const double* q, double* d_gram);

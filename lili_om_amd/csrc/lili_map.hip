@@ -160,10 +160,7 @@ static int map_set_impl(lili_ctx* ctx, int kind, const lili_cloud* cloud, double
     ARGCHK(cloud, "map_set: null cloud");
     ARGCHK(max_sq_radius > 0 && std::isfinite(max_sq_radius), "map_set: max_sq_radius must be positive");
     ARGCHK(cloud->n < (1ll << 28), "map_set: at most 2^28 - 1 map points (32-bit byte offsets into the sorted array)");
-    ARGCHK(cloud->n == 0 || cloud->data, "cloud: null data");
-    ARGCHK(cloud->stride >= 12 && cloud->stride % 4 == 0, "cloud: stride must be a multiple of 4 and >= 12");
-    ARGCHK(cloud->aux_offset < 0 || (size_t)cloud->aux_offset + 4 <= cloud->stride, "cloud: aux_offset outside the point");
-    ARGCHK(cloud->mem == LILI_MEM_HOST || cloud->mem == LILI_MEM_DEVICE, "cloud: bad mem");
+    TRY(lili_cloud_check(ctx, *cloud, "cloud"));
     HIPCHK(hipSetDevice(ctx->device));
     MapIndex& m = ctx->map[kind];
     m.valid = false;
@@ -177,12 +174,8 @@ static int map_set_impl(lili_ctx* ctx, int kind, const lili_cloud* cloud, double
     // The points are read where they lie — the caller's device array, or the staging copy of a host cloud — by the box pass, the count pass and the scatter
     // pass (round 4; rounds 1-3 first copied the map into a float4 array of the library's: 60-80 MB read + 80 MB written per 5 M points, 18 us).
     SrcCloud src{};
-    src.p = reinterpret_cast<const unsigned char*>(cloud->data); src.stride = (int)cloud->stride; src.aux_off = cloud->aux_offset;
-    if (cloud->mem == LILI_MEM_HOST) {
-        HIPCHK(ctx->staging.ensure(cloud->n * cloud->stride));
-        HIPCHK(hipMemcpyAsync(ctx->staging.p, cloud->data, cloud->n * cloud->stride, hipMemcpyHostToDevice, ctx->stream));
-        src.p = ctx->staging.as<unsigned char>();
-    }
+    src.stride = (int)cloud->stride; src.aux_off = cloud->aux_offset;
+    TRY(lili_cloud_sources(ctx, ctx->staging, cloud, 1, kStageHostAlways, &src.p));
     src.f4 = cloud->stride == sizeof(float4) && (reinterpret_cast<uintptr_t>(src.p) & 15) == 0 && (cloud->aux_offset == 12 || cloud->aux_offset < 0);
     // cell edge: >= 1.01 * gate radius so that the 27-cell neighbourhood covers the gate ball
     const int reach = ctx->grid_reach == 2 ? 2 : 1;

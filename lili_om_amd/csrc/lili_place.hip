@@ -547,7 +547,7 @@ int update_submap(lili_ctx* ctx, PlaceState* P, int* n_built) {
 template <int NR> void launch_scan(hipStream_t stream, dim3 grid, const lili::PlScan& a) { hipLaunchKernelGGL(lili::k_place_scan<NR>, grid, dim3(256), 0, stream, a); }
 
 void quat_matrix(const double pose[7], double M[16]) {
-    const double n = std::sqrt(pose[3] * pose[3] + pose[4] * pose[4] + pose[5] * pose[5] + pose[6] * pose[6]);
+    const double n = quat_norm(pose + 3);
     const double w = pose[3] / n, x = pose[4] / n, y = pose[5] / n, z = pose[6] / n;
     const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
                          2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
@@ -557,6 +557,29 @@ void quat_matrix(const double pose[7], double M[16]) {
 void mat_mul4(const double A[16], const double B[16], double C[16]) {
     for (int i = 0; i < 4; i++)
         for (int j = 0; j < 4; j++) { double s = 0.0; for (int k = 0; k < 4; k++) s += A[4 * i + k] * B[4 * k + j]; C[4 * i + j] = s; }
+}
+
+// lili_place_describe / _describe_submap (`who`): the checks, where the n clouds are read from (page-locked rows where they lie, pageable ones staged as they are),
+// `build(P, src)` — which enqueues the clouds' image into P->one —, and the image copied out.  Blocking.
+template <class Build> int describe_clouds(lili_ctx* ctx, const char* who, const lili_cloud* clouds, int n, const lili_place_params* params, float* desc, Build build) {
+    ARGCHK(clouds && desc, std::string(who) + ": null argument");
+    ARGCHK(params_ok(params), std::string(who) + ": bad parameters (n_ring 1..32, n_sector a multiple of 4 in 4..64, max_radius > 0, kind an archive kind)");
+    for (int i = 0; i < n; i++) {
+        TRY(lili_cloud_check(ctx, clouds[i], who));
+        ARGCHK(clouds[i].stride <= (size_t)INT_MAX, std::string(who) + ": stride too large");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    PlaceState* P = place_of(ctx);
+    const size_t cells = (size_t)params->n_sector * params->n_ring;
+    HIPCHK(P->one.ensure(cells * 4));
+    HIPCHK(P->h_out.ensure((size_t)kPlMaxSector * kPlMaxRing * 4));
+    std::vector<const unsigned char*> src((size_t)n);
+    TRY(lili_cloud_sources(ctx, ctx->staging, clouds, n, kReadPinnedInPlace, src.data()));
+    TRY(build(P, src.data()));
+    HIPCHK(hipMemcpyAsync(P->h_out.p, P->one.p, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::memcpy(desc, P->h_out.p, cells * 4);
+    return LILI_OK;
 }
 
 }  // namespace
@@ -633,35 +656,16 @@ int lili_place_update(lili_ctx* ctx, const lili_place_params* params, int* n_bui
 
 int lili_place_describe(lili_ctx* ctx, const lili_cloud* cloud, const lili_place_params* params, float* desc) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(cloud && desc, "place_describe: null argument");
-    ARGCHK(params_ok(params), "place_describe: bad parameters (n_ring 1..32, n_sector a multiple of 4 in 4..64, max_radius > 0, kind an archive kind)");
-    TRY(lili_archive_check_cloud(ctx, cloud));
-    ARGCHK(cloud->stride <= (size_t)INT_MAX, "place_describe: stride too large");
-    HIPCHK(hipSetDevice(ctx->device));
-    PlaceState* P = place_of(ctx);
-    const size_t cells = (size_t)params->n_sector * params->n_ring;
-    HIPCHK(P->one.ensure(cells * 4));
-    HIPCHK(P->h_in.ensure(sizeof(PlSeg) + 64));
-    HIPCHK(P->h_out.ensure((size_t)kPlMaxSector * kPlMaxRing * 4));
-    std::vector<PlSeg> segs;
-    if (cloud->n) {
-        PlSeg s{};
-        s.src = static_cast<const unsigned char*>(cloud->data); s.first = 0; s.stride = (int)cloud->stride; s.slot = 0;
-        if (cloud->mem == LILI_MEM_HOST) {      // page-locked rows are read where they lie, pageable ones are staged as they are
-            if (void* d = lili_pinned_dev_ptr(cloud->data, 4)) s.src = static_cast<const unsigned char*>(d);
-            else {
-                HIPCHK(ctx->staging.ensure(cloud->n * cloud->stride));
-                HIPCHK(hipMemcpyAsync(ctx->staging.p, cloud->data, cloud->n * cloud->stride, hipMemcpyHostToDevice, ctx->stream));
-                s.src = ctx->staging.as<unsigned char>();
-            }
+    return describe_clouds(ctx, "place_describe", cloud, 1, params, desc, [&](PlaceState* P, const unsigned char* const* src) {
+        HIPCHK(P->h_in.ensure(sizeof(PlSeg) + 64));
+        std::vector<PlSeg> segs;
+        if (cloud->n) {
+            PlSeg s{};
+            s.src = src[0]; s.first = 0; s.stride = (int)cloud->stride; s.slot = 0;
+            segs.push_back(s);
         }
-        segs.push_back(s);
-    }
-    TRY(build_images(ctx, P, *params, segs, (long long)cloud->n, P->one.as<unsigned>(), 1, 0));
-    HIPCHK(hipMemcpyAsync(P->h_out.p, P->one.p, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    std::memcpy(desc, P->h_out.p, cells * 4);
-    return LILI_OK;
+        return build_images(ctx, P, *params, segs, (long long)cloud->n, P->one.as<unsigned>(), 1, 0);
+    });
 }
 
 int lili_place_frame(const double pose[7], int level, double frame[7]) {
@@ -706,50 +710,25 @@ int lili_place_window(lili_ctx* ctx, int id, int* first, int* last) {
 
 int lili_place_describe_submap(lili_ctx* ctx, const lili_cloud* clouds, int n, const double* q_rel, const double* t_rel, const lili_place_params* params, float* desc) {
     if (!ctx) return LILI_E_ARG;
-    ARGCHK(clouds && desc, "place_describe_submap: null argument");
     ARGCHK(n >= 1 && n <= kPlMaxMembers, "place_describe_submap: 1..81 clouds");
     ARGCHK((q_rel == nullptr) == (t_rel == nullptr), "place_describe_submap: q_rel and t_rel are both given or both NULL");
-    ARGCHK(params_ok(params), "place_describe_submap: bad parameters (n_ring 1..32, n_sector a multiple of 4 in 4..64, max_radius > 0, kind an archive kind)");
-    size_t stage_bytes = 0;
-    for (int i = 0; i < n; i++) {
-        TRY(lili_archive_check_cloud(ctx, clouds + i));
-        ARGCHK(clouds[i].stride <= (size_t)INT_MAX, "place_describe_submap: stride too large");
-        if (q_rel) ARGCHK(finite_n(q_rel + 4 * i, 4) && finite_n(t_rel + 3 * i, 3), "place_describe_submap: a transform is not finite");
-        if (clouds[i].n && clouds[i].mem == LILI_MEM_HOST && !lili_pinned_dev_ptr(clouds[i].data, 4)) stage_bytes += (clouds[i].n * clouds[i].stride + 255) / 256 * 256;
-    }
-    HIPCHK(hipSetDevice(ctx->device));
-    PlaceState* P = place_of(ctx);
-    const size_t cells = (size_t)params->n_sector * params->n_ring;
-    HIPCHK(P->one.ensure(cells * 4));
-    HIPCHK(P->h_out.ensure((size_t)kPlMaxSector * kPlMaxRing * 4));
-    if (stage_bytes) HIPCHK(ctx->staging.ensure(stage_bytes));
-    std::vector<PlSubSeg> segs;
-    long long total = 0;
-    size_t staged = 0;
-    for (int i = 0; i < n; i++) {
-        const lili_cloud& c = clouds[i];
-        if (!c.n) continue;
-        PlSubSeg s{};
-        s.src = static_cast<const unsigned char*>(c.data); s.first = total; s.stride = (int)c.stride; s.slot = 0;
-        if (c.mem == LILI_MEM_HOST) {      // page-locked rows are read where they lie, pageable ones are staged as they are
-            if (void* d = lili_pinned_dev_ptr(c.data, 4)) s.src = static_cast<const unsigned char*>(d);
-            else {
-                s.src = ctx->staging.as<unsigned char>() + staged;
-                HIPCHK(hipMemcpyAsync(ctx->staging.as<unsigned char>() + staged, c.data, c.n * c.stride, hipMemcpyHostToDevice, ctx->stream));
-                staged += (c.n * c.stride + 255) / 256 * 256;
-            }
+    if (q_rel) ARGCHK(finite_n(q_rel, (size_t)4 * n) && finite_n(t_rel, (size_t)3 * n), "place_describe_submap: a transform is not finite");
+    return describe_clouds(ctx, "place_describe_submap", clouds, n, params, desc, [&](PlaceState* P, const unsigned char* const* src) {
+        std::vector<PlSubSeg> segs;
+        long long total = 0;
+        for (int i = 0; i < n; i++) {
+            const lili_cloud& c = clouds[i];
+            if (!c.n) continue;
+            PlSubSeg s{};
+            s.src = src[i]; s.first = total; s.stride = (int)c.stride; s.slot = 0;
+            const double* q = q_rel ? q_rel + 4 * i : nullptr;
+            if (!q || (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)) s.ident = 1;
+            else { s.q = lili::dq{q[0], q[1], q[2], q[3]}; s.t = lili::d3{t_rel[3 * i], t_rel[3 * i + 1], t_rel[3 * i + 2]}; }
+            segs.push_back(s);
+            total += (long long)c.n;
         }
-        const double* q = q_rel ? q_rel + 4 * i : nullptr;
-        if (!q || (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0)) s.ident = 1;
-        else { s.q = lili::dq{q[0], q[1], q[2], q[3]}; s.t = lili::d3{t_rel[3 * i], t_rel[3 * i + 1], t_rel[3 * i + 2]}; }
-        segs.push_back(s);
-        total += (long long)c.n;
-    }
-    TRY(build_images_sub(ctx, P, *params, segs, total, P->one.as<unsigned>(), 1));
-    HIPCHK(hipMemcpyAsync(P->h_out.p, P->one.p, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    std::memcpy(desc, P->h_out.p, cells * 4);
-    return LILI_OK;
+        return build_images_sub(ctx, P, *params, segs, total, P->one.as<unsigned>(), 1);
+    });
 }
 
 int lili_place_get(lili_ctx* ctx, int id, float* desc) {

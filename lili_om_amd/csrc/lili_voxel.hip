@@ -1576,39 +1576,25 @@ int lili_localmap_ring_size(lili_ctx* ctx, int kind) { return (int)vox_of(ctx)->
 // lili_loop.hip: detectLoopClosure's submap — transformCloud of every cloud, concatenated, then VoxelGrid(leaf) (leaf <= 0: none) — into `out` (float4 rows).  The filter
 // runs on a VoxelBuffers of the loop's own (`priv`, created here) and always the measured way: the local map's buffers, its ring and the key-bit
 // guesses of lili_voxel_filter_stats stay as they are.  Blocking.
-struct LoopVox : ExtState { lili_detail::VoxelBuffers V; DevBuf segs, staging, raw; std::vector<LoopSeg> seg_host; };
+struct LoopVox : ExtState { lili_detail::VoxelBuffers V; DevBuf segs, staging, raw; std::vector<LoopSeg> seg_host; std::vector<const unsigned char*> src; };
 int lili_loop_assemble(lili_ctx* ctx, std::unique_ptr<ExtState>& priv, const lili_cloud* clouds, int n_clouds, const double* t, const double* q, float leaf, DevBuf& out, int64_t* n_raw, int64_t* n_ds) {
     if (!priv) priv.reset(new LoopVox());
     auto* L = static_cast<LoopVox*>(priv.get());
     L->seg_host.assign(n_clouds, LoopSeg{});
-    long long total = 0, host_bytes = 0;
+    long long total = 0;
     for (int k = 0; k < n_clouds; k++) {
-        const lili_cloud& c = clouds[k];
-        ARGCHK(c.n == 0 || c.data, "loop_cloud: null data");
-        ARGCHK(c.stride >= 12 && c.stride % 4 == 0, "loop_cloud: stride must be a multiple of 4 and >= 12");
-        ARGCHK(c.aux_offset < 0 || (size_t)c.aux_offset + 4 <= c.stride, "loop_cloud: aux_offset outside the point");
-        ARGCHK(c.mem == LILI_MEM_HOST || c.mem == LILI_MEM_DEVICE, "loop_cloud: bad mem");
-        if (c.mem == LILI_MEM_HOST && c.n && !lili_pinned_dev_ptr(c.data, 4)) host_bytes += (long long)((c.n * c.stride + 255) / 256 * 256);
-        total += (long long)c.n;
+        TRY(lili_cloud_check(ctx, clouds[k], "loop_cloud"));
+        total += (long long)clouds[k].n;
     }
     ARGCHK(total < (1ll << 31), "loop_cloud: too many points");
-    if (host_bytes) HIPCHK(L->staging.ensure((size_t)host_bytes));
-    long long off = 0;
-    for (int k = 0; k < n_clouds; k++) {      // pageable rows go through one staging buffer as they are; page-locked and device rows are read where they lie
-        const lili_cloud& c = clouds[k];
+    // pageable rows go through one staging buffer as they are; page-locked and device rows are read where they lie
+    L->src.resize(n_clouds);
+    TRY(lili_cloud_sources(ctx, L->staging, clouds, n_clouds, kReadPinnedInPlace, L->src.data()));
+    for (int k = 0; k < n_clouds; k++) {
         LoopSeg& s = L->seg_host[k];
-        s.stride = (int)c.stride; s.aux_off = c.aux_offset;
+        s.stride = (int)clouds[k].stride; s.aux_off = clouds[k].aux_offset; s.src = L->src[k];
         for (int j = 0; j < 3; j++) s.t[j] = t[3 * k + j];
         for (int j = 0; j < 4; j++) s.q[j] = q[4 * k + j];
-        s.src = static_cast<const unsigned char*>(c.data);
-        if (c.mem == LILI_MEM_HOST && c.n) {
-            if (void* d = lili_pinned_dev_ptr(c.data, 4)) s.src = static_cast<const unsigned char*>(d);
-            else {
-                HIPCHK(hipMemcpyAsync(L->staging.as<unsigned char>() + off, c.data, c.n * c.stride, hipMemcpyHostToDevice, ctx->stream));
-                s.src = L->staging.as<unsigned char>() + off;
-                off += (long long)((c.n * c.stride + 255) / 256 * 256);
-            }
-        }
     }
     // first positions (empty clouds keep the position of the next one: the bisection never lands on them)
     { long long first = 0; for (int k = 0; k < n_clouds; k++) { L->seg_host[k].first = first; first += (long long)clouds[k].n; } }
