@@ -1232,6 +1232,24 @@ int lili_global_map_get(lili_ctx* ctx, lili_feature_out* out, int32_t* counts);
 int lili_global_map_stats(lili_ctx* ctx, int32_t* incremental, int32_t* rebuilds, int64_t* points_folded_last);
 /* device memory of the global map: the table and the work buffers of a batch (bytes) */
 int lili_global_map_info(lili_ctx* ctx, int64_t* table_bytes, int64_t* work_bytes);
+/* The part of the map inside a box: the voxels whose index lies in [floorf(lo * inv_leaf), floorf(hi * inv_leaf)] on every axis — inv_leaf the
+ * table's own f32 1.0f / leaf, the product rounded to f32, the index offset by 2^20 and clipped to [0, 2^21 - 1] as the table's keys are formed —, that is the
+ * voxels a point of the closed box would fall into.  Rows (the centroid bits lili_global_map_get gives) and counts come out in table order (ascending key).
+ * out->count = *n = the voxels in the box; the first min(n, out->capacity) rows and counts are copied (capacity 0: only counted); `out` and `counts` (optional)
+ * may be host or device memory; +-inf is allowed on any face.  The cost follows the box, not the table: one bisection pair per (k, j) row of the box (k clipped to
+ * the table's own range), a scan of the run lengths and a gather; no floating-point arithmetic and no atomics — the same bytes on every run.
+ * LILI_E_ARG: lo > hi on an axis, a NaN, or more than 2^24 (k, j) rows after clipping (the message names the count); LILI_E_STATE: no successful
+ * lili_global_map / lili_global_map_import.  Blocking (one read-back: the count). */
+int lili_global_map_crop(lili_ctx* ctx, const float lo[3], const float hi[3], lili_feature_out* out, int32_t* counts, int64_t* n);
+/* The table itself — per voxel the key ((k << 42) | (j << 21) | i, each index offset by 2^20), the running f32 sum (4 floats) and the count, in ascending key order —
+ * and the leaf and kind it was built with: what another context needs to hand back the same centroid bits (centroids alone would not do).  *n = voxels; the first
+ * min(n, capacity) entries are copied (host or device memory; any array may be NULL).  LILI_E_STATE without a map.  Blocking. */
+int lili_global_map_export(lili_ctx* ctx, int64_t capacity, uint64_t* keys, float* sums, int32_t* counts, int64_t* n, float* leaf, int* kind);
+/* An exported table into this context: uploaded, validated on the device (keys strictly ascending, every index below 2^21, counts >= 1: otherwise LILI_E_ARG and an
+ * EMPTY table) and its centroids computed as lili_global_map computes them.  An imported table serves lili_global_map_get, _crop, _export and _info.  The list of
+ * keyframes a table was folded from does NOT travel with it: the next lili_global_map does not extend an imported table, it starts from an empty one and folds
+ * this context's archive (a rebuild, as after a failed call).  Blocking. */
+int lili_global_map_import(lili_ctx* ctx, float leaf, int kind, int64_t n, const uint64_t* keys, const float* sums, const int32_t* counts);
 
 /* ---- place recognition: polar descriptors over the archive (lili_place.hip) -------------------------------
  * Appearance-based loop candidates in the manner of Scan Context (Kim & Kim, IROS 2018): per keyframe an n_sector x n_ring image

@@ -453,6 +453,9 @@ _SIGS = {
     "lili_global_map_get": (C.c_int, [C.c_void_p, C.POINTER(FeatureOut), C.c_void_p]),
     "lili_global_map_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "lili_global_map_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lili_global_map_crop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FeatureOut), C.c_void_p, C.POINTER(C.c_int64)]),
+    "lili_global_map_export": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "lili_global_map_import": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_place_default_params": (None, [C.POINTER(PlaceParams)]),
     "lili_place_layout": (C.c_int, [C.POINTER(PlaceParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "lili_place_update": (C.c_int, [C.c_void_p, C.POINTER(PlaceParams), C.POINTER(C.c_int)]),
@@ -1179,10 +1182,12 @@ class FrontendOdometry:
     prediction (L:415-441)."""
 
     def __init__(self, ctx, params=None, surf_thres=0.28, edge_thres=4.0, near_range=0.1, leaf_query=0.4, leaf_map=0.4, width=20, slot=0,
-                 scan_match_cnt=6, first_match_cnt=8, reference_startup=True):
+                 scan_match_cnt=6, first_match_cnt=8, reference_startup=True, external_map=False, edges=False):
         """reference_startup = False: the replay tools' simpler start (frame 0 enters the ring with its features at the given pose, frame 1 is matched
-        against it with `first_match_cnt` iterations) — same C call, other flags."""
+        against it with `first_match_cnt` iterations) — same C call, other flags.  external_map = True (with edges: the edge features are queries too): every scan is
+        matched with `scan_match_cnt` iterations against the indices the caller set with ScanToMapMatcher.set_input_cloud / lili_map_set, nothing joins the ring."""
         self.reference_startup = bool(reference_startup)
+        self.base_flags = (FRAME_EXTERNAL_MAP if external_map else 0) | (FRAME_EDGES if edges else 0)
         self.ctx, self.lib = ctx, ctx.lib
         self.params = params if params is not None else make_params("frontend")
         self.livox = LivoxParams(surf_thres, edge_thres, near_range)
@@ -1216,8 +1221,11 @@ class FrontendOdometry:
             n = scan.shape[0]
             cloud, curv_off = Cloud(scan.ctypes.data if n else None, n, 20, 12, MEM_HOST), 16
         k = self.n_frames
-        self.opt.n_iters = 0 if k == 0 else (self.first_match_cnt if k == 1 else self.scan_match_cnt)
-        self.opt.flags = (FRAME_PUSH_EMPTY if k == 0 else (FRAME_SELF_MAP if k == 1 else 0)) if self.reference_startup else 0
+        if self.base_flags & FRAME_EXTERNAL_MAP:
+            self.opt.n_iters, self.opt.flags = self.scan_match_cnt, self.base_flags
+        else:
+            self.opt.n_iters = 0 if k == 0 else (self.first_match_cnt if k == 1 else self.scan_match_cnt)
+            self.opt.flags = (FRAME_PUSH_EMPTY if k == 0 else (FRAME_SELF_MAP if k == 1 else 0)) if self.reference_startup else 0
         self.opt.want_timing = 1 if timing else 0
         qi, tp, qp = _f64(q_imu, 4), _f64(t_pred, 3), _f64(q_pred, 4)
         r = self.res
@@ -1244,10 +1252,9 @@ class RotFrontendOdometry(FrontendOdometry):
     def __init__(self, ctx, params=None, n_scans=64, ds_rate=4, ds_v=0.6, near_range=3.0, q_lb=(1.0, 0, 0, 0), leaf_query=0.4, leaf_map=0.4, width=20, slot=0,
                  scan_match_cnt=6, first_match_cnt=8, reference_startup=True, external_map=False, edges=False):
         super().__init__(ctx, params, leaf_query=leaf_query, leaf_map=leaf_map, width=width, slot=slot, scan_match_cnt=scan_match_cnt, first_match_cnt=first_match_cnt,
-                         reference_startup=reference_startup)
+                         reference_startup=reference_startup, external_map=external_map, edges=edges)
         self.rot = RotParams(n_scans, ds_rate, ds_v, near_range)
         self.q_lb = _f64(q_lb, 4)
-        self.base_flags = (FRAME_EXTERNAL_MAP if external_map else 0) | (FRAME_EDGES if edges else 0)
 
     def frame(self, scan, t_pred, q_pred, q_imu=(1.0, 0, 0, 0), timing=False):
         """scan: (n,4) float32 rows x, y, z, intensity (host) or a Cloud (e.g. a device float4 array).  Returns (t, q, info)."""

@@ -129,6 +129,66 @@ class GlobalMap:
         self.ctx._chk(self.lib.lili_global_map_get(self.ctx.h, C.byref(fo), None))
         return fo.count
 
+    def crop_into(self, lo, hi, d_ptr, capacity, d_counts=None):
+        """lili_global_map_crop into a caller's device buffers (float4 rows; int32 counts, optional): returns the voxels in the box — more than `capacity` means only
+        the first `capacity` were written."""
+        lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+        fo, n = FeatureOut(d_ptr, int(capacity), 16, 1, 0), C.c_int64(0)
+        self.ctx._chk(self.lib.lili_global_map_crop(self.ctx.h, _ptr(lo), _ptr(hi), C.byref(fo), d_counts, C.byref(n)))
+        return n.value
+
+    def crop(self, lo, hi, device=False):
+        """The voxels a point of the closed box [lo, hi] would fall into (+-inf allowed): (centroids (m, 4) float32, counts (m,) int32) in table order —
+        numpy arrays, or with device = True torch tensors on the context's device."""
+        lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+        fo, n = FeatureOut(None, 0, 16, MEM_HOST, 0), C.c_int64(0)
+        self.ctx._chk(self.lib.lili_global_map_crop(self.ctx.h, _ptr(lo), _ptr(hi), C.byref(fo), None, C.byref(n)))
+        m = n.value
+        if device:
+            import torch
+            out, cnt = torch.empty((max(m, 1), 4), dtype=torch.float32, device="cuda"), torch.empty(max(m, 1), dtype=torch.int32, device="cuda")
+            if m:
+                self.crop_into(lo, hi, out.data_ptr(), m, cnt.data_ptr())
+            return out[:m], cnt[:m]
+        out, cnt = np.zeros((max(m, 1), 4), np.float32), np.zeros(max(m, 1), np.int32)
+        if m:
+            fo = FeatureOut(out.ctypes.data, m, 16, MEM_HOST, 0)
+            self.ctx._chk(self.lib.lili_global_map_crop(self.ctx.h, _ptr(lo), _ptr(hi), C.byref(fo), _ptr(cnt), C.byref(n)))
+        return out[:m], cnt[:m]
+
+    def export(self):
+        """The table itself: dict(keys (m,) uint64 ascending, sums (m, 4) float32, counts (m,) int32, leaf float32, kind int) — what load_table takes."""
+        n, leaf, kind = C.c_int64(0), C.c_float(0), C.c_int(0)
+        self.ctx._chk(self.lib.lili_global_map_export(self.ctx.h, 0, None, None, None, C.byref(n), C.byref(leaf), C.byref(kind)))
+        m = n.value
+        keys, sums, cnt = np.zeros(max(m, 1), np.uint64), np.zeros((max(m, 1), 4), np.float32), np.zeros(max(m, 1), np.int32)
+        self.ctx._chk(self.lib.lili_global_map_export(self.ctx.h, m, _ptr(keys), _ptr(sums), _ptr(cnt), C.byref(n), C.byref(leaf), C.byref(kind)))
+        return dict(keys=keys[:m], sums=sums[:m], counts=cnt[:m], leaf=np.float32(leaf.value), kind=kind.value)
+
+    def load_table(self, keys, sums, counts, leaf, kind):
+        """An exported table into this context (lili_global_map_import): it serves get / crop / export / info; the next build() does not extend it but starts from
+        an empty table and this context's archive.  Raises LiliError (and leaves no map) if it is not a table."""
+        keys, cnt = np.ascontiguousarray(keys, np.uint64).reshape(-1), np.ascontiguousarray(counts, np.int32).reshape(-1)
+        sums = np.ascontiguousarray(sums, np.float32).reshape(-1, 4)
+        if not keys.shape[0] == sums.shape[0] == cnt.shape[0]:
+            raise ValueError("load_table: keys, sums and counts of one length")
+        self.ctx._chk(self.lib.lili_global_map_import(self.ctx.h, float(np.float32(leaf)), int(kind), keys.shape[0], _ptr(keys), _ptr(sums), _ptr(cnt)))
+        return keys.shape[0]
+
+    FILE_VERSION = 1
+
+    def save(self, path):
+        """numpy.savez of export() plus version = 1 (a path without ".npz" gets it appended, as numpy does)"""
+        np.savez(path, version=np.int32(self.FILE_VERSION), **self.export())
+
+    def load(self, path):
+        """load_table of a file written by save; returns the number of voxels"""
+        with np.load(path) as f:
+            version = int(f["version"])
+            if version != self.FILE_VERSION:
+                raise ValueError(f"{path}: map file version {version}, this package reads version {self.FILE_VERSION}")
+            return self.load_table(f["keys"], f["sums"], f["counts"], np.float32(f["leaf"]), int(f["kind"]))
+
     def stats(self):
         """(incremental calls, rebuilds, points folded by the last call)"""
         a, b, c = C.c_int32(0), C.c_int32(0), C.c_int64(0)

@@ -10,7 +10,9 @@
 //     order pcl::VoxelGrid's box-relative index induces whatever the box is —, the running f32 sum and the count, sorted by key.  A batch of placed points is sorted
 //     stably by its own box-relative voxel index (lili_voxel.hip's radix sort: the same order, 32-bit keys), and every voxel of the batch CONTINUES the left fold
 //     from the table's sum (or from 0.0f): a voxel's members of a later batch all come after those of the earlier ones in concatenation order, so the sequence of f32
-//     additions per voxel is the one-shot filter's for any split into batches.  New keys are merged in by prefix sum and binary search (as k_merge does for the ring).
+//     additions per voxel is the one-shot filter's for any split into batches.  New keys are merged in by prefix sum and binary search (as k_merge does for the ring);
+//   * the table's way out and back in, and the crop: export / import of (key, sum, count) — an imported table serves its readers but is not extended —,
+//     and the voxels inside a box at the cost of the box: one run of the sorted keys per (k, j) row, found by bisection, scanned and gathered.
 // No floating-point atomics anywhere: the order of the additions is the contract.
 #include "lili_launch.h"
 #include "lili_device_math.h"
@@ -145,6 +147,41 @@ __global__ void k_gm_centroid(const float4* __restrict__ tsum, const int* __rest
     out[i] = make_float4(s.x / fn, s.y / fn, s.z / fn, s.w / fn);
 }
 
+// The crop of the table by a box of voxel indices.  The key is k << 42 | j << 21 | i and the table is sorted, so the voxels of one (k, j) pair with i in
+// [i0, i1] are ONE contiguous run of the table: thread r of k_gm_crop_runs takes row (k0 + r / nj, j0 + r % nj) and finds its run by two bisections over the keys —
+// begin = lower_bound(key(k, j, i0)), len = upper_bound(key(k, j, i1)) - begin.  Integer work only.
+struct CropBox { int i0, i1, j0, nj, k0; };
+__global__ void k_gm_crop_runs(const unsigned long long* __restrict__ tkey, int n_tab, CropBox b, int n_rows, int* __restrict__ begin, int* __restrict__ len) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const unsigned long long kj = ((unsigned long long)(b.k0 + r / b.nj) << 42) | ((unsigned long long)(b.j0 + r % b.nj) << 21);
+    const unsigned long long first = kj | (unsigned long long)b.i0, last = kj | (unsigned long long)b.i1;
+    int lo = 0, hi = n_tab;
+    while (lo < hi) { const int mid = (int)(((long long)lo + hi) >> 1); if (tkey[mid] < first) lo = mid + 1; else hi = mid; }
+    const int at = lo;
+    hi = n_tab;
+    while (lo < hi) { const int mid = (int)(((long long)lo + hi) >> 1); if (tkey[mid] <= last) lo = mid + 1; else hi = mid; }
+    begin[r] = at; len[r] = lo - at;
+}
+// The gather, ONE WAVE PER ROW: the wave of row r copies the run [begin[r], begin[r] + len) to the outputs [first[r], first[r] + len), first = the exclusive scan of the
+// lengths — lane t reads the 16-byte row begin + t and writes output first + t, so both sides are runs of neighbouring rows; outputs at or beyond `cap` (the caller's
+// capacity) are not written.  No bisection per output: measured against one thread per output finding its run with seg_of, this form was 10 % faster on both §7n tables.
+__global__ __launch_bounds__(256) void k_gm_crop_gather(const int* __restrict__ first, const int* __restrict__ begin, int n_rows, long long cap, const float4* __restrict__ cen,
+                                                        const int* __restrict__ tcnt, float4* __restrict__ out, int* __restrict__ out_cnt) {
+    const int lane = threadIdx.x & 63;
+    for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < n_rows; r += gridDim.x * 4) {      // (wave-uniform)
+        const int f = first[r], len = first[r + 1] - f, b = begin[r];
+        for (int t = lane; t < len && (long long)f + t < cap; t += 64) { out[f + t] = cen[b + t]; out_cnt[f + t] = tcnt[b + t]; }
+    }
+}
+
+// an imported table is a table: keys strictly ascending, every index below 2^21 (bit 63 clear: three fields of 21 bits), every count >= 1; *bad is raised otherwise
+__global__ void k_gm_validate(const unsigned long long* __restrict__ key, const int* __restrict__ cnt, long long n, int* __restrict__ bad) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if ((key[i] >> 63) || cnt[i] < 1 || (i > 0 && key[i - 1] >= key[i])) *bad = 1;
+}
+
 }  // namespace lili
 
 // `count` float4 rows of device memory into a caller's lili_feature_out (declared in lili_launch.h): out->count = count, the first min(count, capacity) rows are
@@ -196,13 +233,16 @@ struct GlobalMap {
     int64_t n_raw = 0, folded_last = 0;
     int incremental = 0, rebuilds = 0;
     DevBuf raw, spts, flags, slot, head_pos, bkey, pos, is_new, new_rank, bsum, bcnt, long_list, sums, segs, res, out;
+    DevBuf crop_begin, crop_len, crop_first, crop_rows, crop_cnt;      // lili_global_map_crop: the runs, their scan, and the gathered rows and counts
+    unsigned long long key_first = 0, key_last = 0;  // of the table `out` was made from (n_tab >= 1): the crop clips its k range to theirs
     std::vector<lili::GmSeg> seg_host;
-    bool has_map = false;                            // `out` holds the centroids of a successful build
+    bool has_map = false;                            // `out` holds the centroids of a successful build or import (imported: has_map && !valid — the next build starts empty)
     void clear_table() { n_tab = 0; folded.clear(); box_any = false; n_raw = 0; valid = false; has_map = false; }
     size_t table_bytes() const { size_t b = out.cap; for (int k = 0; k < 2; k++) b += key[k].cap + sum[k].cap + cnt[k].cap; return b; }
     size_t work_bytes() const {
         size_t b = lili_vox_sort_bytes(sort.get());
-        for (const DevBuf* d : {&raw, &spts, &flags, &slot, &head_pos, &bkey, &pos, &is_new, &new_rank, &bsum, &bcnt, &long_list, &sums, &segs, &res}) b += d->cap;
+        for (const DevBuf* d : {&raw, &spts, &flags, &slot, &head_pos, &bkey, &pos, &is_new, &new_rank, &bsum, &bcnt, &long_list, &sums, &segs, &res, &crop_begin, &crop_len, &crop_first,
+                                &crop_rows, &crop_cnt}) b += d->cap;
         return b;
     }
 };
@@ -388,6 +428,25 @@ int fold_batch(lili_ctx* ctx, GlobalMap& G, int total) {
     for (int k = 0; k < 6; k++) G.box[k] = nb6[k];
     G.box_any = true;
     return LILI_OK;
+}
+
+// what a built or imported table (G.cur, G.n_tab) owes its readers: the centroids in G.out, and its first and last key on the host.  Blocking.
+int finish_table(lili_ctx* ctx, GlobalMap& G) {
+    if (!G.n_tab) { HIPCHK(hipStreamSynchronize(ctx->stream)); return LILI_OK; }
+    HIPCHK(grow(G.out, (size_t)G.n_tab * 16));
+    hipLaunchKernelGGL(lili::k_gm_centroid, dim3(nblocks(G.n_tab, 256)), dim3(256), 0, ctx->stream, (const float4*)G.sum[G.cur].as<float4>(), (const int*)G.cnt[G.cur].as<int>(), G.n_tab,
+                       G.out.as<float4>());
+    HIPCHK(hipGetLastError());
+    const unsigned long long* d_key = G.key[G.cur].as<unsigned long long>();
+    TRY(lili_readback_add(ctx, &G.key_first, d_key, 8));
+    TRY(lili_readback_add(ctx, &G.key_last, d_key + (G.n_tab - 1), 8));
+    return lili_readback_finish(ctx);
+}
+
+// a face of the crop's box as a voxel index: floorf(x * inv_leaf) in f32, offset by 2^20 and clipped to [0, 2^21 - 1] (abs_voxel_key's index; +-inf clips)
+int crop_index(float x, float inv_leaf) {
+    const float f = std::floor(x * inv_leaf);
+    return f < -1048576.f ? 0 : f >= 1048576.f ? (1 << 21) - 1 : (int)f + (1 << 20);
 }
 
 }  // namespace
@@ -617,13 +676,7 @@ int lili_global_map(lili_ctx* ctx, int kind, int interval, float leaf, int64_t* 
         G.folded.push_back(f);
     }
     G.n_raw += G.folded_last;
-    if (G.n_tab) {
-        HIPCHK(grow(G.out, (size_t)G.n_tab * 16));
-        hipLaunchKernelGGL(lili::k_gm_centroid, dim3(nblocks(G.n_tab, 256)), dim3(256), 0, ctx->stream, (const float4*)G.sum[G.cur].as<float4>(), (const int*)G.cnt[G.cur].as<int>(), G.n_tab,
-                           G.out.as<float4>());
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    TRY(finish_table(ctx, G));
     G.valid = true; G.has_map = true;
     if (n_raw) *n_raw = G.n_raw;
     if (n_map) *n_map = G.n_tab;
@@ -639,6 +692,96 @@ int lili_global_map_get(lili_ctx* ctx, lili_feature_out* out, int32_t* counts) {
     const size_t k = std::min((size_t)G.n_tab, out->capacity);
     if (counts && k) HIPCHK(hipMemcpyAsync(counts, G.cnt[G.cur].p, k * 4, hipMemcpyDefault, ctx->stream));
     return copy_rows_out(ctx, G.out.p, (size_t)G.n_tab, out, "global_map_get");
+}
+
+int lili_global_map_crop(lili_ctx* ctx, const float lo[3], const float hi[3], lili_feature_out* out, int32_t* counts, int64_t* n) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(lo && hi && out, "global_map_crop: null argument");
+    for (int a = 0; a < 3; a++) ARGCHK(lo[a] <= hi[a], "global_map_crop: lo > hi on an axis, or a NaN");      // (a comparison with a NaN is false)
+    GlobalMap& G = archive_of(ctx)->gm;
+    if (!G.has_map) return ctx->fail(LILI_E_STATE, "global_map_crop: no map yet (lili_global_map or lili_global_map_import first)");
+    HIPCHK(hipSetDevice(ctx->device));
+    out->count = 0;
+    if (n) *n = 0;
+    if (!G.n_tab) return LILI_OK;
+    const float inv_leaf = 1.0f / G.leaf;
+    int a0[3], a1[3];
+    for (int a = 0; a < 3; a++) { a0[a] = crop_index(lo[a], inv_leaf); a1[a] = crop_index(hi[a], inv_leaf); }
+    // no table row lies outside the k of its first and last key: an unbounded z face costs the table's own height
+    const int k0 = std::max(a0[2], (int)(G.key_first >> 42)), k1 = std::min(a1[2], (int)(G.key_last >> 42));
+    if (k0 > k1) return LILI_OK;
+    const long long n_rows = (long long)(k1 - k0 + 1) * (a1[1] - a0[1] + 1);
+    if (n_rows > (1ll << 24)) return ctx->fail(LILI_E_ARG, "global_map_crop: the box spans " + std::to_string(n_rows) + " (k, j) rows of voxels, more than 2^24");
+    const int rows = (int)n_rows, n_tab = (int)G.n_tab;
+    const size_t w = (size_t)rows + 1;
+    const long long cap = out->data ? (long long)std::min(out->capacity, (size_t)n_tab) : 0;
+    HIPCHK(grow(G.crop_begin, w * 4)); HIPCHK(grow(G.crop_len, w * 4)); HIPCHK(grow(G.crop_first, w * 4));
+    const lili::CropBox box{a0[0], a1[0], a0[1], a1[1] - a0[1] + 1, k0};
+    hipLaunchKernelGGL(lili::k_gm_crop_runs, dim3(nblocks(rows, 256)), dim3(256), 0, ctx->stream, (const unsigned long long*)G.key[G.cur].as<unsigned long long>(), n_tab, box, rows,
+                       G.crop_begin.as<int>(), G.crop_len.as<int>());
+    TRY(lili_scan_exclusive3(ctx, G.crop_len.as<int>(), rows, G.sums, G.crop_first.as<int>()));
+    if (cap) {
+        HIPCHK(grow(G.crop_rows, (size_t)cap * 16)); HIPCHK(grow(G.crop_cnt, (size_t)cap * 4));
+        hipLaunchKernelGGL(lili::k_gm_crop_gather, dim3(std::min(nblocks(rows, 4), 8192)), dim3(256), 0, ctx->stream, (const int*)G.crop_first.as<int>(), (const int*)G.crop_begin.as<int>(), rows,
+                           cap, (const float4*)G.out.as<float4>(), (const int*)G.cnt[G.cur].as<int>(), G.crop_rows.as<float4>(), G.crop_cnt.as<int>());
+    }
+    HIPCHK(hipGetLastError());
+    int total = 0;
+    TRY(lili_readback_now(ctx, &total, G.crop_first.as<int>() + rows, sizeof(int)));
+    if (total < 0 || total > n_tab) return ctx->fail(LILI_E_STATE, "global_map_crop: internal: voxel count out of range");
+    if (n) *n = total;
+    const size_t k = (size_t)std::min((long long)total, cap);
+    if (counts && k) HIPCHK(hipMemcpyAsync(counts, G.crop_cnt.p, k * 4, hipMemcpyDefault, ctx->stream));
+    return copy_rows_out(ctx, G.crop_rows.p, (size_t)total, out, "global_map_crop");
+}
+
+int lili_global_map_export(lili_ctx* ctx, int64_t capacity, uint64_t* keys, float* sums, int32_t* counts, int64_t* n, float* leaf, int* kind) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(capacity >= 0, "global_map_export: negative capacity");
+    GlobalMap& G = archive_of(ctx)->gm;
+    if (!G.has_map) return ctx->fail(LILI_E_STATE, "global_map_export: no map yet (lili_global_map or lili_global_map_import first)");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t k = (size_t)std::min((long long)capacity, G.n_tab);
+    if (keys && k) HIPCHK(hipMemcpyAsync(keys, G.key[G.cur].p, k * 8, hipMemcpyDefault, ctx->stream));
+    if (sums && k) HIPCHK(hipMemcpyAsync(sums, G.sum[G.cur].p, k * 16, hipMemcpyDefault, ctx->stream));
+    if (counts && k) HIPCHK(hipMemcpyAsync(counts, G.cnt[G.cur].p, k * 4, hipMemcpyDefault, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (n) *n = G.n_tab;
+    if (leaf) *leaf = G.leaf;
+    if (kind) *kind = G.kind;
+    return LILI_OK;
+}
+
+int lili_global_map_import(lili_ctx* ctx, float leaf, int kind, int64_t n, const uint64_t* keys, const float* sums, const int32_t* counts) {
+    if (!ctx) return LILI_E_ARG;
+    ARGCHK(kind >= 0 && kind < kKinds, "global_map_import: unknown kind");
+    ARGCHK(leaf > 0 && std::isfinite(leaf), "global_map_import: leaf must be positive");
+    ARGCHK(n >= 0 && n <= 2147483647ll, "global_map_import: n out of range");
+    ARGCHK(n == 0 || (keys && sums && counts), "global_map_import: null table");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    GlobalMap& G = archive_of(ctx)->gm;
+    G.clear_table();      // (valid stays false: the list of folded keyframes does not travel, the next lili_global_map starts from an empty table)
+    G.kind = kind; G.interval = 0; G.leaf = leaf;
+    if (n) {
+        const int c = G.cur;
+        HIPCHK(grow(G.key[c], (size_t)n * 8)); HIPCHK(grow(G.sum[c], (size_t)n * 16)); HIPCHK(grow(G.cnt[c], (size_t)n * 4)); HIPCHK(G.res.ensure(16));
+        HIPCHK(hipMemcpyAsync(G.key[c].p, keys, (size_t)n * 8, hipMemcpyDefault, ctx->stream));
+        HIPCHK(hipMemcpyAsync(G.sum[c].p, sums, (size_t)n * 16, hipMemcpyDefault, ctx->stream));
+        HIPCHK(hipMemcpyAsync(G.cnt[c].p, counts, (size_t)n * 4, hipMemcpyDefault, ctx->stream));
+        HIPCHK(hipMemsetAsync(G.res.p, 0, 16, ctx->stream));
+        hipLaunchKernelGGL(lili::k_gm_validate, dim3(nblocks(n, 256)), dim3(256), 0, ctx->stream, (const unsigned long long*)G.key[c].as<unsigned long long>(), (const int*)G.cnt[c].as<int>(),
+                           (long long)n, G.res.as<int>());
+        HIPCHK(hipGetLastError());
+        int bad = 0;
+        TRY(lili_readback_now(ctx, &bad, G.res.p, sizeof(int)));
+        if (bad) return ctx->fail(LILI_E_ARG, "global_map_import: not a table (keys strictly ascending, every index below 2^21, counts >= 1)");
+    }
+    G.n_tab = n;
+    const int rc = finish_table(ctx, G);
+    if (rc != LILI_OK) { (void)hipStreamSynchronize(ctx->stream); G.clear_table(); return rc; }
+    G.has_map = true;
+    return LILI_OK;
 }
 
 int lili_global_map_stats(lili_ctx* ctx, int32_t* incremental, int32_t* rebuilds, int64_t* points_folded_last) {
